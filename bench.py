@@ -6,6 +6,12 @@
     python bench.py --config c4                                          # configs[3]: 3 M Gaussians, SH 3, 1237x822
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W           # configs[4] with --config c5 (1297x840)
+    python bench.py --full                                               # + repeats, kernels, rooflines, CPU oracle
+                                                                         #   baseline and parity, secondary measurements
+    python bench.py --dump-outputs DIR                                   # + the last timed step's arrays as DIR/*.npy
+
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line (`value`, `ms_per_step`); every
+other figure of that line is measured under --full.
 
 One "step" is one stage-2 training iteration of the reference (train.py:266-422) on one
 camera view per GPU: rasterizer forward (preprocess, scan, duplicate, radix sort, ranges,
@@ -296,9 +302,16 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure: the --repeats timed blocks, per-kernel timings and "
+                         "rooflines, the CPU oracle baseline and parity, and the secondary measurements (drop_in_step, "
+                         "full_grad_step, iteration); without it the run times exactly --steps steps and prints the headline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (outputs and parameter gradients; "
+                         "a fixed seeded sample of the per-Gaussian rows) as DIR/<name>.npy")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="timed blocks of --steps steps each: the first is the contract's measurement (`value`), all of them "
-                         "give `repeats` = median / min / max ms per step")
+                    help="with --full: timed blocks of --steps steps each: the first is the contract's measurement (`value`), "
+                         "all of them give `repeats` = median / min / max ms per step")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2",
                     help="BASELINE.json configuration (c2 = the headline metric's; c3 relight inference; c4/c5 3 M Gaussians "
                          "at the Mip-NeRF360 images_4 resolutions)")
@@ -314,12 +327,13 @@ def parse_args(argv=None):
     ap.add_argument("--fused", choices=["on", "off"], default="on",
                     help="run the tensor glue between rasterizer and loss.backward() as the fused stage-2 node "
                          "(gi-gs_amd/stage2_fused.py) instead of op-by-op torch")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle leg (cpu_baseline and parity)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle leg (cpu_baseline and parity)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements (drop_in_step, full_grad_step, iteration) that follow the timed region")
+                    help="with --full: skip the secondary measurements (drop_in_step, full_grad_step, iteration) that follow "
+                         "the timed region")
     ap.add_argument("--iteration", action="store_true",
-                    help="print the complete training iteration (it/s, `iteration` / `iteration_stage1`) beside the metric even "
-                         "under --no-extras (it is part of the default line)")
+                    help="print the complete training iteration (it/s, `iteration` / `iteration_stage1`) beside the metric, "
+                         "also without --full or under --no-extras")
     ap.add_argument("--scene", default=None,
                     help="a trained scene instead of the synthetic stand-in: point_cloud.ply (GaussianModel.save_ply) or "
                          "chkpntN.pth (train.py); Gaussian count and SH degree come from the file (SURVEY 8(d): real "
@@ -328,7 +342,7 @@ def parse_args(argv=None):
                     help="with --scene: a Blender / NeRF-synthetic transforms_*.json whose poses and field of view replace "
                          "the orbit cameras (rendered at the config's resolution)")
     ap.add_argument("--cpu-single-res", type=int, default=200,
-                    help="resolution of the bounded single-thread CPU sample (0 = skip)")
+                    help="with --full: resolution of the bounded single-thread CPU sample (0 = skip)")
     args = ap.parse_args(argv)
     cP, cW, cH, cD, cname = CONFIGS[args.config]
     args.gaussians = cP if args.gaussians is None else args.gaussians
@@ -374,6 +388,51 @@ def load_workload(args, W, H):
     n = len(cams)
     cams = [dict(c, index=i, n_views=n) for i, c in enumerate(cams)]
     return sc, cams, tag
+
+
+DUMP_BUDGET = 60_000_000  # bytes of array data --dump-outputs may write in all (under 64 MB with the .npy headers)
+DUMP_GAUSSIANS = 32768  # per-Gaussian rows it keeps (a fixed seeded sample when there are more Gaussians)
+
+
+def dump_outputs(out_dir, arrays, P, H, W):
+    """--dump-outputs: each entry of `arrays` (tensors or numbers; None is skipped) as out_dir/<name>.npy, in float32
+    (float64 for integer data).  Arrays with one row per Gaussian keep the rows of a fixed seeded sample of DUMP_GAUSSIANS
+    Gaussians (their indices: gaussian_index.npy); per-pixel planes ([..., H, W]) keep every pixel unless they would not
+    fit DUMP_BUDGET, and then a fixed seeded sample of pixels (pixel_index.npy).  Same arguments, same files."""
+    def host(v):
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if a.dtype.kind == "f":
+            return a.astype(np.float64 if a.dtype.itemsize == 8 else np.float32)
+        return a.astype(np.float32 if a.dtype.kind == "b" else np.float64)
+
+    gidx = np.sort(np.random.default_rng(0).choice(P, DUMP_GAUSSIANS, replace=False)) if P > DUMP_GAUSSIANS else None
+    out, planes = {}, {}
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == P:
+            if gidx is not None:
+                v = v.detach().index_select(0, torch.from_numpy(gidx).to(v.device))
+            out[name] = host(v)
+        elif isinstance(v, torch.Tensor) and v.dim() >= 2 and tuple(v.shape[-2:]) == (H, W):
+            planes[name] = host(v)
+        else:
+            out[name] = host(v)
+    if gidx is not None:
+        out["gaussian_index"] = gidx.astype(np.float64)
+    room = DUMP_BUDGET - sum(a.nbytes for a in out.values())
+    if sum(a.nbytes for a in planes.values()) > room:
+        per_px = sum(a.nbytes for a in planes.values()) // (H * W) + 8  # + the index itself
+        pidx = np.sort(np.random.default_rng(1).choice(H * W, max(1, room // per_px), replace=False))
+        planes = {k: a.reshape(a.shape[:-2] + (H * W,))[..., pidx] for k, a in planes.items()}
+        out["pixel_index"] = pidx.astype(np.float64)
+    out.update(planes)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BUDGET))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def self_launch(args, argv) -> int:
@@ -482,6 +541,7 @@ def run(args):
     cams_t = [{k: (torch.from_numpy(v).to(dev) if isinstance(v, np.ndarray) else v) for k, v in c.items()} for c in cams]
     yy, xx = torch.meshgrid(torch.linspace(0, 1, H, device=dev), torch.linspace(0, 1, W, device=dev), indexing="ij")
     gt_image = torch.stack([0.5 + 0.3 * torch.sin(6 * xx), 0.5 + 0.3 * torch.cos(5 * yy), 0.4 + 0.2 * xx * yy])
+    torch.manual_seed(0)  # the light's initial texels are random: the same inputs on every run
     light, brdf_lut = make_light(dev)
     rays = pipeline.canonical_rays(cams[0], dev)
     view_dirs = [pipeline.view_dirs_for(c, rays, dev) for c in cams_t]  # per-camera constants, like gt_image
@@ -507,7 +567,7 @@ def run(args):
     if use_dist:
         import diff_gaussian_rasterization as dgr_mod
         slab = dp.GradSlab(flat_params)
-        slab.timing = True
+        slab.timing = args.full  # `comm`: events around every collective
         sink = slab.sink([SINK_NAME.get(k, k) for k in SLAB_KEYS])
     stepper = relighter = g_inf = None
     if inference:
@@ -548,12 +608,14 @@ def run(args):
             dist.barrier()
         torch.cuda.synchronize()
 
+    last_out = [None]  # what the last timed step returned (--dump-outputs)
+
     def timed_block(first):
         """EXACTLY --steps steps between two (barrier + synchronize) brackets; the maximum over ranks."""
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            one_step(first + i)
+            last_out[0] = one_step(first + i)
         barrier()
         dt = time.perf_counter() - t0
         if use_dist:
@@ -571,29 +633,42 @@ def run(args):
     if slab is not None:
         torch.cuda.synchronize()
         slab.comm_stats()  # drop the warm-up collectives' events
-    with gigs_lib.profile() as prof:
+    with (gigs_lib.profile() if args.full else _NULL) as prof:
         elapsed = timed_block(args.warmup)  # the contract's measurement
-    comm = None
-    if slab is not None:
+    comm = repeats = None
+    if slab is not None and args.full:
         comm = slab.comm_stats()
         if comm is not None:
             comm["reduced"] = ("stage-2 non-zero set: albedo, roughness, metallic, light (rest verified zero on the first 2 steps)"
                                if reduce_only is not None else "every gradient")
             comm["floats_per_gaussian"] = round((comm["bytes"] / 4 - sum(p.numel() for p in params_light)) / P, 2)
             comm["backend"] = backend
-    blocks = [elapsed]
-    for b in range(1, max(1, args.repeats)):
-        blocks.append(timed_block(args.warmup + b * args.steps))
-    per_step = sorted(1e3 * x / args.steps for x in blocks)
-    repeats = {"blocks": len(blocks), "steps_per_block": args.steps, "ms_per_step_median": round(per_step[len(per_step) // 2], 4),
-               "ms_per_step_min": round(per_step[0], 4), "ms_per_step_max": round(per_step[-1], 4),
-               "value_median": round(args.steps * world / (1e-3 * per_step[len(per_step) // 2] * args.steps), 3)}
+    if args.full:
+        blocks = [elapsed]
+        for b in range(1, max(1, args.repeats)):
+            blocks.append(timed_block(args.warmup + b * args.steps))
+        per_step = sorted(1e3 * x / args.steps for x in blocks)
+        repeats = {"blocks": len(blocks), "steps_per_block": args.steps,
+                   "ms_per_step_median": round(per_step[len(per_step) // 2], 4),
+                   "ms_per_step_min": round(per_step[0], 4), "ms_per_step_max": round(per_step[-1], 4),
+                   "value_median": round(args.steps * world / (1e-3 * per_step[len(per_step) // 2] * args.steps), 3)}
+    if args.dump_outputs and rank == 0:
+        if inference:
+            arrays = dict(last_out[0])
+        else:
+            arrays = {k: v for k, v in last_out[0].items() if k != "viewspace_points"}
+            arrays["grad_means2D"] = last_out[0]["viewspace_points"].grad
+            # the gradients an optimizer would read: the reduced slab with several ranks, .grad with one
+            grads = slab.views if slab is not None else [p.grad for p in flat_params]
+            names = SLAB_KEYS + ["light_" + n for n, _ in light.named_parameters()]
+            arrays.update(("grad_" + n, gr) for n, gr in zip(names, grads))
+        dump_outputs(args.dump_outputs, arrays, P, H, W)
 
     # multi-rank: the COMPLETE training iterations under data parallelism, on every rank (their collectives need all of
     # them): Stage2Trainer.data_parallel() reduces the stage-2 gradient set, Stage1Trainer.data_parallel() every gradient
     # (what GIGS_BENCH_REDUCE=all measures for the metric's step) -- each with its own `comm`
     dp_extras = {}
-    if use_dist and not inference and (not args.no_extras or args.iteration):
+    if use_dist and not inference and ((args.full and not args.no_extras) or args.iteration):
         import train_iteration
         for p_ in flat_params:
             p_.grad = None
@@ -610,8 +685,8 @@ def run(args):
             dp_extras["iteration_stage1"] = train_iteration.bench_stage1_iteration(sc, gi, args.sh_degree, cams_t, gt_image, **kw)
         except Exception as ex:  # noqa: BLE001
             dp_extras["iteration_stage1"] = {"error": repr(ex)[:400]}
-    line = None
-    if rank == 0:
+    V = R = kernels = roofline = cpu = parity_rep = None
+    if rank == 0 and args.full:
         # V (visible), R (instances) averaged over the views of the timed region (outside it)
         import diff_gaussian_rasterization as dgr
         Vs, Rs = [], []
@@ -699,7 +774,6 @@ def run(args):
                                     "run's live duration, against 1024 SIMDs x 2.4 GHz); its HBM roofline (algorithmic bytes / duration: "
                                     "hbm_*) does not: the z-plane lookups are served by L2 / L1 (the plane is 2.5 MB) and most are "
                                     "skipped by the certification table in LDS (DESIGN.md section 5)")
-        cpu = parity_rep = None
         vi0 = args.warmup % n_views
         if not args.no_cpu_baseline and world == 1:
             if inference:
@@ -708,8 +782,10 @@ def run(args):
             else:
                 cpu, parity_rep = cpu_baseline_and_parity(sc, cams[vi0], gi, args.sh_degree, light, brdf_lut, stepper,
                                                           args.config.upper(), single_thread_res=args.cpu_single_res)
+    line = None
+    if rank == 0:
         extras = {}
-        if (not args.no_extras or args.iteration) and world == 1 and not inference:
+        if ((args.full and not args.no_extras) or args.iteration) and world == 1 and not inference:
             extras = secondary_steps(args, g, light, brdf_lut, gi, cams_t, view_dirs, gt_image, n_views, sc)
         what = ("relight renders/sec (inference, PBR+indirect, mips built once)" if inference
                 else "train-step renders/sec (fwd+bwd, G-buffer+indirect)")
@@ -722,7 +798,8 @@ def run(args):
             "config": {"workload": "%s (%s): %dk %s Gaussians, %dx%d, SH deg %d, GI step=%d start=%d delta=%g"
                                    % (args.config.upper(), cname, P // 1000, "trained (--scene)" if args.scene else "surface",
                                       W, H, args.sh_degree, gi["step"], gi["start"], gi["delta"]),
-                       "P": P, "V": round(V), "R": round(R), "N": N, "M": M, "shade": shade, "hip_graphs": args.graphs, "fused_glue": args.fused,
+                       "P": P, **({"V": round(V), "R": round(R)} if V is not None else {}), "N": H * W, "M": M, "shade": shade,
+                       "hip_graphs": args.graphs, "fused_glue": args.fused,
                        "gi_march": gigs_lib.GI_MARCHES[gigs_lib.current().option("gi_march")],
                        "rasterizer": ("one hipGraph per view" if inference and args.graphs == "on" else
                                       "hipGraph (GIGS_RASTER_GRAPH=1)" if os.environ.get("GIGS_RASTER_GRAPH", "0") == "1"
@@ -735,10 +812,11 @@ def run(args):
                                       else "eager launches, asynchronous binning (no host read-back)"),
                        "parallelism": "view-parallel dp%d, 1 view/GPU/step, flat grad all-reduce%s"
                                       % (world, " of the stage-2 non-zero gradient set" if reduce_only else " of every gradient")},
-            "ranks_seen": ranks_seen, "comm": comm, "repeats": repeats,
-            "roofline": roofline, "roofline_light": None if inference else pmc_light_roofline(), "cpu_baseline": cpu,
-            "kernels": kernels,
+            "ranks_seen": ranks_seen,
         }
+        if args.full:
+            line.update({"comm": comm, "repeats": repeats, "roofline": roofline,
+                         "roofline_light": None if inference else pmc_light_roofline(), "cpu_baseline": cpu, "kernels": kernels})
         line.update(extras)
         line.update(dp_extras)
         if parity_rep is not None:
@@ -790,7 +868,7 @@ def secondary_steps(args, g, light, brdf_lut, gi, cams_t, view_dirs, gt_image, n
         for p in leaves:
             p.grad = None
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         _drop_in_and_full_grad(args, g, light, brdf_lut, gi, cams_t, view_dirs, gt_image, n_views, out, clear)
     clear()
     try:

@@ -7,7 +7,7 @@ mkdir -p $O
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fullsize.py -q -m gpu -k "dense or binning_paths or c4_forward or identical_depths or async_binning" > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
 for b in 1 2 4 8 16; do
-  GIGS_BIN_BANDS=$b timeout -k 10 200 python bench.py --config c4 --steps 20 --warmup 5 --no-cpu-baseline --no-extras --repeats 3 > $O/bench_c4_bands$b.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  GIGS_BIN_BANDS=$b timeout -k 10 200 python bench.py --full --config c4 --steps 20 --warmup 5 --no-cpu-baseline --no-extras --repeats 3 > $O/bench_c4_bands$b.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   python -c "
 import json
 d=json.loads(open('$O/bench_c4_bands$b.json').read().strip().splitlines()[-1])

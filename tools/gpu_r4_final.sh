@@ -16,12 +16,12 @@ f=$(find $O/prof_c4 -name "*kernel_trace.csv" | head -1)
 python tools/step_timeline.py $f --all-queues --min-us 0 --step 5 > $O/c4_step_timeline.txt
 rm -rf $O/prof_c2 $O/prof_c4
 echo "profiles done"
-python bench.py > $O/bench_c2.json 2> $O/bench.err
+python bench.py --full > $O/bench_c2.json 2> $O/bench.err
 echo "bench c2 done"
-python bench.py --config c3 --steps 30 --warmup 5 > $O/bench_c3.json 2>> $O/bench.err
-python bench.py --config c4 --steps 20 --warmup 5 --cpu-single-res 0 > $O/bench_c4.json 2>> $O/bench.err
+python bench.py --full --config c3 --steps 30 --warmup 5 > $O/bench_c3.json 2>> $O/bench.err
+python bench.py --full --config c4 --steps 20 --warmup 5 --cpu-single-res 0 > $O/bench_c4.json 2>> $O/bench.err
 echo "bench c4 done"
-python bench.py --start 64 --no-cpu-baseline --no-extras > $O/bench_c2_start64_readme_setting.json 2>> $O/bench.err
+python bench.py --full --start 64 --no-cpu-baseline --no-extras > $O/bench_c2_start64_readme_setting.json 2>> $O/bench.err
 for f in c2 c3 c4 c2_start64_readme_setting; do python -c "
 import json
 d=json.loads(open('$O/bench_$f.json').read().strip().splitlines()[-1])

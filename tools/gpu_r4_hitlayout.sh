@@ -9,7 +9,7 @@ for rep in 1 2; do
 for lib in "" gpurun_in/lib_old.so; do
   if [ -n "$lib" ]; then export GIGS_LIB=$GRAFT_REPO_ROOT/$lib; else unset GIGS_LIB; fi
   for cfg in c4 c2; do
-  python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-extras --repeats 3 > $O/bench_cmp.json 2>/dev/null
+  python bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-extras --repeats 3 > $O/bench_cmp.json 2>/dev/null
   python -c "
 import json
 d=json.loads(open('$O/bench_cmp.json').read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ python -m pytest tests/test_gpu_pbr.py tests/test_gpu_training.py tests/test_gpu
 tail -2 $O/pytest.log
 for rep in 1 2; do
 for pf in 0 1; do
-  GIGS_LIGHT_PREFETCH=$pf python bench.py --fused off --graphs off --no-cpu-baseline --no-extras --steps 40 --warmup 10 > $O/b.json 2>/dev/null
+  GIGS_LIGHT_PREFETCH=$pf python bench.py --full --fused off --graphs off --no-cpu-baseline --no-extras --steps 40 --warmup 10 > $O/b.json 2>/dev/null
   python -c "
 import json
 d=json.loads(open('$O/b.json').read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_contract.py tests/test_gpu_tra
 tail -2 $O/pytest.log
 for sp in 0 1; do
   for c in c4 c2; do
-  GIGS_SPLIT_SH=$sp timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline > $O/b.json 2> $O/b.err || { tail -30 $O/b.err; exit 1; }
+  GIGS_SPLIT_SH=$sp timeout -k 10 300 python bench.py --full --config $c --steps 20 --warmup 5 --no-cpu-baseline > $O/b.json 2> $O/b.err || { tail -30 $O/b.err; exit 1; }
   python -c "
 import json
 d=json.loads(open('$O/b.json').read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ mkdir -p $O
 for rep in 1 2; do
 for sp in 0 1; do
   for c in c4 c2; do
-  GIGS_SHADE_BWD_SPLIT=$sp timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/b.json 2> $O/b.err || { tail -30 $O/b.err; exit 1; }
+  GIGS_SHADE_BWD_SPLIT=$sp timeout -k 10 300 python bench.py --full --config $c --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/b.json 2> $O/b.err || { tail -30 $O/b.err; exit 1; }
   python -c "
 import json
 d=json.loads(open('$O/b.json').read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ O=gpurun_out/r4t
 mkdir -p $O
 for rep in 1 2 3; do
 for tn in 0 1; do
-  GIGS_GB_TAIL_NODE=$tn python bench.py --config c4 --steps 20 --warmup 5 --no-cpu-baseline --no-extras --repeats 5 > $O/b.json 2>/dev/null
+  GIGS_GB_TAIL_NODE=$tn python bench.py --full --config c4 --steps 20 --warmup 5 --no-cpu-baseline --no-extras --repeats 5 > $O/b.json 2>/dev/null
   python -c "
 import json
 d=json.loads(open('$O/b.json').read().strip().splitlines()[-1])
@@ -16,7 +16,7 @@ print('c4 tail node $tn:', d['value'], d['repeats']['ms_per_step_median'], d['re
 done
 done
 for tn in 0 1; do
-  GIGS_GB_TAIL_NODE=$tn python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-extras --repeats 5 > $O/b.json 2>/dev/null
+  GIGS_GB_TAIL_NODE=$tn python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-extras --repeats 5 > $O/b.json 2>/dev/null
   python -c "
 import json
 d=json.loads(open('$O/b.json').read().strip().splitlines()[-1])
