@@ -29,8 +29,24 @@ __device__ __forceinline__ v3 normalize_where(v3 v) {
   return {v.x / d, v.y / d, v.z / d};
 }
 
-// per-channel 3x3 median of normalize_where(src) with zero padding; NaN window -> NaN (as median3x3_kernel)
-__device__ __forceinline__ v3 median_of_normalized(const float* __restrict__ src, int H, int W, int y, int x) {
+// opacity of gaussian_renderer/__init__.py:160-169 (pad_normal): < 0.004 -> 0, then > 1 - 0.004 -> 1 (fp32 thresholds,
+// as torch compares an fp32 tensor with a Python scalar)
+__device__ __forceinline__ float pad_opacity(float a) {
+  a = a < 0.004f ? 0.0f : a;
+  return a > (float)(1.0 - 0.004) ? 1.0f : a;
+}
+
+// pad_normal's blend over the background normal (0, 0, 1): n * a + (1 - a) * bg, per channel as torch rounds it
+__device__ __forceinline__ v3 pad_normal_over_bg(v3 n, float a) {
+  const float r = 1.0f - a;
+  return {n.x * a + r * 0.0f, n.y * a + r * 0.0f, n.z * a + r * 1.0f};
+}
+
+// per-channel 3x3 median of normalize_where(src) with zero padding; NaN window -> NaN (as median3x3_kernel).
+// opacity != NULL: every tap is first blended over the background normal (pad_normal); padding taps stay zero.
+template <bool kPad>
+__device__ __forceinline__ v3 median_of_normalized(const float* __restrict__ src, const float* __restrict__ opacity,
+                                                   int H, int W, int y, int x) {
   const size_t HW = (size_t)H * W;
   float t0[9], t1[9], t2[9];
   bool n0 = false, n1 = false, n2 = false;
@@ -43,7 +59,9 @@ __device__ __forceinline__ v3 median_of_normalized(const float* __restrict__ src
       v3 v = {0.0f, 0.0f, 0.0f};
       if (!(yy < 0 || yy >= H || xx < 0 || xx >= W)) {
         const size_t q = (size_t)yy * W + xx;
-        v = normalize_where({src[q], src[HW + q], src[2 * HW + q]});
+        v = {src[q], src[HW + q], src[2 * HW + q]};
+        if (kPad) v = pad_normal_over_bg(v, pad_opacity(opacity[q]));
+        v = normalize_where(v);
       }
       t0[k] = v.x; t1[k] = v.y; t2[k] = v.z;
       n0 |= v.x != v.x; n1 |= v.y != v.y; n2 |= v.z != v.z;
@@ -52,10 +70,22 @@ __device__ __forceinline__ v3 median_of_normalized(const float* __restrict__ src
   return {n0 ? nan : median9(t0), n1 ? nan : median9(t1), n2 ? nan : median9(t2)};
 }
 
+// Optional outputs (pad_normal, render.py:212): kPad blends normal_map over the background normal by the thresholded
+// opacity before it is normalised and filtered (the mask still comes from the unpadded map) and also writes
+// normal_world (the filtered world-space map), the padded + normalised normal_map_from_depth and the opacity itself.
+struct GbufferPad {
+  const float* opacity;
+  const float* nfd;
+  float* normal_world;
+  float* nfd_out;
+  float* opacity_out;
+};
+
+template <bool kPad>
 __global__ void __launch_bounds__(256)
 gbuffer_post_kernel(int H, int W, const float* __restrict__ normal_map, const float* __restrict__ out_normal_view,
                     const float* __restrict__ vm, float* __restrict__ normals_view, uint8_t* __restrict__ mask_u8,
-                    float* __restrict__ mask_f, float* __restrict__ onv) {
+                    float* __restrict__ mask_f, float* __restrict__ onv, GbufferPad pad) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= W || y >= H) return;
@@ -63,13 +93,25 @@ gbuffer_post_kernel(int H, int W, const float* __restrict__ normal_map, const fl
   const bool mk = normal_map[p] != 0.0f && normal_map[HW + p] != 0.0f && normal_map[2 * HW + p] != 0.0f;
   if (mask_u8) mask_u8[p] = mk ? 1 : 0;
   if (mask_f) mask_f[p] = mk ? 1.0f : 0.0f;
-  const v3 n = median_of_normalized(normal_map, H, W, y, x);
+  const v3 n = median_of_normalized<kPad>(normal_map, pad.opacity, H, W, y, x);
   // -(n @ R), R = viewmatrix[:3, :3] of the row-major 4x4 tensor
   normals_view[p] = -(n.x * vm[0] + n.y * vm[4] + n.z * vm[8]);
   normals_view[HW + p] = -(n.x * vm[1] + n.y * vm[5] + n.z * vm[9]);
   normals_view[2 * HW + p] = -(n.x * vm[2] + n.y * vm[6] + n.z * vm[10]);
-  const v3 o = median_of_normalized(out_normal_view, H, W, y, x);
+  const v3 o = median_of_normalized<false>(out_normal_view, nullptr, H, W, y, x);
   onv[p] = o.x; onv[HW + p] = o.y; onv[2 * HW + p] = o.z;
+  if (kPad) {
+    if (pad.normal_world) { pad.normal_world[p] = n.x; pad.normal_world[HW + p] = n.y; pad.normal_world[2 * HW + p] = n.z; }
+    if (pad.opacity_out) pad.opacity_out[p] = pad_opacity(pad.opacity[p]);
+    if (pad.nfd_out) {
+      // mask_from_depth = (v == 0).all(0): v * (1 - m) + m * bg, then normalize_where
+      v3 d = {pad.nfd[p], pad.nfd[HW + p], pad.nfd[2 * HW + p]};
+      const float m = (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) ? 1.0f : 0.0f;
+      d = {d.x * (1.0f - m) + m * 0.0f, d.y * (1.0f - m) + m * 0.0f, d.z * (1.0f - m) + m * 1.0f};
+      d = normalize_where(d);
+      pad.nfd_out[p] = d.x; pad.nfd_out[HW + p] = d.y; pad.nfd_out[2 * HW + p] = d.z;
+    }
+  }
 }
 
 // ---- backward of the normal post-processing (stage 1: train.py:327-328 differentiates through
@@ -394,11 +436,29 @@ int gigs_gbuffer_post(int height, int width, const float* normal_map, const floa
       !out_normal_view_filtered)
     return gigs_internal_fail(GIGS_ERR_INVALID, "gbuffer_post: bad argument");
   void* tok; gigs_internal_stage_begin(18, stream, &tok);
-  hipLaunchKernelGGL(gigs::gbuffer_post_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0,
+  hipLaunchKernelGGL(gigs::gbuffer_post_kernel<false>, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, height, width, normal_map, out_normal_view, viewmatrix, normals_view,
-                     normal_mask, normal_mask_f, out_normal_view_filtered);
+                     normal_mask, normal_mask_f, out_normal_view_filtered, gigs::GbufferPad{});
   gigs_internal_stage_end(tok);
   if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "gbuffer_post: launch failed");
+  return 0;
+}
+
+int gigs_gbuffer_post_pad(int height, int width, const float* normal_map, const float* normal_map_from_depth,
+                          const float* opacity_map, const float* out_normal_view, const float* viewmatrix,
+                          uint8_t* normal_mask, float* normal_mask_f, float* normal_world, float* normals_view,
+                          float* out_normal_view_filtered, float* normal_map_from_depth_out, float* opacity_out,
+                          void* stream) {
+  if (height <= 0 || width <= 0 || !normal_map || !opacity_map || !out_normal_view || !viewmatrix || !normals_view ||
+      !out_normal_view_filtered || (normal_map_from_depth_out && !normal_map_from_depth))
+    return gigs_internal_fail(GIGS_ERR_INVALID, "gbuffer_post_pad: bad argument");
+  const gigs::GbufferPad pad{opacity_map, normal_map_from_depth, normal_world, normal_map_from_depth_out, opacity_out};
+  void* tok; gigs_internal_stage_begin(18, stream, &tok);
+  hipLaunchKernelGGL(gigs::gbuffer_post_kernel<true>, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, height, width, normal_map, out_normal_view, viewmatrix, normals_view,
+                     normal_mask, normal_mask_f, out_normal_view_filtered, pad);
+  gigs_internal_stage_end(tok);
+  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "gbuffer_post_pad: launch failed");
   return 0;
 }
 

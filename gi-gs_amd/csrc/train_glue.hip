@@ -28,7 +28,8 @@ constexpr int kSsimHalo = kSsimTile + 2 * kSsimR;  // 42
 struct SsimWindow { float w[2 * kSsimR + 1]; };
 
 // valid in every thread
-__device__ __forceinline__ float block_sum(float v, float* s_red) {
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T* s_red) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
   __syncthreads();
@@ -53,13 +54,18 @@ __device__ __forceinline__ void reduce_rows(const float* __restrict__ partials, 
 // ---- L1 + SSIM ------------------------------------------------------------------------------------------------
 // utils/loss_utils.py:72-98 (`_ssim`, zero-padded depthwise conv, C1 = 0.01^2, C2 = 0.03^2) and :19-20 (l1_loss);
 // combined as train.py:320.
+// kEval (gigs_image_metrics): the same ssim_map, plus the squared error of the channel and the masked squared error
+// with its element count, summed in double into four partials per workgroup (eval_d); no L1, no derivative planes.
+template <bool kEval>
 __global__ void __launch_bounds__(256)
 l1_ssim_fwd_kernel(int H, int W, const float* __restrict__ img, const float* __restrict__ gt, SsimWindow win,
                    float* __restrict__ d_mu1, float* __restrict__ d_e11, float* __restrict__ d_e12,
-                   float* __restrict__ partials) {
+                   float* __restrict__ partials, const uint8_t* __restrict__ mask, double* __restrict__ eval_d) {
   __shared__ float s_x[kSsimHalo][kSsimHalo + 1], s_y[kSsimHalo][kSsimHalo + 1];
   __shared__ float s_h[5][kSsimHalo][kSsimTile + 1];
   __shared__ float s_red[4];
+  __shared__ double s_red_d[4];
+  double e_ss = 0.0, e_se = 0.0, e_sem = 0.0, e_cnt = 0.0;
   const size_t plane = (size_t)blockIdx.z * H * W;
   const int x0 = blockIdx.x * kSsimTile - kSsimR, y0 = blockIdx.y * kSsimTile - kSsimR;
   {
@@ -129,6 +135,13 @@ l1_ssim_fwd_kernel(int H, int W, const float* __restrict__ img, const float* __r
       const float Cc = mu1_sq + mu2_sq + C1, D = sigma1_sq + sigma2_sq + C2;
       const float den = Cc * D;
       const float s = (A * B) / den;
+      if (kEval) {
+        const double d = (double)s_x[ty + kSsimR][tx + kSsimR] - (double)s_y[ty + kSsimR][tx + kSsimR];
+        e_ss += (double)s;
+        e_se += d * d;
+        if (mask && mask[(size_t)y * W + x]) { e_sem += d * d; e_cnt += 1.0; }
+        continue;
+      }
       ss += s;
       l1 += fabsf(s_x[ty + kSsimR][tx + kSsimR] - s_y[ty + kSsimR][tx + kSsimR]);
       if (d_mu1) {
@@ -139,6 +152,17 @@ l1_ssim_fwd_kernel(int H, int W, const float* __restrict__ img, const float* __r
         d_e12[q] = 2.0f * A / den;
       }
     }
+  }
+  if (kEval) {
+    e_ss = block_sum(e_ss, s_red_d);
+    e_se = block_sum(e_se, s_red_d);
+    e_sem = block_sum(e_sem, s_red_d);
+    e_cnt = block_sum(e_cnt, s_red_d);
+    if (threadIdx.x == 0) {
+      const size_t b = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+      eval_d[4 * b] = e_ss; eval_d[4 * b + 1] = e_se; eval_d[4 * b + 2] = e_sem; eval_d[4 * b + 3] = e_cnt;
+    }
+    return;
   }
   l1 = block_sum(l1, s_red);
   ss = block_sum(ss, s_red);
@@ -160,6 +184,103 @@ l1_ssim_finish_kernel(const float* __restrict__ partials, int nrows, float count
     out[0] = (1.0f - lambda) * l1 + lambda * (1.0f - ssim);
     out[1] = l1;
     out[2] = ssim;
+  }
+}
+
+// ---- per-view evaluation metrics (render.py:115-395 NVS, :596-631 albedo, normal_eval.py) -------------------------------
+// The record of one view goes to out + stride * (*slot) and *slot is incremented (slot == NULL: to out), so a replayed
+// graph fills successive records with no host synchronisation.  All sums are doubles added in a fixed order.
+__device__ __forceinline__ double* record_at(double* out, int* slot, int stride) {
+  return slot ? out + (size_t)stride * (size_t)(*slot) : out;
+}
+
+// record {mse_0 .. mse_{C-1}, mean_c psnr_c, mean ssim, masked mse, masked element count}; rows = workgroups per channel
+__global__ void __launch_bounds__(256)
+image_metrics_finish_kernel(const double* __restrict__ part, int C, int rows, double npix, int* slot,
+                            double* __restrict__ out) {
+  __shared__ double s_red[4];
+  double* rec = record_at(out, slot, C + 4);
+  double psnr = 0.0, ss = 0.0, sem = 0.0, cnt = 0.0;
+  for (int c = 0; c < C; c++) {
+    double a = 0.0, b = 0.0, m = 0.0, n = 0.0;
+    for (int r = threadIdx.x; r < rows; r += 256) {
+      const double* q = part + 4 * ((size_t)c * rows + r);
+      a += q[0]; b += q[1]; m += q[2]; n += q[3];
+    }
+    a = block_sum(a, s_red);
+    b = block_sum(b, s_red);
+    m = block_sum(m, s_red);
+    n = block_sum(n, s_red);
+    const double mse = b / npix;
+    ss += a; sem += m; cnt += n;
+    psnr += 20.0 * log10(1.0 / sqrt(mse));  // utils/image_utils.py:31-33
+    if (threadIdx.x == 0) rec[c] = mse;
+  }
+  if (threadIdx.x == 0) {
+    rec[C] = psnr / C;
+    rec[C + 1] = ss / (npix * C);
+    rec[C + 2] = sem / cnt;  // ((a - b) ** 2)[mask].mean(): NaN for an empty mask, as torch's mean of nothing
+    rec[C + 3] = cnt;
+    if (slot) *slot += 1;
+  }
+}
+
+// normal_eval.py:11-18 (get_mae) on what render.py saves and normal_eval.py reads back, per pixel in double:
+//   gt   = (rgba[:3] / 255 - 0.5) * 2 blended with a = rgba[-1] / 255 over (0, 0, 1), then normalised;
+//   pred = the saved plane as torchvision's save_image rounds it (uint8(clamp(x * 255 + 0.5, 0, 255)) in fp32),
+//          / 255, (x - 0.5) * 2, (128, 128, 255) -> (0, 0, 1), then normalised;
+//   sum of arccos(clip(<gt, pred>, -1, 1)) * 180 / pi and the pixel count.  A zero vector normalises to NaN, as numpy.
+__device__ __forceinline__ unsigned png8(float x) {
+  float v = x * 255.0f + 0.5f;
+  v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
+  return v == v ? (unsigned)v : 0u;
+}
+
+__global__ void __launch_bounds__(256)
+normal_angular_error_kernel(int HW, const float* __restrict__ pred, const uint8_t* __restrict__ gt, int gt_channels,
+                            double* __restrict__ part) {
+  __shared__ double s_red[4];
+  double acc = 0.0;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+    const uint8_t* g = gt + (size_t)p * gt_channels;
+    const double a = g[gt_channels - 1] / 255.0;
+    double n[3];
+    for (int c = 0; c < 3; c++) {
+      const double bg = c == 2 ? 1.0 : 0.0;
+      n[c] = (g[c] / 255.0 - 0.5) * 2.0 * a + bg * (1.0 - a);
+    }
+    const double ng = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    unsigned u[3];
+    for (int c = 0; c < 3; c++) u[c] = png8(pred[(size_t)c * HW + p]);
+    double m[3];
+    if (u[0] == 128u && u[1] == 128u && u[2] == 255u) {
+      m[0] = 0.0; m[1] = 0.0; m[2] = 1.0;
+    } else {
+      for (int c = 0; c < 3; c++) m[c] = (u[c] / 255.0 - 0.5) * 2.0;
+    }
+    const double nm = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+    double d = (n[0] / ng) * (m[0] / nm) + (n[1] / ng) * (m[1] / nm);
+    d = d + (n[2] / ng) * (m[2] / nm);
+    d = d < -1.0 ? -1.0 : (d > 1.0 ? 1.0 : d);  // keeps NaN, as np.clip
+    acc += acos(d) * 180.0 / 3.141592653589793;
+  }
+  acc = block_sum(acc, s_red);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// record {sum of angles in degrees, pixel count}
+__global__ void __launch_bounds__(256)
+normal_angular_error_finish_kernel(const double* __restrict__ part, int rows, double npix, int* slot,
+                                   double* __restrict__ out) {
+  __shared__ double s_red[4];
+  double* rec = record_at(out, slot, 2);
+  double a = 0.0;
+  for (int r = threadIdx.x; r < rows; r += 256) a += part[r];
+  a = block_sum(a, s_red);
+  if (threadIdx.x == 0) {
+    rec[0] = a;
+    rec[1] = npix;
+    if (slot) *slot += 1;
   }
 }
 
@@ -713,6 +834,10 @@ static SsimWindow make_window() {
 static inline unsigned ssim_blocks(int H, int W) {
   return (unsigned)(((H + kSsimTile - 1) / kSsimTile) * ((W + kSsimTile - 1) / kSsimTile));
 }
+static inline unsigned mae_blocks(size_t HW) {
+  const size_t b = (HW + 255) / 256;
+  return (unsigned)(b < 1024 ? b : 1024);
+}
 static inline unsigned stream_blocks(size_t HW) {
   const size_t b = (HW + 255) / 256;
   return (unsigned)(b < 2048 ? b : 2048);
@@ -744,12 +869,54 @@ int gigs_l1_ssim_fwd(int channels, int height, int width, const float* image, co
   void* tok; gigs_internal_stage_begin(21, stream, &tok);
   const dim3 grid((width + gigs::kSsimTile - 1) / gigs::kSsimTile, (height + gigs::kSsimTile - 1) / gigs::kSsimTile,
                   channels);
-  hipLaunchKernelGGL(gigs::l1_ssim_fwd_kernel, grid, dim3(256), 0, s, height, width, image, gt, gigs::make_window(),
-                     d_mu1, d_e11, d_e12, scratch);
+  hipLaunchKernelGGL(gigs::l1_ssim_fwd_kernel<false>, grid, dim3(256), 0, s, height, width, image, gt,
+                     gigs::make_window(), d_mu1, d_e11, d_e12, scratch, nullptr, nullptr);
   hipLaunchKernelGGL(gigs::l1_ssim_finish_kernel, dim3(1), dim3(256), 0, s, scratch, (int)(grid.x * grid.y * grid.z),
                      (float)channels * (float)height * (float)width, lambda_dssim, out3);
   gigs_internal_stage_end(tok);
   if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "l1_ssim_fwd: launch failed");
+  return 0;
+}
+
+size_t gigs_image_metrics_scratch_bytes(int channels, int height, int width) {
+  if (channels <= 0 || height <= 0 || width <= 0) return 0;
+  const size_t ssim = 4 * (size_t)channels * gigs::ssim_blocks(height, width);
+  const size_t mae = gigs::mae_blocks((size_t)height * width);
+  return (ssim > mae ? ssim : mae) * sizeof(double);
+}
+
+int gigs_image_metrics(int channels, int height, int width, const float* pred, const float* gt, const uint8_t* mask,
+                       void* scratch, int* slot, double* out, void* stream) {
+  if (channels <= 0 || height <= 0 || width <= 0 || !pred || !gt || !scratch || !out)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "image_metrics: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((width + gigs::kSsimTile - 1) / gigs::kSsimTile, (height + gigs::kSsimTile - 1) / gigs::kSsimTile,
+                  channels);
+  void* tok; gigs_internal_stage_begin(21, stream, &tok);
+  hipLaunchKernelGGL(gigs::l1_ssim_fwd_kernel<true>, grid, dim3(256), 0, s, height, width, pred, gt, gigs::make_window(),
+                     nullptr, nullptr, nullptr, nullptr, mask, (double*)scratch);
+  hipLaunchKernelGGL(gigs::image_metrics_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)scratch, channels,
+                     (int)(grid.x * grid.y), (double)height * (double)width, slot, out);
+  gigs_internal_stage_end(tok);
+  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "image_metrics: launch failed");
+  return 0;
+}
+
+int gigs_normal_angular_error(int height, int width, const float* pred, const uint8_t* gt, int gt_channels,
+                              void* scratch, int* slot, double* out, void* stream) {
+  if (height <= 0 || width <= 0 || !pred || !gt || (gt_channels != 3 && gt_channels != 4) || !scratch || !out)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "normal_angular_error: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t HW = (size_t)height * width;
+  if (HW > 0x7fffffff) return gigs_internal_fail(GIGS_ERR_INVALID, "normal_angular_error: image too large");
+  const unsigned blocks = gigs::mae_blocks(HW);
+  void* tok; gigs_internal_stage_begin(21, stream, &tok);
+  hipLaunchKernelGGL(gigs::normal_angular_error_kernel, dim3(blocks), dim3(256), 0, s, (int)HW, pred, gt, gt_channels,
+                     (double*)scratch);
+  hipLaunchKernelGGL(gigs::normal_angular_error_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)scratch,
+                     (int)blocks, (double)HW, slot, out);
+  gigs_internal_stage_end(tok);
+  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "normal_angular_error: launch failed");
   return 0;
 }
 

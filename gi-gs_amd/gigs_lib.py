@@ -92,6 +92,7 @@ SIGNATURES = {
                                C.POINTER(C.c_int), _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f,
                                C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     "gigs_gbuffer_post": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_gbuffer_post_pad": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_gbuffer_post_bwd": (_i, [_i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_normalize_mask": (_i, [_i, _i, _f, _f, _f, C.c_void_p]),
     "gigs_nonzero_mask": (_i, [_i, _i, _f, _f, C.c_void_p]),
@@ -106,6 +107,9 @@ SIGNATURES = {
     "gigs_loss_scratch_floats": (C.c_size_t, [_i, _i, _i]),
     "gigs_l1_ssim_fwd": (_i, [_i, _i, _i, _f, _f, C.c_float, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_l1_ssim_bwd": (_i, [_i, _i, _i, _f, _f, C.c_float, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_image_metrics_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
+    "gigs_image_metrics": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_normal_angular_error": (_i, [_i, _i, _f, _f, _i, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_fwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_bwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_masked_l1_fwd": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),

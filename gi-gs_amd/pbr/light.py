@@ -1,10 +1,13 @@
-"""CubemapLight with the reference's interface (pbr/light.py:84-207); mip chain and GGX
-pre-filter run in libgigs_hip.so.  Image I/O (cv2) parts of the reference class are out of scope."""
+"""CubemapLight with the reference's interface (pbr/light.py:84-210); mip chain and GGX
+pre-filter run in libgigs_hip.so.  export_envmap samples the base map through pbr.texture.cube_texture; its file
+write needs cv2, imported only when a filename is given.  load_envmap and split_envmap_loss (cv2 image I/O) are out
+of scope."""
 from __future__ import annotations
 
 import os
 import threading
-from typing import Optional
+import math
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
@@ -132,6 +135,32 @@ class CubemapLight(nn.Module):
 
     def xfm(self, mtx) -> None:
         self.mtx = mtx
+
+    def export_envmap(self, filename: Optional[str] = None, res: List[int] = [512, 1024],
+                      return_img: bool = False) -> Optional[torch.Tensor]:
+        """pbr/light.py:172-210: the base cube map as a lat-long panorama [res[0], res[1], 3], differentiable w.r.t.
+        `base`; returned with return_img=True, else written to `filename` with cv2 (BGR, clamped at 0)."""
+        from .texture import cube_texture
+        if not return_img:
+            try:
+                import cv2
+            except ImportError as ex:
+                raise ImportError("CubemapLight.export_envmap(filename=...) writes the image with cv2 (opencv-python), "
+                                  "which is not installed; use return_img=True") from ex
+        dev = self.base.device
+        gy, gx = torch.meshgrid(
+            torch.linspace(0.0 + 1.0 / res[0], 1.0 - 1.0 / res[0], res[0], device=dev),
+            torch.linspace(-1.0 + 1.0 / res[1], 1.0 - 1.0 / res[1], res[1], device=dev),
+            indexing="ij",
+        )
+        sintheta, costheta = torch.sin(gy * math.pi), torch.cos(gy * math.pi)
+        sinphi, cosphi = torch.sin(gx * math.pi), torch.cos(gx * math.pi)
+        reflvec = torch.stack((sintheta * sinphi, costheta, -sintheta * cosphi), dim=-1)  # [H, W, 3]
+        color = cube_texture(self.base, reflvec.contiguous())  # [H, W, 3]
+        if return_img:
+            return color
+        cv2.imwrite(filename, color.detach().clamp(min=0.0).cpu().numpy()[..., ::-1])
+        return None
 
     def clamp_(self, min: Optional[float] = None, max: Optional[float] = None) -> None:
         self.base.clamp_(min, max)

@@ -98,10 +98,24 @@ class Relighter:
 
     # -- the fused sequence replayed from one hipGraph --------------------------------------------------------------
     def _graphed(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
-        from diff_gaussian_rasterization import AsyncBinning, BinningOverflow
         names = ("render_rgb", "render_direct", "IRR", "occlusion", "depth_map", "normal_map", "normal_mask", "radii")
+
+        def core(c, vd):
+            o = self._fused(c, g, vd, None, albedo_ratio)
+            return tuple(o[n] for n in names)
+
+        out = self._replay(cam, g, (view_dirs,), core, names, None if albedo_ratio is None else tuple(albedo_ratio))
+        if alpha_mask is not None:
+            out["render_rgb"] = out["render_rgb"] * alpha_mask
+        return out
+
+    def _replay(self, cam, g, inputs, core, names, key_extra=None, on_capture=None):
+        """Replay the view graph of core(cam, *inputs) -> tuple named `names`, capturing it first (under asynchronous
+        binning) when the image, the field of view, the Gaussian tensors or key_extra changed; the camera pose and
+        `inputs` are the graph's inputs.  on_capture() runs after every capture (the warm-up runs are real runs)."""
+        from diff_gaussian_rasterization import AsyncBinning, BinningOverflow
         key = (int(cam["image_height"]), int(cam["image_width"]), float(cam["tanfovx"]), float(cam["tanfovy"]),
-               tuple(sorted((k, v.data_ptr()) for k, v in g.items())), None if albedo_ratio is None else tuple(albedo_ratio))
+               tuple(sorted((k, v.data_ptr()) for k, v in g.items())), key_extra)
         for _ in range(4):
             if self._graph is None or self._graph_key != key:
                 if self._capacity <= 0:
@@ -114,25 +128,24 @@ class Relighter:
                 self._bin = AsyncBinning(self._capacity, g["means3D"].device)
                 scalars = {k: v for k, v in cam.items() if not isinstance(v, torch.Tensor)}
 
-                def core(viewmatrix, projmatrix, campos, vd):
-                    c = dict(scalars, viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos)
-                    o = self._fused(c, g, vd, None, albedo_ratio)
-                    return tuple(o[n] for n in names)
+                def pose_core(viewmatrix, projmatrix, campos, *rest):
+                    return core(dict(scalars, viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos), *rest)
 
                 with self._bin:
-                    self._graph = pipeline._graphed_inference(core, (cam["viewmatrix"], cam["projmatrix"], cam["campos"], view_dirs))
+                    self._graph = pipeline._graphed_inference(pose_core, (cam["viewmatrix"], cam["projmatrix"],
+                                                                          cam["campos"], *inputs))
                 self._graph_key = key
-            out = dict(zip(names, self._graph(cam["viewmatrix"], cam["projmatrix"], cam["campos"], view_dirs)))
+                if on_capture is not None:
+                    on_capture()
+            out = dict(zip(names, self._graph(cam["viewmatrix"], cam["projmatrix"], cam["campos"], *inputs)))
             self._bin.snapshot()
-            if alpha_mask is not None:
-                out["render_rgb"] = out["render_rgb"] * alpha_mask
             try:
                 out["num_rendered"] = self._bin.check()
                 return out
             except BinningOverflow as ex:
                 self._capacity = -(-int(1.5 * ex.needed) // 65536) * 65536
                 self.close()
-        raise RuntimeError("Relighter: the binning capacity kept overflowing")
+        raise RuntimeError(f"{type(self).__name__}: the binning capacity kept overflowing")
 
     def close(self) -> None:
         """Release the view graph with the device idle before and after (see pipeline.WholeStepGraph._drop_graphs)."""
@@ -179,9 +192,8 @@ class Relighter:
     # -- the same arithmetic as five launches behind the rasterizer ----------------------------------------------
     def _fused(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
         dev = g["means3D"].device
-        gi = self.gi
         background = torch.zeros(3, device=dev)
-        (out, _, st) = pipeline.rasterize(cam, g, self.sh_degree, background, gi, inference=True, derive_normal=True)
+        (out, _, st) = pipeline.rasterize(cam, g, self.sh_degree, background, self.gi, inference=True, derive_normal=True)
         (_, radii, _, depth_map, _, normal_map, occlusion, albedo_map, roughness_map, metallic_map, out_normal_view,
          depth_pos) = out
         H, W = cam["image_height"], cam["image_width"]
@@ -189,35 +201,55 @@ class Relighter:
         normals_view, onv = new("normals_view", 3, H, W), new("onv", 3, H, W)
         mask_u8 = self._buf("mask_u8", (H, W), torch.uint8, dev)
         mask_f = new("mask_f", 1, H, W)
-        render_direct, linear_rgb = torch.empty((3, H, W), device=dev), new("linear_rgb", 3, H, W)
-        render_rgb, acc, loss = torch.empty((3, H, W), device=dev), new("acc", 4 + 4 * 256), new("loss", 1)
         p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         albedo_shade = albedo_map
         if albedo_ratio is not None:
             albedo_shade = albedo_map * torch.as_tensor(albedo_ratio, dtype=torch.float32, device=dev)[:, None, None]
-        light = self.light
-        spec = [s.contiguous() for s in light.specular]
-        spec_ptr = _ptr_array(spec)
-        spec_res = (C.c_int * len(spec))(*[int(s.shape[1]) for s in spec])
-        lut = self.brdf_lut
-        ext = gigs_lib.ShadeExt(planar=1, rough_scale=1.0, rough_bias=0.0, out_linear=p(linear_rgb))
         vm = st.viewmatrix.contiguous().float()
-        vd = view_dirs.contiguous().float()
         with torch.cuda.device(dev):
             s = torch.cuda.current_stream().cuda_stream
             gigs_lib.check(_lib.gigs_gbuffer_post(H, W, p(normal_map), p(out_normal_view), p(vm), p(normals_view), p(mask_u8),
                                                   p(mask_f), p(onv), s), "gbuffer_post")
-            gigs_lib.check(_lib.gigs_shade_fwd_ex(
-                gigs_lib.ctx_ptr(), H, W, p(normals_view), p(vd), p(albedo_shade), p(roughness_map), p(mask_u8), p(occlusion),
-                p(metallic_map) if self.metallic else None, None, p(light.diffuse), int(light.diffuse.shape[1]), len(spec),
-                spec_ptr, spec_res, p(lut), int(lut.shape[-2]), int(lut.shape[-3]), int(self.tone), int(self.gamma),
-                p(render_direct), None, None, None, C.addressof(ext), s), "shade_fwd_ex")
             if self.metallic:
                 F0 = torch.full_like(albedo_map, 0.04)
                 metallic_in = torch.zeros_like(roughness_map)
             else:
                 F0 = torch.addcmul(torch.full_like(albedo_map, (1.0 - float(self.metallic)) * 0.04), albedo_map, metallic_map)
                 metallic_in = metallic_map
+            render_direct, IRR, render_rgb = self._shade_ssr(cam, view_dirs, normals_view, mask_u8, mask_f, onv, depth_pos,
+                                                             albedo_shade, albedo_map, roughness_map, metallic_map,
+                                                             occlusion, F0, metallic_in)
+        if alpha_mask is not None:
+            render_rgb = render_rgb * alpha_mask
+        return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=occlusion, depth_map=depth_map,
+                    normal_map=normals_view, normal_mask=mask_u8.bool()[None], radii=radii)
+
+    def _shade_ssr(self, cam, view_dirs, normals_view, mask_u8, mask_f, onv, depth_pos, albedo_shade, albedo_map,
+                   roughness_map, metallic_map, occlusion, F0, metallic_in):
+        """The launches after the G-buffer post: shade (planar, with the sRGB->linear epilogue), SSR with the caller's
+        F0 / metallic planes, then render_rgb = render_direct + median3x3(linear_to_srgb(IRR)).  Shared with
+        evaluate.NovelViewEvaluator, whose G-buffer post and F0 branch differ."""
+        dev = albedo_map.device
+        gi = self.gi
+        H, W = cam["image_height"], cam["image_width"]
+        new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
+        render_direct, linear_rgb = torch.empty((3, H, W), device=dev), new("linear_rgb", 3, H, W)
+        render_rgb, acc, loss = torch.empty((3, H, W), device=dev), new("acc", 4 + 4 * 256), new("loss", 1)
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        light = self.light
+        spec = [s.contiguous() for s in light.specular]
+        spec_ptr = _ptr_array(spec)
+        spec_res = (C.c_int * len(spec))(*[int(s.shape[1]) for s in spec])
+        lut = self.brdf_lut
+        ext = gigs_lib.ShadeExt(planar=1, rough_scale=1.0, rough_bias=0.0, out_linear=p(linear_rgb))
+        vd = view_dirs.contiguous().float()
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream().cuda_stream
+            gigs_lib.check(_lib.gigs_shade_fwd_ex(
+                gigs_lib.ctx_ptr(), H, W, p(normals_view), p(vd), p(albedo_shade), p(roughness_map), p(mask_u8), p(occlusion),
+                p(metallic_map) if self.metallic else None, None, p(light.diffuse), int(light.diffuse.shape[1]), len(spec),
+                spec_ptr, spec_res, p(lut), int(lut.shape[-2]), int(lut.shape[-3]), int(self.tone), int(self.gamma),
+                p(render_direct), None, None, None, C.addressof(ext), s), "shade_fwd_ex")
             IRR, _ = _ops.SSR(W, H, W / (2.0 * cam["tanfovx"]), H / (2.0 * cam["tanfovy"]), gi["radius"], gi["bias"],
                               gi["thick"], gi["delta"], gi["step"], gi["start"], onv, depth_pos, linear_rgb, albedo_map,
                               roughness_map, metallic_in, F0)
@@ -225,7 +257,4 @@ class Relighter:
             gigs_lib.check(_lib.gigs_stage2_loss_fwd(H, W, p(render_direct), p(IRR), p(render_direct), p(mask_f),
                                                      p(roughness_map), p(metallic_in), p(render_rgb), p(acc), p(loss), s),
                            "stage2_loss_fwd")
-        if alpha_mask is not None:
-            render_rgb = render_rgb * alpha_mask
-        return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=occlusion, depth_map=depth_map,
-                    normal_map=normals_view, normal_mask=mask_u8.bool()[None], radii=radii)
+        return render_direct, IRR, render_rgb

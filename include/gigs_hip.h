@@ -364,6 +364,18 @@ int gigs_shade_bwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
 int gigs_gbuffer_post(int height, int width, const float* normal_map, const float* out_normal_view,
                       const float* viewmatrix, float* normals_view, uint8_t* normal_mask, float* normal_mask_f,
                       float* out_normal_view_filtered, void* stream);
+/* gigs_gbuffer_post_pad = the same post-processing with pad_normal=True (gaussian_renderer/__init__.py:157-199, as
+ * render.py:212 calls it), one pass:
+ *   opacity_out = opacity_map with < 0.004 -> 0, then > 1 - 0.004 -> 1 (may be NULL);
+ *   normal_mask (u8 and/or f32, either may be NULL) from the UNPADDED normal_map;
+ *   normal_world = median3x3(normalize_where(normal_map * a + (1 - a) * (0,0,1))) with a the thresholded opacity (may be
+ *   NULL); normals_view = -(normal_world @ viewmatrix[:3,:3]); out_normal_view_filtered as gigs_gbuffer_post;
+ *   normal_map_from_depth_out = normalize_where(all-zero pixels -> (0,0,1)) of normal_map_from_depth (may be NULL). */
+int gigs_gbuffer_post_pad(int height, int width, const float* normal_map, const float* normal_map_from_depth,
+                          const float* opacity_map, const float* out_normal_view, const float* viewmatrix,
+                          uint8_t* normal_mask, float* normal_mask_f, float* normal_world, float* normals_view,
+                          float* out_normal_view_filtered, float* normal_map_from_depth_out, float* opacity_out,
+                          void* stream);
 /* Stage 1 differentiates through the normal post-processing (train.py:327-328 use render()'s normal_map):
  * gigs_gbuffer_post_bwd = gradient of gigs_gbuffer_post's normals_view w.r.t. normal_map (rotation, the median's tap
  *   selection -- first tap in row-major order equal to the median, as gigs_median3x3_backward --, normalize_where);
@@ -450,6 +462,23 @@ int gigs_l1_ssim_fwd(int channels, int height, int width, const float* image, co
 int gigs_l1_ssim_bwd(int channels, int height, int width, const float* image, const float* gt, float lambda_dssim,
                      const float* d_mu1, const float* d_e11, const float* d_e12, const float* g_loss, float* g_image,
                      void* stream);
+/* Per-view evaluation metrics (render.py's NVS loop and eval_brdf, normal_eval.py), reduced in double in a fixed order:
+ * the same record bit for bit on every run.  `scratch` holds gigs_image_metrics_scratch_bytes(C,H,W) bytes (enough for
+ * both entries with C = 3).  slot == NULL: the record goes to out; otherwise to out + stride * (*slot), and *slot (a
+ * device int) is incremented, so a replayed graph fills successive records without a host synchronisation.
+ * gigs_image_metrics: pred / gt [C,H,W]; record (stride C + 4) = {mse_c of utils/image_utils.py:31-33 per channel,
+ *   mean over c of 20 log10(1 / sqrt(mse_c)) (psnr(a, b).mean()), mean(ssim_map) (utils/loss_utils.py:55-98: the
+ *   ssim_map of gigs_l1_ssim_fwd), ((pred - gt) ** 2)[:, mask].mean() (render.py:601-603; mask u8 [H,W], NULL or empty:
+ *   NaN), the number of masked elements}.
+ * gigs_normal_angular_error: normal_eval.py:11-18 on the images render.py writes and normal_eval.py reads: pred [3,H,W]
+ *   is the float plane render.py saves ((normal + 1) / 2), rounded to 8 bits as torchvision's save_image rounds it;
+ *   gt [H,W,gt_channels] u8 is the ground-truth PNG (alpha = last channel, normal_eval.py:40).  Record (stride 2) =
+ *   {sum of arccos(clip(<gt, pred>, -1, 1)) * 180 / pi, pixel count}. */
+size_t gigs_image_metrics_scratch_bytes(int channels, int height, int width);
+int gigs_image_metrics(int channels, int height, int width, const float* pred, const float* gt, const uint8_t* mask,
+                       void* scratch, int* slot, double* out, void* stream);
+int gigs_normal_angular_error(int height, int width, const float* pred, const uint8_t* gt, int gt_channels,
+                              void* scratch, int* slot, double* out, void* stream);
 int gigs_tv_loss_fwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
                      const float* mask_f, float* scratch, float* loss, void* stream);
 int gigs_tv_loss_bwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
