@@ -262,20 +262,13 @@ class CubemapLight(nn.Module):
         n = len(specular)
         rough = [(idx / (n - 2)) * (self.MAX_ROUGHNESS - self.MIN_ROUGHNESS) + self.MIN_ROUGHNESS for idx in range(n - 1)] + [1.0]
         coarsest = diffuse_in if diffuse_in is not None else specular[-1]
-        diffuse_first = os.environ.get("GIGS_LIGHT_DIFFUSE_LAST", "1") != "1"
-        diffuse = None
-        if diffuse_first:
-            diffuse = diffuse_cubemap(coarsest)
         # the levels are independent: one launch filters them all (and one launch back-propagates them all)
         merged = specular_cubemap_levels(specular, rough, cutoff)
+        # created after the GGX node, the diffuse filter's backward runs BEFORE the GGX backward (autograd walks
+        # the later node first): 0.02 ms of short workgroups in front of the launch that floods every CU
+        diffuse = diffuse_cubemap(coarsest)
         if merged is not None:
-            if not diffuse_first:
-                # created after the GGX node, the diffuse filter's backward runs BEFORE the GGX backward (autograd walks
-                # the later node first): 0.02 ms of short workgroups in front of the launch that floods every CU
-                diffuse = diffuse_cubemap(coarsest)
             return merged, diffuse
-        if not diffuse_first:
-            diffuse = diffuse_cubemap(coarsest)
         for idx in range(n - 1):
             specular[idx] = specular_cubemap(specular[idx], rough[idx], cutoff)
         specular[-1] = specular_cubemap(specular[-1], 1.0, cutoff)

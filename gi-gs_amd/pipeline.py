@@ -12,6 +12,7 @@ plain torch elementwise ops on the GPU; nothing here touches the CPU oracle.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import weakref
@@ -217,30 +218,6 @@ def render(cam: Dict, g: Dict[str, torch.Tensor], sh_degree: int, bg: torch.Tens
 RASTER_KEYS = ("means3D", "opacities", "normal", "albedo", "roughness", "metallic", "shs", "scales", "rotations")
 
 
-class RasterFront(torch.nn.Module):
-    """The operator call of gaussian_renderer.render -- rasterizer, in-op filters, SSAO -- as a static-shape tensor
-    function of the Gaussians and the camera matrices: what torch.cuda.make_graphed_callables needs.  It is capturable
-    only under AsyncBinning (no host read-back, fixed binning capacity); image size, field of view and GI settings are
-    baked into the capture, the camera pose is an input."""
-
-    def __init__(self, H: int, W: int, tanfovx: float, tanfovy: float, gi: Dict, sh_degree: int, inference: bool = False):
-        super().__init__()
-        self.H, self.W, self.tanfovx, self.tanfovy = int(H), int(W), float(tanfovx), float(tanfovy)
-        self.gi, self.sh_degree, self.inference = dict(gi), int(sh_degree), bool(inference)
-
-    def forward(self, means2D, viewmatrix, projmatrix, campos, bg, means3D, opacities, normal, albedo, roughness, metallic,
-                shs, scales, rotations):
-        gi = self.gi
-        st = GaussianRasterizationSettings(
-            image_height=self.H, image_width=self.W, tanfovx=self.tanfovx, tanfovy=self.tanfovy, radius=gi["radius"],
-            bias=gi["bias"], thick=gi["thick"], delta=gi["delta"], step=gi["step"], start=gi["start"], bg=bg,
-            scale_modifier=1.0, viewmatrix=viewmatrix, projmatrix=projmatrix, sh_degree=self.sh_degree, campos=campos,
-            prefiltered=False, debug=False, inference=self.inference, argmax_depth=False)
-        return GaussianRasterizer(st)(means3D=means3D, means2D=means2D, opacities=opacities, normal=normal, shs=shs,
-                                      albedo=albedo, roughness=roughness, metallic=metallic, scales=scales,
-                                      rotations=rotations, derive_normal=True)
-
-
 class DenseScene(RuntimeError):
     """Raised by the graph-capturing steppers only under long_lists = 0 (gigs_options; GIGS_LONG_LISTS=0) for a scene that averages more instances per
     tile than one workgroup sorts in LDS: the caller then keeps the synchronous path.  By default dense scenes (3 M
@@ -253,83 +230,36 @@ def _declined_as_dense(probe: int, tiles: int) -> bool:
     return probe > c.option("bucket_max_mean") * tiles and c.option("long_lists") == 0
 
 
-class GraphedRaster:
-    """RasterFront captured into a hipGraph (forward and backward) under AsyncBinning, with the overflow protocol:
+def camera_model(cam: Dict):
+    """(image height, image width, tanfovx, tanfovy): what a captured step bakes in; the camera pose is an input."""
+    return int(cam["image_height"]), int(cam["image_width"]), float(cam["tanfovx"]), float(cam["tanfovy"])
 
-        out = gr(cam, g, means2D, bg)     # replays the graph; queues a snapshot of the device-side instance counters
-        ... the rest of the step ...
-        gr.check()                         # waits for that snapshot only; raises BinningOverflow after growing the capacity
 
-    The capacity starts at twice the instance count of a first, synchronous forward; memory, not time, scales with it."""
+def _ceil64ki(n: int) -> int:
+    return -(-n // 65536) * 65536
 
-    def __init__(self, cam: Dict, g: Dict[str, torch.Tensor], gi: Dict, sh_degree: int, inference: bool = False,
-                 capacity: Optional[int] = None):
-        self.cfg = (int(cam["image_height"]), int(cam["image_width"]), float(cam["tanfovx"]), float(cam["tanfovy"]))
-        self.gi, self.sh_degree, self.inference = dict(gi), int(sh_degree), bool(inference)
-        self.dev = g["means3D"].device
-        self.capacity = int(capacity) if capacity else 0
-        self.fn = self.bin = None
-        self.recaptures = 0
 
-    def _probe(self, cam, g, bg) -> int:
-        e = torch.Tensor([])
-        H, W, tx, ty = self.cfg
-        with torch.no_grad():
-            res = _ops.rasterize_gaussians(bg, g["means3D"], e, g["opacities"], g["normal"], g["albedo"], g["roughness"],
-                                           g["metallic"], g["scales"], g["rotations"], e, g["shs"], cam["campos"],
-                                           cam["viewmatrix"], cam["projmatrix"], 1.0, tx, ty, H, W, self.sh_degree, False,
-                                           False, self.inference, False)
-        return int(res[0])
+def first_capacity(cam: Dict, g: Dict[str, torch.Tensor], sh_degree: int, inference: bool = False) -> int:
+    """The binning capacity of a first capture under AsyncBinning: twice the instance count of one synchronous forward
+    (memory, not time, scales with it), at least 64 Ki.  Raises DenseScene for a scene declined as dense."""
+    H, W, tanfovx, tanfovy = camera_model(cam)
+    e = torch.Tensor([])
+    bg = torch.zeros(3, device=g["means3D"].device)
+    with torch.no_grad():
+        res = _ops.rasterize_gaussians(bg, g["means3D"], e, g["opacities"], g["normal"], g["albedo"], g["roughness"],
+                                       g["metallic"], g["scales"], g["rotations"], e, g["shs"], cam["campos"],
+                                       cam["viewmatrix"], cam["projmatrix"], 1.0, tanfovx, tanfovy, H, W, sh_degree, False,
+                                       False, inference, False)
+    probe = int(res[0])
+    tiles = ((H + 15) // 16) * ((W + 15) // 16)
+    if _declined_as_dense(probe, tiles):
+        raise DenseScene(f"{probe} instances over {tiles} tiles")
+    return max(65536, _ceil64ki(2 * probe))
 
-    def _args(self, cam, g, means2D, bg):
-        return (means2D, cam["viewmatrix"], cam["projmatrix"], cam["campos"], bg, *[g[k] for k in RASTER_KEYS])
 
-    def _capture(self, cam, g, means2D, bg):
-        H_, W_ = self.cfg[0], self.cfg[1]
-        tiles = ((H_ + 15) // 16) * ((W_ + 15) // 16)
-        if self.capacity <= 0:
-            probe = self._probe(cam, g, bg)
-            if _declined_as_dense(probe, tiles):
-                raise DenseScene(f"{probe} instances over {tiles} tiles")
-            self.capacity = max(65536, -(-2 * probe // 65536) * 65536)
-        self.bin = AsyncBinning(self.capacity, self.dev)
-        H, W, tx, ty = self.cfg
-        mod = RasterFront(H, W, tx, ty, self.gi, self.sh_degree, self.inference)
-        # static inputs: the Gaussian tensors and means2D THEMSELVES (aliases: a replay then finds its inputs in place and
-        # copies nothing -- 40 MB and ten launches per step otherwise); the small per-view camera tensors are copied in
-        args = self._args(cam, g, means2D, bg)
-        sample = tuple((a.detach() if i == 0 or i >= 5 else a.detach().clone()).requires_grad_(a.requires_grad)
-                       for i, a in enumerate(args))
-        with self.bin:
-            if self.inference or not any(a.requires_grad for a in sample):
-                self.fn = _graphed_inference(mod, sample)
-            else:
-                self.fn = graphed(mod, sample)
-        self.recaptures += 1
-
-    def __call__(self, cam, g, means2D, bg):
-        if (int(cam["image_height"]), int(cam["image_width"]), float(cam["tanfovx"]), float(cam["tanfovy"])) != self.cfg:
-            raise ValueError("GraphedRaster: image size / field of view differ from the captured ones")
-        if self.fn is None:
-            self._capture(cam, g, means2D, bg)
-        out = self.fn(*self._args(cam, g, means2D, bg))
-        self.bin.snapshot()
-        return out
-
-    def check(self) -> int:
-        try:
-            return self.bin.check()
-        except BinningOverflow as ex:
-            self.capacity = -(-int(1.5 * ex.needed) // 65536) * 65536
-            self.close()  # next call re-captures with the larger buffer
-            raise
-
-    def close(self) -> None:
-        """Release the captured callable with the device idle before and after (see WholeStepGraph._drop_graphs)."""
-        if self.fn is not None:
-            torch.cuda.synchronize(self.dev)
-            self.fn = None
-            torch.cuda.synchronize(self.dev)
+def grown_capacity(needed: int) -> int:
+    """The binning capacity after an overflow that needed `needed` instances."""
+    return _ceil64ki(int(1.5 * needed))
 
 
 def _graphed_inference(mod, sample):
@@ -460,16 +390,21 @@ class GeometryCache:
         return int(self.flag_host[0]) != 0
 
 
+# Delay in front of the light's GGX backward inside the step graph (WholeStepGraph._capture): 0 = none, the blend
+# backward then loses the race for the CUs (-3 %); 0 to 150 us are within the run-to-run spread.
+LIGHT_BWD_HEAD_START_US = 10
+
+
 class WholeStepGraph:
     """One stage-2 iteration -- rasterizer, SSAO, light filter, shade, SSR, loss, and the whole backward -- captured by
     hand into TWO hipGraphs (forward, backward) that share one memory pool:
 
         replay(forward); record(event); replay(backward); wait(event); read the binning counters
 
-    Compared with chaining torch.cuda.make_graphed_callables pieces (GIGS_RASTER_GRAPH=1: six graph launches) there are
-    no staging copies of activations or of incoming gradients, no zero-filled placeholder gradients, and the ~45 kernel
-    nodes of a step run without the 11-18 us the command processor spends between eager launches; compared with the
-    eager rasterizer the light's filter still starts when the blend kernel starts (an event node recorded by the
+    Compared with chaining torch.cuda.make_graphed_callables pieces (six graph launches, measured slower: DESIGN.md
+    section 5) there are no staging copies of activations or of incoming gradients, no zero-filled placeholder
+    gradients, and the ~45 kernel nodes of a step run without the 11-18 us the command processor spends between eager
+    launches; compared with the eager rasterizer the light's filter still starts when the blend kernel starts (an event node recorded by the
     library inside the forward), not beside the single-workgroup scan kernels it would starve.
 
     Static inputs: the Gaussian tensors and light.base ARE the graph's inputs (aliases: an optimizer that updates them
@@ -495,7 +430,7 @@ class WholeStepGraph:
         # cyclic collector happens to run" (the round-3 host segfault in hip::Graph::UpdateStreams: DESIGN.md section 5)
         self.owner = weakref.proxy(owner)
         self.dev = next(iter(g.values())).device
-        self.cfg = (int(cam["image_height"]), int(cam["image_width"]), float(cam["tanfovx"]), float(cam["tanfovy"]))
+        self.cfg = camera_model(cam)
         self.capacity = 0
         self.gf = self.gb = self.go = self.key = self.adam = None
         self.res = self.grads = self.vp_grad = self.inner = self.bin = None
@@ -554,7 +489,6 @@ class WholeStepGraph:
         """The owner's gradient slab (train_iteration: data_parallel) as gradient sinks of the captured step: the raw
         gradients are written into the slab's views by the activations' backward, xyz's by the rasterizer's.  Also enters
         the frozen-geometry view cache of this variant."""
-        import contextlib
         slabv = getattr(self.owner, "grad_slab", None)
         stack = contextlib.ExitStack()
         if self.cache is not None:
@@ -612,7 +546,6 @@ class WholeStepGraph:
     def _capture(self, cam, g, gt_image, view_dirs):
         import gc
         o = self.owner
-        H, W, _, _ = self.cfg
         bg = torch.zeros(3, device=self.dev)
         prep = o.prepare if o.prepare is not None else (lambda raw: raw)
         with torch.no_grad():
@@ -620,11 +553,7 @@ class WholeStepGraph:
         if self.cache is not None and self.cache.capacity > self.capacity:
             self.capacity = self.cache.capacity  # the record and the replay variant share the slot's chunks
         if self.capacity <= 0:
-            probe = GraphedRaster(cam, ga, o.gi, o.sh_degree)._probe(cam, ga, bg)
-            tiles = ((H + 15) // 16) * ((W + 15) // 16)
-            if _declined_as_dense(probe, tiles):
-                raise DenseScene(f"{probe} instances over {tiles} tiles")
-            self.capacity = max(65536, -(-2 * probe // 65536) * 65536)
+            self.capacity = first_capacity(cam, ga, o.sh_degree)
         if self.cache is not None:
             if self.cache.capacity != self.capacity:
                 self.cache.invalidate()  # entries are carved for the old capacity
@@ -687,13 +616,9 @@ class WholeStepGraph:
         gc.disable()  # see graphed(): a cyclic-GC pass during capture may destroy HIP objects, which HIP refuses
         try:
             gf, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            # GIGS_STEP_GRAPH_PRIO=1 (diagnostic): capture the main branch on a high-priority stream.  Measured: the graph
-            # executor does not turn that into dispatch order (blend backward still 0.54 ms), see the delay node below
-            prio = os.environ.get("GIGS_STEP_GRAPH_PRIO", "0") == "1"
-            cap = torch.cuda.Stream(device=self.dev, priority=-1) if prio else None
             # thread_local: a re-capture (binning overflow) may happen while RCCL's proxy thread is alive and issuing HIP
             # calls of its own, which the default (global) capture mode turns into a capture failure
-            with torch.cuda.graph(gf, stream=cap, capture_error_mode="thread_local"):
+            with torch.cuda.graph(gf, capture_error_mode="thread_local"):
                 with self.bin, self._slab_sinks():
                     res = self.inner(self.s_cam, prep(g), self.s_gt, self.s_vd)
                 self.bin.host.copy_(self.bin.counters, non_blocking=True)
@@ -702,11 +627,11 @@ class WholeStepGraph:
             # former lasts as long as its longest tiles and must get them resident at once; the latter floods every CU
             # with bandwidth-bound workgroups.  Started in that order (as eager launches happen to be: the side stream's
             # event wait costs ~35 us) the blend backward takes 0.30 ms, the other way round 0.51: a delay node gives it
-            # the head start (GIGS_LIGHT_BWD_HEAD_START_US, default 10).
+            # the head start (LIGHT_BWD_HEAD_START_US).
             import pbr.renderutils.ops as light_ops
-            light_ops.bwd_head_start_ns = int(1e3 * float(os.environ.get("GIGS_LIGHT_BWD_HEAD_START_US", "10")))
+            light_ops.bwd_head_start_ns = int(1e3 * LIGHT_BWD_HEAD_START_US)
             try:
-                with torch.cuda.graph(gb, pool=gf.pool(), stream=cap, capture_error_mode="thread_local"):
+                with torch.cuda.graph(gb, pool=gf.pool(), capture_error_mode="thread_local"):
                     # the seed gradient as a persistent tensor: autograd's own ones_like(loss) is a fill node at the head of
                     # the backward graph
                     with self._slab_sinks():
@@ -723,7 +648,7 @@ class WholeStepGraph:
                 from optim import CapturedAdam
                 adam = CapturedAdam(o.optimizers, params, list(grads[:-1]), absent_is_zero=self.viol_dev is not None)
                 go = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(go, pool=gf.pool(), stream=cap, capture_error_mode="thread_local"):
+                with torch.cuda.graph(go, pool=gf.pool(), capture_error_mode="thread_local"):
                     if self.cache is not None:
                         # the update reports whether it moved a geometry bit; the word travels to pinned memory and is cleared
                         adam.launch(watch=GeometryCache.WATCH, changed=self.cache.flag_dev, guard=self.viol_dev)
@@ -769,7 +694,7 @@ class WholeStepGraph:
     def __call__(self, cam, g, gt_image, view_dirs, vkey=None):
         """Returns None (frozen-geometry variants only) when the step must be repeated as a recording: the previous update
         moved geometry, which the host can only know once this step's forward has run."""
-        if (int(cam["image_height"]), int(cam["image_width"]), float(cam["tanfovx"]), float(cam["tanfovy"])) != self.cfg:
+        if camera_model(cam) != self.cfg:
             raise ValueError("WholeStepGraph: image size / field of view differ from the captured ones")
         cache = self.cache
         for _ in range(4):
@@ -799,7 +724,7 @@ class WholeStepGraph:
             self.check_declared()  # this forward has ended, so every earlier update's count has arrived
             r, over = int(self.bin.host[0]), int(self.bin.host[1])
             if over:
-                self.capacity = -(-int(1.5 * over) // 65536) * 65536
+                self.capacity = grown_capacity(over)
                 if cache is not None:
                     cache.invalidate()
                     cache.capacity = self.capacity
@@ -906,7 +831,76 @@ def stage2_loss(render_direct, IRR_linear, gt_image, normal_mask_f, roughness_ma
     return loss + lamb_loss * 0.001, render_rgb.detach()
 
 
-class Stage2Step:
+class _Stepper:
+    """What Stage1Step and Stage2Step share: the whole-step graphs (one WholeStepGraph per camera model, at most four)
+    with their fallback for a scene declined as dense, the eager update, and deterministic teardown.  Steppers and
+    trainers are context managers (`with Stage2Trainer(...) as tr:`) that close on exit.  A subclass provides
+    `optimizers`, `before_update`, `post_update` and `_leaves(raw)` (the tensors whose `.grad` the eager update clears)."""
+
+    def __init__(self):
+        self.whole, self._wholes = None, {}
+        self._dense = False  # declined as dense (DenseScene): synchronous binning with the global radix sort from then on
+
+    def _graph_step(self, cam, raw, gt_image, view_dirs):
+        """The step from the whole-step graphs, or None: the caller's eager path runs instead (GIGS_STEP_GRAPH=0, more
+        camera models than graphs, or a scene declined as dense -- then for good)."""
+        if os.environ.get("GIGS_STEP_GRAPH", "1") != "1" or self._dense:
+            return None
+        try:
+            return self._replay_whole(cam, raw, gt_image, view_dirs)
+        except DenseScene:
+            self._dense = True
+            for w in self._wholes.values():
+                w.close()
+            self.whole = None
+            self._wholes.clear()
+            return None
+
+    def _replay_whole(self, cam, raw, gt_image, view_dirs):
+        # one capture per (image size, field of view): datasets with per-camera intrinsics keep a few of them
+        cfg = camera_model(cam)
+        if self.whole is None or self.whole.cfg != cfg:
+            self.whole = self._wholes.get(cfg)
+            if self.whole is None and len(self._wholes) < 4:
+                self.whole = self._wholes[cfg] = WholeStepGraph(self, cam, raw)
+        if self.whole is None:
+            return None  # more than four distinct camera models: the fifth onwards takes the eager path
+        return self.whole(cam, raw, gt_image, view_dirs)
+
+    def _eager_update(self, raw) -> None:
+        """Complete iteration, eager formulation (train.py:517-522)."""
+        if not self.optimizers:
+            return
+        if self.before_update is not None:
+            self.before_update()
+        for o in self.optimizers:
+            o.step()
+        for leaf in self._leaves(raw):
+            leaf.grad = None  # zero_grad(set_to_none=True)
+        if self.post_update is not None:
+            with torch.no_grad():
+                self.post_update()
+
+    def close(self) -> None:
+        """Deterministic teardown of the whole-step graphs: synchronise, release, synchronise.  The stepper captures
+        again if it is called afterwards."""
+        # the WholeStepGraph objects stay (they remember the binning capacity and count their captures); their graphs go
+        for w in list(self._wholes.values()):
+            w.close()
+        if self.whole is not None:
+            self.whole.close()
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class Stage2Step(_Stepper):
     """One stage-2 iteration of train.py (:266-422) up to and including loss.backward().
 
     graphs=True captures the two launch-bound glue segments (front: ~120 small kernels + build_mips
@@ -925,20 +919,23 @@ class Stage2Step:
         and gt_image), `optimizers` (FusedAdam) are stepped after the backward, `before_update()` runs between the two
         (the multi-GPU gradient all-reduce) and `post_update()` after (cubemap.clamp_, train.py:522).  All of it is
         part of the captured step when graphs=True (pipeline.WholeStepGraph)."""
+        super().__init__()
         self.prepare, self.regularizer, self.optimizers = prepare, regularizer, list(optimizers or [])
         self.post_update, self.before_update = post_update, before_update
         self.gi, self.sh_degree, self.metallic = gi, sh_degree, metallic
         self.fused, self.light, self.brdf_lut = fused, light, brdf_lut
         self.flags = dict(metallic=metallic, indirect=indirect, gamma=gamma, tone=tone)
-        self.back = self.mips = self.side = self.step_begin = self.blend_begin = self.graster = None
+        self.back = self.mips = self.side = self.blend_begin = None
+        self.lights_ready = self.raster_done = None  # events of the fused step (_fused_begin, _fused_step)
         # fused + graphs: the rasterizer's planes live at fixed addresses, the graph reads them in place
-        self.pool = OutputPool() if (fused and graphs and os.environ.get("GIGS_OUTPUT_POOL", "1") == "1") else None
+        self.pool = OutputPool() if (fused and graphs) else None
+        self._abin = None  # fused + graphs, eager rasterizer: its asynchronous binning (_eager_async)
         self.front = Stage2Front(light, brdf_lut, metallic=metallic, indirect=indirect, tone=tone, gamma=gamma)
         self.loss_fn = stage2_loss
         self.graphs = graphs
         self._captured = False
         self._defer_backward = False  # WholeStepGraph's inner step: return the attached loss, the caller differentiates
-        self.whole, self._wholes = None, {}
+        self._static_bg = self._static_m2d = None  # ... and its background and means2D, kept outside the graph
         # frozen-geometry reuse (GeometryCache; graph path only, off by default: the headline step never uses it)
         self.geometry_cache, self.geom_cache = bool(geometry_cache), None
         self.materials_only = bool(materials_only)
@@ -950,87 +947,88 @@ class Stage2Step:
         self.loss_fn = graphed(self.loss_fn, clone(loss_args))
         self._captured = True
 
+    def _make_inner(self):
+        return Stage2Step(self.light, self.brdf_lut, self.gi, self.sh_degree, graphs=False, fused=True,
+                          regularizer=self.regularizer, **self.flags)
+
+    def _leaves(self, g):
+        out, seen = [], set()
+        for t in list(g.values()) + list(self.light.parameters()):
+            for leaf in _grad_leaves(t):
+                if id(leaf) not in seen:
+                    seen.add(id(leaf))
+                    out.append(leaf)
+        return out
+
     def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], gt_image: torch.Tensor, view_dirs: torch.Tensor,
                  extra_loss=None):
         """extra_loss(normal_map, albedo_map, roughness_map, metallic_map) -> scalar added to the loss before
         backward (the BRDF / envmap regularisers of train.py:387-420; see gi-gs_amd/losses.py)."""
         raw = g
-        if (self.fused and self.graphs and extra_loss is None and os.environ.get("GIGS_STEP_GRAPH", "1") == "1"
-                and os.environ.get("GIGS_RASTER_GRAPH", "0") != "1" and not getattr(self, "_dense", False)):
-            try:
-                # one capture per (image size, field of view): datasets with per-camera intrinsics keep a few of them
-                cfg = (int(cam["image_height"]), int(cam["image_width"]), float(cam["tanfovx"]), float(cam["tanfovy"]))
-                if self.geometry_cache:
-                    out = self._cached_geometry_step(cfg, cam, raw, gt_image, view_dirs)
-                    if out is not None:
-                        return out
-                elif self.whole is None or self.whole.cfg != cfg:
-                    self.whole = self._wholes.get(cfg)
-                    if self.whole is None and len(self._wholes) < 4:
-                        self.whole = self._wholes[cfg] = WholeStepGraph(self, cam, g)
-                if self.whole is not None and not self.geometry_cache:
-                    return self.whole(cam, raw, gt_image, view_dirs)
-                # more than four distinct camera models: the fifth onwards takes the piecewise path below
-            except DenseScene:
-                self._dense = True  # synchronous binning with the global radix sort: the rasterizer stays eager
-                for w in self._wholes.values():
-                    w.close()
-                self.whole = None
-                self._wholes.clear()
+        if self.fused and self.graphs and extra_loss is None:
+            out = self._graph_step(cam, raw, gt_image, view_dirs)
+            if out is not None:
+                return out
         regen = (lambda: self.prepare(raw)) if self.prepare is not None else None
         if regen is not None:
             g = regen()
         res = self._step(cam, g, gt_image, view_dirs, extra_loss, regen)
-        if self.optimizers:  # complete iteration, eager formulation: train.py:517-522
-            if self.before_update is not None:
-                self.before_update()
-            for o in self.optimizers:
-                o.step()
-            for leaf in self._leaves(raw):
-                leaf.grad = None  # zero_grad(set_to_none=True)
-            if self.post_update is not None:
-                with torch.no_grad():
-                    self.post_update()
+        self._eager_update(raw)
         return res
 
+    def _replay_whole(self, cam, raw, gt_image, view_dirs):
+        if self.geometry_cache:
+            return self._cached_geometry_step(cam, raw, gt_image, view_dirs)
+        return super()._replay_whole(cam, raw, gt_image, view_dirs)
+
+    def _cached_geometry_step(self, cam, raw, gt_image, view_dirs):
+        """One step through the frozen-geometry variants of the whole-step graphs: replayed from the view's entry when
+        there is one, recorded otherwise; a replay that turns out stale (the previous update moved geometry) is repeated
+        as a recording.  Returns None when this camera model has no slot left (more than four models): the caller's
+        other paths."""
+        if self.geom_cache is None:
+            self.geom_cache = GeometryCache(next(iter(raw.values())).device)
+        cache = self.geom_cache
+        cfg = camera_model(cam)
+        vkey = cache.view_key(cam)
+        mode = cache.mode(vkey, raw)
+        for _ in range(3):
+            key = (cfg, mode)
+            whole = self._wholes.get(key)
+            if whole is None:
+                if len(self._wholes) >= 8:
+                    return None
+                whole = self._wholes[key] = WholeStepGraph(self, cam, raw, cache=cache, mode=mode)
+            self.whole = whole
+            out = whole(cam, raw, gt_image, view_dirs, vkey=vkey)
+            if out is not None:
+                return out
+            mode = "record"
+        raise RuntimeError("Stage2Step: the frozen-geometry step kept being invalidated")
+
     def _step(self, cam, g, gt_image, view_dirs, extra_loss=None, regen=None):
-        """Everything but WholeStepGraph: the chained-graph formulation (GIGS_RASTER_GRAPH=1) and the eager ones.
-        `regen()` rebuilds the rasterizer's inputs from the raw parameters for a repeated step (binning overflow)."""
+        """Everything but WholeStepGraph: the fused formulation (the rasterizer eager, with graphs=True under
+        asynchronous binning) and the op-by-op one.  `regen()` rebuilds the rasterizer's inputs from the raw parameters
+        for a repeated step (binning overflow)."""
         dev = g["means3D"].device
-        if self.fused and self.graphs and os.environ.get("GIGS_RASTER_GRAPH", "0") == "1" and not getattr(self, "_dense", False):
-            try:
-                return self._graphed_step(cam, g, gt_image, view_dirs, extra_loss)
-            except DenseScene:
-                self._dense = True  # keep the rasterizer eager (synchronous binning, global radix sort); the rest stays graphed
-                self.step_begin = None
         # train.py:263-264: black background for PBR (WholeStepGraph's inner step keeps it, and means2D, outside the graph)
-        background = getattr(self, "_static_bg", None)
-        if background is None:
-            background = torch.zeros(3, device=dev)
-        m2d = getattr(self, "_static_m2d", None)
-        if self.fused:
-            if self.step_begin is None:
-                self.step_begin, self.blend_begin = torch.cuda.Event(), torch.cuda.Event()
-                self.blend_begin.record()  # creates the underlying hipEvent; the library re-records it in the forward
-            self.step_begin.record()
+        background = self._static_bg if self._static_bg is not None else torch.zeros(3, device=dev)
+        if self.fused and self.blend_begin is None:
+            self.blend_begin = torch.cuda.Event()
+            self.blend_begin.record()  # creates the underlying hipEvent; the library re-records it in the forward
         lights = []
         hook = after_blend((lambda: lights.extend(self._fused_begin())) if self.fused else None)
         # eager rasterizer without the host read-back: asynchronous binning into a fixed-capacity buffer (sized from one
-        # synchronous probe), the overflow flag checked after the backward has been queued (GIGS_RASTER_ASYNC=0: read back)
-        abin = None
-        if self.fused and self.graphs and os.environ.get("GIGS_RASTER_ASYNC", "1") == "1" and not getattr(self, "_dense", False):
-            abin = self._eager_async(cam, g, background)
+        # synchronous probe), the overflow flag checked after the backward has been queued
+        abin = self._eager_async(cam, g) if (self.fused and self.graphs and not self._dense) else None
         pre_grads = _snapshot_grads(self._leaves(g)) if abin is not None else None
         # the blend-begin event belongs to THIS step's forward: it is part of the library context the forward runs with
         # (gigs_ctx_set_blend_begin_event), not of the process
-        with hook, (abin if abin is not None else _NULLCTX):
-            ev_ctx = gigs_lib.use(gigs_lib.current().derive(blend_event=self.blend_begin)) if self.fused else _NULLCTX
-            with ev_ctx:
-                if self.pool is not None:
-                    with self.pool:
-                        out = rasterize(cam, g, self.sh_degree, background, self.gi, means2D=m2d)
-                else:
-                    out = rasterize(cam, g, self.sh_degree, background, self.gi, means2D=m2d)
+        with hook, (abin if abin is not None else contextlib.nullcontext()):
+            ev_ctx = (gigs_lib.use(gigs_lib.current().derive(blend_event=self.blend_begin)) if self.fused
+                      else contextlib.nullcontext())
+            with ev_ctx, (self.pool if self.pool is not None else contextlib.nullcontext()):
+                out = rasterize(cam, g, self.sh_degree, background, self.gi, means2D=self._static_m2d)
         if abin is not None:
             abin.snapshot()
         ((_, radii, _, _, normal_map_from_depth, normal_map, occlusion_map, albedo_map, roughness_map, metallic_map,
@@ -1045,7 +1043,7 @@ class Stage2Step:
                 try:
                     res["num_rendered"] = abin.check()
                 except BinningOverflow as ex:
-                    self._abin = AsyncBinning(-(-int(1.5 * ex.needed) // 65536) * 65536, dev)
+                    self._abin = AsyncBinning(grown_capacity(ex.needed), dev)
                     _restore_grads(pre_grads)  # the overflowed step's contribution is dropped, earlier ones are kept
                     return self._step(cam, regen() if regen is not None else g, gt_image, view_dirs, extra_loss, regen)
             return res
@@ -1071,6 +1069,126 @@ class Stage2Step:
         loss.backward()
         return dict(loss=loss.detach(), render_rgb=render_rgb, render_direct=render_direct.detach(),
                     IRR=IRR.detach(), viewspace_points=screenspace_points, radii=radii)
+
+
+
+    def _eager_async(self, cam, g):
+        """The eager rasterizer's asynchronous binning; None for a scene declined as dense (the read-back stays)."""
+        if self._abin is None:
+            try:
+                self._abin = AsyncBinning(first_capacity(cam, g, self.sh_degree), g["means3D"].device)
+            except DenseScene:
+                self._dense = True
+                return None
+        return self._abin
+
+    def _fused_begin(self):
+        """Starts light.build_mips() on a side stream, called from inside the rasterizer's forward as soon as its
+        kernels up to the blend are queued (diff_gaussian_rasterization.after_blend; the host call returns after
+        the binning read-back, while the GPU is still sorting): the GGX pre-filter is independent of the G-buffer
+        and overlaps the latency-bound sort / blend kernels.  autograd runs a node's backward on the stream of its forward, so the light's
+        backward likewise overlaps the rasterizer's backward."""
+        from stage2_fused import LightMips
+        if self.mips is None:
+            # light.base's AccumulateGrad lives on the stream the parameter was created on, its gradient is produced on
+            # the side stream: intended here (autograd inserts the event wait), so the advisory warning is switched off
+            if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
+                torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
+            self.side = torch.cuda.Stream()
+            self.mips = LightMips(self.light)
+            self.dummy = torch.zeros(1, device=self.light.base.device)
+            if self.graphs:
+                with torch.no_grad():
+                    self.mips(self.dummy)  # builds the cached filter tables outside the capture
+                self.mips = graphed(self.mips, (self.dummy,))
+        # Start when the blend kernel starts (an event the library records right before launching it): that kernel is
+        # a few long serial walks with most CUs idle.  Measured alternatives: starting at once (next to the sort passes,
+        # which then take 0.3-0.5 instead of 0.22 ms) and starting after the blend kernel (next to the VALU-bound SSAO
+        # march only: 4 % slower overall).
+        self.side.wait_event(self.blend_begin)
+        import pbr.light as pbr_light
+        # this stepper schedules the light itself: the filters are built HERE, on its side stream (not on the light's own
+        # stream, which serves the op-by-op caller: pbr/light.py), so that their backward runs there too
+        with torch.cuda.stream(self.side), pbr_light.build_on_current_stream():
+            out = self.mips(self.dummy)
+            # what the shade waits for: an event of its own, so that work queued on this stream later (the regularisers,
+            # _fused_step) is not waited for with it
+            if self.lights_ready is None:
+                self.lights_ready = torch.cuda.Event()
+            self.lights_ready.record()
+        return out
+
+    def _fused_step(self, cam, gt_image, view_dirs, st, radii, screenspace_points, normal_map, out_normal_view,
+                    albedo_map, roughness_map, metallic_map, occlusion_map, depth_pos, lights, extra_loss=None):
+        """fused=True: everything after the rasterizer is stage2_fused._Stage2Fused (6 kernels instead of ~250)."""
+        from stage2_fused import Stage2FusedBack
+        H, W = cam["image_height"], cam["image_width"]
+        main = torch.cuda.current_stream()
+        # The regularisers (BRDF TV, envmap TV: ~15 small kernels forward, as many backward) read the rasterizer's planes and
+        # the light only -- not the shade, the marches or the loss -- so they go to the light's stream, idle by now, beside the
+        # shade and the SSR march; autograd runs their backward there too, beside the shade backward (on the caller's
+        # stream behind the loss they sat on the critical path both ways: 0.2 ms per iteration at C2).
+        if self.regularizer is not None:
+            if self.raster_done is None:
+                self.raster_done = torch.cuda.Event()
+            self.raster_done.record()  # the rasterizer's planes exist: all the regularisers wait for
+        if self.lights_ready is not None:
+            main.wait_event(self.lights_ready)
+        else:
+            main.wait_stream(self.side)
+        for t in lights:
+            t.record_stream(main)
+        args = (normal_map.detach(), out_normal_view.detach(), albedo_map, roughness_map, metallic_map,
+                occlusion_map.detach(), depth_pos.detach(), st.viewmatrix, view_dirs, gt_image, *lights)
+        if self.back is None:
+            cfg = dict(H=H, W=W, gi=self.gi, focal_x=W / (2.0 * cam["tanfovx"]), focal_y=H / (2.0 * cam["tanfovy"]),
+                       **self.flags)
+            self.back = Stage2FusedBack(self.brdf_lut, cfg)
+            if self.graphs:
+                # pooled rasterizer planes (fixed addresses) become the graph's static inputs themselves: no staging copies
+                pooled = set(t.untyped_storage().data_ptr() for t in self.pool.buffers.values()) if self.pool else set()
+                # ... and so are the filtered light levels (static outputs of the light's own graph): read in place, not staged
+                pooled |= set(t.untyped_storage().data_ptr() for t in lights)
+                sample = tuple(a.detach().requires_grad_(a.requires_grad) if a.untyped_storage().data_ptr() in pooled
+                               else a.detach().clone().requires_grad_(a.requires_grad) for a in args)
+                self.back = graphed(self.back, sample)
+        loss, render_rgb, render_direct, IRR = self.back(*args)
+        if extra_loss is not None:
+            loss = loss + extra_loss(normal_map, albedo_map, roughness_map, metallic_map)
+        if self.regularizer is not None:
+            # queued (host order) behind the fused node so that autograd, which walks later nodes first, starts their backward
+            # before the shade backward; the stream waits only for the rasterizer's planes
+            maps = dict(normal_map=normal_map, albedo_map=albedo_map, roughness_map=roughness_map, metallic_map=metallic_map,
+                        gt_image=gt_image)
+            self.side.wait_event(self.raster_done)
+            with torch.cuda.stream(self.side):
+                reg = self.regularizer(maps)
+            for t in maps.values():
+                t.record_stream(self.side)
+            main.wait_stream(self.side)
+            reg.record_stream(main)
+            loss = loss + reg
+        res = dict(loss=loss.detach(), render_rgb=render_rgb, render_direct=render_direct, IRR=IRR,
+                   viewspace_points=screenspace_points, radii=radii)
+        if self._defer_backward:
+            res["_loss"] = loss
+            return res
+        loss.backward()
+        return res
+
+    def close(self) -> None:
+        """Also releases the graphed callables (piecewise path, fused node, light filters) and the frozen-geometry
+        entries; the stepper captures again if it is called afterwards."""
+        super().close()
+        if self.geom_cache is not None:
+            self.geom_cache.invalidate()  # the per-view entries (tile lists, occlusion planes, hit lists): device memory
+        if self._captured:  # piecewise path: the two graphed callables
+            self.front = Stage2Front(self.light, self.brdf_lut, **self.flags)
+            self.loss_fn = stage2_loss
+            self._captured = False
+        self.back = self.mips = None
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
 
 
 def _grad_leaves(t: torch.Tensor):
@@ -1100,267 +1218,6 @@ def _restore_grads(snapshot):
         p.grad = gr
 
 
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NULLCTX = _NullCtx()
-
-
-def _eager_async(self, cam, g, background):
-    if getattr(self, "_abin", None) is None:
-        probe = GraphedRaster(cam, g, self.gi, self.sh_degree)._probe(cam, g, background)
-        tiles = ((int(cam["image_height"]) + 15) // 16) * ((int(cam["image_width"]) + 15) // 16)
-        if _declined_as_dense(probe, tiles):
-            self._dense = True
-            return None
-        self._abin = AsyncBinning(max(65536, -(-2 * probe // 65536) * 65536), g["means3D"].device)
-    return self._abin
-
-
-def _graphed_step(self, cam, g, gt_image, view_dirs, extra_loss=None):
-    """fused + graphs: the WHOLE step replays from hipGraphs -- the rasterizer with its in-op filters and SSAO too
-    (GraphedRaster: asynchronous binning, no host read-back), the light filter on the side stream from the start of the
-    step, the fused stage-2 node -- six graph launches per iteration.  The binning overflow flag of this step is
-    checked after loss.backward() has been queued (the host then waits for the forward only); on overflow the
-    capacity grows, the graphs are re-captured and the step is repeated on cleared gradients."""
-    from types import SimpleNamespace
-    dev = g["means3D"].device
-    if self.step_begin is None:
-        self.step_begin = torch.cuda.Event()
-        self._bg = torch.zeros(3, device=dev)  # train.py:263-264: black background for PBR
-    pre_grads = _snapshot_grads(self._leaves(g))
-    for attempt in range(4):
-        self.step_begin.record()
-        lights = list(self._fused_begin(self.step_begin))
-        if self.graster is None:
-            self.graster = GraphedRaster(cam, g, self.gi, self.sh_degree)
-        if getattr(self, "_m2d", None) is None or self._m2d.shape != g["means3D"].shape:
-            self._m2d = torch.zeros_like(g["means3D"], requires_grad=True)  # persistent: the graph's static input
-        screenspace_points = self._m2d
-        screenspace_points.grad = None
-        out = self.graster(cam, g, screenspace_points, self._bg)
-        self._static_storages = set(t.untyped_storage().data_ptr() for t in out)
-        (_, radii, _, _, _, normal_map, occlusion_map, albedo_map, roughness_map, metallic_map, out_normal_view, depth_pos) = out
-        res = self._fused_step(cam, gt_image, view_dirs, SimpleNamespace(viewmatrix=cam["viewmatrix"]), radii,
-                               screenspace_points, normal_map, out_normal_view, albedo_map, roughness_map, metallic_map,
-                               occlusion_map, depth_pos, lights, extra_loss)
-        if os.environ.get("GIGS_ASYNC_CHECK", "step") == "lazy":
-            # diagnostic: do not wait for this step's forward here; an overflow of step k is then only noticed at step k + 1
-            res["num_rendered"] = -1
-            return res
-        try:
-            res["num_rendered"] = self.graster.check()
-            return res
-        except BinningOverflow:
-            _restore_grads(pre_grads)
-    raise RuntimeError("Stage2Step: the binning capacity kept overflowing")
-
-
-def _fused_begin(self, start_event=None):
-    """Starts light.build_mips() on a side stream, called from inside the rasterizer's forward as soon as its
-    kernels up to the blend are queued (diff_gaussian_rasterization.after_blend; the host call returns after
-    the binning read-back, while the GPU is still sorting): the GGX pre-filter is independent of the G-buffer
-    and overlaps the latency-bound sort / blend kernels.  autograd runs a node's backward on the stream of its forward, so the light's
-    backward likewise overlaps the rasterizer's backward."""
-    from stage2_fused import LightMips
-    main = torch.cuda.current_stream()
-    if self.mips is None:
-        # light.base's AccumulateGrad lives on the stream the parameter was created on, its gradient is produced on
-        # the side stream: intended here (autograd inserts the event wait), so the advisory warning is switched off
-        if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        self.side = torch.cuda.Stream()
-        self.mips = LightMips(self.light)
-        self.dummy = torch.zeros(1, device=self.light.base.device)
-        if self.graphs:
-            with torch.no_grad():
-                self.mips(self.dummy)  # builds the cached filter tables outside the capture
-            self.mips = graphed(self.mips, (self.dummy,))
-    # Start when the blend kernel starts (an event the library records right before launching it): that kernel is
-    # a few long serial walks with most CUs idle.  Measured alternatives: starting at once (next to the sort passes,
-    # which then take 0.3-0.5 instead of 0.22 ms) and starting after the blend kernel (next to the VALU-bound SSAO
-    # march only: 4 % slower overall).  GIGS_LIGHT_START=step selects the former.
-    if start_event is not None:
-        self.side.wait_event(start_event)
-    elif os.environ.get("GIGS_LIGHT_START", "blend") == "step":
-        self.side.wait_event(self.step_begin)
-    else:
-        self.side.wait_event(self.blend_begin)
-    import pbr.light as pbr_light
-    # this stepper schedules the light itself: the filters are built HERE, on its side stream (not on the light's own
-    # stream, which serves the op-by-op caller: pbr/light.py), so that their backward runs there too
-    with torch.cuda.stream(self.side), pbr_light.build_on_current_stream():
-        out = self.mips(self.dummy)
-        # what the shade waits for: an event of its own, so that work queued on this stream later (the regularisers,
-        # _fused_step) is not waited for with it
-        if getattr(self, "lights_ready", None) is None:
-            self.lights_ready = torch.cuda.Event()
-        self.lights_ready.record()
-    return out
-
-
-def _fused_step(self, cam, gt_image, view_dirs, st, radii, screenspace_points, normal_map, out_normal_view, albedo_map,
-                roughness_map, metallic_map, occlusion_map, depth_pos, lights, extra_loss=None):
-    """fused=True: everything after the rasterizer is stage2_fused._Stage2Fused (6 kernels instead of ~250)."""
-    from stage2_fused import Stage2FusedBack
-    H, W = cam["image_height"], cam["image_width"]
-    main = torch.cuda.current_stream()
-    # The regularisers (BRDF TV, envmap TV: ~15 small kernels forward, as many backward) read the rasterizer's planes and
-    # the light only -- not the shade, the marches or the loss -- so they go to the light's stream, idle by now, beside the
-    # shade and the SSR march; autograd runs their backward there too, beside the shade backward (GIGS_REG_SIDE=0: on the
-    # caller's stream behind the loss, where they sit on the critical path on both ways: 0.2 ms per iteration at C2).
-    reg_side = self.regularizer is not None and os.environ.get("GIGS_REG_SIDE", "1") == "1"
-    if reg_side:
-        if getattr(self, "raster_done", None) is None:
-            self.raster_done = torch.cuda.Event()
-        self.raster_done.record()  # the rasterizer's planes exist: all the regularisers wait for
-    if getattr(self, "lights_ready", None) is not None:
-        main.wait_event(self.lights_ready)
-    else:
-        main.wait_stream(self.side)
-    for t in lights:
-        t.record_stream(main)
-    args = (normal_map.detach(), out_normal_view.detach(), albedo_map, roughness_map, metallic_map,
-            occlusion_map.detach(), depth_pos.detach(), st.viewmatrix, view_dirs, gt_image, *lights)
-    if self.back is None:
-        # light_stream: the fused node's backward issues its light-texture gradient scatter there (stage2_fused.py) -- the
-        # stream on which _fused_begin built the light's filters, hence on which autograd runs their backward, behind that
-        # scatter.  Not under make_graphed_callables, whose per-callable capture cannot leave a forked stream unjoined
-        cfg = dict(H=H, W=W, gi=self.gi, focal_x=W / (2.0 * cam["tanfovx"]), focal_y=H / (2.0 * cam["tanfovy"]),
-                   light_stream=None if self.graphs else self.side, **self.flags)
-        self.back = Stage2FusedBack(self.brdf_lut, cfg)
-        if self.graphs:
-            # pooled rasterizer planes (fixed addresses) become the graph's static inputs themselves: no staging copies
-            pooled = set(t.untyped_storage().data_ptr() for t in self.pool.buffers.values()) if self.pool else set()
-            pooled |= getattr(self, "_static_storages", set())  # outputs of the graphed rasterizer: fixed addresses too
-            # ... and so are the filtered light levels (static outputs of the light's own graph): read in place, not staged
-            pooled |= set(t.untyped_storage().data_ptr() for t in lights)
-            sample = tuple(a.detach().requires_grad_(a.requires_grad) if a.untyped_storage().data_ptr() in pooled
-                           else a.detach().clone().requires_grad_(a.requires_grad) for a in args)
-            self.back = graphed(self.back, sample)
-    loss, render_rgb, render_direct, IRR = self.back(*args)
-    if extra_loss is not None:
-        loss = loss + extra_loss(normal_map, albedo_map, roughness_map, metallic_map)
-    if reg_side:
-        # queued (host order) behind the fused node so that autograd, which walks later nodes first, starts their backward
-        # before the shade backward; the stream waits only for the rasterizer's planes
-        maps = dict(normal_map=normal_map, albedo_map=albedo_map, roughness_map=roughness_map, metallic_map=metallic_map,
-                    gt_image=gt_image)
-        self.side.wait_event(self.raster_done)
-        with torch.cuda.stream(self.side):
-            reg = self.regularizer(maps)
-        for t in maps.values():
-            t.record_stream(self.side)
-        main.wait_stream(self.side)
-        reg.record_stream(main)
-        loss = loss + reg
-    elif self.regularizer is not None:
-        loss = loss + self.regularizer(dict(normal_map=normal_map, albedo_map=albedo_map, roughness_map=roughness_map,
-                                            metallic_map=metallic_map, gt_image=gt_image))
-    res = dict(loss=loss.detach(), render_rgb=render_rgb, render_direct=render_direct, IRR=IRR,
-               viewspace_points=screenspace_points, radii=radii)
-    if self._defer_backward:
-        res["_loss"] = loss
-        return res
-    loss.backward()
-    return res
-
-
-
-def _close_stepper(self):
-    """Deterministic teardown of everything that owns hipGraphs (WholeStepGraphs, graphed callables, the graphed
-    rasterizer): synchronise, release, synchronise.  The stepper captures again if it is called afterwards.  Steppers and
-    trainers are context managers (`with Stage2Trainer(...) as tr:`) that close on exit."""
-    # the WholeStepGraph objects stay (they remember the binning capacity and count their captures); their graphs go
-    for w in list(getattr(self, "_wholes", {}).values()):
-        w.close()
-    if getattr(self, "whole", None) is not None:
-        self.whole.close()
-    if getattr(self, "geom_cache", None) is not None:
-        self.geom_cache.invalidate()  # the per-view entries (tile lists, occlusion planes, hit lists): device memory
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    if getattr(self, "_captured", False):  # piecewise path: the two graphed callables
-        self.front = Stage2Front(self.light, self.brdf_lut, **self.flags)
-        self.loss_fn = stage2_loss
-        self._captured = False
-    if getattr(self, "graster", None) is not None:
-        self.graster.close()
-    for name in ("graster", "back", "mips"):
-        if getattr(self, name, None) is not None:
-            setattr(self, name, None)
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-
-
-def _enter(self):
-    return self
-
-
-def _exit(self, *exc):
-    self.close()
-    return False
-
-def _cached_geometry_step(self, cfg, cam, raw, gt_image, view_dirs):
-    """One step through the frozen-geometry variants of the whole-step graphs: replayed from the view's entry when there
-    is one, recorded otherwise; a replay that turns out stale (the previous update moved geometry) is repeated as a
-    recording.  Returns None when this camera model has no slot left (more than four models): the caller's other paths."""
-    if self.geom_cache is None:
-        self.geom_cache = GeometryCache(next(iter(raw.values())).device)
-    cache = self.geom_cache
-    vkey = cache.view_key(cam)
-    mode = cache.mode(vkey, raw)
-    for _ in range(3):
-        key = (cfg, mode)
-        whole = self._wholes.get(key)
-        if whole is None:
-            if len(self._wholes) >= 8:
-                return None
-            whole = self._wholes[key] = WholeStepGraph(self, cam, raw, cache=cache, mode=mode)
-        self.whole = whole
-        out = whole(cam, raw, gt_image, view_dirs, vkey=vkey)
-        if out is not None:
-            return out
-        mode = "record"
-    raise RuntimeError("Stage2Step: the frozen-geometry step kept being invalidated")
-
-
-Stage2Step._cached_geometry_step = _cached_geometry_step
-
-
-def _make_inner(self):
-    return Stage2Step(self.light, self.brdf_lut, self.gi, self.sh_degree, graphs=False, fused=True, regularizer=self.regularizer,
-                      **self.flags)
-
-
-Stage2Step._make_inner = _make_inner
-Stage2Step.close = _close_stepper
-Stage2Step.__enter__ = _enter
-Stage2Step.__exit__ = _exit
-
-
-def _leaves(self, g):
-    out, seen = [], set()
-    for t in list(g.values()) + list(self.light.parameters()):
-        for leaf in _grad_leaves(t):
-            if id(leaf) not in seen:
-                seen.add(id(leaf))
-                out.append(leaf)
-    return out
-
-
-Stage2Step._leaves = _leaves
-Stage2Step._eager_async = _eager_async
-Stage2Step._graphed_step = _graphed_step
-Stage2Step._fused_begin = _fused_begin
-Stage2Step._fused_step = _fused_step
-
-
 class _Stage1Inner:
     """One stage-1 iteration of train.py (:266-331) up to the loss: render -> fused G-buffer post-processing ->
     0.8 L1 + 0.2 D-SSIM + masked normal L1 + normal TV (losses.stage1_loss: one autograd node)."""
@@ -1388,7 +1245,7 @@ class _Stage1Inner:
         return res
 
 
-class Stage1Step:
+class Stage1Step(_Stepper):
     """One stage-1 iteration (`iteration <= pbr_iteration`, train.py:266-331, 517-520) with Stage2Step's interface and
     formulations: eager, or -- graphs=True -- the whole iteration from hipGraphs (WholeStepGraph: forward, backward and,
     with `optimizers`, the update), the rasterizer under asynchronous binning.  No light, no shade: the loss reaches
@@ -1400,50 +1257,34 @@ class Stage1Step:
 
     def __init__(self, gi: Dict, sh_degree: int, lambda_dssim: float = 0.2, normal_loss_weight: float = 1.0,
                  normal_tv_weight: float = 1.0, graphs: bool = False, prepare=None, optimizers=None, before_update=None):
+        super().__init__()
         self.gi, self.sh_degree, self.graphs = gi, sh_degree, graphs
         self.weights = (lambda_dssim, normal_loss_weight, normal_tv_weight)
         self.prepare, self.optimizers, self.before_update = prepare, list(optimizers or []), before_update
-        self.whole, self._wholes = None, {}
+        self._no_vd = None  # the graph's (unused) view_dirs input
         self._eager = self._make_inner()
 
     def _make_inner(self):
         return _Stage1Inner(self.gi, self.sh_degree, *self.weights)
 
+    def _leaves(self, raw):
+        return raw.values()
+
     def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], gt_image: torch.Tensor, view_dirs=None):
         raw = g
-        if self.graphs and os.environ.get("GIGS_STEP_GRAPH", "1") == "1" and not getattr(self, "_dense", False):
-            try:
-                cfg = (int(cam["image_height"]), int(cam["image_width"]), float(cam["tanfovx"]), float(cam["tanfovy"]))
-                if self.whole is None or self.whole.cfg != cfg:
-                    self.whole = self._wholes.get(cfg)
-                    if self.whole is None and len(self._wholes) < 4:
-                        self.whole = self._wholes[cfg] = WholeStepGraph(self, cam, g)
-                if self.whole is not None:
-                    if getattr(self, "_no_vd", None) is None:
-                        self._no_vd = torch.zeros(1, device=gt_image.device)  # the graph's (unused) view_dirs input
-                    return self.whole(cam, raw, gt_image, view_dirs if view_dirs is not None else self._no_vd)
-            except DenseScene:
-                self._dense = True
-                for w in self._wholes.values():
-                    w.close()
-                self.whole = None
-                self._wholes.clear()
+        if self.graphs:
+            if view_dirs is None:
+                if self._no_vd is None:
+                    self._no_vd = torch.zeros(1, device=gt_image.device)
+                view_dirs = self._no_vd
+            out = self._graph_step(cam, raw, gt_image, view_dirs)
+            if out is not None:
+                return out
         if self.prepare is not None:
             g = self.prepare(raw)
         res = self._eager(cam, g, gt_image)
-        if self.optimizers:
-            if self.before_update is not None:
-                self.before_update()
-            for o in self.optimizers:
-                o.step()
-            for leaf in raw.values():
-                leaf.grad = None
+        self._eager_update(raw)
         return res
-
-
-Stage1Step.close = _close_stepper
-Stage1Step.__enter__ = _enter
-Stage1Step.__exit__ = _exit
 
 
 def stage2_step(cam: Dict, g: Dict[str, torch.Tensor], sh_degree: int, gi: Dict, light, brdf_lut: torch.Tensor,

@@ -114,17 +114,11 @@ class Relighter:
         binning) when the image, the field of view, the Gaussian tensors or key_extra changed; the camera pose and
         `inputs` are the graph's inputs.  on_capture() runs after every capture (the warm-up runs are real runs)."""
         from diff_gaussian_rasterization import AsyncBinning, BinningOverflow
-        key = (int(cam["image_height"]), int(cam["image_width"]), float(cam["tanfovx"]), float(cam["tanfovy"]),
-               tuple(sorted((k, v.data_ptr()) for k, v in g.items())), key_extra)
+        key = (pipeline.camera_model(cam), tuple(sorted((k, v.data_ptr()) for k, v in g.items())), key_extra)
         for _ in range(4):
             if self._graph is None or self._graph_key != key:
                 if self._capacity <= 0:
-                    probe = pipeline.GraphedRaster(cam, g, self.gi, self.sh_degree, inference=True)
-                    r = probe._probe(cam, g, torch.zeros(3, device=g["means3D"].device))
-                    tiles = ((int(cam["image_height"]) + 15) // 16) * ((int(cam["image_width"]) + 15) // 16)
-                    if pipeline._declined_as_dense(r, tiles):
-                        raise pipeline.DenseScene(f"{r} instances over {tiles} tiles")
-                    self._capacity = max(65536, -(-2 * r // 65536) * 65536)
+                    self._capacity = pipeline.first_capacity(cam, g, self.sh_degree, inference=True)
                 self._bin = AsyncBinning(self._capacity, g["means3D"].device)
                 scalars = {k: v for k, v in cam.items() if not isinstance(v, torch.Tensor)}
 
@@ -143,7 +137,7 @@ class Relighter:
                 out["num_rendered"] = self._bin.check()
                 return out
             except BinningOverflow as ex:
-                self._capacity = -(-int(1.5 * ex.needed) // 65536) * 65536
+                self._capacity = pipeline.grown_capacity(ex.needed)
                 self.close()
         raise RuntimeError(f"{type(self).__name__}: the binning capacity kept overflowing")
 

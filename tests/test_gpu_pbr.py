@@ -244,17 +244,15 @@ def test_stage2_fused_matches_unfused(orc, metallic):
     rays = pipeline.canonical_rays(cams[0], DEV)
     vds = [pipeline.view_dirs_for(c, rays, DEV) for c in camts]
     results = {}
-    for mode in ("unfused", "fused", "fused_graph", "fused_graph_raster", "fused_step_graph"):
+    for mode in ("unfused", "fused", "fused_graph", "fused_step_graph"):
         torch.manual_seed(2)
         light = pbr.CubemapLight(base_res=64, device=DEV)
         g = {k: tt(sc[k], grad=True) for k in GAUSS_KEYS}
         # fused_step_graph: the whole iteration as two hand-captured hipGraphs (pipeline.WholeStepGraph, the default);
-        # fused_graph: glue replayed from hipGraphs, rasterizer launched eagerly with asynchronous binning;
-        # fused_graph_raster: the rasterizer captured too, six make_graphed_callables pieces (GIGS_RASTER_GRAPH=1)
-        os.environ["GIGS_RASTER_GRAPH"] = "1" if mode == "fused_graph_raster" else "0"
+        # fused_graph: glue replayed from hipGraphs, rasterizer launched eagerly with asynchronous binning
         os.environ["GIGS_STEP_GRAPH"] = "1" if mode == "fused_step_graph" else "0"
         step = pipeline.Stage2Step(light, lut, gi, 2, metallic=metallic, fused=mode != "unfused",
-                                   graphs=mode in ("fused_graph", "fused_graph_raster", "fused_step_graph"))
+                                   graphs=mode in ("fused_graph", "fused_step_graph"))
         outs = []
         for ci in (0, 1, 0):
             for t in list(g.values()) + [light.base]:
@@ -266,9 +264,8 @@ def test_stage2_fused_matches_unfused(orc, metallic):
         if mode == "fused_step_graph":
             assert step.whole is not None and step.whole.recaptures == 1  # three views, one capture
         results[mode] = outs
-    os.environ.pop("GIGS_RASTER_GRAPH", None)
     os.environ.pop("GIGS_STEP_GRAPH", None)
-    for mode in ("fused", "fused_graph", "fused_graph_raster", "fused_step_graph"):
+    for mode in ("fused", "fused_graph", "fused_step_graph"):
         for (lu, gu, bu, ru, iu), (lf, gf, bf, rf, irf) in zip(results["unfused"], results[mode]):
             assert abs(lu - lf) <= 2e-6 * max(1.0, abs(lu)), (mode, lu, lf)
             torch.testing.assert_close(irf, iu, rtol=0, atol=2e-6)
@@ -281,7 +278,7 @@ def test_stage2_fused_matches_unfused(orc, metallic):
     assert abs(results["fused_graph"][0][0] - results["fused_graph"][1][0]) > 1e-6
 
 
-@pytest.mark.parametrize("raster", ["step_graph", "graph", "eager_async"])
+@pytest.mark.parametrize("raster", ["step_graph", "eager_async"])
 def test_graphed_step_survives_a_binning_overflow(raster, monkeypatch):
     """The whole-step hipGraph bins into a fixed-capacity buffer; a view with more instances than the capacity raises
     the device-side overflow flag, the capacity grows, the graph is re-captured and the step repeated: same loss,
@@ -289,7 +286,6 @@ def test_graphed_step_survives_a_binning_overflow(raster, monkeypatch):
     import pbr
     import pipeline
     from diff_gaussian_rasterization import AsyncBinning
-    monkeypatch.setenv("GIGS_RASTER_GRAPH", "1" if raster == "graph" else "0")
     monkeypatch.setenv("GIGS_STEP_GRAPH", "1" if raster == "step_graph" else "0")
     sc = scenes.surface_scene(P=20_000, sh_degree=2, seed=4, scale_mu=0.03)
     gi = scenes.GI_DEFAULTS
@@ -309,16 +305,12 @@ def test_graphed_step_survives_a_binning_overflow(raster, monkeypatch):
         if mode == "graph" and raster == "step_graph":
             step.whole = pipeline.WholeStepGraph(step, camt, g)
             step.whole.capacity = 65536  # far below this view's instance count
-        elif mode == "graph" and raster == "graph":
-            step.graster = pipeline.GraphedRaster(camt, g, gi, 2, capacity=65536)
         elif mode == "graph":
             step._abin = AsyncBinning(65536, DEV)  # the eager rasterizer's asynchronous binning, same protocol
         o = step(camt, g, gt, vd)
         torch.cuda.synchronize()
         if mode == "graph" and raster == "step_graph":
             assert step.whole.recaptures == 2 and step.whole.capacity > 65536
-        elif mode == "graph" and raster == "graph":
-            assert step.graster.recaptures == 2 and step.graster.capacity > 65536
         elif mode == "graph":
             assert step._abin.capacity > 65536
         if mode == "graph":
@@ -424,7 +416,6 @@ def test_whole_step_graph_gradient_semantics_and_recapture(monkeypatch):
     import pbr
     import pipeline
     monkeypatch.setenv("GIGS_STEP_GRAPH", "1")
-    monkeypatch.setenv("GIGS_RASTER_GRAPH", "0")
     sc = scenes.surface_scene(P=8000, sh_degree=2, seed=21, scale_mu=0.025)
     gi = scenes.GI_DEFAULTS
     H, W = 176, 224
@@ -565,7 +556,6 @@ def test_whole_step_graph_writes_gradients_into_the_all_reduce_slab(monkeypatch)
     import pbr
     import pipeline
     monkeypatch.setenv("GIGS_STEP_GRAPH", "1")
-    monkeypatch.setenv("GIGS_RASTER_GRAPH", "0")
     sc = scenes.surface_scene(P=6000, sh_degree=2, seed=31, scale_mu=0.025)
     gi = scenes.GI_DEFAULTS
     H, W = 160, 208
@@ -653,44 +643,6 @@ def test_grad_slab_attach_with_sink_does_not_double_gradients():
     assert float(plain.abs().max()) > 0
 
 
-def test_shade_backward_in_two_launches_equals_one(monkeypatch):
-    """GIGS_SHADE_BWD_SPLIT=1: the fused node's backward issues the material gradients on the main stream and the
-    light-texture scatter on the light's stream (gigs_shade_ext.part = 1 / 2): same gradients as the single launch, eager and
-    from the whole-step graphs."""
-    import pbr
-    import pipeline
-    sc = scenes.surface_scene(P=6000, sh_degree=2, seed=41, scale_mu=0.025)
-    gi = scenes.GI_DEFAULTS
-    H, W = 144, 176
-    cam = scenes.orbit_camera(1, 6, W, H, radius=3.5)
-    camt = {k: (tt(v) if isinstance(v, np.ndarray) else v) for k, v in cam.items()}
-    torch.manual_seed(2)
-    gt = torch.rand(3, H, W, device=DEV) * 0.5
-    lut = pbr.get_brdf_lut().to(DEV)
-    vd = pipeline.view_dirs_for(camt, pipeline.canonical_rays(cam, DEV), DEV)
-
-    def run(split, graphs):
-        monkeypatch.setenv("GIGS_SHADE_BWD_SPLIT", split)
-        torch.manual_seed(9)
-        light = pbr.CubemapLight(base_res=64, device=DEV)
-        g = {k: tt(sc[k], grad=True) for k in GAUSS_KEYS}
-        step = pipeline.Stage2Step(light, lut, gi, 2, fused=True, graphs=graphs)
-        for _ in range(2):
-            for t in list(g.values()) + [light.base]:
-                t.grad = None
-            o = step(camt, g, gt, vd)
-        torch.cuda.synchronize()
-        return float(o["loss"]), {k: g[k].grad.clone() for k in ("albedo", "roughness", "metallic")}, light.base.grad.clone()
-
-    ref = run("0", False)
-    for graphs in (False, True):
-        got = run("1", graphs)
-        assert abs(got[0] - ref[0]) <= 2e-6 * max(1.0, abs(ref[0]))
-        for k in ref[1]:
-            assert torch.equal(got[1][k], ref[1][k]) or rel_peak(got[1][k].cpu().numpy(), ref[1][k].cpu().numpy()) < 1e-6, k
-        assert rel_peak(got[2].cpu().numpy(), ref[2].cpu().numpy()) < 2e-3  # float atomics: order-dependent rounding
-
-
 def test_hipgraph_lifetime_is_deterministic(monkeypatch):
     """The round-3 host segfault (hip::Graph::UpdateStreams at the first replay of a fresh exec) came from graph execs that
     a cyclic-GC pass destroyed at an arbitrary moment: WholeStepGraph <-> Stage2Step was a reference cycle.  Now the owner
@@ -705,7 +657,6 @@ def test_hipgraph_lifetime_is_deterministic(monkeypatch):
     import pipeline
     import train_iteration
     monkeypatch.setenv("GIGS_STEP_GRAPH", "1")
-    monkeypatch.setenv("GIGS_RASTER_GRAPH", "0")
     sc = scenes.surface_scene(P=6000, sh_degree=2, seed=21, scale_mu=0.03)
     gi = scenes.GI_DEFAULTS
     H, W = 112, 144

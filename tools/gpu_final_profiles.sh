@@ -17,10 +17,9 @@ python tools/pmc_summary.py gpurun_out/pmc > gpurun_out/${TAG}_pmc_summary.txt
 python bench.py --full --steps 30 --warmup 5 > $OUT/bench_${TAG}_c2.json 2> $OUT/bench_${TAG}.err
 python bench.py --full --config c3 --steps 30 --warmup 5 > $OUT/bench_${TAG}_c3.json 2>> $OUT/bench_${TAG}.err
 python bench.py --full --config c4 --steps 10 --warmup 3 > $OUT/bench_${TAG}_c4.json 2>> $OUT/bench_${TAG}.err
-GIGS_RASTER_GRAPH=1 python bench.py --full --no-cpu-baseline > $OUT/bench_${TAG}_c2_rastergraph.json 2>> $OUT/bench_${TAG}.err
 GIGS_STEP_GRAPH=0 python bench.py --full --no-cpu-baseline > $OUT/bench_${TAG}_c2_eager_raster.json 2>> $OUT/bench_${TAG}.err
 python bench.py --full --start 64 --no-cpu-baseline > $OUT/bench_${TAG}_c2_start64.json 2>> $OUT/bench_${TAG}.err
-for f in c2 c3 c4 c2_rastergraph c2_eager_raster c2_start64; do python -c "
+for f in c2 c3 c4 c2_eager_raster c2_start64; do python -c "
 import json
 d=json.loads(open('$OUT/bench_${TAG}_$f.json').read().strip().splitlines()[-1])
 print('$f', d['value'], d['ms_per_step'], d.get('psnr_vs_oracle_db'))"; done
