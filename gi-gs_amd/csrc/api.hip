@@ -713,6 +713,25 @@ int gigs_ssr_ex(gigs_ctx* ctx, int width, int height, float focal_x, float focal
   HIP_TRY(hipGetLastError());
   return 0;
 }
+int gigs_ssr_multi(gigs_ctx* ctx, int n_lights, int width, int height, float focal_x, float focal_y, float radius, float bias,
+                   float thick, float delta, int step, int start, const float* normal_view, const float* pos, const float* rgb,
+                   const float* albedo, const float* roughness, const float* metallic, const float* F0, float* color,
+                   float* abd, void* scratch, void* stream) {
+  if (n_lights < 1 || n_lights > GIGS_MAX_LIGHTS)
+    return fail(GIGS_ERR_INVALID, "ssr_multi: n_lights=%d outside 1..%d", n_lights, GIGS_MAX_LIGHTS);
+  if (width <= 0 || height <= 0 || !normal_view || !pos || !rgb || !albedo || !metallic || !F0 || !color || !abd)
+    return fail(GIGS_ERR_INVALID, "bad argument");
+  if (width >= (1 << 15) || height >= (1 << 15)) return fail(GIGS_ERR_INVALID, "image side above 32767 pixels");
+  StageScope sc(kSsr, (hipStream_t)stream);
+  (void)roughness;  // as gigs_ssr_ex: the reference's SSR reads no roughness
+  const int rc = gigs::launch_ssr_multi(ctx_of(ctx).opt, n_lights, width, height, focal_x, focal_y, radius, bias, thick, delta,
+                                        step, start, normal_view, pos, rgb, albedo, metallic, F0, color, abd, scratch,
+                                        (hipStream_t)stream);
+  if (rc == -1) return fail(GIGS_ERR_INVALID, "delta=%g gives an unbounded or oversized ray set", (double)delta);
+  if (rc) return fail(GIGS_ERR_HIP, "ray table upload failed");
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 int gigs_ssr_hits(gigs_ctx* ctx, int width, int height, float focal_x, float focal_y, float radius, float bias, float thick,
                   float delta, int step, int start, const float* normal_view, const float* pos, const float* rgb,
                   const float* albedo, const float* roughness, const float* metallic, const float* F0, float* color, float* abd,

@@ -935,6 +935,16 @@ __device__ __forceinline__ bool gi_pixel(const GiParams& p, int& x, int& y, int&
 // 9 % faster (1.29 -> 1.17 ms at C2; 6 waves spill and lose it again)
 #define GIGS_SSR_OCC __attribute__((amdgpu_waves_per_eu(5)))
 #endif
+// The march over K radiance planes (kLights > 1, gigs_ssr_multi) holds 3 (K - 1) more accumulators: they do not fit the
+// single-light budget, so those instances ask for GIGS_SSR_MULTI_WAVES ("Relighting under K maps").
+#ifndef GIGS_SSR_MULTI_WAVES
+#define GIGS_SSR_MULTI_WAVES 4
+#endif
+#if GIGS_GI_WAVES > 0
+#define GIGS_SSR_OCC_L(L) GIGS_SSR_OCC
+#else
+#define GIGS_SSR_OCC_L(L) __attribute__((amdgpu_waves_per_eu((L) == 1 ? 5 : GIGS_SSR_MULTI_WAVES)))
+#endif
 
 template <bool kPow2, int kMode, bool kCert>
 __global__ void __launch_bounds__(256) GIGS_GI_OCC
@@ -1084,8 +1094,12 @@ __device__ __forceinline__ void ssr_finish(v3 diffuse, const Tbn& tbn, v3 pos, s
   abd[2 * HW + pix_id] = gd.z;
 }
 
-template <bool kPow2, int kMode, bool kCert, int kHits = 0>
-__global__ void __launch_bounds__(256) GIGS_SSR_OCC
+// The SSR march of one workgroup, gathering kLights radiance planes at once (rgb, color and abd are [kLights,3,H,W]): WHICH
+// pixel a ray hits does not depend on the radiance (see SsrHits), so every light's sum takes the same hits in the same
+// order, each with the single-light expression -- light l's outputs are the single-light march's with rgb = rgb[l], bit
+// for bit.  The per-wave partial sums go through the same 3 KB of LDS one light at a time.
+template <bool kPow2, int kMode, bool kCert, int kHits = 0, int kLights = 1>
+__global__ void __launch_bounds__(256) GIGS_SSR_OCC_L(kLights)
 ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict__ nrm,
            const float* __restrict__ pos_map, const float* __restrict__ rgb,
            const float* __restrict__ albedo_map, const float* __restrict__ metallic_map,
@@ -1107,7 +1121,9 @@ ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict_
   const size_t pix_id = inside ? (size_t)p.W * y + x : 0;
   const v3 pos = {pos_map[pix_id], pos_map[HW + pix_id], pos_map[2 * HW + pix_id]};
   const Tbn tbn = make_tbn({nrm[pix_id], nrm[HW + pix_id], nrm[2 * HW + pix_id]});
-  v3 diffuse = {0, 0, 0};
+  v3 diffuse[kLights];
+#pragma unroll
+  for (int l = 0; l < kLights; l++) diffuse[l] = {0, 0, 0};
   unsigned hpos = 0;  // kHits: hits of this (pixel, wave) so far / the next entry's position
   if (inside && p.start < p.step && !tbn_never_hits(tbn)) {
     const __amdgpu_buffer_rsrc_t pos_z = z_plane_rsrc(pos_map + 2 * HW, HW);
@@ -1120,9 +1136,13 @@ ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict_
     auto add_hit = [&](int q, float cos_t, float sin_t, int ray) {
       if (q >= 0) {
         // rgb * cosf(theta) * sinf(theta), left to right (forward.cu:824-826)
-        diffuse.x += rgb[q] * cos_t * sin_t;
-        diffuse.y += rgb[HW + q] * cos_t * sin_t;
-        diffuse.z += rgb[2 * HW + q] * cos_t * sin_t;
+#pragma unroll
+        for (int l = 0; l < kLights; l++) {
+          const float* c = rgb + (size_t)l * 3 * HW;
+          diffuse[l].x += c[q] * cos_t * sin_t;
+          diffuse[l].y += c[HW + q] * cos_t * sin_t;
+          diffuse[l].z += c[2 * HW + q] * cos_t * sin_t;
+        }
         if constexpr (kHits == 1) hpos++;
         if constexpr (kHits == 2) {
           if (hpos < hits.capacity) hits.entries[hpos] = make_uint2((unsigned)q, (unsigned)ray);
@@ -1196,16 +1216,42 @@ ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict_
   if constexpr (kHits == 1) {
     if (inside) hits.counts[4 * pix_id + wave] = hpos;
   }
-  s_part[wave][0][lane] = diffuse.x;
-  s_part[wave][1][lane] = diffuse.y;
-  s_part[wave][2][lane] = diffuse.z;
+  // lights 0 .. kLights - 2 through LDS one at a time (multi-light instances only) ...
+#pragma unroll
+  for (int l = 0; l < kLights - 1; l++) {
+    s_part[wave][0][lane] = diffuse[l].x;
+    s_part[wave][1][lane] = diffuse[l].y;
+    s_part[wave][2][lane] = diffuse[l].z;
+    __syncthreads();
+    if (wave == 0 && inside) {
+      diffuse[l].x = ((s_part[0][0][lane] + s_part[1][0][lane]) + s_part[2][0][lane]) + s_part[3][0][lane];
+      diffuse[l].y = ((s_part[0][1][lane] + s_part[1][1][lane]) + s_part[2][1][lane]) + s_part[3][1][lane];
+      diffuse[l].z = ((s_part[0][2][lane] + s_part[1][2][lane]) + s_part[2][2][lane]) + s_part[3][2][lane];
+    }
+    __syncthreads();  // wave 0 has read them before the next light overwrites them
+  }
+  // ... and the last one as the single-light kernel has always done it (this exact form keeps its code unchanged)
+  constexpr int kLast = kLights - 1;
+  s_part[wave][0][lane] = diffuse[kLast].x;
+  s_part[wave][1][lane] = diffuse[kLast].y;
+  s_part[wave][2][lane] = diffuse[kLast].z;
   __syncthreads();
   if (wave != 0 || !inside) return;
-  diffuse.x = ((s_part[0][0][lane] + s_part[1][0][lane]) + s_part[2][0][lane]) + s_part[3][0][lane];
-  diffuse.y = ((s_part[0][1][lane] + s_part[1][1][lane]) + s_part[2][1][lane]) + s_part[3][1][lane];
-  diffuse.z = ((s_part[0][2][lane] + s_part[1][2][lane]) + s_part[2][2][lane]) + s_part[3][2][lane];
-  ssr_finish(diffuse, tbn, pos, pix_id, HW, p.nrays_total, albedo_map, metallic_map, F0_map, color, abd);
+  diffuse[kLast].x = ((s_part[0][0][lane] + s_part[1][0][lane]) + s_part[2][0][lane]) + s_part[3][0][lane];
+  diffuse[kLast].y = ((s_part[0][1][lane] + s_part[1][1][lane]) + s_part[2][1][lane]) + s_part[3][1][lane];
+  diffuse[kLast].z = ((s_part[0][2][lane] + s_part[1][2][lane]) + s_part[2][2][lane]) + s_part[3][2][lane];
+#pragma unroll
+  for (int l = 0; l < kLast; l++)
+    ssr_finish(diffuse[l], tbn, pos, pix_id, HW, p.nrays_total, albedo_map, metallic_map, F0_map,
+               color + (size_t)l * 3 * HW, abd + (size_t)l * 3 * HW);
+  if constexpr (kLast > 0) {
+    color += (size_t)kLast * 3 * HW;
+    abd += (size_t)kLast * 3 * HW;
+  }
+  ssr_finish(diffuse[kLast], tbn, pos, pix_id, HW, p.nrays_total, albedo_map, metallic_map, F0_map, color, abd);
 }
+
+constexpr int kSsrMaxLights = 4;  // GIGS_SSR_LIGHTS_PER_MARCH (include/gigs_hip.h)
 
 // The gather that replaces the march for a view whose hit list is known (see SsrHits): per pixel the four waves' hit
 // sequences are summed in their recorded order, the four partial sums combined as the march combines them, and the same
@@ -1422,6 +1468,58 @@ int launch_ssr(const Options& o, int W, int H, float fx, float fy, float radius,
       else GIGS_SSR_LAUNCH(false, 0, false, 0);
   }
 #undef GIGS_SSR_LAUNCH
+  return 0;
+}
+
+// K radiance planes over one geometry (gigs_ssr_multi): the certification table is built once, then ceil(K / kSsrMaxLights)
+// marches gather up to kSsrMaxLights planes each; a chunk of one light is the single-light kernel itself.
+template <int kLights>
+static void launch_ssr_chunk(const GiParams& p, dim3 grid, int mode, bool pow2, size_t cert, const float2* tab,
+                             const float4* rays, const float* normal, const float* pos, const float* rgb, const float* albedo,
+                             const float* metallic, const float* F0, float* color, float* abd, hipStream_t s) {
+  const SsrHits hits = {nullptr, nullptr, nullptr, 0};
+#define GIGS_SSR_LAUNCH(POW2, MODE, CERT, LDS)                                                                         \
+  hipLaunchKernelGGL((ssr_kernel<POW2, MODE, CERT, 0, kLights>), grid, dim3(256), LDS, s, p, rays, normal, pos, rgb, albedo, \
+                     metallic, F0, color, abd, tab, hits)
+  switch (mode) {
+    case 1: GIGS_SSR_LAUNCH(false, 1, false, 0); break;
+    case 2: GIGS_SSR_LAUNCH(false, 2, false, 0); break;
+    case 3: if (cert) GIGS_SSR_LAUNCH(false, 3, true, cert); else GIGS_SSR_LAUNCH(false, 3, false, 0); break;
+    case 4: if (cert) GIGS_SSR_LAUNCH(false, 4, true, cert); else GIGS_SSR_LAUNCH(false, 4, false, 0); break;
+    default:
+      if (pow2) GIGS_SSR_LAUNCH(true, 0, false, 0);
+      else GIGS_SSR_LAUNCH(false, 0, false, 0);
+  }
+#undef GIGS_SSR_LAUNCH
+}
+
+int launch_ssr_multi(const Options& o, int n_lights, int W, int H, float fx, float fy, float radius, float bias, float thick,
+                     float delta, int step, int start, const float* normal, const float* pos, const float* rgb,
+                     const float* albedo, const float* metallic, const float* F0, float* color, float* abd, void* scratch,
+                     hipStream_t s) {
+  RayTable t;
+  const int rc = get_ray_table(delta, s, t);
+  if (rc) return rc;
+  bool pow2;
+  GiParams p = make_params(o, W, H, fx, fy, radius, bias, thick, step, start, t, /*ssr*/ true, pow2);
+  if (W >= (1 << 15) || H >= (1 << 15)) return -2;
+  const dim3 grid = gi_grid(p);
+  const int mode = gi_march_mode(o, step, start);
+  const size_t cert = (start < step) ? prepare_cert(o, p, mode, pos, scratch, s) : 0;
+  const float2* tab = (const float2*)scratch;
+  const size_t plane = (size_t)3 * W * H;
+  for (int l0 = 0; l0 < n_lights; l0 += kSsrMaxLights) {
+    const int n = min(kSsrMaxLights, n_lights - l0);
+    const float* c_rgb = rgb + l0 * plane;
+    float *c_color = color + l0 * plane, *c_abd = abd + l0 * plane;
+    static_assert(kSsrMaxLights == 4, "one case per chunk size");
+    switch (n) {
+      case 1: launch_ssr_chunk<1>(p, grid, mode, pow2, cert, tab, t.dev, normal, pos, c_rgb, albedo, metallic, F0, c_color, c_abd, s); break;
+      case 2: launch_ssr_chunk<2>(p, grid, mode, pow2, cert, tab, t.dev, normal, pos, c_rgb, albedo, metallic, F0, c_color, c_abd, s); break;
+      case 3: launch_ssr_chunk<3>(p, grid, mode, pow2, cert, tab, t.dev, normal, pos, c_rgb, albedo, metallic, F0, c_color, c_abd, s); break;
+      default: launch_ssr_chunk<4>(p, grid, mode, pow2, cert, tab, t.dev, normal, pos, c_rgb, albedo, metallic, F0, c_color, c_abd, s);
+    }
+  }
   return 0;
 }
 

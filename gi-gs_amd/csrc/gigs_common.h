@@ -330,6 +330,10 @@ int launch_ssr(const Options& o, int W, int H, float fx, float fy, float radius,
                const float* metallic, const float* F0, float* color, float* abd, void* scratch, hipStream_t s,
                int hits_mode = 0, unsigned* hit_counts = nullptr, const unsigned* hit_offsets = nullptr,
                void* hit_entries = nullptr, unsigned hit_capacity = 0);
+int launch_ssr_multi(const Options& o, int n_lights, int W, int H, float fx, float fy, float radius, float bias, float thick,
+                     float delta, int step, int start, const float* normal, const float* pos, const float* rgb,
+                     const float* albedo, const float* metallic, const float* F0, float* color, float* abd, void* scratch,
+                     hipStream_t s);
 int launch_ssr_apply(int W, int H, float delta, const unsigned* offsets, const void* entries, const float* normal,
                      const float* pos, const float* rgb, const float* albedo, const float* metallic, const float* F0,
                      float* color, float* abd, hipStream_t s);

@@ -910,6 +910,63 @@ shade_fwd_kernel(ShadeArgs A) {
   if (A.out_roughness) A.out_roughness[p] = q.r;
 }
 
+// gigs_shade_fwd_multi: the planar forward under K lights.  shade_pixel runs once, with light 0; for every further light
+// only the cube_sample reads and the arithmetic behind them are repeated, on the same taps, in shade_pixel's expressions,
+// and the epilogue is shade_fwd_kernel's (render_rgb and out_linear only) -- light k bit for bit as a single-light call.
+constexpr int kShadeMaxLights = 16;  // GIGS_MAX_LIGHTS (include/gigs_hip.h)
+struct ShadeLights {
+  int K;
+  const float* diffuse[kShadeMaxLights];
+  const float* spec[kShadeMaxLights][8];
+};
+
+__device__ __forceinline__ void shade_relight(const ShadeArgs& A, const float* __restrict__ diffuse,
+                                              const float* const* spec, ShadePix& q) {
+  q.dl_raw = q.has_d ? cube_sample(diffuse, q.td) : v3{0, 0, 0};
+  q.dl = A.occlusion ? q.dl_raw * q.occ : q.dl_raw;
+  q.drgb = {q.dl.x * q.a.x, q.dl.y * q.a.y, q.dl.z * q.a.z};
+  q.s0 = q.has0 ? cube_sample(spec[q.l0], q.t0) : v3{0, 0, 0};
+  q.s1 = {0, 0, 0};
+  if (q.l1 != q.l0) {
+    if (q.has1) q.s1 = cube_sample(spec[q.l1], q.t1);
+    q.sp = {q.s0.x * (1 - q.lf) + q.s1.x * q.lf, q.s0.y * (1 - q.lf) + q.s1.y * q.lf, q.s0.z * (1 - q.lf) + q.s1.z * q.lf};
+  } else {
+    q.sp = q.s0;
+  }
+  q.srgb = {q.sp.x * q.refl.x, q.sp.y * q.refl.y, q.sp.z * q.refl.z};
+}
+
+__global__ void __launch_bounds__(256)
+shade_fwd_multi_kernel(ShadeArgs A, ShadeLights Ls) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= A.H * A.W) return;
+  ShadePix q;
+  shade_pixel(A, p, q);  // A.diffuse / A.spec are light 0's
+  const bool mk = A.mask[p] != 0;
+  const size_t plane = 3 * (size_t)A.cs;
+  for (int k = 0; k < Ls.K; k++) {
+    if (k > 0) shade_relight(A, Ls.diffuse[k], Ls.spec[k], q);
+    float rr[3] = {q.drgb.x + q.srgb.x, q.drgb.y + q.srgb.y, q.drgb.z + q.srgb.z};
+    float dd;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      float x = rr[c];
+      if (A.tone) x = aces(x, dd);
+      x = fminf(fmaxf(x, 0.0f), 1.0f);
+      if (A.gamma) x = lin2srgb(x, dd);
+      rr[c] = mk ? x : 0.0f;
+    }
+    float* out = A.render_rgb + k * plane;
+#pragma unroll
+    for (int c = 0; c < 3; c++) out[p + c * (size_t)A.cs] = rr[c];
+    if (A.out_linear) {
+      float* lin = A.out_linear + k * plane;
+#pragma unroll
+      for (int c = 0; c < 3; c++) lin[p + c * (size_t)A.cs] = srgb2lin(rr[c]);
+    }
+  }
+}
+
 constexpr int kShadeBwdBlock = 1024;     // 16 waves share one set of LDS accumulators
 constexpr int kShadeLdsBudget = 30 * 1024;  // floats (120 KB of the CU's 160 KB)
 
@@ -1506,6 +1563,40 @@ int gigs_shade_fwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
   A.render_rgb = render_rgb; A.diffuse_rgb = diffuse_rgb; A.specular_rgb = specular_rgb; A.diffuse_light = diffuse_light;
   void* tok; gigs_internal_stage_begin(14, stream, &tok);
   hipLaunchKernelGGL(gigs::shade_fwd_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, A);
+  gigs_internal_stage_end(tok);
+  PBR_CHECK_LAUNCH();
+  return 0;
+}
+
+int gigs_shade_fwd_multi(gigs_ctx* ctx, int n_lights, int H, int W, const float* normals, const float* view_dirs,
+                         const float* albedo, const float* roughness, const uint8_t* mask, const float* occlusion,
+                         const float* metallic, const float* const* diffuse, int diffuse_res, int n_levels,
+                         const float* const* spec, const int* spec_res, const float* lut, int lut_w, int lut_h, int tone,
+                         int gamma, float* render_rgb, float* out_linear, void* stream) {
+  (void)ctx;
+  if (n_lights < 1 || n_lights > GIGS_MAX_LIGHTS || !diffuse || !spec)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "shade_fwd_multi: n_lights outside 1..GIGS_MAX_LIGHTS or no diffuse / spec arrays");
+  static_assert(gigs::kShadeMaxLights == GIGS_MAX_LIGHTS, "one light limit");
+  gigs::ShadeArgs A;
+  const int rc = fill_shade(A, H, W, normals, view_dirs, albedo, roughness, mask, occlusion, metallic, nullptr, diffuse[0],
+                            diffuse_res, n_levels, spec, spec_res, lut, lut_w, lut_h, tone, gamma);
+  if (rc) return rc;
+  if (!render_rgb) return gigs_internal_fail(GIGS_ERR_INVALID, "shade_fwd_multi: null output");
+  gigs::ShadeLights Ls;
+  memset(&Ls, 0, sizeof(Ls));
+  Ls.K = n_lights;
+  for (int k = 0; k < n_lights; k++) {
+    if (!diffuse[k]) return gigs_internal_fail(GIGS_ERR_INVALID, "shade_fwd_multi: null diffuse map");
+    Ls.diffuse[k] = diffuse[k];
+    for (int l = 0; l < n_levels; l++) {
+      if (!spec[k * n_levels + l]) return gigs_internal_fail(GIGS_ERR_INVALID, "shade_fwd_multi: null specular level");
+      Ls.spec[k][l] = spec[k * n_levels + l];
+    }
+  }
+  A.ps = 1; A.cs = H * W;  // planar, rough_scale 1, rough_bias 0 (fill_shade)
+  A.render_rgb = render_rgb; A.out_linear = out_linear;
+  void* tok; gigs_internal_stage_begin(14, stream, &tok);
+  hipLaunchKernelGGL(gigs::shade_fwd_multi_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, A, Ls);
   gigs_internal_stage_end(tok);
   PBR_CHECK_LAUNCH();
   return 0;

@@ -63,6 +63,8 @@ SIGNATURES = {
                          C.c_void_p]),
     "gigs_ssr_hits": (_i, [C.c_void_p, _i, _i, _fl, _fl, _fl, _fl, _fl, _fl, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f,
                            _i, _f, _f, _f, C.c_uint, _f, C.c_void_p]),
+    "gigs_ssr_multi": (_i, [C.c_void_p, _i, _i, _i, _fl, _fl, _fl, _fl, _fl, _fl, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f,
+                            _f, C.c_void_p]),
     "gigs_ssr_apply": (_i, [_i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_median3x3": (_i, [_i, _i, _i, _f, _f, C.c_void_p]),
     "gigs_median3x3_backward": (_i, [_i, _i, _i, _f, _f, _f, C.c_void_p]),
@@ -88,6 +90,8 @@ SIGNATURES = {
                             C.POINTER(C.c_void_p), C.c_void_p]),
     "gigs_shade_fwd_ex": (_i, [C.c_void_p, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int), _f, _i, _i, _i, _i, _f, _f, _f, _f, C.c_void_p, C.c_void_p]),
+    "gigs_shade_fwd_multi": (_i, [C.c_void_p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, C.POINTER(C.c_void_p), _i, _i,
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int), _f, _i, _i, _i, _i, _f, _f, C.c_void_p]),
     "gigs_shade_bwd_ex": (_i, [C.c_void_p, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int), _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f,
                                C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),

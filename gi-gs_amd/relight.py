@@ -13,11 +13,18 @@ ops); `fused=True` (default) runs the same arithmetic as five library launches a
 (gigs_gbuffer_post, gigs_shade_fwd_ex in planar layout with the sRGB->linear epilogue, gigs_ssr,
 gigs_stage2_loss_fwd for linear_to_srgb + median + sum) on the rasterizer's [C,H,W] planes.
 
-Reference quirks kept on purpose: the `metallic` branches for F0 are swapped (relight.py:236-240):
+    MultiRelighter(lights, ...)(cam, gaussians, ...)   relight_all.bash's loop over target maps, one view at a time:
+                                              the rasterizer, G-buffer post, SSAO and the SSR march run ONCE, then
+                                              K-light launches (gigs_shade_fwd_multi, gigs_ssr_multi) and K finishes
+    RelightEvaluator(light_names).add(...)    relight_eval.py without the file I/O: per light the PSNR / SSIM of the
+                                              8-bit-quantised prediction against its ground truth, kept on the device
+
+Reference quirks kept on purpose, by Relighter and MultiRelighter alike: the `metallic` branches for F0 are swapped (relight.py:236-240):
 with metallic=True the shade uses the metallic map but SSR receives F0 = 0.04 and a zero metallic plane; with
 metallic=False (`metallic` is the Python bool) SSR receives F0 = (1 - False) * 0.04 + albedo * metallic_map.  The
 per-channel albedo ratio read from albedo_ratio.json (:203-220) scales the shade's albedo only.  Image I/O
-(read_hdr, save_image, the JSON) stays with the caller.
+(read_hdr, save_image, the JSON) stays with the caller.  LPIPS is not computed by RelightEvaluator, as in evaluate.py: it
+needs the `lpips` package and its VGG weights.
 """
 from __future__ import annotations
 
@@ -28,7 +35,7 @@ import torch
 
 import gigs_lib
 import pipeline
-from diff_gaussian_rasterization import Gaussian_SSR, _C as _ops, filters
+from diff_gaussian_rasterization import Gaussian_SSR, _C as _ops, _gi_scratch, filters
 from pbr import CubemapLight, get_brdf_lut, pbr_shading
 from pbr.shade import _ptr_array
 
@@ -56,26 +63,15 @@ def make_light(hdri: torch.Tensor, res: int = 256) -> CubemapLight:
     return light
 
 
-class Relighter:
-    """render_set (relight.py:113-251) without the file I/O: build_mips once, then one call per view."""
+class _ViewGraph:
+    """What Relighter and MultiRelighter share: reusable scratch planes, the fused rasterizer + G-buffer post, and the
+    replay of a whole view from one hipGraph under asynchronous binning."""
 
-    def __init__(self, light: CubemapLight, gi: Dict, sh_degree: int, metallic: bool = False, tone: bool = False,
-                 gamma: bool = False, fused: bool = True, pad_normal: bool = False, brdf_lut: Optional[torch.Tensor] = None,
-                 graphs: bool = False):
-        """graphs=True (with fused): the whole view -- rasterizer under asynchronous binning, filters, SSAO, shade, SSR,
-        sRGB / median / sum -- is captured once into ONE hipGraph and replayed per view (camera pose and view
-        directions are its inputs; image size, field of view, GI settings and the Gaussian tensors are baked in).  The
-        tensors it returns are the graph's static outputs: consume them before the next call."""
-        self.light, self.gi, self.sh_degree = light, gi, sh_degree
-        self.metallic, self.tone, self.gamma = bool(metallic), bool(tone), bool(gamma)
-        self.fused, self.pad_normal = bool(fused) and not pad_normal, bool(pad_normal)
-        self.graphs = bool(graphs) and self.fused
+    def _init_view(self, gi: Dict, sh_degree: int, metallic: bool, graphs: bool) -> None:
+        self.gi, self.sh_degree, self.metallic = gi, sh_degree, bool(metallic)
+        self.graphs = bool(graphs)
         self._graph = self._graph_key = self._bin = None
         self._capacity = 0
-        dev = light.base.device
-        self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(dev)
-        with torch.no_grad():
-            light.build_mips()  # relight.py:141: once per run
         self._scratch = {}
 
     def _buf(self, name, shape, dtype, dev):
@@ -84,30 +80,33 @@ class Relighter:
             t = self._scratch[name] = torch.empty(shape, dtype=dtype, device=dev)
         return t
 
-    @torch.no_grad()
-    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], view_dirs: torch.Tensor,
-                 alpha_mask: Optional[torch.Tensor] = None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
-        if self.graphs:
-            try:
-                return self._graphed(cam, g, view_dirs, alpha_mask, albedo_ratio)
-            except pipeline.DenseScene:
-                self.graphs = False
-        if self.fused:
-            return self._fused(cam, g, view_dirs, alpha_mask, albedo_ratio)
-        return self._unfused(cam, g, view_dirs, alpha_mask, albedo_ratio)
-
-    # -- the fused sequence replayed from one hipGraph --------------------------------------------------------------
-    def _graphed(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
-        names = ("render_rgb", "render_direct", "IRR", "occlusion", "depth_map", "normal_map", "normal_mask", "radii")
-
-        def core(c, vd):
-            o = self._fused(c, g, vd, None, albedo_ratio)
-            return tuple(o[n] for n in names)
-
-        out = self._replay(cam, g, (view_dirs,), core, names, None if albedo_ratio is None else tuple(albedo_ratio))
-        if alpha_mask is not None:
-            out["render_rgb"] = out["render_rgb"] * alpha_mask
-        return out
+    def _gbuffer(self, cam, g):
+        """The rasterizer (inference, derived normals, SSAO) and gigs_gbuffer_post, then relight.py:236-240's F0 branch."""
+        dev = g["means3D"].device
+        background = torch.zeros(3, device=dev)
+        (out, _, st) = pipeline.rasterize(cam, g, self.sh_degree, background, self.gi, inference=True, derive_normal=True)
+        (_, radii, _, depth_map, _, normal_map, occlusion, albedo_map, roughness_map, metallic_map, out_normal_view,
+         depth_pos) = out
+        H, W = cam["image_height"], cam["image_width"]
+        new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
+        normals_view, onv = new("normals_view", 3, H, W), new("onv", 3, H, W)
+        mask_u8 = self._buf("mask_u8", (H, W), torch.uint8, dev)
+        mask_f = new("mask_f", 1, H, W)
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        vm = st.viewmatrix.contiguous().float()
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream().cuda_stream
+            gigs_lib.check(_lib.gigs_gbuffer_post(H, W, p(normal_map), p(out_normal_view), p(vm), p(normals_view), p(mask_u8),
+                                                  p(mask_f), p(onv), s), "gbuffer_post")
+            if self.metallic:
+                F0 = torch.full_like(albedo_map, 0.04)
+                metallic_in = torch.zeros_like(roughness_map)
+            else:
+                F0 = torch.addcmul(torch.full_like(albedo_map, (1.0 - float(self.metallic)) * 0.04), albedo_map, metallic_map)
+                metallic_in = metallic_map
+        return dict(radii=radii, depth_map=depth_map, occlusion=occlusion, albedo_map=albedo_map,
+                    roughness_map=roughness_map, metallic_map=metallic_map, depth_pos=depth_pos, normals_view=normals_view,
+                    onv=onv, mask_u8=mask_u8, mask_f=mask_f, F0=F0, metallic_in=metallic_in)
 
     def _replay(self, cam, g, inputs, core, names, key_extra=None, on_capture=None):
         """Replay the view graph of core(cam, *inputs) -> tuple named `names`, capturing it first (under asynchronous
@@ -148,6 +147,58 @@ class Relighter:
             self._graph = self._graph_key = None
             torch.cuda.synchronize()
 
+    @staticmethod
+    def _albedo_shade(albedo_map, albedo_ratio):
+        """relight.py:203-220: the albedo ratio scales the shade's albedo only."""
+        if albedo_ratio is None:
+            return albedo_map
+        return albedo_map * torch.as_tensor(albedo_ratio, dtype=torch.float32, device=albedo_map.device)[:, None, None]
+
+
+class Relighter(_ViewGraph):
+    """render_set (relight.py:113-251) without the file I/O: build_mips once, then one call per view."""
+
+    def __init__(self, light: CubemapLight, gi: Dict, sh_degree: int, metallic: bool = False, tone: bool = False,
+                 gamma: bool = False, fused: bool = True, pad_normal: bool = False, brdf_lut: Optional[torch.Tensor] = None,
+                 graphs: bool = False):
+        """graphs=True (with fused): the whole view -- rasterizer under asynchronous binning, filters, SSAO, shade, SSR,
+        sRGB / median / sum -- is captured once into ONE hipGraph and replayed per view (camera pose and view
+        directions are its inputs; image size, field of view, GI settings and the Gaussian tensors are baked in).  The
+        tensors it returns are the graph's static outputs: consume them before the next call."""
+        self.light = light
+        self.tone, self.gamma = bool(tone), bool(gamma)
+        self.fused, self.pad_normal = bool(fused) and not pad_normal, bool(pad_normal)
+        self._init_view(gi, sh_degree, metallic, bool(graphs) and self.fused)
+        dev = light.base.device
+        self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(dev)
+        with torch.no_grad():
+            light.build_mips()  # relight.py:141: once per run
+
+    @torch.no_grad()
+    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], view_dirs: torch.Tensor,
+                 alpha_mask: Optional[torch.Tensor] = None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        if self.graphs:
+            try:
+                return self._graphed(cam, g, view_dirs, alpha_mask, albedo_ratio)
+            except pipeline.DenseScene:
+                self.graphs = False
+        if self.fused:
+            return self._fused(cam, g, view_dirs, alpha_mask, albedo_ratio)
+        return self._unfused(cam, g, view_dirs, alpha_mask, albedo_ratio)
+
+    # -- the fused sequence replayed from one hipGraph --------------------------------------------------------------
+    def _graphed(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
+        names = ("render_rgb", "render_direct", "IRR", "occlusion", "depth_map", "normal_map", "normal_mask", "radii")
+
+        def core(c, vd):
+            o = self._fused(c, g, vd, None, albedo_ratio)
+            return tuple(o[n] for n in names)
+
+        out = self._replay(cam, g, (view_dirs,), core, names, None if albedo_ratio is None else tuple(albedo_ratio))
+        if alpha_mask is not None:
+            out["render_rgb"] = out["render_rgb"] * alpha_mask
+        return out
+
     # -- the reference's op sequence, operator by operator ------------------------------------------------------
     def _unfused(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
         dev = g["means3D"].device
@@ -185,38 +236,17 @@ class Relighter:
 
     # -- the same arithmetic as five launches behind the rasterizer ----------------------------------------------
     def _fused(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
-        dev = g["means3D"].device
-        background = torch.zeros(3, device=dev)
-        (out, _, st) = pipeline.rasterize(cam, g, self.sh_degree, background, self.gi, inference=True, derive_normal=True)
-        (_, radii, _, depth_map, _, normal_map, occlusion, albedo_map, roughness_map, metallic_map, out_normal_view,
-         depth_pos) = out
-        H, W = cam["image_height"], cam["image_width"]
-        new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
-        normals_view, onv = new("normals_view", 3, H, W), new("onv", 3, H, W)
-        mask_u8 = self._buf("mask_u8", (H, W), torch.uint8, dev)
-        mask_f = new("mask_f", 1, H, W)
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        albedo_shade = albedo_map
-        if albedo_ratio is not None:
-            albedo_shade = albedo_map * torch.as_tensor(albedo_ratio, dtype=torch.float32, device=dev)[:, None, None]
-        vm = st.viewmatrix.contiguous().float()
-        with torch.cuda.device(dev):
-            s = torch.cuda.current_stream().cuda_stream
-            gigs_lib.check(_lib.gigs_gbuffer_post(H, W, p(normal_map), p(out_normal_view), p(vm), p(normals_view), p(mask_u8),
-                                                  p(mask_f), p(onv), s), "gbuffer_post")
-            if self.metallic:
-                F0 = torch.full_like(albedo_map, 0.04)
-                metallic_in = torch.zeros_like(roughness_map)
-            else:
-                F0 = torch.addcmul(torch.full_like(albedo_map, (1.0 - float(self.metallic)) * 0.04), albedo_map, metallic_map)
-                metallic_in = metallic_map
-            render_direct, IRR, render_rgb = self._shade_ssr(cam, view_dirs, normals_view, mask_u8, mask_f, onv, depth_pos,
-                                                             albedo_shade, albedo_map, roughness_map, metallic_map,
-                                                             occlusion, F0, metallic_in)
+        b = self._gbuffer(cam, g)
+        with torch.cuda.device(b["albedo_map"].device):
+            render_direct, IRR, render_rgb = self._shade_ssr(
+                cam, view_dirs, b["normals_view"], b["mask_u8"], b["mask_f"], b["onv"], b["depth_pos"],
+                self._albedo_shade(b["albedo_map"], albedo_ratio), b["albedo_map"], b["roughness_map"], b["metallic_map"],
+                b["occlusion"], b["F0"], b["metallic_in"])
         if alpha_mask is not None:
             render_rgb = render_rgb * alpha_mask
-        return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=occlusion, depth_map=depth_map,
-                    normal_map=normals_view, normal_mask=mask_u8.bool()[None], radii=radii)
+        return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=b["occlusion"],
+                    depth_map=b["depth_map"], normal_map=b["normals_view"], normal_mask=b["mask_u8"].bool()[None],
+                    radii=b["radii"])
 
     def _shade_ssr(self, cam, view_dirs, normals_view, mask_u8, mask_f, onv, depth_pos, albedo_shade, albedo_map,
                    roughness_map, metallic_map, occlusion, F0, metallic_in):
@@ -252,3 +282,169 @@ class Relighter:
                                                      p(roughness_map), p(metallic_in), p(render_rgb), p(acc), p(loss), s),
                            "stage2_loss_fwd")
         return render_direct, IRR, render_rgb
+
+
+MAX_LIGHTS = 16  # GIGS_MAX_LIGHTS (include/gigs_hip.h)
+_MULTI_NAMES = ("render_rgb", "render_direct", "IRR", "occlusion", "depth_map", "normal_map", "normal_mask", "radii")
+
+
+class MultiRelighter(_ViewGraph):
+    """One view under K environment maps (relight_all.bash's list of target maps) at the cost of one G-buffer: the
+    rasterizer, G-buffer post, SSAO and the SSR march do not depend on the light, so they run once; the shade samples the
+    K lights at the same cube taps (gigs_shade_fwd_multi), the march gathers the K radiance planes at the same hits
+    (gigs_ssr_multi), and the finish render_rgb = render_direct + median3x3(linear_to_srgb(IRR)) runs per light.
+    Light k's outputs equal Relighter(lights[k], fused=True)'s bit for bit, with the same reference quirks (module
+    docstring).  render_rgb, render_direct and IRR are [K,3,H,W]; the light-independent planes are returned once.
+
+    graphs=True captures the whole K-light view into one hipGraph, as Relighter(graphs=True) does (same replay, binning
+    and DenseScene fallback); its outputs are the graph's static tensors: consume them before the next call."""
+
+    def __init__(self, lights: Sequence[CubemapLight], gi: Dict, sh_degree: int, metallic: bool = False,
+                 tone: bool = False, gamma: bool = False, graphs: bool = False, brdf_lut: Optional[torch.Tensor] = None):
+        lights = list(lights)
+        if not 1 <= len(lights) <= MAX_LIGHTS:
+            raise ValueError(f"MultiRelighter: 1..{MAX_LIGHTS} lights, got {len(lights)}")
+        res = {tuple(l.base.shape) for l in lights}
+        if len(res) != 1:
+            raise ValueError(f"MultiRelighter: the lights differ in base resolution: {sorted(res)}")
+        self.lights = lights
+        self.tone, self.gamma = bool(tone), bool(gamma)
+        self._init_view(gi, sh_degree, metallic, graphs)
+        dev = lights[0].base.device
+        self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(dev)
+        with torch.no_grad():
+            for light in lights:
+                light.build_mips()  # relight.py:141: once per run and light
+        levels = {tuple(int(s.shape[1]) for s in l.specular) for l in lights}
+        if len(levels) != 1 or len({int(l.diffuse.shape[1]) for l in lights}) != 1:
+            raise ValueError("MultiRelighter: the lights' mip chains differ in level count or resolution")
+
+    @torch.no_grad()
+    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], view_dirs: torch.Tensor,
+                 alpha_mask: Optional[torch.Tensor] = None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        if self.graphs:
+            try:
+                def core(c, vd):
+                    o = self._fused(c, g, vd, None, albedo_ratio)
+                    return tuple(o[n] for n in _MULTI_NAMES)
+
+                out = self._replay(cam, g, (view_dirs,), core, _MULTI_NAMES,
+                                   None if albedo_ratio is None else tuple(albedo_ratio))
+                if alpha_mask is not None:
+                    out["render_rgb"] = out["render_rgb"] * alpha_mask
+                return out
+            except pipeline.DenseScene:
+                self.graphs = False
+        return self._fused(cam, g, view_dirs, alpha_mask, albedo_ratio)
+
+    def _fused(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
+        b = self._gbuffer(cam, g)
+        albedo_map, roughness_map = b["albedo_map"], b["roughness_map"]
+        dev = albedo_map.device
+        gi = self.gi
+        K = len(self.lights)
+        H, W = cam["image_height"], cam["image_width"]
+        render_direct, IRR, render_rgb = (torch.empty((K, 3, H, W), device=dev) for _ in range(3))
+        linear_rgb, abd = self._buf("linear_rgb_k", (K, 3, H, W), torch.float32, dev), self._buf("abd_k", (K, 3, H, W),
+                                                                                                 torch.float32, dev)
+        acc, loss = self._buf("acc", (4 + 4 * 256,), torch.float32, dev), self._buf("loss", (1,), torch.float32, dev)
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        spec = [[s.contiguous() for s in light.specular] for light in self.lights]
+        L = len(spec[0])
+        diffuse_ptr = _ptr_array([light.diffuse for light in self.lights])
+        spec_ptr = _ptr_array([s for chain in spec for s in chain])
+        spec_res = (C.c_int * L)(*[int(s.shape[1]) for s in spec[0]])
+        lut = self.brdf_lut
+        vd = view_dirs.contiguous().float()
+        scratch = _gi_scratch(W, H, dev)
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream().cuda_stream
+            gigs_lib.check(_lib.gigs_shade_fwd_multi(
+                gigs_lib.ctx_ptr(), K, H, W, p(b["normals_view"]), p(vd), p(self._albedo_shade(albedo_map, albedo_ratio)),
+                p(roughness_map), p(b["mask_u8"]), p(b["occlusion"]), p(b["metallic_map"]) if self.metallic else None,
+                diffuse_ptr, int(self.lights[0].diffuse.shape[1]), L, spec_ptr, spec_res, p(lut), int(lut.shape[-2]),
+                int(lut.shape[-3]), int(self.tone), int(self.gamma), p(render_direct), p(linear_rgb), s), "shade_fwd_multi")
+            gigs_lib.check(_lib.gigs_ssr_multi(
+                gigs_lib.ctx_ptr(), K, W, H, float(W / (2.0 * cam["tanfovx"])), float(H / (2.0 * cam["tanfovy"])),
+                float(gi["radius"]), float(gi["bias"]), float(gi["thick"]), float(gi["delta"]), int(gi["step"]),
+                int(gi["start"]), p(b["onv"]), p(b["depth_pos"]), p(linear_rgb), p(albedo_map), p(roughness_map),
+                p(b["metallic_in"]), p(b["F0"]), p(IRR), p(abd), p(scratch), s), "ssr_multi")
+            for k in range(K):  # the loss gigs_stage2_loss_fwd also forms is unused
+                gigs_lib.check(_lib.gigs_stage2_loss_fwd(H, W, p(render_direct[k]), p(IRR[k]), p(render_direct[k]),
+                                                         p(b["mask_f"]), p(roughness_map), p(b["metallic_in"]),
+                                                         p(render_rgb[k]), p(acc), p(loss), s), "stage2_loss_fwd")
+        if alpha_mask is not None:
+            render_rgb = render_rgb * alpha_mask
+        return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=b["occlusion"],
+                    depth_map=b["depth_map"], normal_map=b["normals_view"], normal_mask=b["mask_u8"].bool()[None],
+                    radii=b["radii"])
+
+
+def quantize_8bit(x: torch.Tensor) -> torch.Tensor:
+    """What torchvision.utils.save_image -> PNG -> / 255 makes of a float image: trunc(clamp(x * 255 + 0.5, 0, 255)) / 255
+    (save_image's mul(255).add_(0.5).clamp_(0, 255).to(uint8); relight_eval.py reads the PNG and divides by 255)."""
+    return torch.trunc(torch.clamp(x * 255 + 0.5, 0, 255)) / 255
+
+
+class RelightEvaluator:
+    """relight_eval.py without the file I/O or LPIPS: per light and view the PSNR (mean of the per-channel PSNRs) and SSIM
+    (the training loss's) of the 8-bit-quantised prediction against that light's ground truth, bilinearly resized to the
+    prediction's size first (align_corners=False, relight_eval.py:54).  The records stay on the device (gigs_image_metrics
+    writes row *slot of a per-light table and advances the slot); results() reads them back once."""
+
+    def __init__(self, light_names: Sequence[str], capacity: int = 1024, device="cuda"):
+        self.names = list(light_names)
+        if not self.names:
+            raise ValueError("RelightEvaluator: no light names")
+        self._cap = int(capacity)
+        self._rec = torch.zeros((len(self.names), self._cap, 7), dtype=torch.float64, device=device)
+        self._slot = torch.zeros(len(self.names), dtype=torch.int32, device=device)
+        self._n = 0
+        self._done = []
+        self._scratch = None
+
+    @torch.no_grad()
+    def add(self, render_rgb: torch.Tensor, gt: torch.Tensor) -> None:
+        """render_rgb [K,3,H,W] (MultiRelighter's), gt [K,3,h,w] in [0, 1]; light k is self.names[k]."""
+        import torch.nn.functional as F
+        from evaluate import image_metrics
+        K = len(self.names)
+        if render_rgb.dim() != 4 or gt.dim() != 4 or render_rgb.shape[0] != K or gt.shape[0] != K or render_rgb.shape[1] != 3:
+            raise ValueError(f"RelightEvaluator.add: render_rgb and gt must be [{K},3,H,W]")
+        if self._n >= self._cap:
+            self._flush()
+        H, W = render_rgb.shape[-2:]
+        pred = quantize_8bit(render_rgb.float())
+        gt = gt.float()
+        if tuple(gt.shape[-2:]) != (H, W):
+            gt = F.interpolate(gt, size=(H, W), mode="bilinear", align_corners=False)
+        nbytes = int(_lib.gigs_image_metrics_scratch_bytes(3, H, W))
+        if self._scratch is None or self._scratch.numel() < nbytes:
+            self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=render_rgb.device)
+        for k in range(K):
+            image_metrics(pred[k], gt[k], scratch=self._scratch, slot=self._slot[k:k + 1], out=self._rec[k])
+        self._n += 1
+
+    def _flush(self) -> None:
+        if self._n:
+            self._done.append(self._rec[:, :self._n].cpu())
+            self._slot.zero_()
+            self._n = 0
+
+    def records(self) -> torch.Tensor:
+        """[K, n_views, 7] float64 on the host: image_metrics' records {mse_r, mse_g, mse_b, psnr, ssim, -, -}."""
+        self._flush()
+        return torch.cat(self._done, dim=1) if self._done else torch.zeros((len(self.names), 0, 7), dtype=torch.float64)
+
+    def results(self) -> Dict[str, Dict[str, float]]:
+        """{light name: {"psnr_avg", "ssim_avg", "n_views"}}: relight_eval.py's per-light means."""
+        rec = self.records()
+        n = int(rec.shape[1])
+        out = {}
+        for k, name in enumerate(self.names):
+            if n == 0:
+                out[name] = {"psnr_avg": float("nan"), "ssim_avg": float("nan"), "n_views": 0}
+            else:
+                out[name] = {"psnr_avg": float(rec[k, :, 3].sum() / n), "ssim_avg": float(rec[k, :, 4].sum() / n),
+                             "n_views": n}
+        return out

@@ -198,6 +198,18 @@ int gigs_ssr_apply(int width, int height, float delta, const unsigned* offsets, 
                    const float* pos, const float* rgb, const float* albedo, const float* metallic, const float* F0,
                    float* color, float* abd, void* stream);
 
+/* The indirect-light march over K radiance planes (gigs-hip extension; relighting one view under K environment maps).
+ * rgb, color and abd are [K,3,H,W]; the hits depend on normal_view / pos only, so every pixel marches once per group of up
+ * to GIGS_SSR_LIGHTS_PER_MARCH planes and gathers them all (ceil(K / that) marches; the certification table is built once).
+ * color[k] and abd[k] equal gigs_ssr_ex with rgb = rgb[k] bit for bit, in every march mode (abd = the gathered irradiance
+ * times kD before the albedo: it depends on the light).  1 <= K <= GIGS_MAX_LIGHTS, else GIGS_ERR_INVALID. */
+#define GIGS_MAX_LIGHTS 16
+#define GIGS_SSR_LIGHTS_PER_MARCH 4
+int gigs_ssr_multi(gigs_ctx* ctx, int n_lights, int width, int height, float focal_x, float focal_y, float radius, float bias,
+                   float thick, float delta, int step, int start, const float* normal_view, const float* pos, const float* rgb,
+                   const float* albedo, const float* roughness, const float* metallic, const float* F0, float* color,
+                   float* abd, void* scratch, void* stream);
+
 /* kornia.filters.median_blur(x[None], (3,3))[0] as called at
  * R/diff_gaussian_rasterization/__init__.py:478, 504 (zero padding, NaN-propagating). */
 int gigs_median3x3(int channels, int height, int width, const float* in, float* out, void* stream);
@@ -336,6 +348,16 @@ int gigs_shade_fwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
                       int n_levels, const float* const* spec, const int* spec_res, const float* lut,
                       int lut_w, int lut_h, int tone, int gamma, float* render_rgb, float* diffuse_rgb,
                       float* specular_rgb, float* diffuse_light, const gigs_shade_ext* ext, void* stream);
+/* gigs_shade_fwd_ex in the planar layout (ext->planar = 1, rough_scale 1, bias 0, no background) under K lights at once
+ * (gigs-hip extension): diffuse[k] is light k's diffuse map, spec[k * n_levels + l] its level l; all lights share
+ * diffuse_res, n_levels and spec_res.  The light-independent terms (vectors, cube taps, BRDF LUT, mip level, F0) are
+ * computed once per pixel.  render_rgb[k] ([K,3,H,W]) and out_linear[k] (may be NULL) equal gigs_shade_fwd_ex with light
+ * k bit for bit.  1 <= K <= GIGS_MAX_LIGHTS. */
+int gigs_shade_fwd_multi(gigs_ctx* ctx, int n_lights, int H, int W, const float* normals, const float* view_dirs,
+                         const float* albedo, const float* roughness, const uint8_t* mask, const float* occlusion,
+                         const float* metallic, const float* const* diffuse, int diffuse_res, int n_levels,
+                         const float* const* spec, const int* spec_res, const float* lut, int lut_w, int lut_h, int tone,
+                         int gamma, float* render_rgb, float* out_linear, void* stream);
 int gigs_shade_bwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const float* view_dirs, const float* albedo,
                       const float* roughness, const uint8_t* mask, const float* occlusion,
                       const float* metallic, const float* diffuse, int diffuse_res, int n_levels,
