@@ -6,16 +6,18 @@ normal_eval.py without the file I/O, on the HIP library.
                                                     median -> the float planes render.py saves, plus this view's PSNR
                                                     and SSIM against the composited ground truth, kept on the device;
                                                     light.build_mips() once per run (:142)
-      .results()                                    {"psnr_avg", "ssim_avg", "n_views"}: one read-back
+      .results()                                    {"psnr_avg", "ssim_avg", "n_views"} (+ "lpips_avg" with lpips=):
+                                                    one read-back
     albedo_ratio(gt_albedos, pred_albedos, masks)   render.py:578-586: per-channel median(gt / clamp(pred, 1e-6))
-    albedo_metrics(...)                             render.py:596-631: masked MSE, then PSNR / SSIM of pred * ratio
+    albedo_metrics(...)                             render.py:596-631: masked MSE, then PSNR / SSIM (/ LPIPS) of
+                                                    pred * ratio
     normal_mae(pred_normals, gt_rgba)               normal_eval.py: mean angular error in degrees
 
 The per-view metrics run in libgigs_hip (gigs_image_metrics: per-channel MSE -> the mean of the per-channel PSNRs, as
 utils/image_utils.py:31-33 computes psnr(a, b).mean(); mean SSIM with the training loss's separable window; masked
 MSE; gigs_normal_angular_error for normal_eval.py's get_mae), reduced in double in a fixed order, so a run's numbers
-are the same bit for bit every time.  LPIPS (render.py's lpips_avg, eval_brdf's albedo_lpips) is not computed: it needs
-the `lpips` package and its VGG weights; the results leave it out.
+are the same bit for bit every time.  LPIPS (render.py's lpips_avg, eval_brdf's albedo_lpips) is opt-in: pass an
+`lpips.LPIPS` instance (this package's drop-in, gigs_lpips_vgg) as `lpips=`; without one the results leave it out.
 
 Reference quirks kept on purpose: render.py's F0 branch is not relight.py's (:320-326): with metallic=True F0 =
 (1 - True) * 0.04 + albedo * metallic, i.e. albedo * metallic, and SSR gets the metallic map; otherwise F0 = 0.04 and a
@@ -80,7 +82,7 @@ class NovelViewEvaluator(Relighter):
 
     def __init__(self, light: CubemapLight, gi: Dict, sh_degree: int, metallic: bool = False, tone: bool = False,
                  gamma: bool = False, graphs: bool = True, fused: bool = True, brdf_lut: Optional[torch.Tensor] = None,
-                 capacity: int = 1024):
+                 capacity: int = 1024, lpips=None):
         super().__init__(light, gi, sh_degree, metallic=metallic, tone=tone, gamma=gamma, fused=fused, brdf_lut=brdf_lut,
                          graphs=graphs)
         dev = light.base.device
@@ -90,6 +92,12 @@ class NovelViewEvaluator(Relighter):
         self._slot = torch.zeros(1, dtype=torch.int32, device=dev)
         self._n = 0
         self._done = []
+        # lpips(gt, render_rgb) per view (render.py:381): gigs_lpips_vgg records {lpips, tap 0..4} in a table of their own
+        self.lpips = lpips
+        if lpips is not None:
+            self._lp_rec = torch.zeros((self._cap + 4, 6), dtype=torch.float64, device=dev)
+            self._lp_slot = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._lp_done = []
 
     @torch.no_grad()
     def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], view_dirs: torch.Tensor, gt_image: torch.Tensor,
@@ -101,13 +109,18 @@ class NovelViewEvaluator(Relighter):
         if self.graphs:
             try:
                 out = self._replay(cam, g, (view_dirs, gt_image, alpha_mask), self._core, PLANES,
-                                   on_capture=lambda: self._slot.fill_(self._n))
+                                   on_capture=self._rewind)
             except pipeline.DenseScene:
                 self.graphs = False
         if out is None:
             out = dict(zip(PLANES, self._core(cam, view_dirs, gt_image, alpha_mask, g=g)))
         self._n += 1
         return out
+
+    def _rewind(self) -> None:
+        self._slot.fill_(self._n)
+        if self.lpips is not None:
+            self._lp_slot.fill_(self._n)
 
     def _core(self, cam, view_dirs, gt_image, alpha_mask, g=None):
         g = self._g if g is None else g
@@ -125,6 +138,8 @@ class NovelViewEvaluator(Relighter):
                       normal=(comp(r["normal"]) + 1) / 2, from_depth=(r["from_depth"] + 1) / 2)
         image_metrics(render_rgb, gt, scratch=self._buf("metrics_scratch", (int(_lib.gigs_image_metrics_scratch_bytes(
             3, *render_rgb.shape[1:])),), torch.uint8, dev), slot=self._slot, out=self._rec)
+        if self.lpips is not None:
+            self.lpips.record(gt, render_rgb, slot=self._lp_slot, out=self._lp_rec)
         return tuple(planes[n] for n in PLANES)
 
     def _replay(self, cam, g, inputs, core, names, key_extra=None, on_capture=None):
@@ -195,6 +210,9 @@ class NovelViewEvaluator(Relighter):
         if n:
             self._done.append(self._rec[:n].cpu())
             self._slot.fill_(0)
+            if self.lpips is not None:
+                self._lp_done.append(self._lp_rec[:n].cpu())
+                self._lp_slot.fill_(0)
             self._n = 0
 
     def records(self) -> torch.Tensor:
@@ -202,13 +220,26 @@ class NovelViewEvaluator(Relighter):
         self._flush()
         return torch.cat(self._done) if self._done else torch.zeros((0, 7), dtype=torch.float64)
 
+    def lpips_records(self) -> torch.Tensor:
+        """The per-view LPIPS records so far, [n_views, 6] float64 {lpips, tap 0..4} on the host (needs lpips=)."""
+        if self.lpips is None:
+            raise RuntimeError("NovelViewEvaluator: constructed without lpips=")
+        self._flush()
+        return torch.cat(self._lp_done) if self._lp_done else torch.zeros((0, 6), dtype=torch.float64)
+
     def results(self) -> Dict[str, float]:
-        """render.py:386-395 without lpips: the means of the per-view PSNR and SSIM."""
+        """render.py:386-395: the means of the per-view PSNR and SSIM, and with lpips= the mean of the per-view LPIPS
+        (each the float32 value the lpips call returns, summed in double as render.py:381 does)."""
         rec = self.records()
         n = int(rec.shape[0])
         if n == 0:
-            return {"psnr_avg": float("nan"), "ssim_avg": float("nan"), "n_views": 0}
-        return {"psnr_avg": float(rec[:, 3].sum() / n), "ssim_avg": float(rec[:, 4].sum() / n), "n_views": n}
+            res = {"psnr_avg": float("nan"), "ssim_avg": float("nan"), "n_views": 0}
+        else:
+            res = {"psnr_avg": float(rec[:, 3].sum() / n), "ssim_avg": float(rec[:, 4].sum() / n), "n_views": n}
+        if self.lpips is not None:
+            lp = self.lpips_records()
+            res["lpips_avg"] = float(lp[:, 0].float().double().sum() / n) if n else float("nan")
+        return res
 
 
 def albedo_ratio(gt_albedos: Sequence[torch.Tensor], pred_albedos: Sequence[torch.Tensor],
@@ -221,20 +252,27 @@ def albedo_ratio(gt_albedos: Sequence[torch.Tensor], pred_albedos: Sequence[torc
 
 
 def albedo_metrics(gt_albedos: Sequence[torch.Tensor], pred_albedos: Sequence[torch.Tensor],
-                   masks: Sequence[torch.Tensor], ratio: Optional[torch.Tensor] = None) -> Dict[str, float]:
-    """render.py:596-631 without lpips: per view the masked MSE of the unscaled prediction, then PSNR and SSIM of
-    pred * ratio against gt (all [H,W,3], masked pixels already zeroed as eval_brdf does); means over the views."""
+                   masks: Sequence[torch.Tensor], ratio: Optional[torch.Tensor] = None, lpips=None) -> Dict[str, float]:
+    """render.py:596-631: per view the masked MSE of the unscaled prediction, then PSNR and SSIM of pred * ratio against
+    gt (all [H,W,3], masked pixels already zeroed as eval_brdf does); means over the views.  With lpips= (an
+    lpips.LPIPS) also "albedo_lpips": the mean of lpips(gt, pred * ratio) (:617)."""
     if ratio is None:
         ratio = albedo_ratio(gt_albedos, pred_albedos, masks)
-    psnr = ssim = mse = 0.0
+    psnr = ssim = mse = lp = 0.0
     n = len(gt_albedos)
     for gt, pred, m in zip(gt_albedos, pred_albedos, masks):
         gt_c, pred_c = gt.float().permute(2, 0, 1), pred.float().permute(2, 0, 1)
         mse += float(image_metrics(pred_c, gt_c, mask=m)[5])
-        rec = image_metrics(pred_c * ratio.to(pred_c)[:, None, None], gt_c)
+        scaled = pred_c * ratio.to(pred_c)[:, None, None]
+        rec = image_metrics(scaled, gt_c)
         psnr += float(rec[3])
         ssim += float(rec[4])
-    return {"albedo_psnr": psnr / n, "albedo_ssim": ssim / n, "roughmse": mse / n}
+        if lpips is not None:
+            lp += float(lpips(gt_c, scaled).reshape(()))
+    res = {"albedo_psnr": psnr / n, "albedo_ssim": ssim / n, "roughmse": mse / n}
+    if lpips is not None:
+        res["albedo_lpips"] = lp / n
+    return res
 
 
 def normal_mae(pred_normals: Sequence[torch.Tensor], gt_rgba: Sequence[torch.Tensor]) -> float:

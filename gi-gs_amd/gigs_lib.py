@@ -114,6 +114,10 @@ SIGNATURES = {
     "gigs_image_metrics_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
     "gigs_image_metrics": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_normal_angular_error": (_i, [_i, _i, _f, _f, _i, _f, _f, _f, C.c_void_p]),
+    "gigs_lpips_vgg_weight_floats": (C.c_size_t, []),
+    "gigs_lpips_vgg_pack": (_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _f, C.c_void_p]),
+    "gigs_lpips_vgg_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
+    "gigs_lpips_vgg": (_i, [_i, _i, _i, _f, _f, _i, _f, _f, _f, _f, C.POINTER(C.c_void_p), C.c_void_p]),
     "gigs_tv_loss_fwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_bwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_masked_l1_fwd": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),

@@ -23,8 +23,8 @@ Reference quirks kept on purpose, by Relighter and MultiRelighter a
 with metallic=True the shade uses the metallic map but SSR receives F0 = 0.04 and a zero metallic plane; with
 metallic=False (`metallic` is the Python bool) SSR receives F0 = (1 - False) * 0.04 + albedo * metallic_map.  The
 per-channel albedo ratio read from albedo_ratio.json (:203-220) scales the shade's albedo only.  Image I/O
-(read_hdr, save_image, the JSON) stays with the caller.  LPIPS is not computed by RelightEvaluator, as in evaluate.py: it
-needs the `lpips` package and its VGG weights.
+(read_hdr, save_image, the JSON) stays with the caller.  RelightEvaluator computes LPIPS when given an `lpips.LPIPS`
+(this package's drop-in, gigs_lpips_vgg) as `lpips=`, as in evaluate.py.
 """
 from __future__ import annotations
 
@@ -387,12 +387,13 @@ def quantize_8bit(x: torch.Tensor) -> torch.Tensor:
 
 
 class RelightEvaluator:
-    """relight_eval.py without the file I/O or LPIPS: per light and view the PSNR (mean of the per-channel PSNRs) and SSIM
-    (the training loss's) of the 8-bit-quantised prediction against that light's ground truth, bilinearly resized to the
-    prediction's size first (align_corners=False, relight_eval.py:54).  The records stay on the device (gigs_image_metrics
-    writes row *slot of a per-light table and advances the slot); results() reads them back once."""
+    """relight_eval.py without the file I/O: per light and view the PSNR (mean of the per-channel PSNRs) and SSIM (the
+    training loss's) of the 8-bit-quantised prediction against that light's ground truth, bilinearly resized to the
+    prediction's size first (align_corners=False, relight_eval.py:54).  With lpips= (an lpips.LPIPS) also LPIPS of the same
+    two images, the K lights of a view as one batch.  The records stay on the device (gigs_image_metrics and
+    gigs_lpips_vgg write row *slot of a table and advance the slot); results() reads them back once."""
 
-    def __init__(self, light_names: Sequence[str], capacity: int = 1024, device="cuda"):
+    def __init__(self, light_names: Sequence[str], capacity: int = 1024, device="cuda", lpips=None):
         self.names = list(light_names)
         if not self.names:
             raise ValueError("RelightEvaluator: no light names")
@@ -402,6 +403,11 @@ class RelightEvaluator:
         self._n = 0
         self._done = []
         self._scratch = None
+        self.lpips = lpips
+        if lpips is not None:  # row v * K + k: view v, light k
+            self._lp_rec = torch.zeros((self._cap * len(self.names), 6), dtype=torch.float64, device=device)
+            self._lp_slot = torch.zeros(1, dtype=torch.int32, device=device)
+            self._lp_done = []
 
     @torch.no_grad()
     def add(self, render_rgb: torch.Tensor, gt: torch.Tensor) -> None:
@@ -423,12 +429,17 @@ class RelightEvaluator:
             self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=render_rgb.device)
         for k in range(K):
             image_metrics(pred[k], gt[k], scratch=self._scratch, slot=self._slot[k:k + 1], out=self._rec[k])
+        if self.lpips is not None:
+            self.lpips.record(gt, pred, slot=self._lp_slot, out=self._lp_rec)
         self._n += 1
 
     def _flush(self) -> None:
         if self._n:
             self._done.append(self._rec[:, :self._n].cpu())
             self._slot.zero_()
+            if self.lpips is not None:
+                self._lp_done.append(self._lp_rec[:self._n * len(self.names)].cpu())
+                self._lp_slot.zero_()
             self._n = 0
 
     def records(self) -> torch.Tensor:
@@ -436,10 +447,22 @@ class RelightEvaluator:
         self._flush()
         return torch.cat(self._done, dim=1) if self._done else torch.zeros((len(self.names), 0, 7), dtype=torch.float64)
 
+    def lpips_records(self) -> torch.Tensor:
+        """[K, n_views, 6] float64 on the host: gigs_lpips_vgg's records {lpips, tap 0..4} (needs lpips=)."""
+        if self.lpips is None:
+            raise RuntimeError("RelightEvaluator: constructed without lpips=")
+        self._flush()
+        K = len(self.names)
+        if not self._lp_done:
+            return torch.zeros((K, 0, 6), dtype=torch.float64)
+        return torch.cat(self._lp_done).reshape(-1, K, 6).permute(1, 0, 2).contiguous()
+
     def results(self) -> Dict[str, Dict[str, float]]:
-        """{light name: {"psnr_avg", "ssim_avg", "n_views"}}: relight_eval.py's per-light means."""
+        """{light name: {"psnr_avg", "ssim_avg", "n_views"} (+ "lpips_avg" with lpips=)}: relight_eval.py's per-light
+        means (LPIPS: the float32 values the lpips call returns, summed in double as relight_eval.py:58 does)."""
         rec = self.records()
         n = int(rec.shape[1])
+        lp = self.lpips_records() if self.lpips is not None else None
         out = {}
         for k, name in enumerate(self.names):
             if n == 0:
@@ -447,4 +470,6 @@ class RelightEvaluator:
             else:
                 out[name] = {"psnr_avg": float(rec[k, :, 3].sum() / n), "ssim_avg": float(rec[k, :, 4].sum() / n),
                              "n_views": n}
+            if lp is not None:
+                out[name]["lpips_avg"] = float(lp[k, :, 0].float().double().sum() / n) if n else float("nan")
         return out

@@ -497,6 +497,24 @@ int gigs_image_metrics(int channels, int height, int width, const float* pred, c
                        void* scratch, int* slot, double* out, void* stream);
 int gigs_normal_angular_error(int height, int width, const float* pred, const uint8_t* gt, int gt_channels,
                               void* scratch, int* slot, double* out, void* stream);
+/* LPIPS with the VGG16 backbone (lpips 0.1: net="vgg", lpips=True, spatial=False, eval mode), forward only, f32
+ * arithmetic (the convolutions on f32-input MFMA), the value reduced in double in a fixed order: the same bits on every
+ * call, for an image alone or inside a batch, and for (a, b) and (b, a).
+ * gigs_lpips_vgg_pack: the 13 conv weights [Cout,Cin,3,3] and biases [Cout] of torchvision's vgg16().features (indices
+ *   0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28; host array of device pointers) and the 5 lin weights [C] (lpips'
+ *   lin{k}.model.1.weight) -> `packed` (gigs_lpips_vgg_weight_floats() floats), the layout gigs_lpips_vgg reads.
+ * gigs_lpips_vgg: in0 / in1 [n,3,H,W] planar fp32 (normalize != 0: 2x - 1 first); H, W >= 16, else GIGS_ERR_INVALID.
+ *   `scratch` holds gigs_lpips_vgg_scratch_bytes(n,H,W) bytes (0 for an invalid size).  Record of image i (stride 6) =
+ *   {lpips, mean d of tap 0 .. 4} at out + 6 (*slot + i) and *slot += n (slot == NULL: out + 6 i), as
+ *   gigs_image_metrics.  taps: NULL, or 10 device pointers that receive the raw taps (after the ReLU of conv1_2, conv2_2,
+ *   conv3_3, conv4_3, conv5_3; [n,C,H_l,W_l]) of in0 (taps[0..4]) and in1 (taps[5..9]).  No host synchronisation and no
+ *   allocation: safe to capture in a graph. */
+size_t gigs_lpips_vgg_weight_floats(void);
+int gigs_lpips_vgg_pack(const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, float* packed,
+                        void* stream);
+size_t gigs_lpips_vgg_scratch_bytes(int n, int height, int width);
+int gigs_lpips_vgg(int n, int height, int width, const float* in0, const float* in1, int normalize, const float* packed,
+                   void* scratch, int* slot, double* out, float* const* taps, void* stream);
 int gigs_tv_loss_fwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
                      const float* mask_f, float* scratch, float* loss, void* stream);
 int gigs_tv_loss_bwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
