@@ -769,9 +769,10 @@ activate_bwd_kernel(int P, int K, ActPtrs A, int sh_tiles) {
 __global__ void __launch_bounds__(256)
 densify_stats_kernel(int P, const float* __restrict__ grad2d, const int* __restrict__ radii, float* __restrict__ accum,
                      float* __restrict__ accum_abs, float* __restrict__ accum_abs_max, float* __restrict__ denom,
-                     float* __restrict__ max_radii2D) {
+                     float* __restrict__ max_radii2D, const int* __restrict__ skip) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
+  if (skip && *skip != 0) return;  // guarded form: a captured forward whose binning overflowed adds nothing
   const int r = radii[i];
   if (r <= 0) return;
   const float gx = grad2d[3 * (size_t)i], gy = grad2d[3 * (size_t)i + 1];
@@ -1080,9 +1081,9 @@ int gigs_adam_step_guarded(int n_groups, const gigs_adam_group* groups, double b
   return 0;
 }
 
-int gigs_densify_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum,
-                       float* xyz_gradient_accum_abs, float* xyz_gradient_accum_abs_max, float* denom,
-                       float* max_radii2D, void* stream) {
+int gigs_densify_stats_guarded(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum,
+                               float* xyz_gradient_accum_abs, float* xyz_gradient_accum_abs_max, float* denom,
+                               float* max_radii2D, const int* skip, void* stream) {
   if (P < 0 || (P > 0 && (!viewspace_grad || !radii || !xyz_gradient_accum || !xyz_gradient_accum_abs ||
                           !xyz_gradient_accum_abs_max || !denom || !max_radii2D)))
     return gigs_internal_fail(GIGS_ERR_INVALID, "densify_stats: bad argument");
@@ -1090,10 +1091,17 @@ int gigs_densify_stats(int P, const float* viewspace_grad, const int* radii, flo
   void* tok; gigs_internal_stage_begin(27, stream, &tok);
   hipLaunchKernelGGL(gigs::densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P,
                      viewspace_grad, radii, xyz_gradient_accum, xyz_gradient_accum_abs, xyz_gradient_accum_abs_max,
-                     denom, max_radii2D);
+                     denom, max_radii2D, skip);
   gigs_internal_stage_end(tok);
   if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "densify_stats: launch failed");
   return 0;
+}
+
+int gigs_densify_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum,
+                       float* xyz_gradient_accum_abs, float* xyz_gradient_accum_abs_max, float* denom,
+                       float* max_radii2D, void* stream) {
+  return gigs_densify_stats_guarded(P, viewspace_grad, radii, xyz_gradient_accum, xyz_gradient_accum_abs,
+                                    xyz_gradient_accum_abs_max, denom, max_radii2D, nullptr, stream);
 }
 
 int gigs_gather_rows(int n_tensors, const gigs_gather_tensor* tensors, long long n_rows_out, long long n_rows_in,

@@ -57,6 +57,23 @@ def add_densification_stats(state: DensifyState, viewspace_grad: torch.Tensor, r
                        "densify_stats")
 
 
+def add_densification_stats_guarded(state: DensifyState, viewspace_grad: torch.Tensor, radii: torch.Tensor,
+                                    skip: torch.Tensor) -> None:
+    """add_densification_stats that adds nothing while the device int32 `skip` is non-zero (gigs_densify_stats_guarded):
+    the node a captured stage-1 backward carries, guarded by its forward's binning-overflow counter.  No host work: it is
+    captured as it stands (the three inputs are the graph's static buffers)."""
+    P = int(radii.shape[0])
+    if (viewspace_grad.shape != (P, 3) or state.denom.shape[0] != P or viewspace_grad.dtype != torch.float32
+            or radii.dtype != torch.int32 or skip.dtype != torch.int32 or not viewspace_grad.is_contiguous()):
+        raise ValueError("add_densification_stats_guarded: shapes / dtypes differ")
+    a, b, c, d, m = state.tensors()
+    with torch.cuda.device(viewspace_grad.device):
+        gigs_lib.check(_lib.gigs_densify_stats_guarded(P, viewspace_grad.data_ptr(), radii.data_ptr(), a.data_ptr(),
+                                                       b.data_ptr(), c.data_ptr(), d.data_ptr(), m.data_ptr(),
+                                                       skip.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                       "densify_stats_guarded")
+
+
 def build_rotation(r: torch.Tensor) -> torch.Tensor:
     """utils/general_utils.py:89-110."""
     q = r / torch.sqrt((r * r).sum(dim=1))[:, None]

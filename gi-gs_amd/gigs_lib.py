@@ -133,6 +133,7 @@ SIGNATURES = {
     "gigs_activate_fwd": (_i, [_i, _i, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gigs_activate_bwd": (_i, [_i, _i, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gigs_densify_stats": (_i, [_i, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_densify_stats_guarded": (_i, [_i, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_gather_rows": (_i, [_i, C.c_void_p, C.c_longlong, C.c_longlong, _f, _f, C.c_void_p]),
     "gigs_dist2_scratch_bytes": (C.c_size_t, [_i]),
     "gigs_dist2": (_i, [_i, _f, _f, _f, C.c_size_t, C.c_void_p]),
@@ -315,6 +316,17 @@ class Context:
                     cls._cache.clear()
                 c = cls._cache[key] = cls(key[0], async_capacity, async_counters, blend_event, reuse_binning, materials_only, sh_rest)
         return c
+
+    @classmethod
+    def release(cls, tensors) -> None:
+        """Drop the interned contexts that keep one of `tensors` alive (asynchronous-binning counters, violation counter,
+        split SH input): called when their owner is torn down, so that its buffers go with it (live users re-create theirs
+        on demand)."""
+        ids = {id(t) for t in tensors if t is not None}
+        with cls._lock:
+            for k in [k for k, c in cls._cache.items()
+                      if any(id(t) in ids for t in (c.async_counters, c.materials_only, c.sh_rest) if t is not None)]:
+                del cls._cache[k]
 
     def derive(self, async_binning=None, blend_event="keep", reuse_binning=None, materials_only="keep", sh_rest="keep",
                **options) -> "Context":

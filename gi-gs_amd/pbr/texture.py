@@ -18,6 +18,12 @@ _HEAVY = 64
 _plans = {}
 
 
+def release_plans(d: torch.Tensor) -> None:
+    """Drop the cached gather plans of the direction tensor `d` (its owner is being torn down)."""
+    for k in [k for k, v in _plans.items() if v["dirs"] is d]:
+        del _plans[k]
+
+
 def _gather_plan(d: torch.Tensor, res: int, n: int, build: bool):
     import os
     if os.environ.get("GIGS_CUBE_BWD_GATHER", "1") != "1" or n < _PLAN_MIN_DIRS:

@@ -458,6 +458,7 @@ class WholeStepGraph:
         """Deterministic teardown: the graphs, the captured eager step, the binning buffer and the per-camera caches.  The
         object captures again if it is called afterwards."""
         self._drop_graphs()
+        gigs_lib.Context.release([getattr(self.bin, "counters", None), self.viol_dev, self.split_rest])
         self.inner = self.bin = None
         self._packs.clear()
         self._src = {}
@@ -480,7 +481,9 @@ class WholeStepGraph:
         slot = self.cache.slot if self.cache is not None else None
         slot_key = None if slot is None else tuple(None if t is None else t.data_ptr() for t in (
             (slot.occlusion,) if self.mode == "record" else (slot.occlusion, slot.ssr_offsets, slot.ssr_entries)))
+        ds = getattr(self.owner, "densify_state", None)
         return (slot_key, tuple((t.data_ptr(), tuple(t.shape)) for t in self._params(g)),
+                None if ds is None else tuple(t.data_ptr() for t in ds.tensors()),
                 tuple(sorted((k, v.data_ptr()) for k, v in sink.items())),
                 tuple(sorted((k, v.data_ptr()) for k, v in slabv.items())),
                 self.adam.key() if self.adam is not None else None)
@@ -547,6 +550,8 @@ class WholeStepGraph:
         import gc
         o = self.owner
         bg = torch.zeros(3, device=self.dev)
+        if getattr(o, "bg", None) is not None:
+            bg.copy_(o.bg)  # Stage1Step(bg=...): the background is baked into the capture
         prep = o.prepare if o.prepare is not None else (lambda raw: raw)
         with torch.no_grad():
             ga = prep(g)  # the rasterizer's inputs (for the probe and the shapes); the capture re-derives them
@@ -638,6 +643,12 @@ class WholeStepGraph:
                         grads = torch.autograd.grad(loss, params + [res["viewspace_points"]],
                                                     grad_outputs=self._seed.reshape(loss.shape), allow_unused=True)
                     grads = self._into_slab(g, grads)
+                    ds = getattr(o, "densify_state", None)
+                    if ds is not None:
+                        # train.py:494-498 as a node behind the rasterizer's backward, guarded by this forward's overflow
+                        # counter: a step that is repeated (binning overflow) adds its statistics once
+                        import densify
+                        densify.add_densification_stats_guarded(ds, grads[-1], res["radii"], self.bin.counters[1:])
             finally:
                 light_ops.bwd_head_start_ns = 0
             del loss
@@ -691,9 +702,11 @@ class WholeStepGraph:
             static.copy_(src, non_blocking=True)
             self._src[name] = (src, src._version)
 
-    def __call__(self, cam, g, gt_image, view_dirs, vkey=None):
+    def __call__(self, cam, g, gt_image, view_dirs, vkey=None, update=True):
         """Returns None (frozen-geometry variants only) when the step must be repeated as a recording: the previous update
-        moved geometry, which the host can only know once this step's forward has run."""
+        moved geometry, which the host can only know once this step's forward has run.  update=False: forward and backward
+        only -- the update graph is not replayed (no step is counted) and the gradients are handed out as `.grad`, as
+        without optimizers."""
         if camera_model(cam) != self.cfg:
             raise ValueError("WholeStepGraph: image size / field of view differ from the captured ones")
         cache = self.cache
@@ -749,7 +762,7 @@ class WholeStepGraph:
                     cache.stats["replayed"] += 1
                     r = cache.recorded_R.get(vkey, r)
             params = self._params(g)
-            if self.go is not None:
+            if self.go is not None and update:
                 # complete iteration: all-reduce (multi-GPU) -> Adam + clamp from the third graph; the gradients are
                 # consumed inside the step, the parameters keep .grad = None (zero_grad(set_to_none=True), train.py:518)
                 if self.owner.before_update is not None:
@@ -841,13 +854,13 @@ class _Stepper:
         self.whole, self._wholes = None, {}
         self._dense = False  # declined as dense (DenseScene): synchronous binning with the global radix sort from then on
 
-    def _graph_step(self, cam, raw, gt_image, view_dirs):
+    def _graph_step(self, cam, raw, gt_image, view_dirs, update=True):
         """The step from the whole-step graphs, or None: the caller's eager path runs instead (GIGS_STEP_GRAPH=0, more
         camera models than graphs, or a scene declined as dense -- then for good)."""
         if os.environ.get("GIGS_STEP_GRAPH", "1") != "1" or self._dense:
             return None
         try:
-            return self._replay_whole(cam, raw, gt_image, view_dirs)
+            return self._replay_whole(cam, raw, gt_image, view_dirs, update=update)
         except DenseScene:
             self._dense = True
             for w in self._wholes.values():
@@ -856,7 +869,7 @@ class _Stepper:
             self._wholes.clear()
             return None
 
-    def _replay_whole(self, cam, raw, gt_image, view_dirs):
+    def _replay_whole(self, cam, raw, gt_image, view_dirs, update=True):
         # one capture per (image size, field of view): datasets with per-camera intrinsics keep a few of them
         cfg = camera_model(cam)
         if self.whole is None or self.whole.cfg != cfg:
@@ -865,7 +878,26 @@ class _Stepper:
                 self.whole = self._wholes[cfg] = WholeStepGraph(self, cam, raw)
         if self.whole is None:
             return None  # more than four distinct camera models: the fifth onwards takes the eager path
-        return self.whole(cam, raw, gt_image, view_dirs)
+        return self.whole(cam, raw, gt_image, view_dirs, update=update)
+
+    def _eager_stats(self, res) -> None:
+        """The densification statistics of an eager step (train.py:494-498), when a DensifyState is attached."""
+        ds = getattr(self, "densify_state", None)
+        if ds is None:
+            return
+        vp = res.get("viewspace_points")
+        if vp is None or vp.grad is None or "radii" not in res:
+            raise RuntimeError("densify_state: this step produced no viewspace gradient")
+        import densify
+        densify.add_densification_stats(ds, vp.grad, res["radii"])
+
+    def set_sh_degree(self, sh_degree: int) -> None:
+        """oneupSHdegree (scene/gaussian_model.py:268-270): the active degree is baked into the captured step, so the graphs
+        are released here and the next call re-captures (as after replace_parameters)."""
+        self.close()
+        self.sh_degree = int(sh_degree)
+        if hasattr(self, "_eager"):
+            self._eager = self._make_inner()
 
     def _eager_update(self, raw) -> None:
         """Complete iteration, eager formulation (train.py:517-522)."""
@@ -961,25 +993,29 @@ class Stage2Step(_Stepper):
         return out
 
     def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], gt_image: torch.Tensor, view_dirs: torch.Tensor,
-                 extra_loss=None):
+                 extra_loss=None, update: bool = True):
         """extra_loss(normal_map, albedo_map, roughness_map, metallic_map) -> scalar added to the loss before
-        backward (the BRDF / envmap regularisers of train.py:387-420; see gi-gs_amd/losses.py)."""
+        backward (the BRDF / envmap regularisers of train.py:387-420; see gi-gs_amd/losses.py).  update=False: no
+        optimizer step, the gradients stay in `.grad` (WholeStepGraph.__call__)."""
         raw = g
         if self.fused and self.graphs and extra_loss is None:
-            out = self._graph_step(cam, raw, gt_image, view_dirs)
+            out = self._graph_step(cam, raw, gt_image, view_dirs, update=update)
             if out is not None:
                 return out
         regen = (lambda: self.prepare(raw)) if self.prepare is not None else None
         if regen is not None:
             g = regen()
         res = self._step(cam, g, gt_image, view_dirs, extra_loss, regen)
-        self._eager_update(raw)
+        if update:
+            self._eager_update(raw)
         return res
 
-    def _replay_whole(self, cam, raw, gt_image, view_dirs):
+    def _replay_whole(self, cam, raw, gt_image, view_dirs, update=True):
         if self.geometry_cache:
+            if not update:
+                raise ValueError("Stage2Step: update=False is not available with the frozen-geometry cache")
             return self._cached_geometry_step(cam, raw, gt_image, view_dirs)
-        return super()._replay_whole(cam, raw, gt_image, view_dirs)
+        return super()._replay_whole(cam, raw, gt_image, view_dirs, update=update)
 
     def _cached_geometry_step(self, cam, raw, gt_image, view_dirs):
         """One step through the frozen-geometry variants of the whole-step graphs: replayed from the view's entry when
@@ -1222,8 +1258,9 @@ class _Stage1Inner:
     """One stage-1 iteration of train.py (:266-331) up to the loss: render -> fused G-buffer post-processing ->
     0.8 L1 + 0.2 D-SSIM + masked normal L1 + normal TV (losses.stage1_loss: one autograd node)."""
 
-    def __init__(self, gi: Dict, sh_degree: int, lambda_dssim: float, normal_loss_weight: float, normal_tv_weight: float):
-        self.gi, self.sh_degree = gi, sh_degree
+    def __init__(self, gi: Dict, sh_degree: int, lambda_dssim: float, normal_loss_weight: float, normal_tv_weight: float,
+                 bg: Optional[torch.Tensor] = None):
+        self.gi, self.sh_degree, self.bg = gi, sh_degree, bg
         self.w = (float(lambda_dssim), float(normal_loss_weight), float(normal_tv_weight))
         self._defer_backward = False
         self._static_bg = self._static_m2d = None
@@ -1231,7 +1268,8 @@ class _Stage1Inner:
     def __call__(self, cam, g, gt_image, view_dirs=None):
         import losses
         dev = g["means3D"].device
-        bg = self._static_bg if self._static_bg is not None else torch.zeros(3, device=dev)
+        bg = self._static_bg if self._static_bg is not None else (
+            self.bg if self.bg is not None else torch.zeros(3, device=dev))
         out, screenspace_points, st = rasterize(cam, g, self.sh_degree, bg, self.gi, means2D=self._static_m2d)
         (image, radii, _, _, normal_map_from_depth, normal_map, _, _, _, _, out_normal_view, _) = out
         nfd, nfd_mask, normals_view, _, _ = gbuffer_post_fused(normal_map_from_depth, normal_map, out_normal_view, st.viewmatrix)
@@ -1256,34 +1294,46 @@ class Stage1Step(_Stepper):
     post_update = None
 
     def __init__(self, gi: Dict, sh_degree: int, lambda_dssim: float = 0.2, normal_loss_weight: float = 1.0,
-                 normal_tv_weight: float = 1.0, graphs: bool = False, prepare=None, optimizers=None, before_update=None):
+                 normal_tv_weight: float = 1.0, graphs: bool = False, prepare=None, optimizers=None, before_update=None,
+                 bg: Optional[torch.Tensor] = None, densify_state=None):
+        """bg: the background colour [3] (train.py:199, 254-259; white with -w), black by default.  densify_state: a
+        densify.DensifyState that every iteration updates with its viewspace gradient and radii (train.py:494-498) -- on the
+        graph path a node of the captured backward."""
         super().__init__()
         self.gi, self.sh_degree, self.graphs = gi, sh_degree, graphs
+        self.bg = None if bg is None else torch.as_tensor(bg, dtype=torch.float32).reshape(3)
+        self.densify_state = densify_state
         self.weights = (lambda_dssim, normal_loss_weight, normal_tv_weight)
         self.prepare, self.optimizers, self.before_update = prepare, list(optimizers or []), before_update
         self._no_vd = None  # the graph's (unused) view_dirs input
         self._eager = self._make_inner()
 
     def _make_inner(self):
-        return _Stage1Inner(self.gi, self.sh_degree, *self.weights)
+        return _Stage1Inner(self.gi, self.sh_degree, *self.weights, bg=self.bg)
 
     def _leaves(self, raw):
         return raw.values()
 
-    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], gt_image: torch.Tensor, view_dirs=None):
+    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], gt_image: torch.Tensor, view_dirs=None, update: bool = True):
+        """update=False: forward, backward (and the statistics) without the optimizer step; the gradients stay in `.grad`."""
         raw = g
+        if self.bg is not None and self.bg.device != gt_image.device:
+            self.bg = self.bg.to(gt_image.device)
+            self._eager = self._make_inner()
         if self.graphs:
             if view_dirs is None:
                 if self._no_vd is None:
                     self._no_vd = torch.zeros(1, device=gt_image.device)
                 view_dirs = self._no_vd
-            out = self._graph_step(cam, raw, gt_image, view_dirs)
+            out = self._graph_step(cam, raw, gt_image, view_dirs, update=update)
             if out is not None:
                 return out
         if self.prepare is not None:
             g = self.prepare(raw)
         res = self._eager(cam, g, gt_image)
-        self._eager_update(raw)
+        self._eager_stats(res)
+        if update:
+            self._eager_update(raw)
         return res
 
 

@@ -81,25 +81,38 @@ class Stage2Trainer:
     def __init__(self, raw: Dict[str, torch.Tensor], light, brdf_lut: torch.Tensor, gi: Dict, sh_degree: int,
                  lrs: Optional[Dict[str, float]] = None, light_lr: float = 0.05, graphs: bool = True, glue: str = "hip",
                  brdf_tv_weight: float = 1.0, env_tv_weight: float = 0.01, before_update=None, metallic: bool = True,
-                 geometry_cache: bool = False, materials_only: bool = True):
+                 geometry_cache: bool = False, materials_only: bool = True, indirect: bool = True, gamma: bool = False,
+                 tone: bool = False, optimizer=None, light_optimizer=None):
         """geometry_cache: reuse, per view, what frozen geometry makes constant -- tile lists, occlusion plane (pipeline.
         GeometryCache; graphs only).  Same updates as without it (tested); a secondary figure, never the headline metric.
         materials_only (graphs only): a stage-2 iteration's loss reaches albedo / roughness / metallic and the light, every
         other gradient is an exact zero -- DECLARED here, so those zeros are neither written by the rasterizer's backward,
         nor pushed through the activations' backward, nor read by Adam (which updates the groups with g = 0: same
         arithmetic), and CHECKED on the device by every backward (gigs_ctx_set_materials_only): a violation raises at
-        the next iteration.  Same updates as without it (tested)."""
+        the next iteration.  Same updates as without it (tested).
+        optimizer / light_optimizer: existing optimizers to step instead of fresh ones -- the reference keeps ONE Adam across
+        the stage switch (train.py:186, 517-520), so a stage-1 trainer's `optimizer` (moments and step counts) is handed on
+        here; it must hold `raw`'s tensors under the reference's group names.  indirect / gamma / tone: train.py's flags
+        (the defaults are the ones this trainer has always used)."""
         if glue not in ("hip", "torch"):
             raise ValueError("glue must be 'hip' or 'torch'")
         self.raw, self.light = raw, light
         lrs = dict(DEFAULT_LRS, **(lrs or {}))
-        groups = [{"params": [raw[k]], "lr": lrs[k], "name": k} for k in RAW_KEYS]
         Opt = optim.FusedAdam if glue == "hip" else torch.optim.Adam
-        self.optimizer = Opt(groups, lr=0.0, eps=1e-15)                                   # gaussian_model.py:346
-        self.light_optimizer = Opt([{"name": "cubemap", "params": list(light.parameters()), "lr": light_lr}], lr=light_lr)
+        if optimizer is not None:
+            _check_holds(optimizer, raw)
+            self.optimizer = optimizer
+        else:
+            groups = [{"params": [raw[k]], "lr": lrs[k], "name": k} for k in RAW_KEYS]
+            self.optimizer = Opt(groups, lr=0.0, eps=1e-15)                               # gaussian_model.py:346
+        if light_optimizer is not None:
+            self.light_optimizer = light_optimizer
+        else:
+            self.light_optimizer = Opt([{"name": "cubemap", "params": list(light.parameters()), "lr": light_lr}], lr=light_lr)
         self.regularizer = Stage2Regularizer(light, brdf_tv_weight=brdf_tv_weight, env_tv_weight=env_tv_weight)
         self.stepper = pipeline.Stage2Step(
-            light, brdf_lut, gi, sh_degree, metallic=metallic, graphs=graphs and glue == "hip", fused=glue == "hip",
+            light, brdf_lut, gi, sh_degree, metallic=metallic, indirect=indirect, gamma=gamma, tone=tone,
+            graphs=graphs and glue == "hip", fused=glue == "hip",
             prepare=activations.activate if glue == "hip" else activations.activate_torch, regularizer=self.regularizer,
             optimizers=[self.optimizer, self.light_optimizer], post_update=lambda: light.clamp_(min=0.0),
             before_update=before_update, geometry_cache=geometry_cache and graphs and glue == "hip",
@@ -112,14 +125,31 @@ class Stage2Trainer:
             if group["name"] == name:
                 group["lr"] = lr
 
-    def iteration(self, cam: Dict, gt_image: torch.Tensor, view_dirs: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return self.stepper(cam, self.raw, gt_image, view_dirs)
+    def iteration(self, cam: Dict, gt_image: torch.Tensor, view_dirs: torch.Tensor, update: bool = True) -> Dict[str, torch.Tensor]:
+        """update=False: forward and backward from the same graphs, no Adam (Gaussians or light) and no clamp; the gradients
+        are left in `.grad` (the light's included: `light_step()` applies it)."""
+        return self.stepper(cam, self.raw, gt_image, view_dirs, update=update)
+
+    def light_step(self) -> None:
+        """The light's half of the update after an `update=False` iteration: light_optimizer.step(), zero_grad(set_to_none),
+        cubemap.clamp_(min=0) (train.py:520-523)."""
+        self.light_optimizer.step()
+        for p in self.light.parameters():
+            p.grad = None
+        with torch.no_grad():
+            self.light.clamp_(min=0.0)
+
+    def set_sh_degree(self, sh_degree: int) -> None:
+        """The active SH degree (oneupSHdegree, train.py:241-242): the stepper re-captures at the next iteration."""
+        self.stepper.set_sh_degree(sh_degree)
 
     def close(self) -> None:
         """Deterministic teardown of the stepper's hipGraphs (synchronise, release, synchronise): call it when the trainer
         is done -- a trainer references its stepper and the stepper the trainer's bound methods, so without it the graph
         execs would live until a cyclic-GC pass.  `with Stage2Trainer(...) as tr:` closes on exit."""
         self.stepper.close()
+        from pbr import texture
+        texture.release_plans(self.regularizer.envmap_dirs)  # the envmap TV's cached gather plan goes with the trainer
 
     def __enter__(self):
         return self
@@ -128,10 +158,14 @@ class Stage2Trainer:
         self.close()
         return False
 
-    def replace_parameters(self, raw: Dict[str, torch.Tensor]) -> None:
+    def replace_parameters(self, raw: Dict[str, torch.Tensor], densify_state=None) -> None:
         """After densification / pruning / opacity reset (densify.py on `self.optimizer`, as the reference's
         GaussianModel methods do, scene/gaussian_model.py:580-931): the optimizer's groups hold NEW tensor objects and
-        moments; hand the new dictionary over.  The next iteration re-captures the graphs (once) around them."""
+        moments; hand the new dictionary over.  The next iteration re-captures the graphs (once) around them.
+        densify_state: attach / replace the statistics the iterations update (needs materials_only=False: the declared
+        stage-2 gradient set has no viewspace gradient)."""
+        if densify_state is not None and self.stepper.materials_only:
+            raise ValueError("replace_parameters: densification statistics need materials_only=False")
         missing = [k for k in RAW_KEYS if k not in raw]
         if missing:
             raise KeyError("replace_parameters: missing " + ", ".join(missing))
@@ -140,6 +174,8 @@ class Stage2Trainer:
             raise ValueError("replace_parameters: the tensors must be the ones the optimizer's groups hold")
         self.stepper.close()  # the graphs around the old tensors are released here, with the device idle
         self.raw = {k: raw[k] for k in RAW_KEYS}
+        if densify_state is not None:
+            self.stepper.densify_state = densify_state
         if getattr(self, "_dp_args", None) is not None:  # the gradient slab follows the new tensors
             timing = self.slab.timing
             _attach_slab(self, *self._dp_args, light=self.light)
@@ -172,6 +208,12 @@ class Stage2Trainer:
         `force` issues the collective with a single rank too (a one-GPU RCCL rehearsal).  Returns the slab
         (`.timing = True` + `.comm_stats()` for measurements)."""
         return _attach_slab(self, group, names, average, force, light=self.light)
+
+
+def _check_holds(optimizer, raw) -> None:
+    held = {g.get("name"): g["params"] for g in optimizer.param_groups}
+    if any(k not in held or len(held[k]) != 1 or held[k][0] is not raw[k] for k in RAW_KEYS):
+        raise ValueError("optimizer: its groups must hold raw's tensors under the reference's names")
 
 
 def _attach_slab(trainer, group, names, average, force, light=None):
@@ -210,26 +252,50 @@ class Stage1Trainer:
 
     def __init__(self, raw: Dict[str, torch.Tensor], gi: Dict, sh_degree: int, lrs: Optional[Dict[str, float]] = None,
                  lambda_dssim: float = 0.2, normal_loss_weight: float = 1.0, normal_tv_weight: float = 1.0, graphs: bool = True,
-                 before_update=None, compute_occlusion: bool = True):
+                 before_update=None, compute_occlusion: bool = True, bg: Optional[torch.Tensor] = None, densify_state=None,
+                 optimizer=None):
         """compute_occlusion=False: the operator's SSAO march is switched off for these iterations (start = step in the raster
         settings, what the README's --start 64 does): stage 1 neither reads occlusion_map nor differentiates through it, so
         losses, gradients and updates are unchanged (tested) while the iteration loses its largest kernel.  The default keeps
-        the reference's work."""
+        the reference's work.
+        bg: background colour (white with -w; black by default).  densify_state: a densify.DensifyState updated by every
+        iteration (a node of the captured backward on the graph path).  optimizer: an existing FusedAdam over `raw` (e.g.
+        restored from a checkpoint) instead of a fresh one."""
         self.raw = raw
         if not compute_occlusion:
             gi = dict(gi, start=gi["step"])
         lrs = dict(DEFAULT_LRS, **(lrs or {}))
-        self.optimizer = optim.FusedAdam([{"params": [raw[k]], "lr": lrs[k], "name": k} for k in RAW_KEYS], lr=0.0, eps=1e-15)
+        if optimizer is not None:
+            _check_holds(optimizer, raw)
+            self.optimizer = optimizer
+        else:
+            self.optimizer = optim.FusedAdam([{"params": [raw[k]], "lr": lrs[k], "name": k} for k in RAW_KEYS], lr=0.0, eps=1e-15)
         self.stepper = pipeline.Stage1Step(gi, sh_degree, lambda_dssim, normal_loss_weight, normal_tv_weight, graphs=graphs,
-                                           prepare=activations.activate, optimizers=[self.optimizer], before_update=before_update)
+                                           prepare=activations.activate, optimizers=[self.optimizer], before_update=before_update,
+                                           bg=bg, densify_state=densify_state)
 
     def set_lr(self, name: str, lr: float) -> None:
         for group in self.optimizer.param_groups:
             if group["name"] == name:
                 group["lr"] = lr
 
-    def iteration(self, cam: Dict, gt_image: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return self.stepper(cam, self.raw, gt_image)
+    def iteration(self, cam: Dict, gt_image: torch.Tensor, update: bool = True) -> Dict[str, torch.Tensor]:
+        """update=False: forward, backward and statistics from the same graphs without the Adam step (a densify iteration,
+        train.py:493-520); the gradients are left in `.grad`."""
+        return self.stepper(cam, self.raw, gt_image, update=update)
+
+    def set_sh_degree(self, sh_degree: int) -> None:
+        """The active SH degree (oneupSHdegree, train.py:241-242): the stepper re-captures at the next iteration."""
+        self.stepper.set_sh_degree(sh_degree)
+
+    @property
+    def densify_state(self):
+        return self.stepper.densify_state
+
+    def set_densify_state(self, state) -> None:
+        """Attach, replace or (None) detach the statistics; the next iteration re-captures."""
+        self.stepper.close()
+        self.stepper.densify_state = state
 
     def close(self) -> None:
         """Deterministic teardown of the stepper's hipGraphs (synchronise, release, synchronise): call it when the trainer
@@ -248,12 +314,16 @@ class Stage1Trainer:
         """As Stage2Trainer.data_parallel; a stage-1 loss reaches every Gaussian group, so the whole slab is one collective."""
         return _attach_slab(self, group, names, average, force)
 
-    def replace_parameters(self, raw: Dict[str, torch.Tensor]) -> None:
+    def replace_parameters(self, raw: Dict[str, torch.Tensor], densify_state=None) -> None:
+        """As Stage2Trainer.replace_parameters; densify_state attaches / replaces the statistics (densify_and_prune returns a
+        new one sized for the new set)."""
         held = {id(g["params"][0]) for g in self.optimizer.param_groups}
         if any(k not in raw or id(raw[k]) not in held for k in RAW_KEYS):
             raise ValueError("replace_parameters: pass the tensors the optimizer's groups hold, under the reference's names")
         self.stepper.close()
         self.raw = {k: raw[k] for k in RAW_KEYS}
+        if densify_state is not None:
+            self.stepper.densify_state = densify_state
         if getattr(self, "_dp_args", None) is not None:
             timing = self.slab.timing
             _attach_slab(self, *self._dp_args)

@@ -584,6 +584,12 @@ typedef struct gigs_gather_tensor {
 int gigs_densify_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum,
                        float* xyz_gradient_accum_abs, float* xyz_gradient_accum_abs_max, float* denom,
                        float* max_radii2D, void* stream);
+/* The same with a device guard: nothing is added while *skip != 0 (skip = NULL: unguarded).  Captured behind a
+ * forward under asynchronous binning with skip = its overflow counter, a replay whose binning overflowed -- and that
+ * the caller repeats -- leaves the statistics untouched (gi-gs_amd/pipeline.py: WholeStepGraph). */
+int gigs_densify_stats_guarded(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum,
+                               float* xyz_gradient_accum_abs, float* xyz_gradient_accum_abs_max, float* denom,
+                               float* max_radii2D, const int* skip, void* stream);
 int gigs_gather_rows(int n_tensors, const gigs_gather_tensor* tensors, long long n_rows_out, long long n_rows_in,
                      const int* src_index, const uint8_t* zero_row, void* stream);
 
