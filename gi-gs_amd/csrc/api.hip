@@ -132,6 +132,7 @@ gigs::Options options_from_env() {
   o.spec_max16 = env_int("GIGS_SPEC_MAX16", 1500);
   o.shade_lds_floats = env_int("GIGS_SHADE_LDS_FLOATS", 30 * 1024);
   o.shade_bwd_blocks = std::max(0, env_int("GIGS_SHADE_BWD_BLOCKS", 0));
+  o.shade_bwd_rows = env_int("GIGS_SHADE_BWD_ROWS", 0) != 0;
   return o;
 }
 const gigs::Ctx& ctx_of(const gigs_ctx* c) { return c ? *reinterpret_cast<const gigs::Ctx*>(c) : gigs::default_ctx(); }
@@ -261,6 +262,7 @@ int gigs_ctx_get_options(const gigs_ctx* ctx, gigs_options* out) {
   out->gi_march = o.gi_march; out->gi_cert = o.gi_cert; out->gi_interleave = o.gi_interleave;
   out->gi_tile_log2w = o.gi_tile_log2w; out->gi_zero_rays = o.gi_zero_rays; out->spec_max8 = o.spec_max8;
   out->spec_max16 = o.spec_max16; out->shade_lds_floats = o.shade_lds_floats; out->shade_bwd_blocks = o.shade_bwd_blocks;
+  out->shade_bwd_rows = o.shade_bwd_rows;
   return 0;
 }
 int gigs_ctx_set_options(gigs_ctx* ctx, const gigs_options* in) {
@@ -279,6 +281,7 @@ int gigs_ctx_set_options(gigs_ctx* ctx, const gigs_options* in) {
   o.gi_march = in->gi_march; o.gi_cert = in->gi_cert != 0; o.gi_interleave = in->gi_interleave != 0;
   o.gi_tile_log2w = in->gi_tile_log2w; o.gi_zero_rays = in->gi_zero_rays != 0; o.spec_max8 = in->spec_max8;
   o.spec_max16 = in->spec_max16; o.shade_lds_floats = in->shade_lds_floats; o.shade_bwd_blocks = in->shade_bwd_blocks;
+  o.shade_bwd_rows = in->shade_bwd_rows != 0;
   return 0;
 }
 int gigs_ctx_set_reuse_binning(gigs_ctx* ctx, int on) {

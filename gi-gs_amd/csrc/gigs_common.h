@@ -249,6 +249,7 @@ struct Options {
   int spec_max8, spec_max16;  // GIGS_SPEC_MAX8 / _MAX16
   int shade_lds_floats;  // GIGS_SHADE_LDS_FLOATS
   int shade_bwd_blocks;  // GIGS_SHADE_BWD_BLOCKS (0 = one workgroup per CU)
+  int shade_bwd_rows;    // GIGS_SHADE_BWD_ROWS: 1 = the shade backward's row-major chunks and 16-lane runs (same per-pixel bits)
 };
 struct Ctx {
   Options opt;

@@ -1084,11 +1084,58 @@ cube_texture_bwd_gather_kernel(int n_tex, const int* __restrict__ offsets, const
   if (lane == 63) { d_tex[3 * (size_t)t] = c0; d_tex[3 * (size_t)t + 1] = c1; d_tex[3 * (size_t)t + 2] = c2; }
 }
 
+// Scatter-add of the specular entries that go to GLOBAL levels (8 per lane: 4 taps of l0, 4 of l1), one add per
+// distinct (level, texel) of the whole wave.  key = (level << 24) | texel, or -1; v = the entry's three products as
+// the caller formed them.  A round takes the first pending key of the first lane that has one, every lane sums its
+// own entries with that key (in tap order), wave_sum63 sums the lanes, and lanes 0-2 add the three channels with ONE
+// atomic instruction (a contiguous 12-byte request; non-zero sums only): the same products are added, in another
+// order.  A wave whose 8x8 pixels see more than kWaveDedupRounds distinct texels (noisy normals) hands the rest to
+// run_add3, so the cost per wave stays bounded and the result does not depend on how many keys there are.
+// Must be called by all 64 lanes.
+constexpr int kWaveDedupRounds = 24;
+__device__ __forceinline__ void wave_dedup_add(float* const (&d_spec)[8], int (&key)[8], const float (&v)[8][3]) {
+  const int lane = threadIdx.x & 63;
+  for (int round = 0; round < kWaveDedupRounds; round++) {
+    int first = -1;
+#pragma unroll
+    for (int k = 7; k >= 0; k--) first = key[k] >= 0 ? key[k] : first;
+    const unsigned long long pend = __builtin_amdgcn_ballot_w64(first >= 0);
+    if (pend == 0ull) return;
+    const int K = __builtin_amdgcn_readlane(first, (int)__builtin_ctzll(pend));  // wave-uniform
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const bool m = key[k] == K;
+      s0 += m ? v[k][0] : 0.0f;
+      s1 += m ? v[k][1] : 0.0f;
+      s2 += m ? v[k][2] : 0.0f;
+      key[k] = m ? -1 : key[k];
+    }
+    s0 = wave_sum63(s0); s1 = wave_sum63(s1); s2 = wave_sum63(s2);  // in lane 63
+    const float c0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s0), 63));
+    const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s1), 63));
+    const float c2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s2), 63));
+    const float s = lane == 0 ? c0 : (lane == 1 ? c1 : c2);
+    if (lane < 3 && s != 0.0f) atomicAdd(d_spec[K >> 24] + 3 * (size_t)(K & 0xffffff) + lane, s);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    if (__builtin_amdgcn_ballot_w64(key[k] >= 0) == 0ull) continue;  // wave-uniform
+    float* t = key[k] >= 0 ? d_spec[key[k] >> 24] + 3 * (size_t)(key[k] & 0xffffff) : nullptr;
+    run_add3<false>(t, key[k], v[k][0], v[k][1], v[k][2]);
+  }
+}
+
 // Gradients of the light textures: hundreds of thousands of pixels add into a few thousand texels of
 // the coarse levels (16^2 diffuse, 16^2 / 32^2 specular), which serialises memory-side float atomics on
 // the same addresses (measured: 0.72 of 0.77 ms).  Every level that fits is therefore accumulated per
 // 1024-lane workgroup in LDS (up to 120 KB) and flushed once, non-zero entries only; larger levels take
-// global atomics.  In both cases neighbouring lanes hitting the same texel are pre-summed (run_add3).
+// global atomics.  Neighbouring lanes hitting the same LDS texel are pre-summed (run_add3).
+// kTiles (default): a chunk is a 32 x 32 pixel tile and each wave an 8 x 8 block of it, so that the reflected
+// directions of a wave lie as close together as the surface allows, and the global levels get one add per distinct
+// texel of the wave (wave_dedup_add).  !kTiles (gigs_options.shade_bwd_rows): row-major 1024-pixel chunks, run_add3
+// for every level.  Every per-pixel output is the same in both; the light gradients differ by summation order only.
+template <bool kTiles>
 __global__ void __launch_bounds__(kShadeBwdBlock)
 shade_bwd_kernel(ShadeArgs A) {
   extern __shared__ __align__(16) float s_lds[];
@@ -1096,10 +1143,21 @@ shade_bwd_kernel(ShadeArgs A) {
   __syncthreads();
   // persistent workgroups: each keeps its LDS accumulators across several 1024-pixel chunks, so the zero-fill
   // and the flush (and the flush's global atomics) are paid once per workgroup, not once per chunk
-  const int n_chunks = (A.H * A.W + kShadeBwdBlock - 1) / kShadeBwdBlock;
+  const int tiles_x = (A.W + 31) / 32;
+  const int n_chunks = kTiles ? tiles_x * ((A.H + 31) / 32) : (A.H * A.W + kShadeBwdBlock - 1) / kShadeBwdBlock;
   for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-  const int pg = chunk * kShadeBwdBlock + threadIdx.x;
-  const bool live = pg < A.H * A.W;
+  int pg;
+  bool live;
+  if (kTiles) {
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    const int x = (chunk % tiles_x) * 32 + (wv & 3) * 8 + (ln & 7);
+    const int y = (chunk / tiles_x) * 32 + (wv >> 2) * 8 + (ln >> 3);
+    live = x < A.W && y < A.H;
+    pg = y * A.W + x;
+  } else {
+    pg = chunk * kShadeBwdBlock + threadIdx.x;
+    live = pg < A.H * A.W;
+  }
   const int p = live ? pg : 0;  // dead lanes shade pixel 0 and add nothing: the DPP scans need every lane
   ShadePix q;
   shade_pixel(A, p, q);
@@ -1195,6 +1253,29 @@ shade_bwd_kernel(ShadeArgs A) {
     if (((A.ablate & 4) && A.lds_spec_off[q.l0] >= 0) || ((A.ablate & 8) && A.lds_spec_off[q.l0] < 0)) t0 = nullptr;
     if (((A.ablate & 4) && A.lds_spec_off[q.l1] >= 0) || ((A.ablate & 8) && A.lds_spec_off[q.l1] < 0)) t1 = nullptr;
 #endif
+    if (kTiles) {
+      // entries of LDS-resident levels: run_add3 as below; entries of global levels are collected (an entry whose
+      // three products are 0 adds nothing in either formulation) and added once per distinct texel of the wave
+      const bool glob0 = A.lds_spec_off[q.l0] < 0, glob1 = A.lds_spec_off[q.l1] < 0;
+      int gkey[8];
+      float gv[8][3];
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        const bool first = k < 4;
+        const int idx = first ? ((live && q.has0 && t0) ? q.t0.idx[k] : -1)
+                              : ((live && q.l1 != q.l0 && q.has1 && t1) ? q.t1.idx[k - 4] : -1);
+        const float w = idx >= 0 ? (first ? q.t0.w[k] * wl : q.t1.w[k - 4] * q.lf) : 0.0f;
+        const float v0 = g_sp[0] * w, v1 = g_sp[1] * w, v2 = g_sp[2] * w;
+        const int key = idx >= 0 ? ((first ? q.l0 : q.l1) << 24) | idx : -1;
+        const bool glob = first ? glob0 : glob1;
+        gkey[k] = (glob && (v0 != 0.0f || v1 != 0.0f || v2 != 0.0f)) ? key : -1;
+        gv[k][0] = v0; gv[k][1] = v1; gv[k][2] = v2;
+        const int lkey = glob ? -1 : key;
+        if (__builtin_amdgcn_ballot_w64(lkey >= 0) != 0ull)  // wave-uniform
+          run_add3<false>(lkey >= 0 ? (first ? t0 : t1) + 3 * (size_t)idx : nullptr, lkey, v0, v1, v2);
+      }
+      wave_dedup_add(A.d_spec, gkey, gv);
+    } else {
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const int idx = (live && q.has0 && t0) ? q.t0.idx[k] : -1;
@@ -1206,6 +1287,7 @@ shade_bwd_kernel(ShadeArgs A) {
       const int idx = (live && q.l1 != q.l0 && q.has1 && t1) ? q.t1.idx[k] : -1;
       const float w = idx >= 0 ? q.t1.w[k] * q.lf : 0.0f;
       run_add3<false>(t1 ? t1 + 3 * (size_t)max(idx, 0) : nullptr, idx >= 0 ? (q.l1 << 24) | idx : -1, g_sp[0] * w, g_sp[1] * w, g_sp[2] * w);
+    }
     }
   }
   }  // chunk loop
@@ -1647,15 +1729,18 @@ int gigs_shade_bwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
     if (A.d_spec[i] && used + n <= lds_budget) { A.lds_spec_off[i] = used; used += n; }
   }
   A.lds_total = used;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gigs::shade_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            gigs::kShadeLdsBudget * (int)sizeof(float)) != hipSuccess)
+  // gigs_options.shade_bwd_rows: the previous pixel mapping and scatter (same per-pixel bits; the checker of the default)
+  const bool rows = o.shade_bwd_rows != 0;
+  const void* fn = rows ? reinterpret_cast<const void*>(gigs::shade_bwd_kernel<false>)
+                        : reinterpret_cast<const void*>(gigs::shade_bwd_kernel<true>);
+  static bool attr_set[2] = {false, false};
+  if (!attr_set[rows]) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, gigs::kShadeLdsBudget * (int)sizeof(float)) != hipSuccess)
       return gigs_internal_fail(GIGS_ERR_HIP, "shade_bwd: cannot raise the dynamic LDS limit");
-    attr_set = true;
+    attr_set[rows] = true;
   }
   void* tok; gigs_internal_stage_begin(15, stream, &tok);
-  const int n_chunks = (H * W + gigs::kShadeBwdBlock - 1) / gigs::kShadeBwdBlock;
+  const int n_chunks = rows ? (H * W + gigs::kShadeBwdBlock - 1) / gigs::kShadeBwdBlock : ((W + 31) / 32) * ((H + 31) / 32);
   static const int n_cus = [] {  // one workgroup per CU (120 KB of LDS each); gigs_options.shade_bwd_blocks overrides
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1663,8 +1748,12 @@ int gigs_shade_bwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
   }();
   const int max_blocks = o.shade_bwd_blocks > 0 ? o.shade_bwd_blocks : n_cus;
   const int blocks = (n_chunks < max_blocks) ? n_chunks : max_blocks;
-  hipLaunchKernelGGL(gigs::shade_bwd_kernel, dim3(blocks), dim3(gigs::kShadeBwdBlock), (size_t)used * sizeof(float),
-                     (hipStream_t)stream, A);
+  if (rows)
+    hipLaunchKernelGGL(gigs::shade_bwd_kernel<false>, dim3(blocks), dim3(gigs::kShadeBwdBlock), (size_t)used * sizeof(float),
+                       (hipStream_t)stream, A);
+  else
+    hipLaunchKernelGGL(gigs::shade_bwd_kernel<true>, dim3(blocks), dim3(gigs::kShadeBwdBlock), (size_t)used * sizeof(float),
+                       (hipStream_t)stream, A);
   gigs_internal_stage_end(tok);
   PBR_CHECK_LAUNCH();
   return 0;

@@ -168,7 +168,7 @@ class Options(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
         "struct_bytes", "binning_legacy", "bucket_max_mean", "long_lists", "bucket_target", "bin_bands", "blend_cull",
         "pre_bwd_sh_skip", "gi_march", "gi_cert", "gi_interleave", "gi_tile_log2w", "gi_zero_rays", "spec_max8",
-        "spec_max16", "shade_lds_floats", "shade_bwd_blocks")]
+        "spec_max16", "shade_lds_floats", "shade_bwd_blocks", "shade_bwd_rows")]
 
 
 OPTION_NAMES = tuple(n for n, _ in Options._fields_ if n != "struct_bytes")

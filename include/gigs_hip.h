@@ -80,6 +80,9 @@ typedef struct gigs_options {
   int spec_max16;       /* ... by 16-lane groups (1500).                                            env GIGS_SPEC_MAX16 */
   int shade_lds_floats; /* LDS accumulator budget of the shade backward in floats (30720).    env GIGS_SHADE_LDS_FLOATS */
   int shade_bwd_blocks; /* its persistent workgroups, 0 (default) = one per CU.               env GIGS_SHADE_BWD_BLOCKS */
+  int shade_bwd_rows;   /* 0 (default) its pixels in 32x32 tiles of 8x8-pixel waves, one add per distinct texel of a
+                           wave into the global light levels; 1 = row-major chunks, adds pre-summed in 16-lane runs
+                           (every per-pixel output the same bits).                         env GIGS_SHADE_BWD_ROWS */
 } gigs_options;
 /* A new context holds a copy of the default options.  Destroying a context frees host memory only; work queued
  * with it may still be running. */
