@@ -1,5 +1,5 @@
 """Novel-view evaluation of a trained scene: the reference's render.py (render_set's pbr branch, eval_brdf) and
-normal_eval.py without the file I/O, on the HIP library.
+normal_eval.py without the file I/O (render_scene.py writes the files), on the HIP library.
 
     NovelViewEvaluator(light, gi, sh_degree, ...)   render.py:115-395 per view: render(inference=True, pad_normal=True,
       (cam, g, view_dirs, gt_image, alpha_mask)     derive_normal=True) -> pbr_shading -> Gaussian_SSR -> sRGB + 3x3
@@ -40,6 +40,8 @@ from relight import Relighter
 _lib = gigs_lib.lib()
 
 PLANES = ("pbr", "DIR", "indirect", "albedo", "roughness", "metallic", "occlusion", "normal", "from_depth")
+# extra_planes=True: render.py's diffuse / specular images (:288-317, :348-349) and the raw depth map (:376 normalises it)
+EXTRA_PLANES = ("diffuse", "specular", "depth")
 
 
 def _scratch(dev, C: int, H: int, W: int) -> torch.Tensor:
@@ -82,10 +84,14 @@ class NovelViewEvaluator(Relighter):
 
     def __init__(self, light: CubemapLight, gi: Dict, sh_degree: int, metallic: bool = False, tone: bool = False,
                  gamma: bool = False, graphs: bool = True, fused: bool = True, brdf_lut: Optional[torch.Tensor] = None,
-                 capacity: int = 1024, lpips=None):
+                 capacity: int = 1024, lpips=None, extra_planes: bool = False):
+        """extra_planes=True adds EXTRA_PLANES to the planes a call returns (the shade also writes its diffuse and
+        specular parts); the default returns PLANES, exactly as before."""
         super().__init__(light, gi, sh_degree, metallic=metallic, tone=tone, gamma=gamma, fused=fused, brdf_lut=brdf_lut,
                          graphs=graphs)
         dev = light.base.device
+        self.extra_planes = bool(extra_planes)
+        self.names = PLANES + EXTRA_PLANES if self.extra_planes else PLANES
         self._cap = int(capacity)
         # 4 rows of headroom: the graph's warm-up runs write records before the slot is rewound
         self._rec = torch.zeros((self._cap + 4, 7), dtype=torch.float64, device=dev)
@@ -108,12 +114,12 @@ class NovelViewEvaluator(Relighter):
         out = None
         if self.graphs:
             try:
-                out = self._replay(cam, g, (view_dirs, gt_image, alpha_mask), self._core, PLANES,
+                out = self._replay(cam, g, (view_dirs, gt_image, alpha_mask), self._core, self.names,
                                    on_capture=self._rewind)
             except pipeline.DenseScene:
                 self.graphs = False
         if out is None:
-            out = dict(zip(PLANES, self._core(cam, view_dirs, gt_image, alpha_mask, g=g)))
+            out = dict(zip(self.names, self._core(cam, view_dirs, gt_image, alpha_mask, g=g)))
         self._n += 1
         return out
 
@@ -136,11 +142,14 @@ class NovelViewEvaluator(Relighter):
         planes = dict(pbr=render_rgb, DIR=render_rgb - IRR2, indirect=IRR2, albedo=comp(r["albedo"]),
                       roughness=comp(r["roughness"]), metallic=comp(r["metallic"]), occlusion=comp(r["occlusion"]),
                       normal=(comp(r["normal"]) + 1) / 2, from_depth=(r["from_depth"] + 1) / 2)
+        if self.extra_planes:
+            part = lambda x: comp(torch.where(mask, x.clamp(0.0, 1.0), bg))  # noqa: E731  (render.py:288-317, :348-349)
+            planes.update(diffuse=part(r["diffuse"]), specular=part(r["specular"]), depth=r["depth"])
         image_metrics(render_rgb, gt, scratch=self._buf("metrics_scratch", (int(_lib.gigs_image_metrics_scratch_bytes(
             3, *render_rgb.shape[1:])),), torch.uint8, dev), slot=self._slot, out=self._rec)
         if self.lpips is not None:
             self.lpips.record(gt, render_rgb, slot=self._lp_slot, out=self._lp_rec)
-        return tuple(planes[n] for n in PLANES)
+        return tuple(planes[n] for n in self.names)
 
     def _replay(self, cam, g, inputs, core, names, key_extra=None, on_capture=None):
         self._g = g
@@ -158,7 +167,7 @@ class NovelViewEvaluator(Relighter):
         dev = g["means3D"].device
         background = torch.zeros(3, device=dev)
         (out, _, st) = pipeline.rasterize(cam, g, self.sh_degree, background, self.gi, inference=True, derive_normal=True)
-        (_, _, opacity_map, _, nfd, normal_map, occlusion, albedo_map, roughness_map, metallic_map, out_normal_view,
+        (_, _, opacity_map, depth_map, nfd, normal_map, occlusion, albedo_map, roughness_map, metallic_map, out_normal_view,
          depth_pos) = out
         H, W = cam["image_height"], cam["image_width"]
         new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
@@ -173,12 +182,16 @@ class NovelViewEvaluator(Relighter):
                                                       p(mask_u8), p(mask_f), None, p(normals_view), p(onv), p(nfd_out),
                                                       None, s), "gbuffer_post_pad")
         F0, metallic_in = self._branch(albedo_map, roughness_map, metallic_map)
-        _, IRR, render_rgb = self._shade_ssr(cam, view_dirs, normals_view, mask_u8, mask_f, onv, depth_pos, albedo_map,
-                                             albedo_map, roughness_map, metallic_map, occlusion, F0, metallic_in)
+        res = self._shade_ssr(cam, view_dirs, normals_view, mask_u8, mask_f, onv, depth_pos, albedo_map, albedo_map,
+                              roughness_map, metallic_map, occlusion, F0, metallic_in, parts=self.extra_planes)
+        IRR, render_rgb = res[1], res[2]
         IRR2 = filters.median_blur(pipeline.linear_to_srgb(IRR)[None, ...], (3, 3))[0]
-        return dict(render_rgb=render_rgb, IRR2=IRR2, normal_mask=mask_u8.bool()[None], albedo=albedo_map,
-                    roughness=roughness_map, metallic=metallic_in, occlusion=occlusion, normal=normals_view,
-                    from_depth=nfd_out)
+        out = dict(render_rgb=render_rgb, IRR2=IRR2, normal_mask=mask_u8.bool()[None], albedo=albedo_map,
+                   roughness=roughness_map, metallic=metallic_in, occlusion=occlusion, normal=normals_view,
+                   from_depth=nfd_out)
+        if self.extra_planes:
+            out.update(diffuse=res[3], specular=res[4], depth=depth_map)
+        return out
 
     # -- render.py's op sequence, operator by operator -------------------------------------------------------------
     def _unfused_pad(self, cam, g, view_dirs):
@@ -201,9 +214,13 @@ class NovelViewEvaluator(Relighter):
         IRR, _ = ssr(r["out_normal_view"], r["depth_pos"], pipeline.srgb_to_linear(render_direct), albedo_map,
                      roughness_map, metallic_in, F0)
         IRR2 = filters.median_blur(pipeline.linear_to_srgb(IRR)[None, ...], (3, 3))[0]
-        return dict(render_rgb=render_direct + IRR2, IRR2=IRR2, normal_mask=normal_mask, albedo=albedo_map,
-                    roughness=roughness_map, metallic=metallic_in, occlusion=r["occlusion_map"], normal=r["normal_map"],
-                    from_depth=r["normal_map_from_depth"])
+        out = dict(render_rgb=render_direct + IRR2, IRR2=IRR2, normal_mask=normal_mask, albedo=albedo_map,
+                   roughness=roughness_map, metallic=metallic_in, occlusion=r["occlusion_map"], normal=r["normal_map"],
+                   from_depth=r["normal_map_from_depth"])
+        if self.extra_planes:
+            out.update(diffuse=res["diffuse_rgb"].permute(2, 0, 1), specular=res["specular_rgb"].permute(2, 0, 1),
+                       depth=r["depth_map"])
+        return out
 
     def _flush(self) -> None:
         n = self._n

@@ -118,6 +118,9 @@ SIGNATURES = {
     "gigs_lpips_vgg_pack": (_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _f, C.c_void_p]),
     "gigs_lpips_vgg_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
     "gigs_lpips_vgg": (_i, [_i, _i, _i, _f, _f, _i, _f, _f, _f, _f, C.POINTER(C.c_void_p), C.c_void_p]),
+    "gigs_pack_images": (_i, [_i, _f, C.c_void_p]),
+    "gigs_plane_minmax": (_i, [C.c_longlong, _f, _f, _f, C.c_void_p]),
+    "gigs_png_filter": (_i, [_i, _f, C.c_void_p]),
     "gigs_tv_loss_fwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_bwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_masked_l1_fwd": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
@@ -203,6 +206,21 @@ class GatherTensor(C.Structure):
     """gigs_gather_tensor of include/gigs_hip.h."""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_floats", C.c_int), ("zero_new", C.c_int)]
 
+
+class PackDesc(C.Structure):
+    """gigs_pack_desc of include/gigs_hip.h."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("lohi", C.c_void_p), ("channels", C.c_int), ("height", C.c_int),
+                ("width", C.c_int), ("dst_x", C.c_int), ("dst_stride", C.c_int), ("bias", C.c_float)]
+
+
+class FilterDesc(C.Structure):
+    """gigs_filter_desc of include/gigs_hip.h."""
+    _fields_ = [("sheet", C.c_void_p), ("out", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("stride", C.c_int),
+                ("reserved", C.c_int)]
+
+
+MAX_IMAGES = 4096  # GIGS_MAX_IMAGES
+MINMAX_SCRATCH_FLOATS = 512  # GIGS_MINMAX_SCRATCH_FLOATS
 
 _lib = None
 

@@ -23,7 +23,7 @@ Reference quirks kept on purpose, by Relighter and MultiRelighter a
 with metallic=True the shade uses the metallic map but SSR receives F0 = 0.04 and a zero metallic plane; with
 metallic=False (`metallic` is the Python bool) SSR receives F0 = (1 - False) * 0.04 + albedo * metallic_map.  The
 per-channel albedo ratio read from albedo_ratio.json (:203-220) scales the shade's albedo only.  Image I/O
-(read_hdr, save_image, the JSON) stays with the caller.  RelightEvaluator computes LPIPS when given an `lpips.LPIPS`
+(read_hdr, save_image, the JSON) is relight_scene.py's, on top of image_writer.py.  RelightEvaluator computes LPIPS when given an `lpips.LPIPS`
 (this package's drop-in, gigs_lpips_vgg) as `lpips=`, as in evaluate.py.
 """
 from __future__ import annotations
@@ -249,16 +249,18 @@ class Relighter(_ViewGraph):
                     radii=b["radii"])
 
     def _shade_ssr(self, cam, view_dirs, normals_view, mask_u8, mask_f, onv, depth_pos, albedo_shade, albedo_map,
-                   roughness_map, metallic_map, occlusion, F0, metallic_in):
+                   roughness_map, metallic_map, occlusion, F0, metallic_in, parts=False):
         """The launches after the G-buffer post: shade (planar, with the sRGB->linear epilogue), SSR with the caller's
         F0 / metallic planes, then render_rgb = render_direct + median3x3(linear_to_srgb(IRR)).  Shared with
-        evaluate.NovelViewEvaluator, whose G-buffer post and F0 branch differ."""
+        evaluate.NovelViewEvaluator, whose G-buffer post and F0 branch differ.  parts=True also has the shade write
+        pbr_shading's diffuse_rgb and specular_rgb [3,H,W] and returns them behind the three planes."""
         dev = albedo_map.device
         gi = self.gi
         H, W = cam["image_height"], cam["image_width"]
         new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
         render_direct, linear_rgb = torch.empty((3, H, W), device=dev), new("linear_rgb", 3, H, W)
         render_rgb, acc, loss = torch.empty((3, H, W), device=dev), new("acc", 4 + 4 * 256), new("loss", 1)
+        diffuse_rgb, specular_rgb = (torch.empty((3, H, W), device=dev) for _ in range(2)) if parts else (None, None)
         p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         light = self.light
         spec = [s.contiguous() for s in light.specular]
@@ -273,7 +275,7 @@ class Relighter(_ViewGraph):
                 gigs_lib.ctx_ptr(), H, W, p(normals_view), p(vd), p(albedo_shade), p(roughness_map), p(mask_u8), p(occlusion),
                 p(metallic_map) if self.metallic else None, None, p(light.diffuse), int(light.diffuse.shape[1]), len(spec),
                 spec_ptr, spec_res, p(lut), int(lut.shape[-2]), int(lut.shape[-3]), int(self.tone), int(self.gamma),
-                p(render_direct), None, None, None, C.addressof(ext), s), "shade_fwd_ex")
+                p(render_direct), p(diffuse_rgb), p(specular_rgb), None, C.addressof(ext), s), "shade_fwd_ex")
             IRR, _ = _ops.SSR(W, H, W / (2.0 * cam["tanfovx"]), H / (2.0 * cam["tanfovy"]), gi["radius"], gi["bias"],
                               gi["thick"], gi["delta"], gi["step"], gi["start"], onv, depth_pos, linear_rgb, albedo_map,
                               roughness_map, metallic_in, F0)
@@ -281,6 +283,8 @@ class Relighter(_ViewGraph):
             gigs_lib.check(_lib.gigs_stage2_loss_fwd(H, W, p(render_direct), p(IRR), p(render_direct), p(mask_f),
                                                      p(roughness_map), p(metallic_in), p(render_rgb), p(acc), p(loss), s),
                            "stage2_loss_fwd")
+        if parts:
+            return render_direct, IRR, render_rgb, diffuse_rgb, specular_rgb
         return render_direct, IRR, render_rgb
 
 

@@ -1,0 +1,202 @@
+"""A trained scene under new environment maps, on disk: the reference's relight.py (and relight_eval.py with --gt_dir)
+over relight.MultiRelighter, relight.RelightEvaluator and image_writer.ImageWriter.
+
+    python gi-gs_amd/relight_scene.py -m <out> --checkpoint <out>/chkpntN.pth --hdri a.hdr [b.hdr ...]
+                                      [--metallic --tone --gamma --skip_train --skip_test --gt_dir DIR --lpips_weights DIR]
+    relight_scene(args) -> {split: {...}}
+
+Flags and defaults are relight.py's (:340-356), with --hdri taking one or more maps (Radiance .hdr or .npy [H,W,3]): K
+maps go through MultiRelighter, up to its limit of 16 per pass (more maps run in passes of 16).  <light> is the map's
+file name up to the first dot (:286).  Per split it writes (`planned_paths` is the table):
+
+    <out>/<split>/envmap_relight_<light>.png                                       relight.py:142-145
+    <out>/<split>/ours_<iter>/relight/<image_name>_<light>.png                     :249-251
+    <out>/<split>/ours_<iter>/relight/<image_name>_<light>_occlusion.png           :184-186
+    <out>/<split>/ours_<iter>/relight/<light>.json                                 with --gt_dir: relight_eval.py:68-85
+
+The albedo ratio is read from <out>/test/ours_<iter>/pbr/albedo_ratio.json (:203-210) when that file exists; without it
+the albedo is not scaled (the reference fails there).  With --gt_dir the ground truth of view <image_name> under <light>
+is <gt_dir>/<light>/<image_name>.png; each view feeds RelightEvaluator, and <light>.json holds psnr_avg, ssim_avg (and
+lpips_avg with --lpips_weights) over the split's views -- relight_eval.py's metrics without its fixed view list r_0010 ..
+and its 400 x 400 resize target (the ground truth is resized to the prediction's size).
+
+Deviation: the reference writes <split>/envmap_relight.png, which every light of relight_all.bash overwrites; here the
+file carries the light's name.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+from argparse import Namespace
+from typing import Dict, List, Optional, Sequence
+
+if __package__ in (None, ""):  # run as a script: make the package's modules importable
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import render_scene as rs  # noqa: E402
+
+MAX_LIGHTS = 16  # relight.MAX_LIGHTS
+
+
+def light_name(path: str) -> str:
+    return os.path.basename(path).split(".")[0]  # relight.py:286
+
+
+# ---- file names (pure) ----------------------------------------------------------------------------------------------------
+def view_paths(out: str, split: str, iteration: int, image_name: str, lights: Sequence[str]) -> List[str]:
+    base = os.path.join(rs.split_dir(out, split, iteration), "relight")
+    files = []
+    for light in lights:
+        files.append(os.path.join(base, "%s_%s.png" % (image_name, light)))
+        files.append(os.path.join(base, "%s_%s_occlusion.png" % (image_name, light)))
+    return files
+
+
+def planned_paths(out: str, split: str, iteration: int, image_names: Sequence[str], lights: Sequence[str],
+                  with_metrics: bool = False) -> List[str]:
+    """Every file relight_scene writes for a split."""
+    files = [os.path.join(out, split, "envmap_relight_%s.png" % light) for light in lights]
+    for name in image_names:
+        files.extend(view_paths(out, split, iteration, name, lights))
+    if with_metrics:
+        files.extend(os.path.join(rs.split_dir(out, split, iteration), "relight", light + ".json") for light in lights)
+    return files
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Testing script parameters")
+    rs.add_model_arguments(p)
+    for k in ("skip_train", "skip_test", "quiet", "tone", "gamma", "metallic"):
+        p.add_argument("--" + k, action="store_true")
+    p.add_argument("--hdri", type=str, nargs="+", default=None, help="The environment maps for relighting (.hdr or .npy).")
+    p.add_argument("--checkpoint", type=str, default=None, help="The path to the checkpoint to load.")
+    for k, v in rs.GI_FLAGS.items():
+        p.add_argument("--" + k, type=type(v), default=v)
+    p.add_argument("--gt_dir", type=str, default=None, help="ground truth: <gt_dir>/<light>/<image_name>.png")
+    p.add_argument("--lpips_weights", type=str, default=None, help="directory with vgg16-397923af.pth and vgg.pth")
+    p.add_argument("--workers", type=int, default=12, help="PNG encoder threads (at most 16)")
+    return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> Namespace:
+    return build_parser().parse_args(argv)
+
+
+def _read_gt(path: str, dev):
+    import numpy as np
+    import torch
+    from PIL import Image
+    arr = np.array(Image.open(path))[..., :3]
+    return torch.from_numpy(arr).to(dev).permute(2, 0, 1) / 255.0  # relight_eval.py:52-53
+
+
+def relight_split(args: Namespace, split: str, infos, g, sh_degree: int, lights, names: List[str], iteration: int, dev,
+                  ratio, lp=None) -> Dict:
+    import torch
+
+    import dataset_readers as dr
+    import image_writer
+    import pbr
+    import pipeline
+    import relight
+    out = args.model_path
+    image_names = [ci.image_name for ci in infos]
+    for path in planned_paths(out, split, iteration, image_names, names):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    gi = {k: getattr(args, k) for k in rs.GI_FLAGS}
+    lut = pbr.get_brdf_lut().to(dev)
+    res: Dict = {"n_views": len(infos), "lights": list(names)}
+    t0 = time.perf_counter()
+    with image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
+        for first in range(0, len(lights), MAX_LIGHTS):
+            chunk, chunk_names = lights[first:first + MAX_LIGHTS], names[first:first + MAX_LIGHTS]
+            mr = relight.MultiRelighter(chunk, gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
+                                        graphs=True, brdf_lut=lut)  # build_mips per light (:141)
+            ev = relight.RelightEvaluator(chunk_names, device=dev, lpips=lp) if args.gt_dir else None
+            try:
+                wr.submit([(os.path.join(out, split, "envmap_relight_%s.png" % n),
+                            light.export_envmap(return_img=True).permute(2, 0, 1).clamp(min=0.0, max=1.0))
+                           for n, light in zip(chunk_names, chunk)])
+                rays = None
+                for ci in infos:
+                    c = dr.camera_from_info(ci, args.resolution, device=dev)
+                    if rays is None:
+                        rays = pipeline.canonical_rays(c, dev)
+                    o = mr(c, g, pipeline.view_dirs_for(c, rays, dev), alpha_mask=c["gt_alpha_mask"], albedo_ratio=ratio)
+                    paths = view_paths(out, split, iteration, ci.image_name, chunk_names)
+                    images = []
+                    for k in range(len(chunk)):
+                        images.append((paths[2 * k], o["render_rgb"][k]))
+                        images.append((paths[2 * k + 1], o["occlusion"]))
+                    wr.submit(images)
+                    if ev is not None:
+                        gt = [_read_gt(os.path.join(args.gt_dir, n, ci.image_name + ".png"), dev) for n in chunk_names]
+                        ev.add(o["render_rgb"], torch.stack(gt))
+                if ev is not None:
+                    for n, m in ev.results().items():
+                        m = {k: v for k, v in m.items() if k != "n_views"}
+                        path = os.path.join(rs.split_dir(out, split, iteration), "relight", n + ".json")
+                        with open(path, "w") as f:
+                            json.dump(m, f, indent=4)
+                        res.setdefault("metrics", {})[n] = m
+            finally:
+                mr.close()
+    res.update(files=wr.files, png_bytes=wr.bytes_written, submit_blocked_s=round(wr.blocked_s, 4),
+               total_s=round(time.perf_counter() - t0, 4))
+    return res
+
+
+def relight_scene(args) -> Dict[str, Dict]:
+    """relight.py's launch (:254-334) for every map of --hdri.  `args`: a Namespace from parse_args, a dict of overrides
+    or an argv list."""
+    import torch
+
+    import image_writer
+    import pipeline
+    import relight
+    args = rs.combine_args(rs.as_namespace(args, parse_args))
+    if not args.hdri:
+        raise ValueError("--hdri: at least one environment map is required")
+    if not torch.cuda.is_available():
+        raise RuntimeError("relight_scene needs the GPU")
+    hdris = [args.hdri] if isinstance(args.hdri, str) else list(args.hdri)
+    names = [light_name(p) for p in hdris]
+    if len(set(names)) != len(names):
+        raise ValueError("--hdri: two maps share the light name %s" % sorted(n for n in names if names.count(n) > 1)[0])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    args.source_path = os.path.abspath(args.source_path)
+    g, sh_degree, ck, cams = rs.load_trained(args, dev)
+    iteration = int(ck["iteration"])
+    lights = [relight.make_light(torch.from_numpy(image_writer.load_latlong(p)).to(dev), res=256) for p in hdris]
+    ratio = None
+    ratio_path = os.path.join(rs.split_dir(args.model_path, "test", iteration), "pbr", "albedo_ratio.json")
+    if os.path.exists(ratio_path):
+        with open(ratio_path) as f:
+            ratio = tuple(float(v) for v in json.load(f)["three_channel_ratio"])
+    lp = rs.load_lpips(args)
+    results: Dict[str, Dict] = {}
+    try:
+        for split, skip in (("train", args.skip_train), ("test", args.skip_test)):
+            if not skip and cams[split]:
+                results[split] = relight_split(args, split, cams[split], g, sh_degree, lights, names, iteration, dev, ratio, lp)
+                results[split]["albedo_ratio"] = ratio
+        return results
+    finally:
+        pipeline._collect_idle()
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
+    print("Rendering " + (args.model_path or os.path.dirname(os.path.abspath(args.checkpoint or "."))))
+    print(json.dumps(relight_scene(args)))
+    return 0
+
+
+if __name__ == "__main__":
+    import importlib
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    importlib.import_module("gi-gs_amd")
+    sys.exit(main())

@@ -105,7 +105,7 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--" + k, type=int, default=TRAIN_FLAGS[k])
     for k in ("tone", "gamma", "metallic", "indirect"):
         p.add_argument("--" + k, action="store_true")
-    p.add_argument("--hdri", type=str, default=None, help="latitude-longitude HDR map (.npy [H,W,3] float32) for the initial light")
+    p.add_argument("--hdri", type=str, default=None, help="latitude-longitude HDR map (.npy [H,W,3] float32 or Radiance .hdr) for the initial light")
     p.add_argument("--init_points", type=int, default=NEW_FLAGS["init_points"], help="random initial points of a Blender scene")
     p.add_argument("--sh_up_interval", type=int, default=NEW_FLAGS["sh_up_interval"])
     p.add_argument("--seed", type=int, default=NEW_FLAGS["seed"])
@@ -297,10 +297,9 @@ def _light(args, dev, opacity_lr):
     import torch
     from pbr import CubemapLight
     if args.hdri:
+        import image_writer
         import relight
-        if not args.hdri.endswith(".npy"):
-            raise ValueError("--hdri: pass the latitude-longitude map as a .npy [H,W,3] float32 array")
-        light = relight.make_light(torch.from_numpy(np.load(args.hdri).astype(np.float32)).to(dev), res=256)
+        light = relight.make_light(torch.from_numpy(image_writer.load_latlong(args.hdri)).to(dev), res=256)
         light.train()
     else:
         light = CubemapLight(base_res=256, device=dev)                      # train.py:210-212 without the private HDRI

@@ -518,6 +518,45 @@ int gigs_lpips_vgg_pack(const float* const* conv_w, const float* const* conv_b, 
 size_t gigs_lpips_vgg_scratch_bytes(int n, int height, int width);
 int gigs_lpips_vgg(int n, int height, int width, const float* in0, const float* in1, int normalize, const float* packed,
                    void* scratch, int* slot, double* out, float* const* taps, void* stream);
+/* Writing images (gigs-hip extension; the device half of image_writer.py): float planes -> 8-bit RGB sheets -> the
+ * scanline stream of a PNG, i.e. everything of an encoder but the deflate.  `desc` is a DEVICE table of n descriptors
+ * (0 <= n <= GIGS_MAX_IMAGES); all images go through one launch.  No host synchronisation and no allocation: safe to
+ * capture in a graph, and the table may be rewritten between replays.  A descriptor with a NULL pointer, a size <= 0 or
+ * channels outside {1, 3} is skipped; the caller is responsible for the bounds the descriptors imply.
+ * gigs_pack_images: src [channels,H,W] fp32 -> dst[y * dst_stride + 3 * (dst_x + x) + c] (bytes; channels == 1 is
+ *   replicated to three, as torchvision's make_grid does for save_image).  v = trunc(clamp(x * 255 + bias, 0, 255)) with
+ *   the product and the sum rounded separately, which is bit for bit torch's x.mul(255).add_(bias).clamp_(0, 255)
+ *   .to(torch.uint8): bias = 0.5 is torchvision.utils.save_image, bias = 0 is ToPILImage's mul(255).byte() (the latter
+ *   stated from memory of torchvision's source, which was not at hand to check).  NaN -> 0 (torch leaves the conversion
+ *   of NaN to uint8 undefined); +inf -> 255, -inf -> 0.  lohi != NULL: two device floats {lo, hi}, and
+ *   x = (x - lo) / (hi - lo) (correctly rounded division) comes first: render.py:376's depth image.
+ * gigs_plane_minmax: {min, max} of count floats -> out2 (device), through `scratch` (GIGS_MINMAX_SCRATCH_FLOATS floats)
+ *   in a fixed order without float atomics.  NaNs are ignored (torch's min() / max() would propagate them).
+ * gigs_png_filter: sheet [H, stride bytes] with 3 * width bytes used per row -> out, H * (1 + 3 * width) bytes: per row
+ *   the filter type, then the filtered row (PNG specification, section 9: None, Sub, Up, Average, Paeth with bpp = 3;
+ *   the row above row 0 and the pixel left of pixel 0 are zero).  Each row takes the filter with the smallest sum of
+ *   |residual as int8| (libpng's heuristic); ties go to the lowest filter type. */
+#define GIGS_MAX_IMAGES 4096
+#define GIGS_MINMAX_SCRATCH_FLOATS 512
+typedef struct gigs_pack_desc {
+  const float* src;
+  uint8_t* dst;
+  const float* lohi;
+  int channels, height, width;
+  int dst_x;      /* pixels */
+  int dst_stride; /* bytes per sheet row */
+  float bias;
+} gigs_pack_desc;
+typedef struct gigs_filter_desc {
+  const uint8_t* sheet;
+  uint8_t* out;
+  int height, width;
+  int stride; /* bytes per sheet row */
+  int reserved;
+} gigs_filter_desc;
+int gigs_pack_images(int n, const gigs_pack_desc* desc, void* stream);
+int gigs_plane_minmax(long long count, const float* src, float* scratch, float* out2, void* stream);
+int gigs_png_filter(int n, const gigs_filter_desc* desc, void* stream);
 int gigs_tv_loss_fwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
                      const float* mask_f, float* scratch, float* loss, void* stream);
 int gigs_tv_loss_bwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
