@@ -363,6 +363,8 @@ specular_divide_weights_kernel(int N, const float* __restrict__ bounds, const ui
 // already divided by wsum.
 // Sum over groups of kLanes consecutive lanes (8 = half a DPP row, 16 = a row, 64 = the wave); the total is
 // valid in the last lane of every group.
+typedef float pbr_f2 __attribute__((ext_vector_type(2)));
+
 template <int kLanes>
 __device__ __forceinline__ float group_sum_last(float v) {
   v += pbr_dpp<0xb1>(v);
@@ -381,12 +383,17 @@ __device__ __forceinline__ float group_sum_last(float v) {
 // face rectangles (`bounds`), and its weights are ONE contiguous run of the table (the rectangles in face
 // order, `offsets[6 o]` onward), so the kernel treats the window as a flat candidate list:
 //   * all six rectangles are loaded up front (six independent 16-byte loads: one memory round trip instead
-//     of one per face) and every candidate index is mapped to its face with selects;
-//   * the weight stream and the texel gathers of kU candidates per lane are issued together, the gathers
-//     unconditionally (a rejected candidate, weight -1, still lies inside its face);
+//     of one per face) and kept in LDS, one 20-word record per texel; a lane keeps the face it is in;
+//   * an iteration issues the texel gathers of kU candidates per lane unconditionally (a rejected candidate,
+//     weight -1, still lies inside its face) and, before it consumes anything, the weight loads of the NEXT
+//     iteration: it waits for one memory round trip, and the weight stream stays in flight across iterations;
 //   * kLanes = 8 / 16 pack eight / four texels into a wave for the levels whose windows hold ~10^2..10^3
 //     candidates (the fixed per-texel work is shared by the wave), kLanes = 64 gives a whole wave to a texel.
-// The pass streams the table once (0.74 GB per direction for the reference's 256..16 chain): it is HBM-bound.
+// The lane-to-candidate assignment, the order of a lane's additions and the reduction are fixed: results are
+// bit-identical from one version of the loop to the next.
+// The pass streams the table once (0.74 GB per direction for the reference's 256..16 chain).  Plain loads, not
+// nontemporal ones: the kU loads of an 8- or 16-lane group fall into one cache line, and a nontemporal load drops
+// the line behind it (measured: +20 % time).
 template <bool kBackward, bool kNorm, int kLanes>
 __device__ __forceinline__ void specular_apply_body(int block, int N, const float* __restrict__ src,
                                                     const float* __restrict__ bounds, const uint32_t* __restrict__ offsets,
@@ -402,83 +409,146 @@ __device__ __forceinline__ void specular_apply_body(int block, int N, const floa
   const int g = lane % kLanes;
   const int stride = (kBackward && !kNorm) ? 4 : 3;
 
-  int wd[6], pre[7], base[6];
-  float inv[6];
+  // The six face rectangles of a texel -- prefix counts, widths, first texels -- are the same for all kLanes lanes of
+  // its group and are needed again only where a lane crosses into the next face.  They live in LDS, 20 words per
+  // texel, not in 25 registers per lane: the registers go to the loads in flight below.
+  __shared__ int face_tab[4 * kPerWave * 20];
+  int* tab = face_tab + ((threadIdx.x >> 6) * kPerWave + lane / kLanes) * 20;  // [0..6] pre, [8..13] wd, [14..19] base
   const float4* b4 = reinterpret_cast<const float4*>(bounds + 24 * (size_t)o);
   const uint32_t first = offsets[6 * (size_t)o];
-  pre[0] = 0;
+  int n_all;
+  {
+    int wd[6], pre[7], base[6];
+    pre[0] = 0;
 #pragma unroll
-  for (int s = 0; s < 6; ++s) {
-    const float4 b = b4[s];
-    const int xmin = (int)b.x, xmax = (int)b.y, ymin = (int)b.z, ymax = (int)b.w;
-    const bool empty = xmin > xmax || ymin > ymax;
-    wd[s] = empty ? 1 : xmax - xmin + 1;
-    pre[s + 1] = pre[s] + (empty ? 0 : wd[s] * (ymax - ymin + 1));
-    base[s] = empty ? 0 : (s * N + ymin) * N + xmin;
-    // row = floor((loc + 0.5) / wd): the half-texel slack dwarfs the 1-ulp error of the hardware reciprocal
-    inv[s] = __builtin_amdgcn_rcpf((float)wd[s]);
+    for (int s = 0; s < 6; ++s) {
+      const float4 b = b4[s];
+      const int xmin = (int)b.x, xmax = (int)b.y, ymin = (int)b.z, ymax = (int)b.w;
+      const bool empty = xmin > xmax || ymin > ymax;
+      wd[s] = empty ? 1 : xmax - xmin + 1;
+      pre[s + 1] = pre[s] + (empty ? 0 : wd[s] * (ymax - ymin + 1));
+      base[s] = empty ? 0 : (s * N + ymin) * N + xmin;
+    }
+    n_all = pre[6];
+    if (g == 0) {
+#pragma unroll
+      for (int s = 0; s < 7; ++s) tab[s] = pre[s];
+#pragma unroll
+      for (int s = 0; s < 6; ++s) { tab[8 + s] = wd[s]; tab[14 + s] = base[s]; }
+    }
+    // written and read by lanes of the same wave only: LDS operations of a wave complete in order
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
-  const int n = valid ? pre[6] : 0;
-  const float* wrow = W + first;
+  const int n = valid ? n_all : 0;
+  // Both streams are addressed as a wave-uniform base plus a 32-bit byte offset (a 64-bit address per load in flight
+  // would cost the registers the pipeline below needs).  The texels of a wave are consecutive and so are their runs
+  // of the table, so the weights are addressed from the first lane's run.
+  const uint32_t first0 = __builtin_amdgcn_readfirstlane(first);
+  const char* wbase = reinterpret_cast<const char*>(W + first0);
+  const char* tbase = reinterpret_cast<const char*>(src);
+  const int wrel = (int)(first - first0);
+  auto load_w = [&](int i) { return *reinterpret_cast<const float*>(wbase + (uint32_t)(4 * (wrel + i))); };
 
-  float wsum = 0.0f, c0 = 0, c1 = 0, c2 = 0;
-  // face of candidate i: the last face with pre[k] <= i (empty faces are overridden by the next one)
-  int f_wd, f_base, f_pre, f_end;
+  pbr_f2 acc01 = {0.0f, 0.0f}, accw2 = {0.0f, 0.0f};  // (c0, c1) and (weight sum, c2)
+  // Face of candidate i: the last face with pre[k] <= i (empty faces are overridden by the next one).  Candidate i of
+  // a face with first candidate `pre`, width wd and first texel `base` is the texel base + loc + row (N - wd), with
+  // loc = i - pre and row = floor(loc / wd); kept per face are the byte offset of (base - pre) and the byte stride
+  // of a row, so that a candidate's offset is two shift-adds and one 24-bit multiply-add (row < N, the row stride
+  // < 16 N: both far below 2^24), none of them a full 32-bit multiply.
+  int f_pre, f_end;
+  uint32_t f_off, f_row;
   float f_inv;
   auto find_face = [&](int i) {
-    f_wd = wd[0]; f_base = base[0]; f_pre = 0; f_end = pre[1]; f_inv = inv[0];
+    int k = 0;
 #pragma unroll
-    for (int k = 1; k < 6; k++) {
-      const bool ge = i >= pre[k];
-      f_wd = ge ? wd[k] : f_wd; f_base = ge ? base[k] : f_base; f_pre = ge ? pre[k] : f_pre;
-      f_end = ge ? pre[k + 1] : f_end; f_inv = ge ? inv[k] : f_inv;
-    }
+    for (int j = 1; j < 6; j++) k += i >= tab[j] ? 1 : 0;  // the prefix counts do not decrease
+    f_pre = tab[k]; f_end = tab[k + 1];
+    const int f_wd = tab[8 + k];
+    f_off = (uint32_t)(4 * stride * (tab[14 + k] - f_pre)); f_row = (uint32_t)(4 * stride * (N - f_wd));
+    // row = floor((loc + 0.5) / wd): the half-texel slack dwarfs the 1-ulp error of the hardware reciprocal
+    f_inv = __builtin_amdgcn_rcpf((float)f_wd);
   };
+  auto texel_offset = [&](int i) {
+    const uint32_t row = (uint32_t)(int)(((float)(i - f_pre) + 0.5f) * f_inv), ui = (uint32_t)i;
+    uint32_t lin = (ui << (stride == 3 ? 2 : 4)) + f_off;
+    // 12 i = 8 i + 4 i; in assembly because the compiler folds the two shift-adds back into a 32-bit multiply
+    if (stride == 3) asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(lin) : "v"(ui), "v"(lin));
+    return __umul24(row, f_row) + lin;
+  };
+  // The weight stream is software-pipelined: batch k+1's weights are requested before batch k is consumed (their
+  // addresses depend on no data), so an iteration waits for one memory round trip -- its gathers -- instead of two.
+  // ic: the batch's candidate indices, clamped into the list (a candidate past its end reads the last one's weight
+  // and texel; its weight is replaced by -1)
+  float wn[kU];
+  int ic[kU];
+#pragma unroll
+  for (int u = 0; u < kU; u++) { wn[u] = -1.0f; ic[u] = min(g + kLanes * u, n - 1); }
+  if (n > 0) {
+#pragma unroll
+    for (int u = 0; u < kU; u++) wn[u] = load_w(ic[u]);
+  }
   find_face(g);
   for (int i0 = g; i0 < n; i0 += kLanes * kU) {
     float w[kU];
-    int idx[kU];
-    // Lanes walk their candidates in increasing order, so the face changes at most five times per texel:
-    // the select chain runs only in iterations where some lane of the wave crosses a face (or the list) end.
-    const bool cross = i0 + kLanes * (kU - 1) >= f_end && f_end < n;  // running past the END OF THE LIST is handled below
+    uint32_t off[kU];
+    // Lanes walk their candidates in increasing order, so the face changes at most five times per texel: the table
+    // is read only in iterations where some lane of the wave crosses a face end (past the END OF THE LIST the
+    // clamped candidates stay in the last face).
+    const bool cross = i0 + kLanes * (kU - 1) >= f_end && f_end < n;
     if (__any(cross)) {
 #pragma unroll
       for (int u = 0; u < kU; u++) {
-        const int i = i0 + kLanes * u;
-        const bool in = i < n;
-        const int ic = in ? i : 0;
-        w[u] = in ? wrow[i] : -1.0f;
-        find_face(ic);
-        const int loc = ic - f_pre;
-        const int yy = (int)(((float)loc + 0.5f) * f_inv), xx = loc - yy * f_wd;
-        idx[u] = f_base + yy * N + xx;
+        find_face(ic[u]);
+        off[u] = texel_offset(ic[u]);
       }
       find_face(min(i0 + kLanes * kU, n - 1));
     } else {
 #pragma unroll
-      for (int u = 0; u < kU; u++) {
-        const int i = i0 + kLanes * u;
-        const bool in = i < n;
-        w[u] = in ? wrow[i] : -1.0f;
-        const int loc = in ? i - f_pre : 0;
-        const int yy = (int)(((float)loc + 0.5f) * f_inv), xx = loc - yy * f_wd;
-        idx[u] = f_base + yy * N + xx;
-      }
+      for (int u = 0; u < kU; u++) off[u] = texel_offset(ic[u]);
     }
+    // all kU gathers, unconditionally (a rejected candidate, weight -1, still lies inside its face) ...
     float t0[kU], t1[kU], t2[kU];
 #pragma unroll
     for (int u = 0; u < kU; u++) {
-      const float* t = src + (size_t)stride * idx[u];
+      const float* t = reinterpret_cast<const float*>(tbase + off[u]);
       t0[u] = t[0]; t1[u] = t[1]; t2[u] = t[2];
     }
+    // ... then this batch's weights and the request for the next batch's
+#pragma unroll
+    for (int u = 1; u < kU; u++) w[u] = i0 + kLanes * u < n ? wn[u] : -1.0f;
+    // candidate 0 is always inside the list; the explicit move frees wn[0] for the load below (left to the compiler,
+    // the copy lands at the end of the loop, behind a wait for that load)
+    asm volatile("v_mov_b32 %0, %1" : "=v"(w[0]) : "v"(wn[0]));
 #pragma unroll
     for (int u = 0; u < kU; u++) {
-      if (w[u] >= 0.0f) {  // -1 marks candidates outside the cone
-        c0 += t0[u] * w[u]; c1 += t1[u] * w[u]; c2 += t2[u] * w[u];
-        wsum += w[u];
-      }
+      ic[u] = min(i0 + kLanes * (kU + u), n - 1);
+      wn[u] = load_w(ic[u]);
+    }
+    // every gathered value is used here whatever its weight: the compiler must not sink a gather below the sign
+    // test of its weight (it did: a second, dependent round trip per batch)
+#pragma unroll
+    for (int u = 0; u < kU; u++) asm volatile("" : "+v"(t0[u]), "+v"(t1[u]), "+v"(t2[u]));
+    // -1 marks candidates outside the cone: they never touch an accumulator (0 * Inf).  The products are formed for
+    // every candidate and ADDED under an execution mask of the lanes with w >= 0 (false for a NaN weight, like the
+    // comparison in C++): five vector instructions per candidate where the compiler's select per accumulator takes nine.
+#pragma unroll
+    for (int u = 0; u < kU; u++) {
+      const pbr_f2 wp = {w[u], t2[u] * w[u]};
+      const pbr_f2 p01 = {t0[u] * w[u], t1[u] * w[u]};
+      unsigned long long saved;
+      asm volatile("s_mov_b64 %[sv], exec\n\t"
+                   "v_cmpx_le_f32_e32 vcc, 0, %[w]\n\t"
+                   "v_pk_add_f32 %[a01], %[a01], %[p01]\n\t"
+                   "v_pk_add_f32 %[aw2], %[aw2], %[wp]\n\t"
+                   "s_mov_b64 exec, %[sv]"
+                   : [a01] "+v"(acc01), [aw2] "+v"(accw2), [sv] "=&s"(saved)
+                   : [w] "v"(w[u]), [p01] "v"(p01), [wp] "v"(wp)
+                   : "vcc");
     }
   }
+  float c0 = acc01.x, c1 = acc01.y, c2 = accw2.y, wsum = accw2.x;
   c0 = group_sum_last<kLanes>(c0); c1 = group_sum_last<kLanes>(c1); c2 = group_sum_last<kLanes>(c2);
   if (!kBackward) wsum = group_sum_last<kLanes>(wsum);
   if (g == kLanes - 1 && valid) {
