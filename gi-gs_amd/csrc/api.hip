@@ -119,9 +119,7 @@ gigs::Options options_from_env() {
   o.pre_bwd_sh_skip = env_int("GIGS_PRE_BWD_SH_SKIP", 1) != 0;
   o.gi_march = 4;
   if (const char* e = getenv("GIGS_GI_MARCH")) {
-    static const char* names[] = {"exact", "hoist", "hoist_fma", "proj_nr", "proj"};
-    for (int i = 0; i < 5; i++)
-      if (strcmp(e, names[i]) == 0) o.gi_march = i;
+    if (strcmp(e, "exact") == 0) o.gi_march = 0;  // "proj" is the default; so is every other string
   }
   o.gi_cert = env_int("GIGS_GI_CERT", 1) != 0;
   o.gi_interleave = env_int("GIGS_GI_INTERLEAVE", 1) != 0;
@@ -268,7 +266,7 @@ int gigs_ctx_get_options(const gigs_ctx* ctx, gigs_options* out) {
 int gigs_ctx_set_options(gigs_ctx* ctx, const gigs_options* in) {
   if (!ctx) return fail(GIGS_ERR_INVALID, "gigs_ctx_set_options: the default context is immutable, create one");
   if (!in || in->struct_bytes < (int)sizeof(gigs_options)) return fail(GIGS_ERR_INVALID, "gigs_ctx_set_options: set struct_bytes = sizeof(gigs_options)");
-  if (in->gi_march < 0 || in->gi_march > 4) return fail(GIGS_ERR_INVALID, "gi_march must be 0..4");
+  if (in->gi_march != 0 && in->gi_march != 4) return fail(GIGS_ERR_INVALID, "gi_march must be 0 (exact) or 4 (proj)");
   if (in->gi_tile_log2w < 0 || in->gi_tile_log2w > 6) return fail(GIGS_ERR_INVALID, "gi_tile_log2w must be 0..6");
   if (in->long_lists < -1 || in->long_lists > 1) return fail(GIGS_ERR_INVALID, "long_lists must be -1, 0 or 1");
   if (in->bucket_target < 256 || in->bucket_max_mean < 0 || in->bin_bands < 0 || in->bin_bands > 64)

@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "gigs_common.h"
@@ -213,7 +214,7 @@ struct GiParams {
   int nrays;        // rays [n_live, nrays) behind them go round-robin to the waves (zero-weight rays: none for SSAO, one for SSR)
   int nrays_total;  // all rays of the reference's loops (SSR's nrSamples)
   int tile_log2w;  // the 64 pixels of a workgroup form a (1 << tile_log2w) x (64 >> tile_log2w) rectangle
-  int ray_interleave;  // fast marches: wave w takes ray pairs w, w + 4, ... instead of the w-th quarter of the ray set
+  int ray_interleave;  // projective march: wave w takes ray pairs w, w + 4, ... instead of the w-th quarter of the ray set
   int cert_shift;      // certification blocks are (1 << cert_shift)^2 pixels; 0 = no certification table
   int cert_w, cert_h;  // blocks per row / column of the image; the table is (cert_w + 1) x (cert_h + 1): last column / row = border
   float cert_d0;       // certification needs den > cert_d0 (CertK::d0)
@@ -558,33 +559,25 @@ __device__ __forceinline__ bool tbn_never_hits(const Tbn& m) {
 
 
 // ------------------------------------------------------------------------------------------
-// Tolerance-spending marches (GIGS_GI_MARCH; kMode > 0)
+// The projective march (GIGS_GI_MARCH=proj, the default)
 // ------------------------------------------------------------------------------------------
 // The exact march above reproduces the oracle's pixel choice bit for bit and pays for it with ~31 VALU
 // instructions per ray-step.  north_star's bar for the fp planes is 1e-4 mean per-pixel L1, and the reference's
 // own binary is an FMA-contracted compilation of the same lines (nvcc -fmad=true), so its projected coordinates
-// already differ from the contraction-free oracle in the last place.  The variants below spend that tolerance:
-//
-//   kMode 1 "hoist"      per-ray step vector k = ((sv*a)*a*radius) (then * j/step), sp = pos + (j/step)*k with a
-//                        separate multiply and add; both quotients IEEE-correct (the shared-reciprocal chain);
-//                        q*f + c as multiply and add.  Only the order of the multiplies differs from forward.cu:693.
-//   kMode 2 "hoist_fma"  the same with FMAs for pos + fj*k and q*f + c (what nvcc's contraction does to ssr.h:133).
-//   kMode 3 "proj_nr"    projective form: numerators (pos.xy*f + fj*Bxy), denominator (pos.z + 1e-7 + fj*Bz), one
-//                        v_rcp_f32 refined by one Newton step, t = n*r + (c + 0.5): 3 packed FMAs + rcp per sample.
-//   kMode 4 "proj"       kMode 3 with the raw 1-ulp v_rcp_f32.
-//
-// In modes 3/4 the depth test z in [spz - thick, spz + bias] is evaluated as |z - (den + cm)| <= hh with
+// already differ from the contraction-free oracle in the last place.  The projective march spends that tolerance:
+// per sample the numerators (pos.xy*f + fj*Bxy) and the denominator (pos.z + 1e-7 + fj*Bz) with fj = j/step and
+// B the per-ray step vector, one raw (1-ulp) v_rcp_f32, t = n*r + (c + 0.5): 3 packed FMAs + rcp.
+// The depth test z in [spz - thick, spz + bias] is evaluated as |z - (den + cm)| <= hh with
 // cm = (bias - thick)/2 - 1e-7, hh = (bias + thick)/2 (same interval, different rounding of its ends).
-// Every mode keeps the march's control flow: in-order resolution, break on leaving the image, first hit wins.
-// tools/gi_variants.py measures each mode against mode 0 (= the oracle, bit for bit) on the C2 view and the GI test
-// scenes; DESIGN.md section 5 holds the table and the choice of default.
+// The march's control flow is kept: in-order resolution, break on leaving the image, first hit wins.
+// tools/gi_variants.py measures it against the exact march (= the oracle, bit for bit) on the C2 view and the GI test
+// scenes; DESIGN.md section 5 holds the table and the choice of default.  (Three intermediate formulations were measured
+// in round 2, profiles/r02/gi_variants.json, and removed: see the git history.)
 struct FastPix {
-  f32x2 Axy;      // modes 1/2: pos.xy;            modes 3/4: pos.xy * (fx, fy)
-  float Dz;       // modes 1/2: pos.z;             modes 3/4: pos.z + 1e-7
+  f32x2 Axy;      // pos.xy * (fx, fy)
+  float Dz;       // pos.z + 1e-7
   f32x2 cxy;      // (cx, cy) + round_pix's addend
-  f32x2 c0xy;     // (cx, cy)
-  f32x2 fxy;
-  float cm, hh, bias, thick;
+  float cm, hh;
 };
 
 __device__ __forceinline__ int cvt_flr(float t) {  // (int)floor(t), saturating, NaN -> 0: one VOP1 instruction
@@ -593,7 +586,7 @@ __device__ __forceinline__ int cvt_flr(float t) {  // (int)floor(t), saturating,
   return r;
 }
 
-template <int kMode, int kGroup>
+template <int kGroup>
 __device__ __forceinline__ void march2_fast(const GiParams& p, const FastPix& c, const f32x2* Bxy, f32x2 Bz2,
                                             __amdgpu_buffer_rsrc_t pos_z, int* hit) {
   bool open[2] = {true, true};
@@ -602,50 +595,21 @@ __device__ __forceinline__ void march2_fast(const GiParams& p, const FastPix& c,
   for (int j0 = p.start; j0 < p.step; j0 += kGroup) {
     unsigned off[2][kGroup];
     bool inb[2][kGroup];
-    f32x2 ta[kGroup], tb[kGroup];  // modes 1/2: spz + bias, spz - thick; modes 3/4: mid (ta only)
+    f32x2 ta[kGroup];  // middle of the hit interval
 #pragma unroll
     for (int g = 0; g < kGroup; g++) {
       const float fj = p.fjt[j0 - p.start + g];  // j / step
       const f32x2 fj2 = {fj, fj};
       const bool in_range = (j0 + g) < p.step;
-      f32x2 r;
-      f32x2 den;
-      if constexpr (kMode >= 3) {
-        den = __builtin_elementwise_fma(Bz2, fj2, Dz2);
-        ta[g] = den + c.cm;
-        r = f32x2{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-        if constexpr (kMode == 3) {
-          const f32x2 e0 = __builtin_elementwise_fma(-den, r, f32x2{1.0f, 1.0f});
-          r = __builtin_elementwise_fma(e0, r, r);
-        }
-      } else {
-        const f32x2 spz = (kMode == 2) ? __builtin_elementwise_fma(Bz2, fj2, Dz2) : Dz2 + Bz2 * fj2;
-        den = spz + 0.0000001f;
-        ta[g] = spz + c.bias;
-        tb[g] = spz - c.thick;
-        const f32x2 r0 = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-        const f32x2 e0 = __builtin_elementwise_fma(-den, r0, f32x2{1.0f, 1.0f});
-        r = __builtin_elementwise_fma(e0, r0, r0);
-      }
+      const f32x2 den = __builtin_elementwise_fma(Bz2, fj2, Dz2);
+      ta[g] = den + c.cm;
+      const f32x2 r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
 #pragma unroll
       for (int k = 0; k < 2; k++) {
         const float rk = k == 0 ? r.x : r.y;
         const f32x2 rr = {rk, rk};
-        f32x2 t;
-        if constexpr (kMode >= 3) {
-          const f32x2 n = __builtin_elementwise_fma(Bxy[k], fj2, c.Axy);
-          t = __builtin_elementwise_fma(n, rr, c.cxy);
-        } else {
-          const f32x2 sp = (kMode == 2) ? __builtin_elementwise_fma(Bxy[k], fj2, c.Axy) : c.Axy + Bxy[k] * fj2;
-          const float d = k == 0 ? den.x : den.y;
-          const f32x2 nd = {-d, -d};
-          const f32x2 q0 = sp * rr;
-          const f32x2 e1 = __builtin_elementwise_fma(nd, q0, sp);
-          const f32x2 q1 = __builtin_elementwise_fma(e1, rr, q0);
-          const f32x2 e2 = __builtin_elementwise_fma(nd, q1, sp);
-          const f32x2 qv = __builtin_elementwise_fma(e2, rr, q1);
-          t = ((kMode == 2) ? __builtin_elementwise_fma(qv, c.fxy, c.c0xy) : qv * c.fxy + c.c0xy) + 0.49999997f;
-        }
+        const f32x2 n = __builtin_elementwise_fma(Bxy[k], fj2, c.Axy);
+        const f32x2 t = __builtin_elementwise_fma(n, rr, c.cxy);
         const int ix = cvt_flr(t.x);
         const int iy = cvt_flr(t.y);
         inb[k][g] = in_range && (unsigned)ix < (unsigned)p.W && (unsigned)iy < (unsigned)p.H;
@@ -665,12 +629,7 @@ __device__ __forceinline__ void march2_fast(const GiParams& p, const FastPix& c,
 #pragma unroll
       for (int g = 0; g < kGroup; g++) {
         const float z = zn[2 * g + k];
-        bool h;
-        if constexpr (kMode >= 3) {
-          h = inb[k][g] && fabsf(z - (k == 0 ? ta[g].x : ta[g].y)) <= c.hh;
-        } else {
-          h = inb[k][g] && (z <= (k == 0 ? ta[g].x : ta[g].y)) && (z >= (k == 0 ? tb[g].x : tb[g].y));
-        }
+        const bool h = inb[k][g] && fabsf(z - (k == 0 ? ta[g].x : ta[g].y)) <= c.hh;
         hit[k] = (open[k] && h) ? (int)off[k][g] : hit[k];
         open[k] = open[k] && inb[k][g] && !h;
       }
@@ -718,10 +677,9 @@ __host__ __device__ __forceinline__ CertK cert_consts(float bias, float thick) {
 // kTabOff: LDS byte address of the table (the kernels' dynamic LDS starts right after their static arrays; checked at
 // kernel entry).  The lookups are written as instructions because the compiler adds the -- constant -- base with a
 // v_add per lookup instead of using the ds_read offset field.
-template <int kMode, int kGroup, int kTabOff>
+template <int kGroup, int kTabOff>
 __device__ __forceinline__ void march2_cert(const GiParams& p, const FastPix& c, const CertPix& cp, const f32x2* Bxy16,
                                             f32x2 Bz2, __amdgpu_buffer_rsrc_t pos_z, int* hit) {
-  static_assert(kMode >= 3, "certification is wired into the projective marches");
   // Lane predicates are kept as 64-bit wave masks in SGPRs (ballots of single compares, combined with scalar logic,
   // turned back into a lane predicate only where a select needs one): written with per-lane bools the compiler moves
   // them through VGPRs (v_cndmask 0/1 + v_cmp_ne per use) -- a third of the march's vector instructions.
@@ -761,11 +719,7 @@ __device__ __forceinline__ void march2_cert(const GiParams& p, const FastPix& c,
       const f32x2 fj2 = {fj, fj};
       const f32x2 den = __builtin_elementwise_fma(Bz2, fj2, Dz2);
       dn[g] = den;
-      f32x2 r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-      if constexpr (kMode == 3) {
-        const f32x2 e0 = __builtin_elementwise_fma(-den, r, f32x2{1.0f, 1.0f});
-        r = __builtin_elementwise_fma(e0, r, r);
-      }
+      const f32x2 r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
 #pragma unroll
       for (int k = 0; k < 2; k++) {
         const float rk = k == 0 ? r.x : r.y;
@@ -842,23 +796,14 @@ __device__ __forceinline__ void march2_cert(const GiParams& p, const FastPix& c,
   }
 }
 
-// per-pixel constants of the fast marches and the per-ray vectors
-template <int kMode>
+// per-pixel constants of the projective march and the per-ray vectors
 __device__ __forceinline__ FastPix make_fast(const GiParams& p, v3 pos, float cx, float cy) {
   FastPix c;
-  c.fxy = f32x2{p.fx, p.fy};
   c.cxy = f32x2{cx + 0.49999997f, cy + 0.49999997f};
-  c.c0xy = f32x2{cx, cy};
-  c.bias = p.bias; c.thick = p.thick;
   c.cm = 0.5f * (p.bias - p.thick) - 0.0000001f;
   c.hh = 0.5f * (p.bias + p.thick);
-  if constexpr (kMode >= 3) {
-    c.Axy = f32x2{pos.x * p.fx, pos.y * p.fy};
-    c.Dz = pos.z + 0.0000001f;
-  } else {
-    c.Axy = f32x2{pos.x, pos.y};
-    c.Dz = pos.z;
-  }
+  c.Axy = f32x2{pos.x * p.fx, pos.y * p.fy};
+  c.Dz = pos.z + 0.0000001f;
   return c;
 }
 // rows of the tangent frame pre-scaled so that B = M * ts is the per-ray step vector (times j/step per sample)
@@ -873,30 +818,19 @@ __device__ __forceinline__ CertPix make_cert(const GiParams& p, const FastPix& c
   return cp;
 }
 // xy_scale = 2^-cert_shift when the march runs in block units (exact), else 1
-template <int kMode>
 __device__ __forceinline__ FastTbn make_fast_tbn(const GiParams& p, const Tbn& m, float a, float xy_scale = 1.0f) {
   const float s = a * a * p.radius;
-  const float sx = (kMode >= 3 ? s * p.fx : s) * xy_scale, sy = (kMode >= 3 ? s * p.fy : s) * xy_scale;
+  const float sx = (s * p.fx) * xy_scale, sy = (s * p.fy) * xy_scale;
   FastTbn r;
   r.mx = {m.t.x * sx, m.b.x * sx, m.n.x * sx};
   r.my = {m.t.y * sy, m.b.y * sy, m.n.y * sy};
   r.mz = {m.t.z * s, m.b.z * s, m.n.z * s};
   return r;
 }
-template <int kMode>
-__device__ __forceinline__ void fast_ray(const GiParams& p, const Tbn& tbn, const FastTbn& ft, float a, float4 ra, f32x2& bxy,
-                                         float& bz) {
-  float bx, by;
-  if constexpr (kMode >= 3) {
-    bx = __builtin_fmaf(ft.mx.z, ra.z, __builtin_fmaf(ft.mx.y, ra.y, ft.mx.x * ra.x));
-    by = __builtin_fmaf(ft.my.z, ra.z, __builtin_fmaf(ft.my.y, ra.y, ft.my.x * ra.x));
-    bz = __builtin_fmaf(ft.mz.z, ra.z, __builtin_fmaf(ft.mz.y, ra.y, ft.mz.x * ra.x));
-  } else {
-    const v3 sv = tbn_apply(tbn, ra.x, ra.y, ra.z);  // as the reference computes sampleVec
-    bx = ((sv.x * a) * a) * p.radius;
-    by = ((sv.y * a) * a) * p.radius;
-    bz = ((sv.z * a) * a) * p.radius;
-  }
+__device__ __forceinline__ void fast_ray(const FastTbn& ft, float4 ra, f32x2& bxy, float& bz) {
+  const float bx = __builtin_fmaf(ft.mx.z, ra.z, __builtin_fmaf(ft.mx.y, ra.y, ft.mx.x * ra.x));
+  const float by = __builtin_fmaf(ft.my.z, ra.z, __builtin_fmaf(ft.my.y, ra.y, ft.my.x * ra.x));
+  bz = __builtin_fmaf(ft.mz.z, ra.z, __builtin_fmaf(ft.mz.y, ra.y, ft.mz.x * ra.x));
   bxy = f32x2{bx, by};
 }
 
@@ -946,13 +880,19 @@ __device__ __forceinline__ bool gi_pixel(const GiParams& p, int& x, int& y, int&
 #define GIGS_SSR_OCC_L(L) __attribute__((amdgpu_waves_per_eu((L) == 1 ? 5 : GIGS_SSR_MULTI_WAVES)))
 #endif
 
-template <bool kPow2, int kMode, bool kCert>
+// What a kernel instance marches with (gi_dispatch_march picks it).  The exact march has a cheaper form for a power-of-two
+// step; certification exists in front of the projective march only.
+enum class March { kExactPow2, kExact, kProj, kProjCert };
+constexpr bool march_is_proj(March m) { return m == March::kProj || m == March::kProjCert; }
+
+template <March kMarch>
 __global__ void __launch_bounds__(256) GIGS_GI_OCC
 ssao_kernel(GiParams p, const float4* __restrict__ rays, float sum_w,
             const float* __restrict__ nrm, const float* __restrict__ pos_map,
             float* __restrict__ occlusion, const float2* __restrict__ cert_tab) {
   __shared__ float s_part[kGiWaves][64];
   extern __shared__ float2 s_cert[];
+  constexpr bool kPow2 = kMarch == March::kExactPow2, kCert = kMarch == March::kProjCert;
   constexpr int kCertOff = sizeof(float) * kGiWaves * 64;  // dynamic LDS follows the static array
   if constexpr (kCert) {
     if ((unsigned)(size_t)s_cert != (unsigned)kCertOff) __builtin_trap();  // the march addresses the table by this constant
@@ -979,12 +919,12 @@ ssao_kernel(GiParams p, const float4* __restrict__ rays, float sum_w,
       const int chunk = (p.n_live + kGiWaves - 1) / kGiWaves;
       const int r0 = wave * chunk, r1 = min(p.n_live, r0 + chunk);
       const bool mag_ok = gi_mag_ok(pos, a, p.radius);
-      if constexpr (kMode > 0) {
-        // absurd magnitudes (|pos| >= 2^59) are outside the fast marches' contract: such a pixel takes no hits
+      if constexpr (march_is_proj(kMarch)) {
+        // absurd magnitudes (|pos| >= 2^59) are outside the projective march's contract: such a pixel takes no hits
         if (mag_ok) {
-          const FastPix c = make_fast<kMode>(p, pos, cx, cy);
+          const FastPix c = make_fast(p, pos, cx, cy);
           const float inv_scale = kCert ? __uint_as_float((127u - (unsigned)p.cert_shift) << 23) : 1.0f;  // 2^-shift
-          const FastTbn ft = make_fast_tbn<kMode>(p, tbn, a, inv_scale);
+          const FastTbn ft = make_fast_tbn(p, tbn, a, inv_scale);
           const CertPix cp = make_cert(p, c, inv_scale);
           // the four waves of a workgroup share its 64 pixels and split the ray set: contiguous quarters (a quarter of the
           // azimuths each), or interleaved pairs (every wave sees every direction: equal work per wave -- the workgroup
@@ -994,12 +934,12 @@ ssao_kernel(GiParams p, const float4* __restrict__ rays, float sum_w,
           auto pair = [&](int r, int rb) {
             f32x2 Bxy[2], Bz2;
             float bz0, bz1;
-            fast_ray<kMode>(p, tbn, ft, a, rays[2 * r], Bxy[0], bz0);
-            fast_ray<kMode>(p, tbn, ft, a, rays[2 * rb], Bxy[1], bz1);
+            fast_ray(ft, rays[2 * r], Bxy[0], bz0);
+            fast_ray(ft, rays[2 * rb], Bxy[1], bz1);
             Bz2 = f32x2{bz0, bz1};
             int hit[2];
-            if constexpr (kCert) march2_cert<kMode, kGiGroup, kCertOff>(p, c, cp, Bxy, Bz2, pos_z, hit);
-            else march2_fast<kMode, kGiGroup>(p, c, Bxy, Bz2, pos_z, hit);
+            if constexpr (kCert) march2_cert<kGiGroup, kCertOff>(p, c, cp, Bxy, Bz2, pos_z, hit);
+            else march2_fast<kGiGroup>(p, c, Bxy, Bz2, pos_z, hit);
             occ += hit[0] >= 0 ? rays[2 * r + 1].y : 0.0f;
             occ += (hit[1] >= 0 && rb != r) ? rays[2 * rb + 1].y : 0.0f;
           };
@@ -1098,7 +1038,7 @@ __device__ __forceinline__ void ssr_finish(v3 diffuse, const Tbn& tbn, v3 pos, s
 // pixel a ray hits does not depend on the radiance (see SsrHits), so every light's sum takes the same hits in the same
 // order, each with the single-light expression -- light l's outputs are the single-light march's with rgb = rgb[l], bit
 // for bit.  The per-wave partial sums go through the same 3 KB of LDS one light at a time.
-template <bool kPow2, int kMode, bool kCert, int kHits = 0, int kLights = 1>
+template <March kMarch, int kHits = 0, int kLights = 1>
 __global__ void __launch_bounds__(256) GIGS_SSR_OCC_L(kLights)
 ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict__ nrm,
            const float* __restrict__ pos_map, const float* __restrict__ rgb,
@@ -1107,6 +1047,8 @@ ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict_
            const float2* __restrict__ cert_tab, SsrHits hits) {
   __shared__ float s_part[kGiWaves][3][64];
   extern __shared__ float2 s_cert[];
+  static_assert(kHits == 0 || march_is_proj(kMarch), "hit lists exist for the projective march only");
+  constexpr bool kPow2 = kMarch == March::kExactPow2, kCert = kMarch == March::kProjCert;
   constexpr int kCertOff = sizeof(float) * kGiWaves * 3 * 64;  // dynamic LDS follows the static array
   if constexpr (kCert) {
     if ((unsigned)(size_t)s_cert != (unsigned)kCertOff) __builtin_trap();  // the march addresses the table by this constant
@@ -1151,11 +1093,11 @@ ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict_
       }
       (void)ray;
     };
-    if constexpr (kMode > 0) {
+    if constexpr (march_is_proj(kMarch)) {
       if (mag_ok) {  // see ssao_kernel
-        const FastPix c = make_fast<kMode>(p, pos, cx, cy);
+        const FastPix c = make_fast(p, pos, cx, cy);
         const float inv_scale = kCert ? __uint_as_float((127u - (unsigned)p.cert_shift) << 23) : 1.0f;  // 2^-shift
-        const FastTbn ft = make_fast_tbn<kMode>(p, tbn, a, inv_scale);
+        const FastTbn ft = make_fast_tbn(p, tbn, a, inv_scale);
         const CertPix cp = make_cert(p, c, inv_scale);
         const int rs = p.ray_interleave ? 2 * wave : r0, re = p.ray_interleave ? p.n_live : r1;
         const int rstep = p.ray_interleave ? 2 * kGiWaves : 2;
@@ -1163,12 +1105,12 @@ ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict_
           const float4 ra0 = rays[2 * r], ra1 = rays[2 * rb];
           f32x2 Bxy[2], Bz2;
           float bz0, bz1;
-          fast_ray<kMode>(p, tbn, ft, a, ra0, Bxy[0], bz0);
-          fast_ray<kMode>(p, tbn, ft, a, ra1, Bxy[1], bz1);
+          fast_ray(ft, ra0, Bxy[0], bz0);
+          fast_ray(ft, ra1, Bxy[1], bz1);
           Bz2 = f32x2{bz0, bz1};
           int hit[2];
-          if constexpr (kCert) march2_cert<kMode, kGiGroup, kCertOff>(p, c, cp, Bxy, Bz2, pos_z, hit);
-          else march2_fast<kMode, kGiGroup>(p, c, Bxy, Bz2, pos_z, hit);
+          if constexpr (kCert) march2_cert<kGiGroup, kCertOff>(p, c, cp, Bxy, Bz2, pos_z, hit);
+          else march2_fast<kGiGroup>(p, c, Bxy, Bz2, pos_z, hit);
           if (rb == r) hit[1] = -1;
           if (__any(hit[0] >= 0 || hit[1] >= 0)) {
             add_hit(hit[0], ra0.w, rays[2 * r + 1].x, r);
@@ -1297,7 +1239,7 @@ static GiParams make_params(const Options& o, int W, int H, float fx, float fy, 
   pow2 = step > 0 && (step & (step - 1)) == 0 && step <= (1 << 20);
   p.inv_step = pow2 ? 1.0f / (float)step : 0.0f;
   if (step - start > 64 - kGiGroup) pow2 = false;  // a partial last group may index kGiGroup - 1 entries past step - 1
-  // j / step: exact for a power-of-two step; otherwise the correctly rounded quotient (read by the fast marches only)
+  // j / step: exact for a power-of-two step; otherwise the correctly rounded quotient (read by the projective march only)
   for (int k = 0; k < 64; k++) p.fjt[k] = pow2 ? (float)(start + k) * p.inv_step : (float)(start + k) / (float)step;
   for (int k = 0; k < 64; k++) p.fjc[k] = p.fjt[k < step - 1 - start ? k : (step - 1 - start > 0 ? step - 1 - start : 0)];
   // gi_tile_log2w: tuning knob for the pixel rectangle of a workgroup (3 = 8x8 ... 6 = 64x1)
@@ -1360,7 +1302,7 @@ size_t gi_scratch_bytes(int W, int H) {
 static size_t prepare_cert(const Options& o, GiParams& p, int mode, const float* pos, void* scratch, hipStream_t s) {
   p.cert_shift = p.cert_w = p.cert_h = 0;
   p.cert_d0 = cert_consts(p.bias, p.thick).d0;
-  if (!scratch || mode < 3 || !o.gi_cert) return 0;
+  if (!scratch || mode != 4 || !o.gi_cert) return 0;
   const int sh = cert_shift_for(p.W, p.H);
   if (!sh) return 0;
   p.cert_shift = sh;
@@ -1371,16 +1313,29 @@ static size_t prepare_cert(const Options& o, GiParams& p, int mode, const float*
   return cert_table_bytes(p.W, p.H, sh);
 }
 
-// gigs_options.gi_march: 0 exact | 1 hoist | 2 hoist_fma | 3 proj_nr | 4 proj (see the block comment above march2_fast;
-// GIGS_GI_MARCH names them in the environment).  The fast marches read the j/step table, so marches of more than
-// 64 - kGiGroup steps take the exact path.
+// gigs_options.gi_march: 0 exact | 4 proj (see the block comment above march2_fast; GIGS_GI_MARCH names them in the
+// environment).  The projective march reads the j/step table, so marches of more than 64 - kGiGroup steps take the exact
+// path.
 #ifndef GIGS_GI_DEFAULT_MODE
 #define GIGS_GI_DEFAULT_MODE 4  // "proj": measured 1.3e-7 mean L1 / 1e-4 changed pixels vs the exact march at C2
 #endif
 static int gi_march_mode(const Options& o, int step, int start) {
-  int mode = (o.gi_march >= 0 && o.gi_march <= 4) ? o.gi_march : GIGS_GI_DEFAULT_MODE;
+  int mode = (o.gi_march == 0 || o.gi_march == 4) ? o.gi_march : GIGS_GI_DEFAULT_MODE;
   if (step - start > 64 - kGiGroup || step <= 0) mode = 0;
   return mode;
+}
+// Calls f(the march as a std::integral_constant, the kernel's dynamic LDS bytes) for what gi_march_mode, make_params
+// (pow2) and prepare_cert (the certification table's size, 0 = none) decided.
+template <March kMarch> using MarchTag = std::integral_constant<March, kMarch>;
+template <class F>
+static void gi_dispatch_march(int mode, bool pow2, size_t cert, F&& f) {
+  if (mode == 4) {
+    if (cert) f(MarchTag<March::kProjCert>{}, cert);
+    else f(MarchTag<March::kProj>{}, (size_t)0);
+  } else {
+    if (pow2) f(MarchTag<March::kExactPow2>{}, (size_t)0);
+    else f(MarchTag<March::kExact>{}, (size_t)0);
+  }
 }
 static dim3 gi_grid(const GiParams& p) {
   const int tw = 1 << p.tile_log2w, th = 64 >> p.tile_log2w;
@@ -1400,18 +1355,9 @@ int launch_ssao(const Options& o, int W, int H, float fx, float fy, float radius
   const int mode = gi_march_mode(o, step, start);
   const size_t cert = (start < step) ? prepare_cert(o, p, mode, pos, scratch, s) : 0;
   const float2* tab = (const float2*)scratch;
-#define GIGS_SSAO_LAUNCH(POW2, MODE, CERT, LDS) \
-  hipLaunchKernelGGL((ssao_kernel<POW2, MODE, CERT>), grid, dim3(256), LDS, s, p, t.dev, t.sum_w, normal, pos, occlusion, tab)
-  switch (mode) {
-    case 1: GIGS_SSAO_LAUNCH(false, 1, false, 0); break;
-    case 2: GIGS_SSAO_LAUNCH(false, 2, false, 0); break;
-    case 3: if (cert) GIGS_SSAO_LAUNCH(false, 3, true, cert); else GIGS_SSAO_LAUNCH(false, 3, false, 0); break;
-    case 4: if (cert) GIGS_SSAO_LAUNCH(false, 4, true, cert); else GIGS_SSAO_LAUNCH(false, 4, false, 0); break;
-    default:
-      if (pow2) GIGS_SSAO_LAUNCH(true, 0, false, 0);
-      else GIGS_SSAO_LAUNCH(false, 0, false, 0);
-  }
-#undef GIGS_SSAO_LAUNCH
+  gi_dispatch_march(mode, pow2, cert, [&](auto m, size_t lds) {
+    hipLaunchKernelGGL((ssao_kernel<decltype(m)::value>), grid, dim3(256), lds, s, p, t.dev, t.sum_w, normal, pos, occlusion, tab);
+  });
   return 0;
 }
 
@@ -1443,31 +1389,19 @@ int launch_ssr(const Options& o, int W, int H, float fx, float fy, float radius,
   const size_t cert = (start < step) ? prepare_cert(o, p, mode, pos, scratch, s) : 0;
   const float2* tab = (const float2*)scratch;
   const SsrHits hits = {hit_counts, hit_offsets, (uint2*)hit_entries, hit_capacity};
-  if (hits_mode != 0) {
-    // the hit-list variants exist for the default march only (mode 4, with or without certification); -3 = not available
-    if (mode != 4 || (hits_mode != 1 && hits_mode != 2) || !(start < step)) return -3;
-    if (hits_mode == 1) {
-      if (cert) hipLaunchKernelGGL((ssr_kernel<false, 4, true, 1>), grid, dim3(256), cert, s, p, t.dev, normal, pos, rgb, albedo, metallic, F0, color, abd, tab, hits);
-      else hipLaunchKernelGGL((ssr_kernel<false, 4, false, 1>), grid, dim3(256), 0, s, p, t.dev, normal, pos, rgb, albedo, metallic, F0, color, abd, tab, hits);
-    } else {
-      if (cert) hipLaunchKernelGGL((ssr_kernel<false, 4, true, 2>), grid, dim3(256), cert, s, p, t.dev, normal, pos, rgb, albedo, metallic, F0, color, abd, tab, hits);
-      else hipLaunchKernelGGL((ssr_kernel<false, 4, false, 2>), grid, dim3(256), 0, s, p, t.dev, normal, pos, rgb, albedo, metallic, F0, color, abd, tab, hits);
+  // the hit-list variants exist for the default march only (mode 4, with or without certification); -3 = not available
+  if (hits_mode != 0 && (mode != 4 || (hits_mode != 1 && hits_mode != 2) || !(start < step))) return -3;
+  gi_dispatch_march(mode, pow2, cert, [&](auto m, size_t lds) {
+    constexpr March kMarch = decltype(m)::value;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, p, t.dev, normal, pos, rgb, albedo, metallic, F0, color, abd, tab, hits);
+    };
+    if constexpr (march_is_proj(kMarch)) {
+      if (hits_mode == 1) return launch(ssr_kernel<kMarch, 1>);
+      if (hits_mode == 2) return launch(ssr_kernel<kMarch, 2>);
     }
-    return 0;
-  }
-#define GIGS_SSR_LAUNCH(POW2, MODE, CERT, LDS)                                                                          \
-  hipLaunchKernelGGL((ssr_kernel<POW2, MODE, CERT>), grid, dim3(256), LDS, s, p, t.dev, normal, pos, rgb, albedo, metallic, \
-                     F0, color, abd, tab, hits)
-  switch (mode) {
-    case 1: GIGS_SSR_LAUNCH(false, 1, false, 0); break;
-    case 2: GIGS_SSR_LAUNCH(false, 2, false, 0); break;
-    case 3: if (cert) GIGS_SSR_LAUNCH(false, 3, true, cert); else GIGS_SSR_LAUNCH(false, 3, false, 0); break;
-    case 4: if (cert) GIGS_SSR_LAUNCH(false, 4, true, cert); else GIGS_SSR_LAUNCH(false, 4, false, 0); break;
-    default:
-      if (pow2) GIGS_SSR_LAUNCH(true, 0, false, 0);
-      else GIGS_SSR_LAUNCH(false, 0, false, 0);
-  }
-#undef GIGS_SSR_LAUNCH
+    launch(ssr_kernel<kMarch>);
+  });
   return 0;
 }
 
@@ -1478,19 +1412,10 @@ static void launch_ssr_chunk(const GiParams& p, dim3 grid, int mode, bool pow2, 
                              const float4* rays, const float* normal, const float* pos, const float* rgb, const float* albedo,
                              const float* metallic, const float* F0, float* color, float* abd, hipStream_t s) {
   const SsrHits hits = {nullptr, nullptr, nullptr, 0};
-#define GIGS_SSR_LAUNCH(POW2, MODE, CERT, LDS)                                                                         \
-  hipLaunchKernelGGL((ssr_kernel<POW2, MODE, CERT, 0, kLights>), grid, dim3(256), LDS, s, p, rays, normal, pos, rgb, albedo, \
-                     metallic, F0, color, abd, tab, hits)
-  switch (mode) {
-    case 1: GIGS_SSR_LAUNCH(false, 1, false, 0); break;
-    case 2: GIGS_SSR_LAUNCH(false, 2, false, 0); break;
-    case 3: if (cert) GIGS_SSR_LAUNCH(false, 3, true, cert); else GIGS_SSR_LAUNCH(false, 3, false, 0); break;
-    case 4: if (cert) GIGS_SSR_LAUNCH(false, 4, true, cert); else GIGS_SSR_LAUNCH(false, 4, false, 0); break;
-    default:
-      if (pow2) GIGS_SSR_LAUNCH(true, 0, false, 0);
-      else GIGS_SSR_LAUNCH(false, 0, false, 0);
-  }
-#undef GIGS_SSR_LAUNCH
+  gi_dispatch_march(mode, pow2, cert, [&](auto m, size_t lds) {
+    hipLaunchKernelGGL((ssr_kernel<decltype(m)::value, 0, kLights>), grid, dim3(256), lds, s, p, rays, normal, pos, rgb, albedo,
+                       metallic, F0, color, abd, tab, hits);
+  });
 }
 
 int launch_ssr_multi(const Options& o, int n_lights, int W, int H, float fx, float fy, float radius, float bias, float thick,

@@ -241,7 +241,7 @@ struct Options {
   int bin_bands;         // GIGS_BIN_BANDS: passes of the by-tile scatter over bands of tile rows (0 = by density: 1 / 4)
   int blend_cull;        // GIGS_BLEND_CULL
   int pre_bwd_sh_skip;   // GIGS_PRE_BWD_SH_SKIP
-  int gi_march;          // GIGS_GI_MARCH: 0 exact, 1 hoist, 2 hoist_fma, 3 proj_nr, 4 proj
+  int gi_march;          // GIGS_GI_MARCH: 0 exact, 4 proj
   int gi_cert;           // GIGS_GI_CERT
   int gi_interleave;     // GIGS_GI_INTERLEAVE
   int gi_tile_log2w;     // GIGS_GI_TILE_LOG2W

@@ -175,7 +175,8 @@ class Options(C.Structure):
 
 
 OPTION_NAMES = tuple(n for n, _ in Options._fields_ if n != "struct_bytes")
-GI_MARCHES = ("exact", "hoist", "hoist_fma", "proj_nr", "proj")
+GI_MARCHES = {0: "exact", 4: "proj"}  # gigs_options.gi_march: value -> name
+_GI_MARCH_VALUES = {name: value for value, name in GI_MARCHES.items()}
 
 
 class SpecLevel(C.Structure):
@@ -355,7 +356,9 @@ class Context:
         opts = list(self.opts)
         for k, v in options.items():
             if k == "gi_march" and isinstance(v, str):
-                v = GI_MARCHES.index(v)
+                if v not in _GI_MARCH_VALUES:
+                    raise ValueError(f"gi_march {v!r}: one of {sorted(_GI_MARCH_VALUES)}")
+                v = _GI_MARCH_VALUES[v]
             opts[OPTION_NAMES.index(k)] = int(v)
         cap, cnt = self.async_capacity, self.async_counters
         if async_binning is False:

@@ -69,9 +69,9 @@ typedef struct gigs_options {
                            same keys, point_list, ranges.                                          env GIGS_BIN_BANDS */
   int blend_cull;       /* 1 (default); 0 = blend forward without the quadrant cull (same bits). env GIGS_BLEND_CULL */
   int pre_bwd_sh_skip;  /* 1 (default); 0 = the preprocess backward evaluates every chain.   env GIGS_PRE_BWD_SH_SKIP */
-  int gi_march;         /* SSAO / SSR march: 0 exact (the oracle's pixel choices bit for bit), 1 hoist, 2 hoist_fma,
-                           3 proj_nr, 4 proj (default).              env GIGS_GI_MARCH=exact|hoist|hoist_fma|proj_nr|proj */
-  int gi_cert;          /* 1 (default) coarse-depth certification in front of marches 3 / 4 (same bits). env GIGS_GI_CERT */
+  int gi_march;         /* SSAO / SSR march: 0 exact (the oracle's pixel choices bit for bit), 4 proj (default); no other
+                           value is valid.                                                   env GIGS_GI_MARCH=exact|proj */
+  int gi_cert;          /* 1 (default) coarse-depth certification in front of the proj march (same bits). env GIGS_GI_CERT */
   int gi_interleave;    /* 1 (default) interleaved ray pairs per wave, 0 contiguous quarters.     env GIGS_GI_INTERLEAVE */
   int gi_tile_log2w;    /* pixel rectangle of a march workgroup, 2^k x 64/2^k, k = 0..6 (3).      env GIGS_GI_TILE_LOG2W */
   int gi_zero_rays;     /* 0 (default) the zero-weight rays (theta = 0: 32 of 512 at delta 0.0625) are not marched -- their

@@ -64,6 +64,7 @@ def test_contexts_are_independent_and_validated():
     """gigs_ctx (include/gigs_hip.h): host-only API -- options round-trip, two contexts do not see each other, the default
     context is immutable, out-of-range values are rejected.  (The GPU suite drives two contexts on two streams.)"""
     import ctypes as C
+    import pytest
     import gigs_lib
     gl = gigs_lib.lib()
     dflt = gigs_lib.Options()
@@ -88,8 +89,14 @@ def test_contexts_are_independent_and_validated():
     oa.gi_march = 9
     assert gl.gigs_ctx_set_options(a, C.byref(oa)) < 0
     assert gl.gigs_ctx_get_options(a, C.byref(ob)) == 0 and ob.gi_march == 0  # nothing changed
-    oa.gi_march, oa.struct_bytes = 1, 8
-    assert gl.gigs_ctx_set_options(a, C.byref(oa)) < 0
+    for retired in (1, 2, 3):  # the marches between exact and proj are gone: rejected, and the message names what is left
+        oa.gi_march = retired
+        assert gl.gigs_ctx_set_options(a, C.byref(oa)) < 0
+        assert b"0 (exact)" in gl.gigs_last_error() and b"4 (proj)" in gl.gigs_last_error()
+        assert gl.gigs_ctx_get_options(a, C.byref(ob)) == 0 and ob.gi_march == 0  # nothing changed
+    oa.gi_march, oa.struct_bytes = 4, 8
+    assert gl.gigs_ctx_set_options(a, C.byref(oa)) < 0 and b"struct_bytes" in gl.gigs_last_error()
+    assert gl.gigs_ctx_get_options(a, C.byref(ob)) == 0 and ob.gi_march == 0
     assert gl.gigs_ctx_set_async_binning(a, 1 << 20, None) == 0 and gl.gigs_ctx_set_async_binning(a, 0, None) == 0
     gl.gigs_ctx_destroy(a)
     gl.gigs_ctx_destroy(b)
@@ -102,6 +109,10 @@ def test_contexts_are_independent_and_validated():
         assert gigs_lib.current() is c1
         assert gigs_lib.current().derive(gi_march="exact") is c1  # same settings, same native object
     assert gigs_lib.current() is base
+    assert gigs_lib.GI_MARCHES[base.option("gi_march")] == "proj"
+    for name in ("hoist", "hoist_fma", "proj_nr", "nonsense"):
+        with pytest.raises(ValueError, match="gi_march"):
+            base.derive(gi_march=name)
 
 
 def test_no_launch_path_reads_the_environment():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Launches the SSAO kernel of the C2 bench view a few times in one march configuration (for rocprofv3 --pmc passes).
-    python3 tools/gi_pmc_driver.py <exact|hoist_fma|proj> <cert 0|1>"""
+    python3 tools/gi_pmc_driver.py <exact|proj> <cert 0|1>"""
 import importlib
 import os
 import sys

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""Accuracy and speed of the GI march variants (GIGS_GI_MARCH) on the GPU.
+"""Accuracy and speed of the projective GI march (GIGS_GI_MARCH=proj) against the exact one on the GPU.
 
 Mode "exact" reproduces the CPU oracle bit for bit (tests/test_gpu_parity.py::test_gi_passes_match_oracle), so it
-is the yardstick here: every other mode is compared with it on the same inputs -- mean per-pixel L1, largest
+is the yardstick here: "proj" is compared with it on the same inputs -- mean per-pixel L1, largest
 difference, fraction of changed pixels -- for SSAO (operator inputs: raw view-space normal, filtered depth
 positions) and SSR (train.py's inputs), on the C2 bench view and on the GI scenes of the parity tests, at several GI
 settings.  Timing: hipEvents around 10 launches after 2 warm-up launches.
@@ -30,7 +30,7 @@ import pipeline  # noqa: E402
 import scenes  # noqa: E402
 
 DEV = "cuda:0"
-MODES = ["exact", "hoist", "hoist_fma", "proj_nr", "proj"]
+MODES = ["exact", "proj"]
 KEYS = ["means3D", "opacities", "normal", "albedo", "roughness", "metallic", "shs", "scales", "rotations"]
 
 
@@ -108,11 +108,8 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only-sweep", action="store_true")
-    ap.add_argument("--modes", default="", help="comma-separated subset of the non-exact modes (default: all)")
     ap.add_argument("--no-sweep", action="store_true")
     args = ap.parse_args()
-    if args.modes:
-        MODES[1:] = args.modes.split(",")
     report = {"modes": MODES, "cases": []}
     for name, sc, cam, deg, gis in ([] if args.only_sweep else cases(not args.quick)):
         for gi in gis:
@@ -142,7 +139,7 @@ def main():
         for log2w in (2, 3, 4, 5, 6):
             gigs_lib.set_options(gi_tile_log2w=log2w)
             row = {}
-            for mode in ("exact", "hoist_fma", "proj"):
+            for mode in MODES:
                 _, t = run_mode(mode, gb, cam, gi, args.reps)
                 row[mode] = t
             gigs_lib.set_options(gi_cert=0)
