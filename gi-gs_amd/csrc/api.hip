@@ -131,6 +131,9 @@ gigs::Options options_from_env() {
   o.shade_lds_floats = env_int("GIGS_SHADE_LDS_FLOATS", 30 * 1024);
   o.shade_bwd_blocks = std::max(0, env_int("GIGS_SHADE_BWD_BLOCKS", 0));
   o.shade_bwd_rows = env_int("GIGS_SHADE_BWD_ROWS", 0) != 0;
+  o.spec_sparse = env_int("GIGS_SPEC_SPARSE", 1) != 0;
+  o.spec_sparse_permille = env_int("GIGS_SPEC_SPARSE_PERMILLE", 37);
+  if (o.spec_sparse_permille < 0 || o.spec_sparse_permille > 1000) o.spec_sparse_permille = 37;
   return o;
 }
 const gigs::Ctx& ctx_of(const gigs_ctx* c) { return c ? *reinterpret_cast<const gigs::Ctx*>(c) : gigs::default_ctx(); }
@@ -260,7 +263,7 @@ int gigs_ctx_get_options(const gigs_ctx* ctx, gigs_options* out) {
   out->gi_march = o.gi_march; out->gi_cert = o.gi_cert; out->gi_interleave = o.gi_interleave;
   out->gi_tile_log2w = o.gi_tile_log2w; out->gi_zero_rays = o.gi_zero_rays; out->spec_max8 = o.spec_max8;
   out->spec_max16 = o.spec_max16; out->shade_lds_floats = o.shade_lds_floats; out->shade_bwd_blocks = o.shade_bwd_blocks;
-  out->shade_bwd_rows = o.shade_bwd_rows;
+  out->shade_bwd_rows = o.shade_bwd_rows; out->spec_sparse = o.spec_sparse; out->spec_sparse_permille = o.spec_sparse_permille;
   return 0;
 }
 int gigs_ctx_set_options(gigs_ctx* ctx, const gigs_options* in) {
@@ -273,13 +276,14 @@ int gigs_ctx_set_options(gigs_ctx* ctx, const gigs_options* in) {
     return fail(GIGS_ERR_INVALID, "bucket_target >= 256, bucket_max_mean >= 0, 0 <= bin_bands <= 64");
   if (in->spec_max8 < 0 || in->spec_max16 < in->spec_max8) return fail(GIGS_ERR_INVALID, "0 <= spec_max8 <= spec_max16");
   if (in->shade_lds_floats < 0 || in->shade_bwd_blocks < 0) return fail(GIGS_ERR_INVALID, "shade_lds_floats, shade_bwd_blocks >= 0");
+  if (in->spec_sparse_permille < 0 || in->spec_sparse_permille > 1000) return fail(GIGS_ERR_INVALID, "0 <= spec_sparse_permille <= 1000");
   gigs::Options& o = reinterpret_cast<gigs::Ctx*>(ctx)->opt;
   o.binning_legacy = in->binning_legacy != 0; o.bucket_max_mean = in->bucket_max_mean; o.long_lists = in->long_lists;
   o.bucket_target = in->bucket_target; o.bin_bands = in->bin_bands; o.blend_cull = in->blend_cull != 0; o.pre_bwd_sh_skip = in->pre_bwd_sh_skip != 0;
   o.gi_march = in->gi_march; o.gi_cert = in->gi_cert != 0; o.gi_interleave = in->gi_interleave != 0;
   o.gi_tile_log2w = in->gi_tile_log2w; o.gi_zero_rays = in->gi_zero_rays != 0; o.spec_max8 = in->spec_max8;
   o.spec_max16 = in->spec_max16; o.shade_lds_floats = in->shade_lds_floats; o.shade_bwd_blocks = in->shade_bwd_blocks;
-  o.shade_bwd_rows = in->shade_bwd_rows != 0;
+  o.shade_bwd_rows = in->shade_bwd_rows != 0; o.spec_sparse = in->spec_sparse != 0; o.spec_sparse_permille = in->spec_sparse_permille;
   return 0;
 }
 int gigs_ctx_set_reuse_binning(gigs_ctx* ctx, int on) {

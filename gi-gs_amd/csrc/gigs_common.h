@@ -250,6 +250,8 @@ struct Options {
   int shade_lds_floats;  // GIGS_SHADE_LDS_FLOATS
   int shade_bwd_blocks;  // GIGS_SHADE_BWD_BLOCKS (0 = one workgroup per CU)
   int shade_bwd_rows;    // GIGS_SHADE_BWD_ROWS: 1 = the shade backward's row-major chunks and 16-lane runs (same per-pixel bits)
+  int spec_sparse;       // GIGS_SPEC_SPARSE: 1 = the GGX backward scatters levels with few nonzero gradient texels
+  int spec_sparse_permille;  // GIGS_SPEC_SPARSE_PERMILLE: list capacity of a level, in thousandths of its texels
 };
 struct Ctx {
   Options opt;

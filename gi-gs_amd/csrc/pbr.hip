@@ -626,6 +626,272 @@ static void launch_specular_apply(const Options& o, int res, int avg_window, con
 }
 
 // ------------------------------------------------------------------------------------------
+// Backward of the filter for gradients that are mostly exact zeros (gigs_specular_cubemap_multi_bwd_sparse).
+// The shade backward zero-fills the level gradients and adds into the sampled texels only, so a fine level receives a
+// few thousand nonzero texels (or none: every pixel rougher than the level's range).  The gather above still streams
+// the level's whole table.  Instead: a census lists the nonzero texels of every level, and a level whose list fits its
+// capacity is SCATTERED from them with their runs of the forward table -- W_fwd[o][i] is the same float as
+// W_swapped[i][o] (specular_weights_kernel evaluates one expression for both), so (w / wsum[o]) * g[o] is the very
+// product the gather forms from its pre-divided table; only the order of the additions differs.
+// state: [0..7] working counters, [8..15] path taken (1 scatter, 0 gather), [16..23] nonzero texels counted.
+// ------------------------------------------------------------------------------------------
+struct SparseLevel {
+  int total, cap, block_begin, group_begin, N;
+  int vec;  // src and dst are 16-byte aligned: the census may use 16-byte accesses
+  int chunks;  // waves that share one listed texel's window in the scatter
+  int lds;     // a level with wide windows: scattered through LDS images of face tiles
+  const float* src;
+  float* dst;
+  const float* bounds;
+  const uint32_t* offsets;
+  const float* Wfwd;
+  const float* wsum;
+  int* list;
+};
+struct SparseLevels { int n; SparseLevel lv[8]; };
+
+constexpr int kCensusPerThread = 4;  // texels per thread: 48 contiguous bytes of gradient, three 16-byte loads
+
+// One pass over the incoming gradients of all levels: dst = 0, and the indices of the texels with a channel != 0
+// (true for NaN, false for -0) go to the level's list.  A workgroup claims its slots with ONE returning atomic on the
+// level's counter; the counter keeps counting past the capacity (the count decides the path), the list does not grow past it.
+__global__ void __launch_bounds__(256) specular_census_kernel(SparseLevels L, int* __restrict__ state) {
+  int k = 0;
+#pragma unroll
+  for (int i = 1; i < 8; i++)
+    if (i < L.n && (int)blockIdx.x >= L.lv[i].block_begin) k = i;
+  const SparseLevel& v = L.lv[k];
+  const int lane = threadIdx.x & 63;
+  const int t0 = (((int)blockIdx.x - v.block_begin) * 256 + (int)threadIdx.x) * kCensusPerThread;
+  bool nz[kCensusPerThread];
+  if (v.vec && t0 + kCensusPerThread <= v.total) {
+    // texel index a multiple of 4: byte offset a multiple of 48 from an aligned base
+    const float4* s4 = reinterpret_cast<const float4*>(v.src + 3 * (size_t)t0);
+    float4* d4 = reinterpret_cast<float4*>(v.dst + 3 * (size_t)t0);
+    const float4 a = s4[0], b = s4[1], c = s4[2];
+    nz[0] = a.x != 0.0f || a.y != 0.0f || a.z != 0.0f;
+    nz[1] = a.w != 0.0f || b.x != 0.0f || b.y != 0.0f;
+    nz[2] = b.z != 0.0f || b.w != 0.0f || c.x != 0.0f;
+    nz[3] = c.y != 0.0f || c.z != 0.0f || c.w != 0.0f;
+    const float4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+    d4[0] = z; d4[1] = z; d4[2] = z;
+  } else {
+#pragma unroll
+    for (int j = 0; j < kCensusPerThread; j++) {
+      nz[j] = false;
+      if (t0 + j < v.total) {
+        const float* s = v.src + 3 * (size_t)(t0 + j);
+        float* d = v.dst + 3 * (size_t)(t0 + j);
+        nz[j] = s[0] != 0.0f || s[1] != 0.0f || s[2] != 0.0f;
+        d[0] = 0.0f; d[1] = 0.0f; d[2] = 0.0f;
+      }
+    }
+  }
+  unsigned long long m[kCensusPerThread];
+  int wave_total = 0;
+#pragma unroll
+  for (int j = 0; j < kCensusPerThread; j++) { m[j] = __ballot(nz[j]); wave_total += __popcll(m[j]); }
+  // one returning atomic per workgroup: 1536 waves of a 256^2 level adding to one address took 15 us
+  __shared__ int wave_base[5];
+  const int wave = threadIdx.x >> 6;
+  if (lane == 0) wave_base[wave] = wave_total;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t01 = wave_base[0] + wave_base[1], t012 = t01 + wave_base[2], all = t012 + wave_base[3];
+    const int first = all ? atomicAdd(state + k, all) : 0;
+    wave_base[3] = first + t012; wave_base[2] = first + t01; wave_base[1] = first + wave_base[0]; wave_base[0] = first;
+  }
+  __syncthreads();
+  if (wave_total == 0) return;  // wave-uniform
+  int base = wave_base[wave];
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int j = 0; j < kCensusPerThread; j++) {
+    const int slot = base + __popcll(m[j] & below);
+    if (nz[j] && slot < v.cap) v.list[slot] = t0 + j;
+    base += __popcll(m[j]);
+  }
+}
+
+// `chunks` waves per slot of every level's list.  The waves of a listed texel o share its window 64 candidates at a
+// time.  A lane forms the quotient w / wsum[o] and the texel of ONE candidate; the adds are then issued by DWORD of dst
+// -- three instructions per 64 candidates, lane L of instruction j adding channel (64 j + L) % 3 of candidate
+// (64 j + L) / 3, fetched from that candidate's lane -- so that one atomic instruction covers 64 consecutive floats of
+// dst wherever the window's row goes on (256 contiguous bytes, the shape the memory-side adders take at full rate).
+// A wave is latency-bound (weight load, then its atomics), so a texel's window is shared by as many waves as leave each
+// about two trips, and a trip requests kScatterU weights before it consumes one.  The run of the table and the face
+// rectangles are read exactly as specular_apply_body reads them: rectangles in face order, row-major inside one.
+constexpr int kScatterU = 2;
+constexpr int kLdsTile = 32;  // a level with wide windows is accumulated in LDS images of 32 x 32 texels (12 KB)
+constexpr int kLdsParts = 8;  // workgroups that share one such tile
+constexpr int kLdsWide = 16;  // wide: the mean window holds at least 1 / 16 of the level's texels
+
+__global__ void __launch_bounds__(256) specular_scatter_kernel(SparseLevels L, int* __restrict__ state) {
+  const int lane = threadIdx.x & 63;
+  const int group = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (blockIdx.x == 0 && threadIdx.x < 8 && (int)threadIdx.x < L.n) {
+    // the report the caller may read, and the flags the gather's workgroups test (nobody reads them in this kernel)
+    const int c = state[threadIdx.x];
+    state[8 + threadIdx.x] = c <= L.lv[threadIdx.x].cap ? 1 : 0;
+    state[16 + threadIdx.x] = c;
+  }
+  int k = 0;
+#pragma unroll
+  for (int i = 1; i < 8; i++)
+    if (i < L.n && group >= L.lv[i].group_begin) k = i;
+  const SparseLevel& v = L.lv[k];
+  const int count = state[k];
+  if (count > v.cap) return;  // a gathered level
+  if (v.lds) {
+    // A level with wide windows: a texel of dst receives a term from a large share of the listed texels.  Added one by
+    // one with global atomics, each term would be rounded at the size of the running sum; here a workgroup sums its share
+    // of the list into an LDS image of ONE kLdsTile^2 tile of a face first and adds that image to dst once -- 8 partial
+    // sums per texel, like the partial sums of the gather's lanes, and 1 / 8 of the list per image.
+    __shared__ float img[kLdsTile * kLdsTile * 3];
+    const int N = v.N, nt = (N + kLdsTile - 1) / kLdsTile, bl = (group - v.group_begin) >> 2;
+    const int face = bl % 6, tile = (bl / 6) % (nt * nt), part = bl / (6 * nt * nt);
+    const int tx0 = (tile % nt) * kLdsTile, ty0 = (tile / nt) * kLdsTile;
+    const int tx1 = min(tx0 + kLdsTile, N) - 1, ty1 = min(ty0 + kLdsTile, N) - 1;
+    const int wave = (int)threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < kLdsTile * kLdsTile * 3; i += 256) img[i] = 0.0f;
+    __syncthreads();
+    const int listed = min(count, v.cap);
+    for (int slot = part + kLdsParts * wave; slot < listed; slot += kLdsParts * 4) {
+      const int o = __builtin_amdgcn_readfirstlane(v.list[slot]);
+      const float4* b4 = reinterpret_cast<const float4*>(v.bounds + 24 * (size_t)o);
+      int before = 0, xmin = 0, xmax = -1, ymin = 0, ymax = -1;
+#pragma unroll
+      for (int s = 0; s < 6; ++s) {
+        const float4 b = b4[s];
+        const int x0 = (int)b.x, x1 = (int)b.y, y0 = (int)b.z, y1 = (int)b.w;
+        const int cnt = (x0 > x1 || y0 > y1) ? 0 : (x1 - x0 + 1) * (y1 - y0 + 1);
+        if (s < face) before += cnt;
+        if (s == face && cnt) { xmin = x0; xmax = x1; ymin = y0; ymax = y1; }
+      }
+      // the part of o's rectangle on this face that lies in the tile
+      const int ix0 = max(xmin, tx0), ix1 = min(xmax, tx1), iy0 = max(ymin, ty0), iy1 = min(ymax, ty1);
+      if (ix0 > ix1 || iy0 > iy1) continue;  // wave-uniform
+      const int wd = xmax - xmin + 1, iw = ix1 - ix0 + 1, ni = iw * (iy1 - iy0 + 1);
+      const float* W = v.Wfwd + v.offsets[6 * (size_t)o] + before;
+      const float ws = v.wsum[o], inv = 1.0f / (float)iw;
+      const float* g = v.src + 3 * (size_t)o;
+      const float g0 = g[0], g1 = g[1], g2 = g[2];
+      for (int i = lane; i < ni; i += 64) {
+        const int ry = (int)(((float)i + 0.5f) * inv), y = iy0 + ry, x = ix0 + (i - ry * iw);
+        const float w = W[(y - ymin) * wd + (x - xmin)];  // row-major over the face's rectangle
+        if (!(w >= 0.0f)) continue;  // -1 marks a candidate outside the cone
+        float* t = img + 3 * ((y - ty0) * kLdsTile + (x - tx0));
+        const float q = w / ws;
+        const float v0 = q * g0, v1 = q * g1, v2 = q * g2;
+        if (v0 != 0.0f) atomicAdd(t, v0);
+        if (v1 != 0.0f) atomicAdd(t + 1, v1);
+        if (v2 != 0.0f) atomicAdd(t + 2, v2);
+      }
+    }
+    __syncthreads();
+    const int row3 = 3 * (tx1 - tx0 + 1), cells = row3 * (ty1 - ty0 + 1);
+    for (int i = threadIdx.x; i < cells; i += 256) {
+      const int yy = i / row3, xc = i - yy * row3;
+      const float val = img[3 * yy * kLdsTile + xc];
+      if (val != 0.0f) atomicAdd(v.dst + 3 * ((size_t)(face * N + ty0 + yy) * N + tx0) + xc, val);
+    }
+    return;
+  }
+  const int slot = (group - v.group_begin) / v.chunks, chunk = (group - v.group_begin) % v.chunks;
+  if (slot >= count || slot >= v.cap) return;  // past the end of the list
+  const int o = __builtin_amdgcn_readfirstlane(v.list[slot]);
+  const int N = v.N;
+  int pre[7], wd[6], base[6];
+  float inv[6];
+  pre[0] = 0;
+  const float4* b4 = reinterpret_cast<const float4*>(v.bounds + 24 * (size_t)o);
+#pragma unroll
+  for (int s = 0; s < 6; ++s) {
+    const float4 b = b4[s];
+    const int xmin = (int)b.x, xmax = (int)b.y, ymin = (int)b.z, ymax = (int)b.w;
+    const bool empty = xmin > xmax || ymin > ymax;
+    wd[s] = empty ? 1 : xmax - xmin + 1;
+    inv[s] = 1.0f / (float)wd[s];  // as specular_weights_kernel laid the run out
+    pre[s + 1] = pre[s] + (empty ? 0 : wd[s] * (ymax - ymin + 1));
+    base[s] = empty ? 0 : (s * N + ymin) * N + xmin;
+  }
+  const int n = pre[6];
+  const float* W = v.Wfwd + v.offsets[6 * (size_t)o];
+  const float ws = v.wsum[o];
+  const float* g = v.src + 3 * (size_t)o;
+  const float g0 = g[0], g1 = g[1], g2 = g[2];
+  const int step = 64 * v.chunks;
+  // lane L of add instruction j: candidate lane (64 j + L) / 3 and channel (64 j + L) % 3
+  int from[3];
+  float gch[3];
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const int D = 64 * j + lane, ch = D % 3;
+    from[j] = D / 3;
+    gch[j] = ch == 0 ? g0 : ch == 1 ? g1 : g2;
+  }
+  const int ch0 = lane % 3;  // channels of the three instructions: ch0, (ch0 + 1) % 3, (ch0 + 2) % 3 (64 % 3 = 1)
+  for (int c0 = 64 * chunk; c0 < n; c0 += step * kScatterU) {
+    float w[kScatterU];
+#pragma unroll
+    for (int u = 0; u < kScatterU; u++) {
+      const int c = c0 + u * step + lane;
+      w[u] = c < n ? W[c] : -1.0f;  // -1 marks a candidate outside the cone
+    }
+#pragma unroll
+    for (int u = 0; u < kScatterU; u++) {
+      if (c0 + u * step >= n) break;  // wave-uniform
+      const int c = c0 + u * step + lane;
+      float q = -1.0f;
+      int texel = 0;
+      if (w[u] >= 0.0f) {
+        int f = 0;
+#pragma unroll
+        for (int j = 1; j < 6; j++) f += c >= pre[j] ? 1 : 0;  // the last face with pre <= c: empty faces are skipped
+        int f_pre = pre[0], f_wd = wd[0], f_base = base[0];
+        float f_inv = inv[0];
+#pragma unroll
+        for (int j = 1; j < 6; j++)
+          if (f == j) { f_pre = pre[j]; f_wd = wd[j]; f_base = base[j]; f_inv = inv[j]; }
+        const int loc = c - f_pre;
+        const int row = (int)(((float)loc + 0.5f) * f_inv);
+        texel = f_base + row * N + (loc - row * f_wd);
+        q = w[u] / ws;  // the float the gather's pre-divided table holds for this pair
+      }
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const float qq = __shfl(q, from[j]);
+        const int tt = __shfl(texel, from[j]);
+        const int ch = ch0 + j >= 3 ? ch0 + j - 3 : ch0 + j;
+        const float val = qq * gch[j];
+        // NaN quotients (0 / 0) must reach dst like the gather's: only the -1 marker and exact zeros are skipped
+        if (!(qq < 0.0f) && val != 0.0f) atomicAdd(v.dst + 3 * (size_t)tt + ch, val);
+      }
+    }
+  }
+}
+
+// specular_apply_multi_kernel<true> whose workgroups of a scattered level return at entry; it runs last of the three
+// and clears the working counters for the next call (no kernel reads them after the scatter).
+__global__ void __launch_bounds__(256) specular_apply_multi_bwd_sparse_kernel(SpecLevels L, int* __restrict__ state) {
+  int k = 0;
+#pragma unroll
+  for (int i = 1; i < 8; i++)
+    if (i < L.n && (int)blockIdx.x >= L.lv[i].block_begin) k = i;
+  if (blockIdx.x == 0 && threadIdx.x < 8) state[threadIdx.x] = 0;
+  if (state[8 + k] != 0) return;
+  const SpecLevel& v = L.lv[k];
+  const int block = (int)blockIdx.x - v.block_begin;
+  if (v.lanes == 8) specular_apply_body<true, true, 8>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out);
+  else if (v.lanes == 16) specular_apply_body<true, true, 16>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out);
+  else specular_apply_body<true, true, 64>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out);
+}
+
+static int spec_sparse_capacity(const Options& o, int res) {
+  return (int)((long long)6 * res * res * o.spec_sparse_permille / 1000);
+}
+
+// ------------------------------------------------------------------------------------------
 // cube / 2-D texture sampling
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ int cube_face_uv(float x, float y, float z, float& u, float& v) {
@@ -1532,6 +1798,57 @@ int gigs_specular_cubemap_multi_w(gigs_ctx* ctx, int n_levels, const gigs_spec_l
   void* tok; gigs_internal_stage_begin(backward ? 17 : 16, stream, &tok);
   if (backward) hipLaunchKernelGGL(gigs::specular_apply_multi_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
   else hipLaunchKernelGGL(gigs::specular_apply_multi_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
+  gigs_internal_stage_end(tok);
+  PBR_CHECK_LAUNCH();
+  return 0;
+}
+
+int gigs_spec_sparse_capacity(const gigs_ctx* ctx, int res) {
+  if (res <= 0 || res > 4096) return gigs_internal_fail(GIGS_ERR_INVALID, "spec_sparse_capacity: bad resolution");
+  return gigs::spec_sparse_capacity(*gigs_internal_options(ctx), res);
+}
+
+int gigs_specular_cubemap_multi_bwd_sparse(gigs_ctx* ctx, int n_levels, const gigs_spec_level* levels,
+                                           const float* const* weights_fwd, const float* const* wsum, int* state,
+                                           int* lists, void* stream) {
+  const gigs::Options& o = *gigs_internal_options(ctx);
+  if (!o.spec_sparse) return gigs_specular_cubemap_multi_w(ctx, n_levels, levels, 1, stream);
+  if (n_levels <= 0 || n_levels > 8 || !levels || !weights_fwd || !wsum || !state || !lists)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_multi_bwd_sparse: bad argument");
+  gigs::SpecLevels L;
+  gigs::SparseLevels S;
+  L.n = S.n = n_levels;
+  int blocks = 0, census_blocks = 0, groups = 0;
+  size_t list_begin = 0;
+  for (int i = 0; i < n_levels; i++) {
+    const gigs_spec_level& a = levels[i];
+    if (a.res <= 0 || a.res > 4096 || !a.src || !a.bounds || !a.offsets || !a.weights || !a.dst || !weights_fwd[i] || !wsum[i])
+      return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_multi_bwd_sparse: bad level");
+    gigs::SpecLevel& v = L.lv[i];
+    v.N = a.res; v.lanes = gigs::spec_lanes_for(o, a.avg_window); v.block_begin = blocks;
+    v.src = a.src; v.bounds = a.bounds; v.offsets = a.offsets; v.W = a.weights; v.dst = a.dst; v.wsum_out = a.wsum;
+    const int total = 6 * a.res * a.res;
+    const int waves = v.lanes == 64 ? total : (total + (64 / v.lanes) - 1) / (64 / v.lanes);
+    blocks += (waves + 3) / 4;
+    gigs::SparseLevel& q = S.lv[i];
+    q.total = total; q.cap = gigs::spec_sparse_capacity(o, a.res); q.block_begin = census_blocks; q.group_begin = groups; q.N = a.res;
+    q.vec = ((((uintptr_t)a.src) | ((uintptr_t)a.dst)) & 15) == 0;
+    q.src = a.src; q.dst = a.dst; q.bounds = a.bounds; q.offsets = a.offsets; q.Wfwd = weights_fwd[i]; q.wsum = wsum[i];
+    q.list = lists + list_begin;
+    const int per_block = 256 * gigs::kCensusPerThread;
+    census_blocks += (total + per_block - 1) / per_block;
+    // 64 candidates per wave and step: about two trips of kScatterU steps per wave at the level's mean window
+    q.chunks = std::min(32, std::max(1, (std::max(1, a.avg_window) + 64 * 2 * gigs::kScatterU - 1) / (64 * 2 * gigs::kScatterU)));
+    q.lds = (long long)a.avg_window * gigs::kLdsWide >= total;
+    const int nt = (a.res + gigs::kLdsTile - 1) / gigs::kLdsTile;
+    groups += q.lds ? 4 * 6 * nt * nt * gigs::kLdsParts : (q.cap * q.chunks + 3) / 4 * 4;  // whole workgroups per level
+    list_begin += (size_t)q.cap;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  void* tok; gigs_internal_stage_begin(17, stream, &tok);
+  hipLaunchKernelGGL(gigs::specular_census_kernel, dim3(census_blocks), dim3(256), 0, s, S, state);
+  hipLaunchKernelGGL(gigs::specular_scatter_kernel, dim3(std::max(1, (groups + 3) / 4)), dim3(256), 0, s, S, state);
+  hipLaunchKernelGGL(gigs::specular_apply_multi_bwd_sparse_kernel, dim3(blocks), dim3(256), 0, s, L, state);
   gigs_internal_stage_end(tok);
   PBR_CHECK_LAUNCH();
   return 0;

@@ -79,6 +79,9 @@ SIGNATURES = {
     "gigs_specular_cubemap_fwd_w": (_i, [C.c_void_p, _i, _f, _f, _f, _f, _i, _f, _f, C.c_void_p]),
     "gigs_specular_cubemap_bwd_w": (_i, [C.c_void_p, _i, _f, _f, _f, _i, _f, _i, _f, C.c_void_p]),
     "gigs_specular_cubemap_multi_w": (_i, [C.c_void_p, _i, C.c_void_p, _i, C.c_void_p]),
+    "gigs_spec_sparse_capacity": (_i, [C.c_void_p, _i]),
+    "gigs_specular_cubemap_multi_bwd_sparse": (_i, [C.c_void_p, _i, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "gigs_cubemap_mip_fwd": (_i, [_i, _i, _f, _f, C.c_void_p]),
     "gigs_cubemap_mip_bwd_add": (_i, [_i, _f, _f, _f, C.c_void_p]),
     "gigs_cubemap_mip_bwd_add2": (_i, [_i, _f, _f, _f, _f, C.c_void_p]),
@@ -171,7 +174,7 @@ class Options(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
         "struct_bytes", "binning_legacy", "bucket_max_mean", "long_lists", "bucket_target", "bin_bands", "blend_cull",
         "pre_bwd_sh_skip", "gi_march", "gi_cert", "gi_interleave", "gi_tile_log2w", "gi_zero_rays", "spec_max8",
-        "spec_max16", "shade_lds_floats", "shade_bwd_blocks", "shade_bwd_rows")]
+        "spec_max16", "shade_lds_floats", "shade_bwd_blocks", "shade_bwd_rows", "spec_sparse", "spec_sparse_permille")]
 
 
 OPTION_NAMES = tuple(n for n, _ in Options._fields_ if n != "struct_bytes")
@@ -220,6 +223,7 @@ class FilterDesc(C.Structure):
                 ("reserved", C.c_int)]
 
 
+SPEC_SPARSE_STATE_INTS = 32  # GIGS_SPEC_SPARSE_STATE_INTS
 MAX_IMAGES = 4096  # GIGS_MAX_IMAGES
 MINMAX_SCRATCH_FLOATS = 512  # GIGS_MINMAX_SCRATCH_FLOATS
 

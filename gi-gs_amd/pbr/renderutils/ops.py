@@ -203,7 +203,9 @@ class _specular_levels(torch.autograd.Function):
     def backward(ctx, *douts):
         import ctypes as C
         dev = next(d for d in douts if d is not None).device
-        gs, arr, keep = [], (gigs_lib.SpecLevel * len(douts))(), []
+        n = len(douts)
+        gs, arr, keep = [], (gigs_lib.SpecLevel * n)(), []
+        w_fwd, w_sum = (C.c_void_p * n)(), (C.c_void_p * n)()
         for i, (d, res, (bounds, tables)) in enumerate(zip(douts, ctx.shapes, ctx.meta)):
             d = torch.zeros((6, res, res, 3), dtype=torch.float32, device=dev) if d is None else _gpu(d, "dout")
             keep.append(d)
@@ -211,12 +213,69 @@ class _specular_levels(torch.autograd.Function):
             gs.append(g)
             arr[i] = gigs_lib.SpecLevel(res, _avg_window(tables, res), d.data_ptr(), bounds.data_ptr(), tables[0].data_ptr(),
                                         tables[3].data_ptr(), g.data_ptr(), None)
+            w_fwd[i], w_sum[i] = tables[1].data_ptr(), tables[4].data_ptr()
         with torch.cuda.device(dev):
             if bwd_head_start_ns > 0:  # see gigs_stream_delay: set by pipeline.WholeStepGraph while it captures the backward
                 gigs_lib.check(_lib.gigs_stream_delay(int(bwd_head_start_ns), _stream()), "stream_delay")
-            gigs_lib.check(_lib.gigs_specular_cubemap_multi_w(gigs_lib.ctx_ptr(), len(douts), C.cast(arr, C.c_void_p), 1, _stream()),
-                           "specular_cubemap_multi_w")
+            # nonzero-texel census, scatter of the sparse levels, gather of the others (gigs_options.spec_sparse = 0: the gather)
+            state, lists = _sparse_buffers(tuple(ctx.shapes), dev)
+            gigs_lib.check(_lib.gigs_specular_cubemap_multi_bwd_sparse(gigs_lib.ctx_ptr(), n, C.cast(arr, C.c_void_p), w_fwd, w_sum,
+                                                                       None if state is None else state.data_ptr(),
+                                                                       None if lists is None else lists.data_ptr(), _stream()),
+                           "specular_cubemap_multi_bwd_sparse")
         return (None, *gs)
+
+
+# Persistent device buffers of gigs_specular_cubemap_multi_bwd_sparse: the state ints (zero before the first call; the
+# library clears its counters itself afterwards) and the levels' index lists.  A pair belongs to ONE owner: eager calls
+# share one pair per (level chain, capacities, device, stream) -- a stream orders its own calls -- and every graph capture
+# takes a pair of its own, because a replay is ordered with nothing an eager stream does.  The pair of a capture comes from
+# the spares that eager calls of the same chain leave zero-filled (a stepper warms up eagerly before it captures), so the
+# graph holds no fill node for the state; without a spare it is allocated inside the capture.  The dictionaries grow with
+# the distinct chains, capacities and streams of a process, a few hundred bytes to 200 KB per entry.
+_sparseBuffers = {}
+_sparseSpares = {}
+_sparseCaptured = []
+
+
+def _new_sparse_pair(caps, device):
+    return (torch.zeros(gigs_lib.SPEC_SPARSE_STATE_INTS, dtype=torch.int32, device=device),
+            torch.empty(max(1, sum(caps)), dtype=torch.int32, device=device))
+
+
+def _sparse_buffers(shapes, device):
+    if not gigs_lib.current().option("spec_sparse"):
+        return None, None  # the library launches the gather alone and reads neither
+    caps = tuple(gigs_lib.check(_lib.gigs_spec_sparse_capacity(gigs_lib.ctx_ptr(), r), "spec_sparse_capacity") for r in shapes)
+    chain = (shapes, caps, str(device))
+    if torch.cuda.is_current_stream_capturing():
+        spares = _sparseSpares.get(chain)
+        pair = spares.pop() if spares else _new_sparse_pair(caps, device)
+        _sparseCaptured.append(pair)  # a graph may be replayed as long as the process lives: so does its pair (< 200 KB)
+    else:
+        key = chain + (_stream(),)
+        if key not in _sparseBuffers:
+            _sparseBuffers[key] = _new_sparse_pair(caps, device)
+        if not _sparseSpares.get(chain):
+            _sparseSpares[chain] = [_new_sparse_pair(caps, device)]
+        pair = _sparseBuffers[key]
+    _sparseLast[(shapes, str(device))] = pair[0]
+    return pair
+
+
+_sparseLast = {}
+
+
+def spec_sparse_report(shapes, device=None):
+    """[(scattered, nonzero texels)] per level from the last backward queued for the chain `shapes` (level resolutions),
+    or None if none ran: a device read after a synchronisation, for tests and diagnostics."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    state = _sparseLast.get((tuple(shapes), str(device)))
+    if state is None:
+        return None
+    torch.cuda.synchronize(device)
+    v = state.cpu().tolist()
+    return [(bool(v[8 + i]), v[16 + i]) for i in range(len(shapes))]
 
 
 def specular_cubemap_levels(mips, roughnesses, cutoff=0.99):
@@ -262,7 +321,7 @@ def _weight_tables(res, roughness, cutoff, device):
                                                               float(cos_cut), swap, wt.data_ptr(), _stream()),
                                    "specular_weights")
                     tabs.append(wt)
-            scaled = None
+            scaled = wsum = None
             if os.environ.get("GIGS_SPEC_PRESCALED", "1") == "1" and used + total * 12 <= _TABLE_MAX_BYTES:
                 # weight sums of the forward (independent of the cubemap's values), then the backward table divided by them
                 with torch.cuda.device(device):
@@ -277,7 +336,7 @@ def _weight_tables(res, roughness, cutoff, device):
                     gigs_lib.check(_lib.gigs_specular_weights_divide(res, bounds.data_ptr(), offsets.data_ptr(),
                                                                      tabs[1].data_ptr(), wsum.data_ptr(), scaled.data_ptr(),
                                                                      _stream()), "specular_weights_divide")
-            _weightTables[key] = (offsets, tabs[0], tabs[1], scaled)
+            _weightTables[key] = (offsets, tabs[0], tabs[1], scaled, wsum if scaled is not None else None)
     return _weightTables[key]
 
 

@@ -83,6 +83,10 @@ typedef struct gigs_options {
   int shade_bwd_rows;   /* 0 (default) its pixels in 32x32 tiles of 8x8-pixel waves, one add per distinct texel of a
                            wave into the global light levels; 1 = row-major chunks, adds pre-summed in 16-lane runs
                            (every per-pixel output the same bits).                         env GIGS_SHADE_BWD_ROWS */
+  int spec_sparse;      /* 1 (default): gigs_specular_cubemap_multi_bwd_sparse scatters the levels whose incoming gradient
+                           has few nonzero texels; 0 = it launches what gigs_specular_cubemap_multi_w launches. env GIGS_SPEC_SPARSE */
+  int spec_sparse_permille; /* capacity of a level's list of nonzero texels in thousandths of its texels, 0..1000 (37): a
+                           level with more nonzero texels is gathered.                     env GIGS_SPEC_SPARSE_PERMILLE */
 } gigs_options;
 /* A new context holds a copy of the default options.  Destroying a context frees host memory only; work queued
  * with it may still be running. */
@@ -287,6 +291,26 @@ typedef struct gigs_spec_level {
   float* wsum;
 } gigs_spec_level;
 int gigs_specular_cubemap_multi_w(gigs_ctx* ctx, int n_levels, const gigs_spec_level* levels, int backward, void* stream);
+/* The backward of the above (levels as for backward = 1) for gradients that are mostly exact zeros, which is what the shade
+ * backward hands the fine levels: it zero-fills them and adds into the sampled texels only.  Three launches, every decision
+ * taken on the device (fixed grids, no read-back: capturable in a graph and replayable with other gradients):
+ *   census   one pass over every level's src: zero-fills dst, counts the texels with a channel != 0 (NaN counts, -0 does
+ *            not) and lists their indices, up to the level's capacity = gigs_spec_sparse_capacity(ctx, res);
+ *   scatter  a level whose count is within its capacity is SPARSE: every listed texel o adds (w / wsum[o]) * src[o] into the
+ *            dst texels of its window with float atomics, w >= 0 from o's run of the FORWARD table weights_fwd[level]
+ *            (the products of the gather's pre-divided table, in arrival order);
+ *   gather   the kernel of gigs_specular_cubemap_multi_w, whose workgroups of a sparse level return at entry; the other
+ *            levels get the same bits as from gigs_specular_cubemap_multi_w.
+ * wsum[level] = the forward's weight sums [6,res,res].  state: GIGS_SPEC_SPARSE_STATE_INTS device ints, zero before the
+ * first call and owned by one stream at a time; after a call state[8 + l] = 1 if level l was scattered, 0 if gathered, and
+ * state[16 + l] = its count of nonzero texels (state[0..7] are the working counters: the last kernel clears them for the
+ * next call).  lists: device ints, the levels' capacities in level order.  With gigs_options.spec_sparse = 0 the call is
+ * gigs_specular_cubemap_multi_w(backward = 1) and touches neither state nor lists. */
+#define GIGS_SPEC_SPARSE_STATE_INTS 32
+int gigs_spec_sparse_capacity(const gigs_ctx* ctx, int res);
+int gigs_specular_cubemap_multi_bwd_sparse(gigs_ctx* ctx, int n_levels, const gigs_spec_level* levels,
+                                           const float* const* weights_fwd, const float* const* wsum, int* state,
+                                           int* lists, void* stream);
 /* cubemap_mip (pbr/light.py:54-79): forward 2x2 average pool [6,2r,2r,C] -> [6,r,r,C]; backward =
  * bilinear cube lookup of 0.25*dout at every fine texel direction, dout [6,r,r,3] -> din [6,2r,2r,3]. */
 int gigs_cubemap_mip_fwd(int res_out, int channels, const float* in, float* out, void* stream);
