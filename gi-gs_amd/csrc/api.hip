@@ -772,6 +772,30 @@ int gigs_ssr_apply(int width, int height, float delta, const unsigned* offsets, 
   return 0;
 }
 
+size_t gigs_ssr_apply_multi_scratch_bytes(int n_lights, int width, int height) {
+  if (n_lights < 1 || n_lights > GIGS_MAX_LIGHTS || width <= 0 || height <= 0) return 0;
+  return gigs::ssr_apply_multi_scratch_bytes(n_lights, width, height);
+}
+int gigs_ssr_apply_multi(int n_lights, int width, int height, float delta, const unsigned* offsets, const void* entries,
+                         const float* normal_view, const float* pos, const float* rgb, const float* albedo,
+                         const float* metallic, const float* F0, float* color, float* abd, void* scratch, void* stream) {
+  if (n_lights < 1 || n_lights > GIGS_MAX_LIGHTS)
+    return fail(GIGS_ERR_INVALID, "ssr_apply_multi: n_lights=%d outside 1..%d", n_lights, GIGS_MAX_LIGHTS);
+  if (width <= 0 || height <= 0 || !offsets || !normal_view || !pos || !rgb || !albedo || !metallic || !F0 || !color || !abd)
+    return fail(GIGS_ERR_INVALID, "bad argument");
+  if ((size_t)offsets % 16 != 0 || (size_t)scratch % 16 != 0)
+    return fail(GIGS_ERR_INVALID, "ssr_apply_multi: offsets and scratch must be 16-byte aligned");
+  if (n_lights > 1 && !scratch)
+    return fail(GIGS_ERR_INVALID, "ssr_apply_multi: %d lights need gigs_ssr_apply_multi_scratch_bytes of scratch", n_lights);
+  StageScope sc(kSsr, (hipStream_t)stream);
+  const int rc = gigs::launch_ssr_apply_multi(n_lights, width, height, delta, offsets, entries, normal_view, pos, rgb, albedo,
+                                              metallic, F0, color, abd, scratch, (hipStream_t)stream);
+  if (rc == -1) return fail(GIGS_ERR_INVALID, "delta=%g gives an unbounded or oversized ray set", (double)delta);
+  if (rc) return fail(GIGS_ERR_HIP, "ray table upload failed");
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 int gigs_ssr(int width, int height, float focal_x, float focal_y, float radius, float bias,
              float thick, float delta, int step, int start, const float* normal_view,
              const float* pos, const float* rgb, const float* albedo, const float* roughness,

@@ -340,6 +340,10 @@ int launch_ssr_multi(const Options& o, int n_lights, int W, int H, float fx, flo
 int launch_ssr_apply(int W, int H, float delta, const unsigned* offsets, const void* entries, const float* normal,
                      const float* pos, const float* rgb, const float* albedo, const float* metallic, const float* F0,
                      float* color, float* abd, hipStream_t s);
+int launch_ssr_apply_multi(int n_lights, int W, int H, float delta, const unsigned* offsets, const void* entries,
+                           const float* normal, const float* pos, const float* rgb, const float* albedo, const float* metallic,
+                           const float* F0, float* color, float* abd, void* scratch, hipStream_t s);
+size_t ssr_apply_multi_scratch_bytes(int n_lights, int W, int H);
 void launch_median3x3(int C, int H, int W, const float* in, float* out, hipStream_t s);
 void launch_median3x3_bwd(int C, int H, int W, const float* in, const float* gout, float* gin,
                           hipStream_t s);

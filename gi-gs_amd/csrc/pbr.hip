@@ -958,6 +958,63 @@ __device__ __forceinline__ bool cube_taps(int res, float dx, float dy, float dz,
   return true;
 }
 
+// cube_taps with the texel coordinates formed in double (gigs_cube_texture_fwd_precise; resampling a light onto another
+// cube grid, relight.rotate_light).  In float the coordinate u * res - 0.5 carries half an ulp of a value up to res -- 1.9e-6
+// texels at res 64, 7.6e-6 at 256 -- on top of res times the roundings of u, which a resample of a light writes into every
+// texel as noise; in double the weights are exact to float rounding.  Face choice and tap indices are cube_taps' (the
+// comparisons of float inputs are exact either way, and a wrapped tap's index comes from the same float path).
+__device__ __forceinline__ bool cube_taps_precise(int res, float dx, float dy, float dz, Taps& t) {
+  double x = dx, y = dy, z = dz;
+  const double ax = fabs(x), ay = fabs(y), az = fabs(z);
+  int face;
+  double c;
+  if (az > fmax(ax, ay)) { face = 4; c = z; }
+  else if (ay > ax) { face = 2; c = y; y = z; }
+  else { face = 0; c = x; x = z; }
+  if (c < 0.0) face += 1;
+  const double m = (1.0 / fabs(c)) * 0.5;
+  const double m0 = (face == 0 || face == 5) ? -m : m;
+  const double m1 = (face != 2) ? -m : m;
+  double u = x * m0 + 0.5, v = y * m1 + 0.5;
+  if (!isfinite(u) || !isfinite(v)) return false;
+  u = fmin(fmax(u, 0.0), 1.0);
+  v = fmin(fmax(v, 0.0), 1.0);
+  const double fu = u * (double)res - 0.5, fv = v * (double)res - 0.5;
+  const double flu = floor(fu), flv = floor(fv);
+  const int iu0 = (int)flu, iv0 = (int)flv;
+  const double tu = fu - flu, tv = fv - flv;
+  double w[4], wsum = 0.0;
+  bool dropped = false;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int ox = k & 1, oy = k >> 1;
+    const int ix = iu0 + ox, iy = iv0 + oy;
+    w[k] = (ox ? tu : 1.0 - tu) * (oy ? tv : 1.0 - tv);
+    const bool out_x = ix < 0 || ix >= res, out_y = iy < 0 || iy >= res;
+    int idx;
+    if (!out_x && !out_y) {
+      idx = (face * res + iy) * res + ix;
+    } else if (out_x && out_y) {
+      idx = -1;
+      dropped = true;
+    } else {  // the neighbouring face's texel, as cube_taps finds it
+      const float a = 2.0f * (((float)ix + 0.5f) / (float)res) - 1.0f;
+      const float b = 2.0f * (((float)iy + 0.5f) / (float)res) - 1.0f;
+      const v3 d = cube_dir_raw(a, b, face);
+      float u2, v2;
+      const int f2 = cube_face_uv(d.x, d.y, d.z, u2, v2);
+      const int x2 = min(res - 1, max(0, (int)floorf(u2 * (float)res)));
+      const int y2 = min(res - 1, max(0, (int)floorf(v2 * (float)res)));
+      idx = (f2 * res + y2) * res + x2;
+    }
+    t.idx[k] = idx;
+    if (idx >= 0) wsum += w[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) t.w[k] = t.idx[k] < 0 ? 0.0f : (float)(dropped ? w[k] / wsum : w[k]);
+  return true;
+}
+
 __device__ __forceinline__ v3 cube_sample(const float* __restrict__ tex, const Taps& t) {
   v3 r = {0, 0, 0};
 #pragma unroll
@@ -1036,6 +1093,18 @@ cube_texture_fwd_kernel(int res, const float* __restrict__ tex, int n, const flo
   }
 }
 
+// The same lookup with double-precision texel coordinates (cube_taps_precise): out is [n,3].
+__global__ void __launch_bounds__(256)
+cube_texture_fwd_precise_kernel(int res, const float* __restrict__ tex, int n, const float* __restrict__ dirs,
+                                float* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  Taps t;
+  v3 v = {0, 0, 0};
+  if (cube_taps_precise(res, dirs[3 * (size_t)i], dirs[3 * (size_t)i + 1], dirs[3 * (size_t)i + 2], t)) v = cube_sample(tex, t);
+  out[3 * (size_t)i] = v.x; out[3 * (size_t)i + 1] = v.y; out[3 * (size_t)i + 2] = v.z;
+}
+
 // latlong_to_cubemap (relight.py:92-111): every cube texel looks its direction up in an equirectangular map.
 //   gy, gx = linspace(-1 + 1/res, 1 - 1/res, res)   (torch: start + i*step below the middle, end - (n-1-i)*step above)
 //   v = normalize(cube_to_dir(face, gx, gy));  tu = atan2(v.x, -v.z) / (2 pi) + 0.5;  tv = acos(clamp(v.y, -1, 1)) / pi
@@ -1080,6 +1149,59 @@ latlong_to_cubemap_kernel(int res_y, int res_x, int Hl, int Wl, int C, const flo
     const float a = latlong[((size_t)iv0 * Wl + iu0) * C + c] * (1.0f - fu) + latlong[((size_t)iv0 * Wl + iu1) * C + c] * fu;
     const float b = latlong[((size_t)iv1 * Wl + iu0) * C + c] * (1.0f - fu) + latlong[((size_t)iv1 * Wl + iu1) * C + c] * fu;
     cube[(size_t)i * C + c] = a * (1.0f - fv) + b * fv;
+  }
+}
+
+// The same conversion under n_rot rotations of the environment (gigs_latlong_to_cubemap_rot; blockIdx.y = rotation):
+// env_R(d) = env(R^T d), so the texel's normalised direction is replaced by R^T dir before the lookup and everything else is
+// latlong_to_cubemap_kernel's expression for expression.  The matrix is wave-uniform; one that is exactly the identity
+// skips the product (x * 1 + y * 0 + z * 0 is not x for a non-finite or negative-zero component), which makes that slice the
+// unrotated kernel's bit for bit.
+__global__ void __launch_bounds__(256)
+latlong_to_cubemap_rot_kernel(int res_y, int res_x, int Hl, int Wl, int C, const float* __restrict__ latlong,
+                              const float* __restrict__ rotations, float* __restrict__ cube) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int n = 6 * res_y * res_x;
+  if (i >= n) return;
+  const float* R = rotations + 9 * (size_t)blockIdx.y;
+  const float r00 = R[0], r01 = R[1], r02 = R[2], r10 = R[3], r11 = R[4], r12 = R[5], r20 = R[6], r21 = R[7], r22 = R[8];
+  const bool identity = r00 == 1.0f && r11 == 1.0f && r22 == 1.0f && r01 == 0.0f && r02 == 0.0f && r10 == 0.0f &&
+                        r12 == 0.0f && r20 == 0.0f && r21 == 0.0f;
+  const int face = i / (res_y * res_x), rem = i - face * res_y * res_x;
+  const int ty = rem / res_x, tx = rem - ty * res_x;
+  const float gy = torch_linspace(-1.0f + 1.0f / (float)res_y, 1.0f - 1.0f / (float)res_y, res_y, ty);
+  const float gx = torch_linspace(-1.0f + 1.0f / (float)res_x, 1.0f - 1.0f / (float)res_x, res_x, tx);
+  float rx, ry, rz;  // cube_to_dir (relight.py:75-89)
+  switch (face) {
+    case 0: rx = 1.0f; ry = -gy; rz = -gx; break;
+    case 1: rx = -1.0f; ry = -gy; rz = gx; break;
+    case 2: rx = gx; ry = 1.0f; rz = gy; break;
+    case 3: rx = gx; ry = -1.0f; rz = -gy; break;
+    case 4: rx = gx; ry = -gy; rz = 1.0f; break;
+    default: rx = -gx; ry = -gy; rz = -1.0f; break;
+  }
+  const float inv = 1.0f / fmaxf(sqrtf(rx * rx + ry * ry + rz * rz), 1e-12f);  // F.normalize
+  rx *= inv; ry *= inv; rz *= inv;
+  if (!identity) {  // R^T dir: column j of R against dir, x then y then z
+    const float qx = (r00 * rx + r10 * ry) + r20 * rz;
+    const float qy = (r01 * rx + r11 * ry) + r21 * rz;
+    const float qz = (r02 * rx + r12 * ry) + r22 * rz;
+    rx = qx; ry = qy; rz = qz;
+  }
+  const float kPi = 3.14159265358979323846f;
+  const float tu = atan2f(rx, -rz) / (2.0f * kPi) + 0.5f;
+  const float tv = acosf(fminf(fmaxf(ry, -1.0f), 1.0f)) / kPi;
+  const float u = tu * (float)Wl - 0.5f, v = tv * (float)Hl - 0.5f;
+  const float fu0 = floorf(u), fv0 = floorf(v);
+  const float fu = u - fu0, fv = v - fv0;
+  auto wrap = [](int a, int m) { a %= m; return a < 0 ? a + m : a; };
+  const int iu0 = wrap((int)fu0, Wl), iu1 = wrap((int)fu0 + 1, Wl);
+  const int iv0 = wrap((int)fv0, Hl), iv1 = wrap((int)fv0 + 1, Hl);
+  float* out = cube + ((size_t)blockIdx.y * n + i) * C;
+  for (int c = 0; c < C; c++) {
+    const float a = latlong[((size_t)iv0 * Wl + iu0) * C + c] * (1.0f - fu) + latlong[((size_t)iv0 * Wl + iu1) * C + c] * fu;
+    const float b = latlong[((size_t)iv1 * Wl + iu0) * C + c] * (1.0f - fu) + latlong[((size_t)iv1 * Wl + iu1) * C + c] * fu;
+    out[c] = a * (1.0f - fv) + b * fv;
   }
 }
 
@@ -1909,6 +2031,18 @@ int gigs_cube_texture_fwd(int res, const float* cubemap, int n, const float* dir
   return 0;
 }
 
+int gigs_cube_texture_fwd_precise(int res, const float* cubemap, int n, const float* dirs, float* out, void* stream) {
+  if (res <= 0 || n < 0 || !cubemap || (n > 0 && (!dirs || !out)))
+    return gigs_internal_fail(GIGS_ERR_INVALID, "cube_texture_fwd_precise: bad argument");
+  if (n == 0) return 0;
+  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  hipLaunchKernelGGL(gigs::cube_texture_fwd_precise_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, res,
+                     cubemap, n, dirs, out);
+  gigs_internal_stage_end(tok);
+  PBR_CHECK_LAUNCH();
+  return 0;
+}
+
 int gigs_latlong_to_cubemap(int res_y, int res_x, int lat_h, int lat_w, int channels, const float* latlong, float* cubemap,
                             void* stream) {
   if (res_y <= 0 || res_x <= 0 || lat_h <= 0 || lat_w <= 0 || channels <= 0 || !latlong || !cubemap)
@@ -1917,6 +2051,21 @@ int gigs_latlong_to_cubemap(int res_y, int res_x, int lat_h, int lat_w, int chan
   void* tok; gigs_internal_stage_begin(16, stream, &tok);
   hipLaunchKernelGGL(gigs::latlong_to_cubemap_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, res_y, res_x,
                      lat_h, lat_w, channels, latlong, cubemap);
+  gigs_internal_stage_end(tok);
+  PBR_CHECK_LAUNCH();
+  return 0;
+}
+
+int gigs_latlong_to_cubemap_rot(int res_y, int res_x, int lat_h, int lat_w, int channels, const float* latlong, int n_rot,
+                                const float* rotations, float* cubemap, void* stream) {
+  if (n_rot < 1 || n_rot > 1024)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "latlong_to_cubemap_rot: n_rot outside 1..1024");
+  if (res_y <= 0 || res_x <= 0 || lat_h <= 0 || lat_w <= 0 || channels <= 0 || !latlong || !rotations || !cubemap)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "latlong_to_cubemap_rot: bad argument");
+  const int n = 6 * res_y * res_x;
+  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  hipLaunchKernelGGL(gigs::latlong_to_cubemap_rot_kernel, dim3((n + 255) / 256, n_rot), dim3(256), 0, (hipStream_t)stream,
+                     res_y, res_x, lat_h, lat_w, channels, latlong, rotations, cubemap);
   gigs_internal_stage_end(tok);
   PBR_CHECK_LAUNCH();
   return 0;

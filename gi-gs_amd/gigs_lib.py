@@ -66,6 +66,8 @@ SIGNATURES = {
     "gigs_ssr_multi": (_i, [C.c_void_p, _i, _i, _i, _fl, _fl, _fl, _fl, _fl, _fl, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f,
                             _f, C.c_void_p]),
     "gigs_ssr_apply": (_i, [_i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_ssr_apply_multi_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
+    "gigs_ssr_apply_multi": (_i, [_i, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_median3x3": (_i, [_i, _i, _i, _f, _f, C.c_void_p]),
     "gigs_median3x3_backward": (_i, [_i, _i, _i, _f, _f, _f, C.c_void_p]),
     "gigs_bilateral3x3": (_i, [_i, _i, _i, _fl, _fl, _fl, _f, _f, C.c_void_p]),
@@ -107,10 +109,12 @@ SIGNATURES = {
     "gigs_stage2_loss_bwd": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_stage2_loss_fwd_grad": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_cube_texture_fwd": (_i, [_i, _f, _i, _f, _f, _i, C.c_void_p]),
+    "gigs_cube_texture_fwd_precise": (_i, [_i, _f, _i, _f, _f, C.c_void_p]),
     "gigs_cube_texture_bwd": (_i, [_i, _i, _f, _f, _f, _i, C.c_void_p]),
     "gigs_cube_taps": (_i, [_i, _i, _f, _f, _f, C.c_void_p]),
     "gigs_cube_texture_bwd_gather": (_i, [_i, _i, _i, _f, _f, _f, _i, _i, _f, _f, _f, C.c_void_p]),
     "gigs_latlong_to_cubemap": (_i, [_i, _i, _i, _i, _i, _f, _f, C.c_void_p]),
+    "gigs_latlong_to_cubemap_rot": (_i, [_i, _i, _i, _i, _i, _f, _i, _f, _f, C.c_void_p]),
     "gigs_loss_scratch_floats": (C.c_size_t, [_i, _i, _i]),
     "gigs_l1_ssim_fwd": (_i, [_i, _i, _i, _f, _f, C.c_float, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_l1_ssim_bwd": (_i, [_i, _i, _i, _f, _f, C.c_float, _f, _f, _f, _f, _f, C.c_void_p]),

@@ -108,3 +108,24 @@ class _CubeTexture(torch.autograd.Function):
 def cube_texture(cubemap: torch.Tensor, dirs: torch.Tensor, planar: bool = False) -> torch.Tensor:
     """cubemap [6,res,res,3], dirs [...,3] -> [...,3] (or [3,...] planes); differentiable w.r.t. the cubemap."""
     return _CubeTexture.apply(cubemap, dirs, planar)
+
+
+@torch.no_grad()
+def cube_texture_precise(cubemap: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
+    """cube_texture's forward with the texel coordinates formed in double (gigs_cube_texture_fwd_precise): for resampling a
+    light onto another cube grid, where the float lookup's coordinate rounding (it grows with the resolution) would end up in
+    every texel.  cubemap [6,res,res,3], dirs [...,3] -> [...,3]; no gradient."""
+    if not cubemap.is_cuda:
+        raise RuntimeError("cube_texture_precise needs CUDA/HIP tensors: gigs-hip has no CPU path")
+    if cubemap.dim() != 4 or cubemap.shape[0] != 6 or cubemap.shape[1] != cubemap.shape[2] or cubemap.shape[3] != 3:
+        raise ValueError("cube_texture_precise: cubemap must be [6,res,res,3]")
+    if dirs.shape[-1] != 3:
+        raise ValueError("cube_texture_precise: dirs must be [...,3]")
+    cubemap = cubemap.detach().contiguous().float()
+    d = dirs.detach().contiguous().float()
+    out = torch.empty(tuple(d.shape), dtype=torch.float32, device=cubemap.device)
+    with torch.cuda.device(cubemap.device):
+        gigs_lib.check(_lib.gigs_cube_texture_fwd_precise(int(cubemap.shape[1]), cubemap.data_ptr(), d.numel() // 3, d.data_ptr(),
+                                                          out.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                       "cube_texture_fwd_precise")
+    return out

@@ -19,6 +19,14 @@ gigs_stage2_loss_fwd for linear_to_srgb + median + sum) on the rasterizer's [C,H
     RelightEvaluator(light_names).add(...)    relight_eval.py without the file I/O: per light the PSNR / SSIM of the
                                               8-bit-quantised prediction against its ground truth, kept on the device
 
+    TurntableRelighter(lights, ...)(cam, gaussians, ...)   one view under ANY number of lights (a turntable: N rotations of
+                                              one map): the march runs once and records its hit list (gigs_ssr_hits), then
+                                              every chunk of <= 16 lights is a shade (gigs_shade_fwd_multi), a gather at the
+                                              recorded hits (gigs_ssr_apply_multi) and the per-light finish
+    rotation_about / yaw_rotations / rotated_lights / rotate_light   lights turned in their own frame: the BASE is resampled
+                                              under the rotation and then pre-filtered like any other light (DESIGN.md,
+                                              "Turntables": the pre-filters are not rotation-covariant)
+
 Reference quirks kept on purpose, by Relighter and MultiRelighter alike: the `metallic` branches for F0 are swapped (relight.py:236-240):
 with metallic=True the shade uses the metallic map but SSR receives F0 = 0.04 and a zero metallic plane; with
 metallic=False (`metallic` is the Python bool) SSR receives F0 = (1 - False) * 0.04 + albedo * metallic_map.  The
@@ -61,6 +69,107 @@ def make_light(hdri: torch.Tensor, res: int = 256) -> CubemapLight:
     light.base.data = latlong_to_cubemap(hdri, [res, res])
     light.eval()
     return light
+
+
+# ---- rotated lights ---------------------------------------------------------------------------------------------------
+# Rotations live in the light's own frame: the cube / latitude-longitude frame of relight.py:75-111, +y towards tv = 0 (the
+# shade's swizzle (-n.y, n.z, -n.x) maps world +z to it: the up axis of a Blender scene).  R is a right-handed 3x3 rotation
+# and the rotated environment is env_R(d) = env(R^T d).  Anchor: torch.roll(latlong, +s, dims=1) is the rotation about +y by
+# -2 pi s / W (tu = atan2(x, -z) / 2 pi + 0.5 grows with the angle of a right-handed turn about +y).
+MAX_ROTATIONS = 1024  # gigs_latlong_to_cubemap_rot
+
+
+def rotation_about(axis: Sequence[float], angle: float) -> torch.Tensor:
+    """The right-handed rotation by `angle` (radians) about `axis` as a [3,3] float64 tensor (Rodrigues).  Entries within
+    1e-15 of an integer are that integer, so whole quarter turns about a coordinate axis are exact signed permutations and
+    angle 0 is exactly the identity."""
+    a = torch.as_tensor(axis, dtype=torch.float64).reshape(3)
+    n = float(a.norm())
+    if not n > 0.0:
+        raise ValueError("rotation_about: the axis has no direction")
+    x, y, z = (a / n).tolist()
+    k = torch.tensor([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]], dtype=torch.float64)
+    import math
+    r = torch.eye(3, dtype=torch.float64) + math.sin(angle) * k + (1.0 - math.cos(angle)) * (k @ k)
+    return torch.where((r - r.round()).abs() < 1e-15, r.round() + 0.0, r)
+
+
+def yaw_rotations(n: int, axis: Sequence[float] = (0.0, 1.0, 0.0)) -> torch.Tensor:
+    """[n,3,3]: n equal right-handed steps of a full turn about `axis` (default +y, the light's up), the identity first."""
+    import math
+    if n < 1:
+        raise ValueError("yaw_rotations: n must be at least 1")
+    return torch.stack([rotation_about(axis, 2.0 * math.pi * k / n) for k in range(n)])
+
+
+def _rotations_f32(rotations, dev) -> torch.Tensor:
+    r = torch.as_tensor(rotations).detach().to(torch.float64).reshape(-1, 3, 3)
+    if r.shape[0] < 1:
+        raise ValueError("no rotation given")
+    return r.to(device=dev, dtype=torch.float32).contiguous()
+
+
+def latlong_to_cubemap_rot(latlong_map: torch.Tensor, res: List[int], rotations) -> torch.Tensor:
+    """latlong_to_cubemap under each of `rotations` [n,3,3] in one launch: [n, 6, res[0], res[1], C].  The slice of an exact
+    identity equals latlong_to_cubemap bit for bit."""
+    if not latlong_map.is_cuda:
+        raise RuntimeError("latlong_map must be a CUDA/HIP tensor: gigs-hip has no CPU path")
+    lat = latlong_map.contiguous().float()
+    rot = _rotations_f32(rotations, lat.device)
+    n = int(rot.shape[0])
+    if n > MAX_ROTATIONS:
+        raise ValueError(f"latlong_to_cubemap_rot: at most {MAX_ROTATIONS} rotations per call, got {n}")
+    Hl, Wl, Cn = lat.shape
+    cube = torch.empty((n, 6, int(res[0]), int(res[1]), Cn), dtype=torch.float32, device=lat.device)
+    with torch.cuda.device(lat.device):
+        gigs_lib.check(_lib.gigs_latlong_to_cubemap_rot(int(res[0]), int(res[1]), Hl, Wl, Cn, lat.data_ptr(), n, rot.data_ptr(),
+                                                        cube.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                       "latlong_to_cubemap_rot")
+    return cube
+
+
+def _light_of(base: torch.Tensor) -> CubemapLight:
+    light = CubemapLight(base_res=int(base.shape[1]), device=base.device)
+    light.base.data = base.contiguous()
+    light.eval()
+    return light
+
+
+def rotated_lights(hdri: torch.Tensor, rotations, res: int = 256) -> List[CubemapLight]:
+    """make_light for every rotation of a latitude-longitude map: what relight.py would build if it were handed the
+    rotated .hdr (the base cubemap sampled at R^T dir; the mips are built from it, unchanged, by whoever uses the light)."""
+    rot = torch.as_tensor(rotations).reshape(-1, 3, 3)
+    lights: List[CubemapLight] = []
+    for first in range(0, int(rot.shape[0]), MAX_ROTATIONS):
+        cubes = latlong_to_cubemap_rot(hdri, [res, res], rot[first:first + MAX_ROTATIONS])
+        lights.extend(_light_of(c) for c in cubes)
+    return lights
+
+
+def cube_texel_dirs(res: int, dev) -> torch.Tensor:
+    """[6,res,res,3]: the unnormalised texel-centre directions of a cubemap (relight.py:75-89 over linspace(-1 + 1/res, ..))."""
+    lin = torch.linspace(-1.0 + 1.0 / res, 1.0 - 1.0 / res, res, device=dev)
+    gy, gx = torch.meshgrid(lin, lin, indexing="ij")
+    one = torch.ones_like(gx)
+    faces = ((one, -gy, -gx), (-one, -gy, gx), (gx, one, gy), (gx, -one, -gy), (gx, -gy, one), (-gx, -gy, -one))
+    return torch.stack([torch.stack(f, dim=-1) for f in faces])
+
+
+@torch.no_grad()
+def rotate_light(light: CubemapLight, rotations) -> List[CubemapLight]:
+    """A cube light (the trained light of a checkpoint) under each rotation: base_R = the cube lookup of light.base at R^T dir
+    of the texel-centre directions (pbr.texture.cube_texture's lookup with its texel coordinates formed in double,
+    cube_texture_precise: the float lookup's coordinate rounding grows with the resolution and would be written into every
+    texel).  This is a bilinear cube resample, so it LOW-PASSES the base (every rotation that is not a cube symmetry blurs it
+    by up to a texel, and rotating twice blurs twice): rotate the original light by the composed rotation, and prefer
+    rotated_lights when the latitude-longitude source exists."""
+    from pbr.texture import cube_texture_precise
+    base = light.base.detach()
+    dirs = cube_texel_dirs(int(base.shape[1]), base.device)
+    out = []
+    for r in _rotations_f32(rotations, base.device):
+        out.append(_light_of(cube_texture_precise(base, dirs @ r)))  # row vector times R = R^T dir
+    return out
 
 
 class _ViewGraph:
@@ -308,20 +417,13 @@ class MultiRelighter(_ViewGraph):
         lights = list(lights)
         if not 1 <= len(lights) <= MAX_LIGHTS:
             raise ValueError(f"MultiRelighter: 1..{MAX_LIGHTS} lights, got {len(lights)}")
-        res = {tuple(l.base.shape) for l in lights}
-        if len(res) != 1:
-            raise ValueError(f"MultiRelighter: the lights differ in base resolution: {sorted(res)}")
+        _check_lights("MultiRelighter", lights)
         self.lights = lights
         self.tone, self.gamma = bool(tone), bool(gamma)
         self._init_view(gi, sh_degree, metallic, graphs)
         dev = lights[0].base.device
         self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(dev)
-        with torch.no_grad():
-            for light in lights:
-                light.build_mips()  # relight.py:141: once per run and light
-        levels = {tuple(int(s.shape[1]) for s in l.specular) for l in lights}
-        if len(levels) != 1 or len({int(l.diffuse.shape[1]) for l in lights}) != 1:
-            raise ValueError("MultiRelighter: the lights' mip chains differ in level count or resolution")
+        _build_lights("MultiRelighter", lights)
 
     @torch.no_grad()
     def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], view_dirs: torch.Tensor,
@@ -343,7 +445,7 @@ class MultiRelighter(_ViewGraph):
 
     def _fused(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
         b = self._gbuffer(cam, g)
-        albedo_map, roughness_map = b["albedo_map"], b["roughness_map"]
+        albedo_map = b["albedo_map"]
         dev = albedo_map.device
         gi = self.gi
         K = len(self.lights)
@@ -351,32 +453,176 @@ class MultiRelighter(_ViewGraph):
         render_direct, IRR, render_rgb = (torch.empty((K, 3, H, W), device=dev) for _ in range(3))
         linear_rgb, abd = self._buf("linear_rgb_k", (K, 3, H, W), torch.float32, dev), self._buf("abd_k", (K, 3, H, W),
                                                                                                  torch.float32, dev)
-        acc, loss = self._buf("acc", (4 + 4 * 256,), torch.float32, dev), self._buf("loss", (1,), torch.float32, dev)
         p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        spec = [[s.contiguous() for s in light.specular] for light in self.lights]
-        L = len(spec[0])
-        diffuse_ptr = _ptr_array([light.diffuse for light in self.lights])
-        spec_ptr = _ptr_array([s for chain in spec for s in chain])
-        spec_res = (C.c_int * L)(*[int(s.shape[1]) for s in spec[0]])
-        lut = self.brdf_lut
         vd = view_dirs.contiguous().float()
         scratch = _gi_scratch(W, H, dev)
         with torch.cuda.device(dev):
             s = torch.cuda.current_stream().cuda_stream
-            gigs_lib.check(_lib.gigs_shade_fwd_multi(
-                gigs_lib.ctx_ptr(), K, H, W, p(b["normals_view"]), p(vd), p(self._albedo_shade(albedo_map, albedo_ratio)),
-                p(roughness_map), p(b["mask_u8"]), p(b["occlusion"]), p(b["metallic_map"]) if self.metallic else None,
-                diffuse_ptr, int(self.lights[0].diffuse.shape[1]), L, spec_ptr, spec_res, p(lut), int(lut.shape[-2]),
-                int(lut.shape[-3]), int(self.tone), int(self.gamma), p(render_direct), p(linear_rgb), s), "shade_fwd_multi")
+            _shade_lights(self, self.lights, H, W, b, vd, self._albedo_shade(albedo_map, albedo_ratio), render_direct,
+                          linear_rgb, s)
             gigs_lib.check(_lib.gigs_ssr_multi(
                 gigs_lib.ctx_ptr(), K, W, H, float(W / (2.0 * cam["tanfovx"])), float(H / (2.0 * cam["tanfovy"])),
                 float(gi["radius"]), float(gi["bias"]), float(gi["thick"]), float(gi["delta"]), int(gi["step"]),
-                int(gi["start"]), p(b["onv"]), p(b["depth_pos"]), p(linear_rgb), p(albedo_map), p(roughness_map),
+                int(gi["start"]), p(b["onv"]), p(b["depth_pos"]), p(linear_rgb), p(albedo_map), p(b["roughness_map"]),
                 p(b["metallic_in"]), p(b["F0"]), p(IRR), p(abd), p(scratch), s), "ssr_multi")
-            for k in range(K):  # the loss gigs_stage2_loss_fwd also forms is unused
-                gigs_lib.check(_lib.gigs_stage2_loss_fwd(H, W, p(render_direct[k]), p(IRR[k]), p(render_direct[k]),
-                                                         p(b["mask_f"]), p(roughness_map), p(b["metallic_in"]),
-                                                         p(render_rgb[k]), p(acc), p(loss), s), "stage2_loss_fwd")
+            _finish_lights(self, H, W, b, render_direct, IRR, render_rgb, s)
+        if alpha_mask is not None:
+            render_rgb = render_rgb * alpha_mask
+        return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=b["occlusion"],
+                    depth_map=b["depth_map"], normal_map=b["normals_view"], normal_mask=b["mask_u8"].bool()[None],
+                    radii=b["radii"])
+
+
+def _check_lights(who: str, lights) -> None:
+    res = {tuple(l.base.shape) for l in lights}
+    if len(res) != 1:
+        raise ValueError(f"{who}: the lights differ in base resolution: {sorted(res)}")
+
+
+def _build_lights(who: str, lights) -> None:
+    with torch.no_grad():
+        for light in lights:
+            light.build_mips()  # relight.py:141: once per run and light
+    levels = {tuple(int(s.shape[1]) for s in l.specular) for l in lights}
+    if len(levels) != 1 or len({int(l.diffuse.shape[1]) for l in lights}) != 1:
+        raise ValueError(f"{who}: the lights' mip chains differ in level count or resolution")
+
+
+def _shade_lights(view, lights, H, W, b, vd, albedo_shade, render_direct, linear_rgb, s) -> None:
+    """gigs_shade_fwd_multi of the G-buffer `b` under `lights` (at most MAX_LIGHTS) into render_direct / linear_rgb [K,3,H,W]."""
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    spec = [[x.contiguous() for x in light.specular] for light in lights]
+    L = len(spec[0])
+    diffuse_ptr = _ptr_array([light.diffuse for light in lights])
+    spec_ptr = _ptr_array([x for chain in spec for x in chain])
+    spec_res = (C.c_int * L)(*[int(x.shape[1]) for x in spec[0]])
+    lut = view.brdf_lut
+    gigs_lib.check(_lib.gigs_shade_fwd_multi(
+        gigs_lib.ctx_ptr(), len(lights), H, W, p(b["normals_view"]), p(vd), p(albedo_shade), p(b["roughness_map"]),
+        p(b["mask_u8"]), p(b["occlusion"]), p(b["metallic_map"]) if view.metallic else None, diffuse_ptr,
+        int(lights[0].diffuse.shape[1]), L, spec_ptr, spec_res, p(lut), int(lut.shape[-2]), int(lut.shape[-3]),
+        int(view.tone), int(view.gamma), p(render_direct), p(linear_rgb), s), "shade_fwd_multi")
+
+
+def _finish_lights(view, H, W, b, render_direct, IRR, render_rgb, s) -> None:
+    """render_rgb[k] = render_direct[k] + median3x3(linear_to_srgb(IRR[k])); the loss gigs_stage2_loss_fwd also forms is unused."""
+    dev = render_direct.device
+    acc, loss = view._buf("acc", (4 + 4 * 256,), torch.float32, dev), view._buf("loss", (1,), torch.float32, dev)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    for k in range(int(render_direct.shape[0])):
+        gigs_lib.check(_lib.gigs_stage2_loss_fwd(H, W, p(render_direct[k]), p(IRR[k]), p(render_direct[k]), p(b["mask_f"]),
+                                                 p(b["roughness_map"]), p(b["metallic_in"]), p(render_rgb[k]), p(acc), p(loss),
+                                                 s), "stage2_loss_fwd")
+
+
+class TurntableRelighter(_ViewGraph):
+    """One view under any number of lights of equal base resolution -- usually rotated_lights(...) of one map, a turntable or
+    a lighting sweep, but any list: only the shade samples and the radiance gathered at the march's hits depend on the light.
+    Per call the rasterizer, G-buffer post and SSAO run once and the SSR march runs once as a recording (gigs_ssr_hits: count,
+    prefix sum, one read-back of the total to size the entries, fill); then every chunk of up to MAX_LIGHTS lights is one
+    gigs_shade_fwd_multi, one gigs_ssr_apply_multi over the recorded hits (the chunk's radiance packed pixel-major first) and the per-light finish.  Outputs are
+    MultiRelighter's with K = len(lights); light k equals Relighter(lights[k], fused=True) bit for bit, quirks included.
+
+    The gather is only launched with a complete list: the total read back is compared with the entries' capacity, and a
+    mismatch (a total beyond 2^31 - 1 wraps the 32-bit prefix) sends the view through gigs_ssr_multi instead.  The hit list
+    exists for the default march only (gi_march = proj, start < step); any other march also takes gigs_ssr_multi per chunk,
+    with the same results.  Eager only (the read-back sizes a buffer): no hipGraph."""
+
+    def __init__(self, lights: Sequence[CubemapLight], gi: Dict, sh_degree: int, metallic: bool = False,
+                 tone: bool = False, gamma: bool = False, brdf_lut: Optional[torch.Tensor] = None):
+        lights = list(lights)
+        if not lights:
+            raise ValueError("TurntableRelighter: no lights")
+        _check_lights("TurntableRelighter", lights)
+        self.lights = lights
+        self.tone, self.gamma = bool(tone), bool(gamma)
+        self._init_view(gi, sh_degree, metallic, False)
+        self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(lights[0].base.device)
+        _build_lights("TurntableRelighter", lights)
+        self._entries = None  # the hit list's {hit pixel, ray} pairs, grown on demand
+        self.last_hits = None  # hits of the last view's list, None where it took the march
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        self._entries = None
+        self._scratch = {}
+        super().close()
+
+    def _record_hits(self, cam, b, a, scratch, s):
+        """The march as a recording -> (offsets, entries) of a complete list, or None where there is none to be had."""
+        gi = self.gi
+        if gigs_lib.current().option("gi_march") != 4 or not int(gi["start"]) < int(gi["step"]):
+            return None
+        dev = b["albedo_map"].device
+        H, W = cam["image_height"], cam["image_width"]
+        n = H * W
+        counts = self._buf("hit_counts", (4 * n,), torch.int32, dev)
+        offsets = self._buf("hit_offsets", (4 * n + 1,), torch.int32, dev)
+        color, abd = self._buf("hit_color", (3, H, W), torch.float32, dev), self._buf("hit_abd", (3, H, W), torch.float32, dev)
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        # which pixel a ray hits does not depend on the radiance: any plane serves the recording passes, their outputs are unused
+        planes = (p(b["onv"]), p(b["depth_pos"]), p(b["albedo_map"]), p(b["albedo_map"]), p(b["roughness_map"]),
+                  p(b["metallic_in"]), p(b["F0"]), p(color), p(abd))
+        if _lib.gigs_ssr_hits(gigs_lib.ctx_ptr(), *a, *planes, 1, p(counts), None, None, 0, p(scratch), s) != 0:
+            return None  # a march without a hit list (more steps than the projective march's table holds)
+        offsets[:1].zero_()
+        torch.cumsum(counts, 0, dtype=torch.int32, out=offsets[1:])
+        total = int(offsets[-1])  # the one read-back
+        if total < 0:
+            return None
+        if self._entries is None or self._entries.device != dev or int(self._entries.shape[0]) < total:
+            self._entries = torch.empty((max(1 << 16, int(1.3 * total)), 2), dtype=torch.int32, device=dev)
+        capacity = int(self._entries.shape[0])
+        if total > capacity:
+            return None
+        gigs_lib.check(_lib.gigs_ssr_hits(gigs_lib.ctx_ptr(), *a, *planes, 2, None, p(offsets), p(self._entries), capacity,
+                                          p(scratch), s), "ssr_hits (fill)")
+        self.last_hits = total
+        return offsets, self._entries
+
+    @torch.no_grad()
+    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], view_dirs: torch.Tensor,
+                 alpha_mask: Optional[torch.Tensor] = None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        b = self._gbuffer(cam, g)
+        albedo_map = b["albedo_map"]
+        dev = albedo_map.device
+        gi = self.gi
+        N = len(self.lights)
+        H, W = cam["image_height"], cam["image_width"]
+        render_direct, IRR, render_rgb = (torch.empty((N, 3, H, W), device=dev) for _ in range(3))
+        Kmax = min(N, MAX_LIGHTS)
+        linear_rgb = self._buf("linear_rgb_k", (Kmax, 3, H, W), torch.float32, dev)
+        abd = self._buf("abd_k", (Kmax, 3, H, W), torch.float32, dev)
+        packed = self._buf("packed_rgb", (max(16, int(_lib.gigs_ssr_apply_multi_scratch_bytes(Kmax, W, H))),), torch.uint8, dev)
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        vd = view_dirs.contiguous().float()
+        albedo_shade = self._albedo_shade(albedo_map, albedo_ratio)
+        scratch = _gi_scratch(W, H, dev)
+        a = (W, H, float(W / (2.0 * cam["tanfovx"])), float(H / (2.0 * cam["tanfovy"])), float(gi["radius"]),
+             float(gi["bias"]), float(gi["thick"]), float(gi["delta"]), int(gi["step"]), int(gi["start"]))
+        self.last_hits = None
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream().cuda_stream
+            hits = self._record_hits(cam, b, a, scratch, s)
+            for first in range(0, N, MAX_LIGHTS):
+                chunk = self.lights[first:first + MAX_LIGHTS]
+                K = len(chunk)
+                rd, irr = render_direct[first:first + K], IRR[first:first + K]
+                _shade_lights(self, chunk, H, W, b, vd, albedo_shade, rd, linear_rgb[:K], s)
+                if hits is not None:
+                    gigs_lib.check(_lib.gigs_ssr_apply_multi(
+                        K, W, H, float(gi["delta"]), p(hits[0]), p(hits[1]), p(b["onv"]), p(b["depth_pos"]), p(linear_rgb),
+                        p(albedo_map), p(b["metallic_in"]), p(b["F0"]), p(irr), p(abd), p(packed), s), "ssr_apply_multi")
+                else:
+                    gigs_lib.check(_lib.gigs_ssr_multi(
+                        gigs_lib.ctx_ptr(), K, *a, p(b["onv"]), p(b["depth_pos"]), p(linear_rgb), p(albedo_map),
+                        p(b["roughness_map"]), p(b["metallic_in"]), p(b["F0"]), p(irr), p(abd), p(scratch), s), "ssr_multi")
+                _finish_lights(self, H, W, b, rd, irr, render_rgb[first:first + K], s)
         if alpha_mask is not None:
             render_rgb = render_rgb * alpha_mask
         return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=b["occlusion"],

@@ -1,13 +1,17 @@
 """A trained scene under new environment maps, on disk: the reference's relight.py (and relight_eval.py with --gt_dir)
-over relight.MultiRelighter, relight.RelightEvaluator and image_writer.ImageWriter.
+over relight.TurntableRelighter, relight.RelightEvaluator and image_writer.ImageWriter.
 
     python gi-gs_amd/relight_scene.py -m <out> --checkpoint <out>/chkpntN.pth --hdri a.hdr [b.hdr ...]
                                       [--metallic --tone --gamma --skip_train --skip_test --gt_dir DIR --lpips_weights DIR]
+                                      [--rotations N [--rotation_axis x y z]]
     relight_scene(args) -> {split: {...}}
 
-Flags and defaults are relight.py's (:340-356), with --hdri taking one or more maps (Radiance .hdr or .npy [H,W,3]): K
-maps go through MultiRelighter, up to its limit of 16 per pass (more maps run in passes of 16).  <light> is the map's
-file name up to the first dot (:286).  Per split it writes (`planned_paths` is the table):
+Flags and defaults are relight.py's (:340-356), with --hdri taking one or more maps (Radiance .hdr or .npy [H,W,3]): all
+maps of a view go through one TurntableRelighter call (one G-buffer and one march per view, any number of lights).
+<light> is the map's file name up to the first dot (:286).  --rotations N (a turntable) relights every map under N equal
+right-handed steps of a full turn about the light's up axis (+y of the map's frame, or --rotation_axis), the identity
+first: the lights are then <light>_r000 .. _r<N-1>, and --gt_dir is refused (no dataset has ground truth for rotated
+maps).  Per split it writes (`planned_paths` is the table):
 
     <out>/<split>/envmap_relight_<light>.png                                       relight.py:142-145
     <out>/<split>/ours_<iter>/relight/<image_name>_<light>.png                     :249-251
@@ -39,6 +43,13 @@ if __package__ in (None, ""):  # run as a script: make the package's modules imp
 import render_scene as rs  # noqa: E402
 
 MAX_LIGHTS = 16  # relight.MAX_LIGHTS
+
+
+def rotated_names(names: Sequence[str], rotations: int) -> List[str]:
+    """The light names of a run: the maps' own, or <light>_r000 .. per map with --rotations N."""
+    if rotations <= 0:
+        return list(names)
+    return ["%s_r%03d" % (n, k) for n in names for k in range(rotations)]
 
 
 def light_name(path: str) -> str:
@@ -77,12 +88,25 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--" + k, type=type(v), default=v)
     p.add_argument("--gt_dir", type=str, default=None, help="ground truth: <gt_dir>/<light>/<image_name>.png")
     p.add_argument("--lpips_weights", type=str, default=None, help="directory with vgg16-397923af.pth and vgg.pth")
+    p.add_argument("--rotations", type=int, default=0, help="relight every map under N equal turns about its up axis")
+    p.add_argument("--rotation_axis", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                   help="axis of --rotations in the map's frame (default 0 1 0)")
     p.add_argument("--workers", type=int, default=12, help="PNG encoder threads (at most 16)")
     return p
 
 
 def parse_args(argv: Optional[List[str]] = None) -> Namespace:
     return build_parser().parse_args(argv)
+
+
+def check_rotations(args: Namespace) -> int:
+    """--rotations as a count (0 = none); refuses a negative count and --rotations together with --gt_dir."""
+    n = int(getattr(args, "rotations", 0) or 0)
+    if n < 0:
+        raise ValueError("--rotations: a count of turns, got %d" % n)
+    if n > 0 and getattr(args, "gt_dir", None):
+        raise ValueError("--rotations with --gt_dir: there is no ground truth for rotated maps")
+    return n
 
 
 def _read_gt(path: str, dev):
@@ -111,39 +135,39 @@ def relight_split(args: Namespace, split: str, infos, g, sh_degree: int, lights,
     res: Dict = {"n_views": len(infos), "lights": list(names)}
     t0 = time.perf_counter()
     with image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
-        for first in range(0, len(lights), MAX_LIGHTS):
-            chunk, chunk_names = lights[first:first + MAX_LIGHTS], names[first:first + MAX_LIGHTS]
-            mr = relight.MultiRelighter(chunk, gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
-                                        graphs=True, brdf_lut=lut)  # build_mips per light (:141)
-            ev = relight.RelightEvaluator(chunk_names, device=dev, lpips=lp) if args.gt_dir else None
-            try:
+        tr = relight.TurntableRelighter(lights, gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
+                                        brdf_lut=lut)  # build_mips per light (:141)
+        ev = relight.RelightEvaluator(names, device=dev, lpips=lp) if args.gt_dir else None
+        try:
+            for first in range(0, len(lights), MAX_LIGHTS):  # one batch of files per MAX_LIGHTS lights
                 wr.submit([(os.path.join(out, split, "envmap_relight_%s.png" % n),
                             light.export_envmap(return_img=True).permute(2, 0, 1).clamp(min=0.0, max=1.0))
-                           for n, light in zip(chunk_names, chunk)])
-                rays = None
-                for ci in infos:
-                    c = dr.camera_from_info(ci, args.resolution, device=dev)
-                    if rays is None:
-                        rays = pipeline.canonical_rays(c, dev)
-                    o = mr(c, g, pipeline.view_dirs_for(c, rays, dev), alpha_mask=c["gt_alpha_mask"], albedo_ratio=ratio)
-                    paths = view_paths(out, split, iteration, ci.image_name, chunk_names)
-                    images = []
-                    for k in range(len(chunk)):
-                        images.append((paths[2 * k], o["render_rgb"][k]))
-                        images.append((paths[2 * k + 1], o["occlusion"]))
-                    wr.submit(images)
-                    if ev is not None:
-                        gt = [_read_gt(os.path.join(args.gt_dir, n, ci.image_name + ".png"), dev) for n in chunk_names]
-                        ev.add(o["render_rgb"], torch.stack(gt))
+                           for n, light in zip(names[first:first + MAX_LIGHTS], lights[first:first + MAX_LIGHTS])])
+            rays = None
+            for ci in infos:
+                c = dr.camera_from_info(ci, args.resolution, device=dev)
+                if rays is None:
+                    rays = pipeline.canonical_rays(c, dev)
+                o = tr(c, g, pipeline.view_dirs_for(c, rays, dev), alpha_mask=c["gt_alpha_mask"], albedo_ratio=ratio)
+                paths = view_paths(out, split, iteration, ci.image_name, names)
+                images = []
+                for k in range(len(lights)):
+                    images.append((paths[2 * k], o["render_rgb"][k]))
+                    images.append((paths[2 * k + 1], o["occlusion"]))
+                for first in range(0, len(images), 2 * MAX_LIGHTS):
+                    wr.submit(images[first:first + 2 * MAX_LIGHTS])
                 if ev is not None:
-                    for n, m in ev.results().items():
-                        m = {k: v for k, v in m.items() if k != "n_views"}
-                        path = os.path.join(rs.split_dir(out, split, iteration), "relight", n + ".json")
-                        with open(path, "w") as f:
-                            json.dump(m, f, indent=4)
-                        res.setdefault("metrics", {})[n] = m
-            finally:
-                mr.close()
+                    gt = [_read_gt(os.path.join(args.gt_dir, n, ci.image_name + ".png"), dev) for n in names]
+                    ev.add(o["render_rgb"], torch.stack(gt))
+            if ev is not None:
+                for n, m in ev.results().items():
+                    m = {k: v for k, v in m.items() if k != "n_views"}
+                    path = os.path.join(rs.split_dir(out, split, iteration), "relight", n + ".json")
+                    with open(path, "w") as f:
+                        json.dump(m, f, indent=4)
+                    res.setdefault("metrics", {})[n] = m
+        finally:
+            tr.close()
     res.update(files=wr.files, png_bytes=wr.bytes_written, submit_blocked_s=round(wr.blocked_s, 4),
                total_s=round(time.perf_counter() - t0, 4))
     return res
@@ -157,7 +181,9 @@ def relight_scene(args) -> Dict[str, Dict]:
     import image_writer
     import pipeline
     import relight
-    args = rs.combine_args(rs.as_namespace(args, parse_args))
+    args = rs.as_namespace(args, parse_args)
+    n_rot = check_rotations(args)  # before anything is read
+    args = rs.combine_args(args)
     if not args.hdri:
         raise ValueError("--hdri: at least one environment map is required")
     if not torch.cuda.is_available():
@@ -170,7 +196,13 @@ def relight_scene(args) -> Dict[str, Dict]:
     args.source_path = os.path.abspath(args.source_path)
     g, sh_degree, ck, cams = rs.load_trained(args, dev)
     iteration = int(ck["iteration"])
-    lights = [relight.make_light(torch.from_numpy(image_writer.load_latlong(p)).to(dev), res=256) for p in hdris]
+    maps = [torch.from_numpy(image_writer.load_latlong(p)).to(dev) for p in hdris]
+    if n_rot:
+        turns = relight.yaw_rotations(n_rot, args.rotation_axis or (0.0, 1.0, 0.0))
+        lights = [light for m in maps for light in relight.rotated_lights(m, turns, res=256)]
+        names = rotated_names(names, n_rot)
+    else:
+        lights = [relight.make_light(m, res=256) for m in maps]
     ratio = None
     ratio_path = os.path.join(rs.split_dir(args.model_path, "test", iteration), "pbr", "albedo_ratio.json")
     if os.path.exists(ratio_path):

@@ -217,6 +217,19 @@ int gigs_ssr_multi(gigs_ctx* ctx, int n_lights, int width, int height, float foc
                    const float* albedo, const float* roughness, const float* metallic, const float* F0, float* color,
                    float* abd, void* scratch, void* stream);
 
+/* gigs_ssr_apply for K radiance planes (gigs-hip extension; one view under many lights, relight.TurntableRelighter): rgb,
+ * color and abd are [K,3,H,W], everything else as in gigs_ssr_apply.  The list is walked once per pass of up to 8 planes:
+ * the pass first packs its planes pixel-major into `scratch` (gigs_ssr_apply_multi_scratch_bytes(K, width, height) bytes,
+ * 16-byte aligned, used during the call's kernels only; may be NULL for K = 1), so that a hit is a few adjacent 16-byte
+ * loads for all its lights; each hit entry and its ray weights are read once per pass, and every light keeps its own sums
+ * in gigs_ssr_apply's order.  color[k] / abd[k] equal gigs_ssr_apply with rgb = rgb[k] bit for bit, hence gigs_ssr_ex /
+ * gigs_ssr_multi for the geometry the list was recorded with.  `offsets` must be 16-byte aligned and the list complete
+ * (offsets[4 N] <= the capacity it was filled with: the caller's check).  1 <= K <= GIGS_MAX_LIGHTS, else GIGS_ERR_INVALID. */
+size_t gigs_ssr_apply_multi_scratch_bytes(int n_lights, int width, int height);
+int gigs_ssr_apply_multi(int n_lights, int width, int height, float delta, const unsigned* offsets, const void* entries,
+                         const float* normal_view, const float* pos, const float* rgb, const float* albedo,
+                         const float* metallic, const float* F0, float* color, float* abd, void* scratch, void* stream);
+
 /* kornia.filters.median_blur(x[None], (3,3))[0] as called at
  * R/diff_gaussian_rasterization/__init__.py:478, 504 (zero padding, NaN-propagating). */
 int gigs_median3x3(int channels, int height, int width, const float* in, float* out, void* stream);
@@ -457,12 +470,26 @@ int gigs_stage2_loss_fwd_grad(int height, int width, const float* render_direct,
  * The backward accumulates into d_cubemap [6,res,res,3] (caller zeroes); directions get no gradient. */
 int gigs_cube_texture_fwd(int res, const float* cubemap, int n, const float* dirs, float* out, int planar,
                           void* stream);
+/* gigs_cube_texture_fwd (out [n,3]) with the texel coordinates and weights formed in double (gigs-hip extension; resampling
+ * a light onto another cube grid, relight.rotate_light): the float lookup's coordinate error grows with res (half an ulp of
+ * u * res - 0.5: 1.9e-6 texels at res 64, 7.6e-6 at 256) and a resample would write it into every texel.  Same faces and taps;
+ * forward only. */
+int gigs_cube_texture_fwd_precise(int res, const float* cubemap, int n, const float* dirs, float* out, void* stream);
 /* latlong_to_cubemap (relight.py:92-111): cubemap [6,res_y,res_x,C] from an equirectangular map [lat_h,lat_w,C]:
  * texel direction = normalize(cube_to_dir(face, linspace(-1+1/res, 1-1/res))), tu = atan2(x,-z)/(2pi)+0.5,
  * tv = acos(clamp(y))/pi, then the 2D lookup dr.texture(latlong, (tu,tv), filter_mode="linear") -- nvdiffrast
  * (third party, absent): bilinear, texel centres at (i+0.5)/size, boundary_mode "wrap".  PARITY UNPINNED. */
 int gigs_latlong_to_cubemap(int res_y, int res_x, int lat_h, int lat_w, int channels, const float* latlong,
                             float* cubemap, void* stream);
+/* The same conversion for n_rot rotations of the map in one launch (gigs-hip extension; turntables): rotations is
+ * [n_rot,3,3] row-major on the device, R right-handed in the cube / latitude-longitude frame above (+y towards tv = 0),
+ * the rotated environment env_R(d) = env(R^T d); cubemap is [n_rot,6,res_y,res_x,C].  Per texel the expressions above with
+ * the normalised direction replaced by R^T dir (three multiply-adds per component, in column order); a matrix that is
+ * exactly the identity skips the product, so its slice equals gigs_latlong_to_cubemap bit for bit.  The result is the
+ * rotated BASE: pre-filter it like any other light (the reference's pre-filters are not rotation-covariant, DESIGN.md
+ * "Turntables").  1 <= n_rot <= 1024, else GIGS_ERR_INVALID. */
+int gigs_latlong_to_cubemap_rot(int res_y, int res_x, int lat_h, int lat_w, int channels, const float* latlong, int n_rot,
+                                const float* rotations, float* cubemap, void* stream);
 int gigs_cube_texture_bwd(int res, int n, const float* dirs, const float* g_out, float* d_cubemap, int planar,
                           void* stream);
 /* The lookup's backward as a gather, for a direction set that does not change between calls (the envmap TV's panorama grid).

@@ -1,0 +1,168 @@
+"""CPU: turntable relighting's host side -- the rotation helpers and their sign convention against the oracle's
+latitude-longitude conversion, relight_scene's --rotations flags and file table, the new entry points' declarations, and
+the new kernels' register budget as hipcc reports it."""
+import ctypes
+import os
+import re
+import subprocess
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import stage2_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("gigs_ssr_apply_multi", "gigs_ssr_apply_multi_scratch_bytes", "gigs_latlong_to_cubemap_rot",
+       "gigs_cube_texture_fwd_precise")
+_f32 = np.float32
+
+
+def rot_latlong_ref(latlong, res, R, dtype=np.float32):
+    """stage2_ref.latlong_to_cubemap with the normalised texel direction v replaced by R^T v (the row vector times R):
+    the cubemap of the environment env_R(d) = env(R^T d).  `dtype` is the precision of the direction arithmetic."""
+    latlong = np.ascontiguousarray(latlong, _f32)
+    R = np.asarray(R, dtype)
+    cube = np.zeros((6, res, res, latlong.shape[-1]), _f32)
+    lin = np.linspace(-1.0 + 1.0 / res, 1.0 - 1.0 / res, res, dtype=_f32)
+    gy, gx = np.meshgrid(lin, lin, indexing="ij")
+    for s in range(6):
+        v = stage2_ref.cube_to_dir(s, gx, gy).astype(dtype)
+        v = v / np.maximum(np.sqrt((v * v).sum(-1, keepdims=True, dtype=dtype)), dtype(1e-12))
+        v = (v[..., 0:1] * R[0] + v[..., 1:2] * R[1] + v[..., 2:3] * R[2]).astype(dtype)
+        tu = np.arctan2(v[..., 0:1], -v[..., 2:3]).astype(dtype) / dtype(2 * np.pi) + dtype(0.5)
+        tv = np.arccos(np.clip(v[..., 1:2], -1, 1)).astype(dtype) / dtype(np.pi)
+        cube[s] = stage2_ref.texture2d_linear_wrap(latlong, np.concatenate([tu, tv], -1).astype(_f32))
+    return cube
+
+
+def within_conversion_limits(got, ref):
+    """test_gpu_relight.py::test_latlong_to_cubemap_matches_oracle's limits -> (ok, mean, max)."""
+    d = np.abs(got - ref)
+    ok = d.mean() <= 1e-5 * max(1.0, float(np.abs(ref).mean())) and d.max() <= 2e-3 * float(np.abs(ref).max())
+    return ok, float(d.mean()), float(d.max())
+
+
+def test_rotation_about_is_a_right_handed_rotation():
+    import relight
+    for axis, angle in (((0, 1, 0), 0.7), ((1, 2, -0.5), 2.1), ((0, 0, 3), -4.0), ((1, 0, 0), np.pi / 2)):
+        r = relight.rotation_about(axis, angle).numpy()
+        assert r.dtype == np.float64 and r.shape == (3, 3)
+        assert np.abs(r @ r.T - np.eye(3)).max() <= 1e-14 and abs(np.linalg.det(r) - 1.0) <= 1e-14
+        a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+        assert np.abs(r @ a - a).max() <= 1e-14  # the axis stays
+        # right-handed: a vector perpendicular to the axis turns towards axis x vector for a small positive angle
+        perp = np.cross(a, [0.3, -0.2, 0.9])
+        assert np.dot(np.cross(perp, relight.rotation_about(axis, 1e-3).numpy() @ perp), a) > 0
+        assert abs(np.trace(r) - (1 + 2 * np.cos(angle))) <= 1e-14
+    assert torch.equal(relight.rotation_about((0, 1, 0), 0.0), torch.eye(3, dtype=torch.float64))
+    with pytest.raises(ValueError):
+        relight.rotation_about((0, 0, 0), 1.0)
+
+
+def test_yaw_rotations_quarter_turn_and_roll_anchor():
+    """yaw_rotations starts with the exact identity and takes equal steps; a quarter turn about +y is the signed
+    permutation x -> -z, z -> x.  Sign anchor: np.roll(latlong, +s, axis=1) is the rotation about +y by -2 pi s / W, checked
+    through the oracle's own conversion of the rolled map."""
+    import relight
+    rot = relight.yaw_rotations(4)
+    assert tuple(rot.shape) == (4, 3, 3) and torch.equal(rot[0], torch.eye(3, dtype=torch.float64))
+    assert torch.equal(rot[1], torch.tensor([[0, 0, 1], [0, 1, 0], [-1, 0, 0]], dtype=torch.float64))
+    assert torch.equal(rot[2], torch.tensor([[-1, 0, 0], [0, 1, 0], [0, 0, -1]], dtype=torch.float64))
+    assert not bool((rot == 0).logical_and(torch.signbit(rot)).any())  # no negative zeros
+    seven = relight.yaw_rotations(7)
+    assert (seven[3] - seven[1] @ seven[1] @ seven[1]).abs().max() <= 1e-14
+    assert torch.equal(relight.yaw_rotations(3, axis=(0, 0, 1))[1], relight.rotation_about((0, 0, 1), 2 * np.pi / 3))
+    with pytest.raises(ValueError):
+        relight.yaw_rotations(0)
+    import scenes
+    env = scenes.synthetic_envmap(32, 64, seed=3)
+    for s, res in ((7, 16), (-16, 16)):  # -16 = a quarter of the width: yaw_rotations(4)[1]
+        R = relight.rotation_about((0, 1, 0), -2 * np.pi * s / 64).numpy()
+        if s == -16:
+            assert np.array_equal(R, rot[1].numpy())
+        ok, mean, mx = within_conversion_limits(rot_latlong_ref(env, res, R.astype(_f32)),
+                                                stage2_ref.latlong_to_cubemap(np.roll(env, s, 1), [res, res]))
+        assert ok, (s, mean, mx)
+        wrong, _, _ = within_conversion_limits(rot_latlong_ref(env, res, R.T.astype(_f32)),
+                                               stage2_ref.latlong_to_cubemap(np.roll(env, s, 1), [res, res]))
+        assert not wrong, s  # the opposite turn is told apart
+
+
+def test_relight_scene_rotation_flags_and_file_table():
+    import relight_scene as rls
+    a = rls.parse_args(["--checkpoint", "x/chkpnt1.pth", "--hdri", "a.hdr"])
+    assert a.rotations == 0 and a.rotation_axis is None and rls.check_rotations(a) == 0
+    a = rls.parse_args(["--checkpoint", "x/chkpnt1.pth", "--hdri", "a.hdr", "--rotations", "12", "--rotation_axis", "0", "0", "1"])
+    assert a.rotations == 12 and a.rotation_axis == [0.0, 0.0, 1.0] and rls.check_rotations(a) == 12
+    assert rls.rotated_names(["a", "b"], 0) == ["a", "b"]
+    names = rls.rotated_names(["bridge", "city"], 3)
+    assert names == ["bridge_r000", "bridge_r001", "bridge_r002", "city_r000", "city_r001", "city_r002"]
+    assert rls.rotated_names(["m"], 1000)[-1] == "m_r999"
+    got = rls.planned_paths("out", "test", 30000, ["r_0", "r_1"], names)
+    base = os.path.join("out", "test", "ours_30000", "relight")
+    assert len(got) == len(set(got)) == 6 + 2 * 6 * 2
+    assert got[0] == os.path.join("out", "test", "envmap_relight_bridge_r000.png")
+    assert os.path.join(base, "r_1_city_r002.png") in got and os.path.join(base, "r_0_bridge_r001_occlusion.png") in got
+    # --rotations with --gt_dir is refused up front: before the checkpoint, the maps or the GPU are touched
+    bad = ["--checkpoint", "nowhere/chkpnt1.pth", "--hdri", "a.hdr", "--rotations", "3", "--gt_dir", "gt"]
+    with pytest.raises(ValueError, match="rotated maps"):
+        rls.check_rotations(rls.parse_args(bad))
+    with pytest.raises(ValueError, match="rotated maps"):
+        rls.relight_scene(bad)
+    with pytest.raises(ValueError, match="--rotations"):
+        rls.relight_scene(["--checkpoint", "nowhere/chkpnt1.pth", "--hdri", "a.hdr", "--rotations", "-2"])
+
+
+def test_turntable_entries_declared_and_exported():
+    import gigs_lib
+    import relight
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gigs_hip.h")).read(), flags=re.S)
+    lib = ctypes.CDLL(gigs_lib.LIB_PATH)
+    for name in NEW:
+        assert re.search(r"\b%s\s*\(" % name, hdr), name
+        assert name in gigs_lib.SIGNATURES, name
+        assert hasattr(lib, name), name
+    for name in ("TurntableRelighter", "rotated_lights", "rotate_light", "rotation_about", "yaw_rotations"):
+        assert hasattr(relight, name), name
+    assert "low-pass" in relight.rotate_light.__doc__.lower()  # the docstring owns up to the resample
+    from pbr import CubemapLight
+    a, b = CubemapLight(base_res=16, device="cpu"), CubemapLight(base_res=32, device="cpu")
+    with pytest.raises(ValueError, match="resolution"):
+        relight.TurntableRelighter([a, b], {}, 2)
+    with pytest.raises(ValueError):
+        relight.TurntableRelighter([], {}, 2)
+    assert not hasattr(a, "specular")  # refused before any mips were built
+
+
+def test_new_kernels_compile_for_gfx950_without_scratch(tmp_path):
+    """gi-gs_amd/build.py's compiler and flags on the two sources that gained kernels: every instance of the hit-list
+    gather (the single-light one included) and the rotated conversion use no scratch memory."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gigs_build", os.path.join(ROOT, "gi-gs_amd", "build.py"))
+    bld = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bld)
+    assert "--offload-arch=gfx950" in bld.FLAGS and "gi.hip" in bld.SOURCES and "pbr.hip" in bld.SOURCES
+
+    def compile_one(src):
+        cmd = [bld.HIPCC, *bld.FLAGS, "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+               os.path.join(bld.CSRC, src), "-o", str(tmp_path / (src + ".out"))]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return r.stderr
+
+    with ThreadPoolExecutor(max_workers=2) as ex:
+        log = "\n".join(ex.map(compile_one, ["gi.hip", "pbr.hip"]))
+    found = {}
+    for block in re.split(r"(?=remark: [^\n]*Function Name:)", log):
+        m = re.search(r"Function Name: (\S+)", block)
+        s = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", block)
+        if m and s and any(k in m.group(1) for k in ("ssr_apply_kernel", "ssr_pack_kernel", "latlong_to_cubemap_rot_kernel",
+                                                        "cube_texture_fwd_precise_kernel")):
+            found[m.group(1)] = int(s.group(1))
+    lights = sorted(int(re.search(r"ssr_apply_kernelILi(\d+)E", k).group(1)) for k in found if "ssr_apply_kernel" in k)
+    assert lights[:4] == [1, 2, 3, 4] and 1 < max(lights) <= 16, found
+    assert any("latlong_to_cubemap_rot_kernel" in k for k in found) and any("ssr_pack_kernel" in k for k in found), found
+    assert any("cube_texture_fwd_precise_kernel" in k for k in found), found
+    assert all(v == 0 for v in found.values()), found
