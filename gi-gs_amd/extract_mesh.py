@@ -1,0 +1,115 @@
+"""A trained scene on disk as a triangle mesh with its recovered materials (mesh.py): the views of a split are rendered,
+their depth and material planes fused into a truncated signed distance volume, and the zero level set written as a PLY
+(scene_io.save_mesh_ply: position, world normal, albedo as colour, roughness, metallic per vertex).
+
+    python gi-gs_amd/extract_mesh.py -m <out> --checkpoint <out>/chkpntN.pth [--grid 256] [--bounds x0 y0 z0 x1 y1 z1]
+                                     [--trunc_voxels 4] [--min_weight 2] [--opacity_min 0.5] [--no_carve]
+                                     [--split train] -o mesh.ply                                            (CLI)
+    extract_mesh(args) -> {...}                                                                            (API)
+
+The scene path, the SH degree and the resolution come from <out>/cfg_args as in render_scene.py, command-line values
+first.  --grid is the number of samples along the longest axis of the box; without --bounds the box is
+mesh.auto_bounds of the Gaussians.  A relative -o lands in <out>.  Prints the counts of views, samples, vertices and
+faces and the time of each phase.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+from argparse import Namespace
+from typing import Dict, List, Optional
+
+if __package__ in (None, ""):  # run as a script: make the package's modules importable
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_parser() -> argparse.ArgumentParser:
+    import render_scene
+    p = argparse.ArgumentParser(description="Mesh extraction parameters")
+    render_scene.add_model_arguments(p)
+    p.add_argument("--checkpoint", type=str, default=None, help="The path to the checkpoint to load.")
+    for k, v in render_scene.GI_FLAGS.items():
+        p.add_argument("--" + k, type=type(v), default=v)
+    p.add_argument("--grid", type=int, default=256, help="samples along the longest axis of the box")
+    p.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    p.add_argument("--trunc_voxels", type=float, default=4.0, help="truncation distance in voxels")
+    p.add_argument("--min_weight", type=float, default=2.0, help="views a sample needs to take part in the mesh")
+    p.add_argument("--opacity_min", type=float, default=0.5, help="pixels below this opacity are background")
+    p.add_argument("--no_carve", action="store_true", help="background pixels leave their samples alone")
+    p.add_argument("--split", choices=("train", "test"), default="train")
+    p.add_argument("-o", "--output", type=str, default="mesh.ply")
+    return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> Namespace:
+    return build_parser().parse_args(argv)
+
+
+def extract_mesh(args) -> Dict:
+    """`args`: a Namespace from parse_args, a dict of overrides or an argv list."""
+    import torch
+
+    import dataset_readers as dr
+    import mesh
+    import pipeline
+    import render_scene
+    import scene_io
+    args = render_scene.combine_args(render_scene.as_namespace(args, parse_args))
+    if not torch.cuda.is_available():
+        raise RuntimeError("extract_mesh needs the GPU")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    args.source_path = os.path.abspath(args.source_path)
+    sync = torch.cuda.synchronize
+    t0 = time.perf_counter()
+    g, sh_degree, _, cams = render_scene.load_trained(args, dev)
+    infos = cams[args.split]
+    if not infos:
+        raise ValueError("extract_mesh: the %s split has no views" % args.split)
+    t1 = time.perf_counter()
+    try:
+        if args.bounds is not None:
+            lo, hi = args.bounds[:3], args.bounds[3:]
+        else:
+            lo, hi = mesh.auto_bounds(g)
+        voxel, dims = mesh.grid_for_bounds(lo, hi, args.grid)
+        vol = mesh.TSDFVolume(lo, voxel, dims, args.trunc_voxels * voxel, opacity_min=args.opacity_min,
+                              carve=not args.no_carve, device=dev)
+        gi = {k: getattr(args, k) for k in render_scene.GI_FLAGS}
+        views = [dr.camera_from_info(ci, args.resolution, device=dev) for ci in infos]
+        sync()
+        t2 = time.perf_counter()
+        mesh.fuse_views(g, sh_degree, views, gi, vol)
+        sync()
+        t3 = time.perf_counter()
+        m = vol.extract(args.min_weight)
+        sync()
+        t4 = time.perf_counter()
+        path = args.output if os.path.isabs(args.output) else os.path.join(args.model_path, args.output)
+        scene_io.save_mesh_ply(path, *m)
+        t5 = time.perf_counter()
+    finally:
+        pipeline._collect_idle()
+    return dict(path=path, views=len(views), samples=vol.n_samples, dims=list(dims), voxel=voxel,
+                lo=[float(v) for v in lo], hi=[float(v) for v in hi], vertices=int(m.vertices.shape[0]),
+                faces=int(m.faces.shape[0]), load_s=round(t1 - t0, 4), cameras_s=round(t2 - t1, 4),
+                fuse_s=round(t3 - t2, 4), extract_s=round(t4 - t3, 4), write_s=round(t5 - t4, 4))
+
+
+def main(argv=None) -> int:
+    res = extract_mesh(parse_args(argv))
+    print("views %d, samples %d (%d x %d x %d), vertices %d, faces %d" % (res["views"], res["samples"], *res["dims"],
+                                                                        res["vertices"], res["faces"]))
+    print("load %.3f s, cameras %.3f s, render + fuse %.3f s, extract %.3f s, write %.3f s" % (
+        res["load_s"], res["cameras_s"], res["fuse_s"], res["extract_s"], res["write_s"]))
+    print(json.dumps(res))
+    return 0
+
+
+if __name__ == "__main__":
+    import importlib
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    importlib.import_module("gi-gs_amd")
+    sys.exit(main())

@@ -128,6 +128,9 @@ SIGNATURES = {
     "gigs_pack_images": (_i, [_i, _f, C.c_void_p]),
     "gigs_plane_minmax": (_i, [C.c_longlong, _f, _f, _f, C.c_void_p]),
     "gigs_png_filter": (_i, [_i, _f, C.c_void_p]),
+    "gigs_tsdf_integrate": (_i, [C.c_void_p, _i, C.c_void_p, C.c_void_p]),
+    "gigs_mesh_count": (_i, [C.c_void_p, _fl, _f, _f, C.c_void_p]),
+    "gigs_mesh_write": (_i, [C.c_void_p, _fl, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_fwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_bwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_masked_l1_fwd": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
@@ -227,6 +230,22 @@ class FilterDesc(C.Structure):
                 ("reserved", C.c_int)]
 
 
+class TsdfGrid(C.Structure):
+    """gigs_tsdf_grid of include/gigs_hip.h."""
+    _fields_ = [("lo", C.c_float * 3), ("voxel", C.c_float), ("dims", C.c_int * 3), ("trunc", C.c_float),
+                ("opacity_min", C.c_float), ("carve", C.c_int), ("tsdf", C.c_void_p), ("weight", C.c_void_p),
+                ("attr_weight", C.c_void_p), ("attr", C.c_void_p)]
+
+
+class TsdfView(C.Structure):
+    """gigs_tsdf_view of include/gigs_hip.h."""
+    _fields_ = [("viewmatrix", C.c_float * 16), ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("width", C.c_int),
+                ("height", C.c_int), ("opacity", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p),
+                ("albedo", C.c_void_p), ("roughness", C.c_void_p), ("metallic", C.c_void_p)]
+
+
+TSDF_MAX_VIEWS = 8  # GIGS_TSDF_MAX_VIEWS
+TSDF_MAX_AXIS = 1024  # GIGS_TSDF_MAX_AXIS
 SPEC_SPARSE_STATE_INTS = 32  # GIGS_SPEC_SPARSE_STATE_INTS
 MAX_IMAGES = 4096  # GIGS_MAX_IMAGES
 MINMAX_SCRATCH_FLOATS = 512  # GIGS_MINMAX_SCRATCH_FLOATS

@@ -608,6 +608,57 @@ typedef struct gigs_filter_desc {
 int gigs_pack_images(int n, const gigs_pack_desc* desc, void* stream);
 int gigs_plane_minmax(long long count, const float* src, float* scratch, float* out2, void* stream);
 int gigs_png_filter(int n, const gigs_filter_desc* desc, void* stream);
+/* Meshes (gigs-hip extension; the device half of mesh.py): TSDF fusion of rendered planes into a volume, and naive
+ * surface nets on the volume.  The volume: samples s(i,j,k) = lo + (i,j,k) voxel, i < dims[0] (fastest), j < dims[1],
+ * k < dims[2], each axis 1..GIGS_TSDF_MAX_AXIS and fewer than 2^31 samples G; device arrays tsdf [G] (initially 1),
+ * weight [G] (0), attr_weight [G] (0) and attr [8][G] (0; planar: world normal xyz, albedo rgb, roughness, metallic), all
+ * fp32.  The two structures are HOST memory; the calls neither synchronise nor allocate.
+ * gigs_tsdf_integrate: applies n_views (0..GIGS_TSDF_MAX_VIEWS) views in order, one thread per sample, no atomics: the
+ *   result is deterministic, and n views in one call equal n calls of one view bit for bit.  Per sample and view, every
+ *   product and sum rounded on its own and IEEE division:
+ *     p = xform_point_4x3(s, viewmatrix) (the rasterizer's layout: m[0], m[4], m[8], m[12] make x);  p.z <= 0.2: skip
+ *     u = p.x / p.z * fx + (W - 1) / 2, v = p.y / p.z * fy + (H - 1) / 2 with fx = W / (2 tanfovx), fy = H / (2 tanfovy):
+ *       the pixel convention of the rasterizer's ndc2pix;  pixel (floor(u + 0.5), floor(v + 0.5)), outside the image: skip
+ *     O = opacity, D = depth at that pixel.  O < opacity_min is background: with carve the sample is free space (d = 1,
+ *       no attributes), without carve it is skipped.  Otherwise sdf = D - p.z; not sdf >= -trunc: skip;
+ *       d = min(1, sdf / trunc)
+ *     tsdf = (tsdf * weight + d) / (weight + 1), weight += 1; if not background and sdf <= trunc, each attribute the same
+ *       way with attr_weight, then attr_weight += 1
+ *   planes: opacity, depth, roughness, metallic [H,W]; normal, albedo [3,H,W].
+ * gigs_mesh_count: cell_flags [(dims[0]-1)(dims[1]-1)(dims[2]-1)] (x fastest) = 1 for an active cell (all eight samples
+ *   have weight >= min_weight and the signs of tsdf differ; tsdf < 0 is inside), else 0; sample_quads [G] = how many of a
+ *   sample's +x, +y, +z edges get a quad (ends differ in sign, the four cells around the edge exist and are valid).
+ *   Needs every axis >= 2.
+ * gigs_mesh_write: cell_offsets / quad_offsets = the exclusive prefix sums of those arrays.  One vertex per active cell,
+ *   vertex cell_offsets[cell]: position lo + (cell index + mean offset of the zero crossings f0 / (f0 - f1) on the cell's
+ *   edges whose ends differ in sign, the 12 edges in a fixed order) voxel; attributes = the sum over the same crossings'
+ *   endpoints of (interpolation weight) x (sample attribute) over the sum of the weights, where an endpoint with
+ *   attr_weight == 0 has weight 0 (no endpoint left: 0); the normal is normalised last, a zero normal stays zero.  Two
+ *   triangles (a fixed diagonal) per quad at faces[6 (quad_offsets[sample] + quads of lower axes)], counter-clockwise
+ *   as seen from the positive end.  vertices, normals, albedo [vertex_capacity,3], roughness, metallic
+ *   [vertex_capacity], faces [face_capacity,3] int32: an index outside a capacity sets *overflow (device int, cleared
+ *   by the caller) to 1 and stores nothing. */
+#define GIGS_TSDF_MAX_VIEWS 8
+#define GIGS_TSDF_MAX_AXIS 1024
+typedef struct gigs_tsdf_grid {
+  float lo[3];
+  float voxel;
+  int dims[3];
+  float trunc, opacity_min;
+  int carve;
+  float *tsdf, *weight, *attr_weight, *attr;
+} gigs_tsdf_grid;
+typedef struct gigs_tsdf_view {
+  float viewmatrix[16];
+  float tanfovx, tanfovy;
+  int width, height;
+  const float *opacity, *depth, *normal, *albedo, *roughness, *metallic;
+} gigs_tsdf_view;
+int gigs_tsdf_integrate(const gigs_tsdf_grid* grid, int n_views, const gigs_tsdf_view* views, void* stream);
+int gigs_mesh_count(const gigs_tsdf_grid* grid, float min_weight, int* cell_flags, int* sample_quads, void* stream);
+int gigs_mesh_write(const gigs_tsdf_grid* grid, float min_weight, const int* cell_offsets, const int* quad_offsets,
+                    int vertex_capacity, int face_capacity, float* vertices, float* normals, float* albedo, float* roughness,
+                    float* metallic, int* faces, int* overflow, void* stream);
 int gigs_tv_loss_fwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
                      const float* mask_f, float* scratch, float* loss, void* stream);
 int gigs_tv_loss_bwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
