@@ -1268,9 +1268,9 @@ struct ShadePix {
   bool has_d, has0, has1;
 };
 
-__device__ __forceinline__ void shade_pixel(const ShadeArgs& A, int p, ShadePix& q) {
+// n: the shading normal of pixel p (A.normals' value, or the one the caller has just formed in registers)
+__device__ __forceinline__ void shade_pixel_n(const ShadeArgs& A, int p, v3 n, ShadePix& q) {
   const size_t e = (size_t)p * A.ps, cs = A.cs;
-  const v3 n = {A.normals[e], A.normals[e + cs], A.normals[e + 2 * cs]};
   const v3 v = {A.view_dirs[3 * p], A.view_dirs[3 * p + 1], A.view_dirs[3 * p + 2]};
   q.a = {A.albedo[e], A.albedo[e + cs], A.albedo[e + 2 * cs]};
   q.r = A.roughness[p] * A.rough_scale + A.rough_bias;  // scale 1, bias 0 (exact) unless the caller fuses the remap
@@ -1329,12 +1329,13 @@ __device__ __forceinline__ void shade_pixel(const ShadeArgs& A, int p, ShadePix&
   q.srgb = {q.sp.x * q.refl.x, q.sp.y * q.refl.y, q.sp.z * q.refl.z};
 }
 
-__global__ void __launch_bounds__(256)
-shade_fwd_kernel(ShadeArgs A) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= A.H * A.W) return;
-  ShadePix q;
-  shade_pixel(A, p, q);
+__device__ __forceinline__ void shade_pixel(const ShadeArgs& A, int p, ShadePix& q) {
+  const size_t e = (size_t)p * A.ps, cs = A.cs;
+  shade_pixel_n(A, p, {A.normals[e], A.normals[e + cs], A.normals[e + 2 * cs]}, q);
+}
+
+// the forward's epilogue: tone map / gamma, mask, every output plane (mk: the pixel's normal mask)
+__device__ __forceinline__ void shade_fwd_store(const ShadeArgs& A, int p, const ShadePix& q, bool mk) {
   float rr[3] = {q.drgb.x + q.srgb.x, q.drgb.y + q.srgb.y, q.drgb.z + q.srgb.z};
   float dd;
 #pragma unroll
@@ -1350,7 +1351,6 @@ shade_fwd_kernel(ShadeArgs A) {
     drgb = {lin2srgb(drgb.x, dd), lin2srgb(drgb.y, dd), lin2srgb(drgb.z, dd)};
     srgb = {lin2srgb(srgb.x, dd), lin2srgb(srgb.y, dd), lin2srgb(srgb.z, dd)};
   }
-  const bool mk = A.mask[p] != 0;
   const size_t e = (size_t)p * A.ps, cs = A.cs;
 #pragma unroll
   for (int c = 0; c < 3; c++) {
@@ -1366,6 +1366,84 @@ shade_fwd_kernel(ShadeArgs A) {
     for (int c = 0; c < 3; c++) A.out_linear[e + c * cs] = srgb2lin(rr[c]);
   }
   if (A.out_roughness) A.out_roughness[p] = q.r;
+}
+
+__global__ void __launch_bounds__(256)
+shade_fwd_kernel(ShadeArgs A) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= A.H * A.W) return;
+  ShadePix q;
+  shade_pixel(A, p, q);
+  shade_fwd_store(A, p, q, A.mask[p] != 0);
+}
+
+// gigs_shade_fwd_post: the G-buffer post-processing of stage2.hip's gbuffer_post_kernel<false> and shade_fwd_kernel in one
+// launch (planar layout).  A workgroup (64 x 4 pixels) stages normalize_where(normal_map) and
+// normalize_where(out_normal_view) for its tile and a 1-pixel halo in LDS -- each tap normalised once, not once per
+// window it belongs to; padding taps are zero --, every lane forms its six medians, the rotation and the mask from
+// there in gbuffer_post_kernel's expressions, stores normals_view / mask / onv (the backward and SSR read them) and
+// shades its pixel from the normal and the mask it holds in registers.
+struct ShadePostArgs {
+  const float *normal_map, *out_normal_view, *vm;
+  float* normals_view;
+  uint8_t* mask_u8;
+  float *mask_f, *onv;
+};
+constexpr int kPostW = 64, kPostH = 4;
+
+__global__ void __launch_bounds__(256)
+shade_fwd_post_kernel(ShadeArgs A, ShadePostArgs P) {
+  __shared__ float s_n[2][3][kPostH + 2][kPostW + 2];
+  const int H = A.H, W = A.W;
+  const size_t HW = (size_t)H * W;
+  constexpr int kHalo = (kPostH + 2) * (kPostW + 2);
+  for (int i = threadIdx.x; i < 2 * kHalo; i += 256) {
+    const int m = i / kHalo, r = i - m * kHalo;
+    const int ty = r / (kPostW + 2), tx = r - ty * (kPostW + 2);
+    const int yy = (int)blockIdx.y * kPostH - 1 + ty, xx = (int)blockIdx.x * kPostW - 1 + tx;
+    v3 v = {0.0f, 0.0f, 0.0f};
+    if (!(yy < 0 || yy >= H || xx < 0 || xx >= W)) {
+      const float* src = m ? P.out_normal_view : P.normal_map;
+      const size_t t = (size_t)yy * W + xx;
+      v = normalize_where({src[t], src[HW + t], src[2 * HW + t]});
+    }
+    s_n[m][0][ty][tx] = v.x; s_n[m][1][ty][tx] = v.y; s_n[m][2][ty][tx] = v.z;
+  }
+  __syncthreads();
+  const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
+  const int x = blockIdx.x * kPostW + lx, y = blockIdx.y * kPostH + ly;
+  if (x >= W || y >= H) return;
+  const int p = y * W + x;
+  const bool mk = P.normal_map[p] != 0.0f && P.normal_map[HW + p] != 0.0f && P.normal_map[2 * HW + p] != 0.0f;
+  P.mask_u8[p] = mk ? 1 : 0;
+  if (P.mask_f) P.mask_f[p] = mk ? 1.0f : 0.0f;
+  float med[2][3];
+#pragma unroll
+  for (int m = 0; m < 2; m++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      float t[9];
+      bool has_nan = false;
+      int k = 0;
+#pragma unroll
+      for (int dy = 0; dy <= 2; dy++)
+#pragma unroll
+        for (int dx = 0; dx <= 2; dx++, k++) {
+          t[k] = s_n[m][c][ly + dy][lx + dx];
+          has_nan |= t[k] != t[k];
+        }
+      med[m][c] = has_nan ? __builtin_nanf("") : median9(t);  // NaN window -> NaN (median_of_normalized)
+    }
+  // -(n @ R), R = viewmatrix[:3, :3] of the row-major 4x4 tensor
+  const float* vm = P.vm;
+  const v3 n = {-(med[0][0] * vm[0] + med[0][1] * vm[4] + med[0][2] * vm[8]),
+                -(med[0][0] * vm[1] + med[0][1] * vm[5] + med[0][2] * vm[9]),
+                -(med[0][0] * vm[2] + med[0][1] * vm[6] + med[0][2] * vm[10])};
+  P.normals_view[p] = n.x; P.normals_view[HW + p] = n.y; P.normals_view[2 * HW + p] = n.z;
+  P.onv[p] = med[1][0]; P.onv[HW + p] = med[1][1]; P.onv[2 * HW + p] = med[1][2];
+  ShadePix q;
+  shade_pixel_n(A, p, n, q);
+  shade_fwd_store(A, p, q, mk);
 }
 
 // gigs_shade_fwd_multi: the planar forward under K lights.  shade_pixel runs once, with light 0; for every further light
@@ -2181,6 +2259,34 @@ int gigs_shade_fwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
   A.render_rgb = render_rgb; A.diffuse_rgb = diffuse_rgb; A.specular_rgb = specular_rgb; A.diffuse_light = diffuse_light;
   void* tok; gigs_internal_stage_begin(14, stream, &tok);
   hipLaunchKernelGGL(gigs::shade_fwd_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, A);
+  gigs_internal_stage_end(tok);
+  PBR_CHECK_LAUNCH();
+  return 0;
+}
+
+int gigs_shade_fwd_post(gigs_ctx* ctx, int H, int W, const float* normal_map, const float* out_normal_view,
+                        const float* viewmatrix, float* normals_view, uint8_t* normal_mask, float* normal_mask_f,
+                        float* out_normal_view_filtered, const float* view_dirs, const float* albedo,
+                        const float* roughness, const float* occlusion, const float* metallic, const float* diffuse,
+                        int diffuse_res, int n_levels, const float* const* spec, const int* spec_res, const float* lut,
+                        int lut_w, int lut_h, int tone, int gamma, float* render_rgb, const gigs_shade_ext* ext,
+                        void* stream) {
+  (void)ctx;
+  if (!normal_map || !out_normal_view || !viewmatrix || !normals_view || !normal_mask || !out_normal_view_filtered)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "shade_fwd_post: bad argument");
+  if (!ext || !ext->planar) return gigs_internal_fail(GIGS_ERR_INVALID, "shade_fwd_post: needs the planar layout (ext->planar)");
+  gigs::ShadeArgs A;
+  const int rc = fill_shade(A, H, W, normals_view, view_dirs, albedo, roughness, normal_mask, occlusion, metallic, nullptr,
+                            diffuse, diffuse_res, n_levels, spec, spec_res, lut, lut_w, lut_h, tone, gamma);
+  if (rc) return rc;
+  if (!render_rgb) return gigs_internal_fail(GIGS_ERR_INVALID, "shade_fwd_post: null output");
+  if (apply_shade_ext(A, ext, false)) return GIGS_ERR_INVALID;
+  A.render_rgb = render_rgb;
+  const gigs::ShadePostArgs P{normal_map, out_normal_view, viewmatrix, normals_view, normal_mask, normal_mask_f,
+                              out_normal_view_filtered};
+  void* tok; gigs_internal_stage_begin(14, stream, &tok);
+  hipLaunchKernelGGL(gigs::shade_fwd_post_kernel, dim3((W + gigs::kPostW - 1) / gigs::kPostW, (H + gigs::kPostH - 1) / gigs::kPostH),
+                     dim3(256), 0, (hipStream_t)stream, A, P);
   gigs_internal_stage_end(tok);
   PBR_CHECK_LAUNCH();
   return 0;

@@ -21,6 +21,15 @@ __device__ __forceinline__ float median9(float* v) {
   return v[4];
 }
 
+// F.normalize(v, dim=0) where |v| > 0, v itself otherwise (gaussian_renderer/__init__.py:160-163, 191-194);
+// a NaN vector stays NaN (|v| > 0 is false).
+__device__ __forceinline__ v3 normalize_where(v3 v) {
+  const float n = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);
+  if (!(n > 0.0f)) return v;
+  const float d = fmaxf(n, 1e-12f);
+  return {v.x / d, v.y / d, v.z / d};
+}
+
 // linear -> sRGB and its derivative (train.py:54-68 / pbr/shade.py:50-63)
 __device__ __forceinline__ float lin2srgb(float x, float& d) {  // pbr/shade.py:50-63
   const float eps = 1.1920929e-07f;

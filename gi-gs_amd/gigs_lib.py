@@ -95,6 +95,8 @@ SIGNATURES = {
                             C.POINTER(C.c_void_p), C.c_void_p]),
     "gigs_shade_fwd_ex": (_i, [C.c_void_p, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int), _f, _i, _i, _i, _i, _f, _f, _f, _f, C.c_void_p, C.c_void_p]),
+    "gigs_shade_fwd_post": (_i, [C.c_void_p, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i,
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int), _f, _i, _i, _i, _i, _f, C.c_void_p, C.c_void_p]),
     "gigs_shade_fwd_multi": (_i, [C.c_void_p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, C.POINTER(C.c_void_p), _i, _i,
                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int), _f, _i, _i, _i, _i, _f, _f, C.c_void_p]),
     "gigs_shade_bwd_ex": (_i, [C.c_void_p, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, C.POINTER(C.c_void_p),
@@ -108,6 +110,8 @@ SIGNATURES = {
     "gigs_stage2_loss_fwd": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_stage2_loss_bwd": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_stage2_loss_fwd_grad": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_stage2_loss_gather_scratch_bytes": (C.c_size_t, [_i, _i]),
+    "gigs_stage2_loss_gather": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_size_t, C.c_void_p]),
     "gigs_cube_texture_fwd": (_i, [_i, _f, _i, _f, _f, _i, C.c_void_p]),
     "gigs_cube_texture_fwd_precise": (_i, [_i, _f, _i, _f, _f, C.c_void_p]),
     "gigs_cube_texture_bwd": (_i, [_i, _i, _f, _f, _f, _i, C.c_void_p]),

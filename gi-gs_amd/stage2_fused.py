@@ -2,8 +2,8 @@
 
 The reference expresses this stretch of train.py (:293-402) as ~120 torch ops forward and as many
 backward; `pipeline.Stage2Front` / `pipeline.stage2_loss` restate it op by op.  Here the same
-arithmetic runs as five kernels forward (gigs_gbuffer_post, gigs_shade_fwd_ex, gigs_ssr,
-gigs_stage2_loss_fwd_grad + its 1-thread finish) and ONE backward (gigs_shade_bwd_ex: the loss's
+arithmetic runs as four kernels forward (gigs_shade_fwd_post: the G-buffer post-processing inside the
+shade; gigs_ssr; gigs_stage2_loss_gather + its finish) and ONE backward (gigs_shade_bwd_ex: the loss's
 gradient planes are written by the forward pass for a unit upstream gradient and scaled there),
 all reading and writing the rasterizer's [C,H,W] planes directly.
 
@@ -15,6 +15,7 @@ tests/test_gpu_pbr.py::test_stage2_fused_matches_unfused compares the two formul
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict
 
 import torch
@@ -32,6 +33,11 @@ def _p(t):
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _switch(name: str) -> bool:
+    """A/B switch of the node: "0" goes back to the previous kernel sequence."""
+    return os.environ.get(name, "1") == "1"
 
 
 class _Stage2Fused(torch.autograd.Function):
@@ -67,13 +73,21 @@ class _Stage2Fused(torch.autograd.Function):
         gi = cfg["gi"]
         with torch.cuda.device(dev):
             s = _stream()
-            gigs_lib.check(_lib.gigs_gbuffer_post(H, W, _p(normal_map), _p(out_normal_view), _p(viewmatrix),
-                                                  _p(normals_view), _p(mask_u8), _p(mask_f), _p(onv), s), "gbuffer_post")
-            gigs_lib.check(_lib.gigs_shade_fwd_ex(
-                gigs_lib.ctx_ptr(), H, W, _p(normals_view), _p(view_dirs), _p(albedo_map), _p(roughness_map), _p(mask_u8), _p(occlusion),
-                _p(metallic_map) if use_metallic else None, None, _p(diffuse), int(diffuse.shape[1]), len(specular),
-                spec_ptr, spec_res, _p(lut), int(lut.shape[-2]), int(lut.shape[-3]), int(bool(cfg["tone"])),
-                int(bool(cfg["gamma"])), _p(render_direct), None, None, None, C.addressof(ext), s), "shade_fwd_ex")
+            if _switch("GIGS_SHADE_POST_FUSED"):
+                gigs_lib.check(_lib.gigs_shade_fwd_post(
+                    gigs_lib.ctx_ptr(), H, W, _p(normal_map), _p(out_normal_view), _p(viewmatrix), _p(normals_view), _p(mask_u8),
+                    _p(mask_f), _p(onv), _p(view_dirs), _p(albedo_map), _p(roughness_map), _p(occlusion),
+                    _p(metallic_map) if use_metallic else None, _p(diffuse), int(diffuse.shape[1]), len(specular), spec_ptr,
+                    spec_res, _p(lut), int(lut.shape[-2]), int(lut.shape[-3]), int(bool(cfg["tone"])), int(bool(cfg["gamma"])),
+                    _p(render_direct), C.addressof(ext), s), "shade_fwd_post")
+            else:
+                gigs_lib.check(_lib.gigs_gbuffer_post(H, W, _p(normal_map), _p(out_normal_view), _p(viewmatrix),
+                                                      _p(normals_view), _p(mask_u8), _p(mask_f), _p(onv), s), "gbuffer_post")
+                gigs_lib.check(_lib.gigs_shade_fwd_ex(
+                    gigs_lib.ctx_ptr(), H, W, _p(normals_view), _p(view_dirs), _p(albedo_map), _p(roughness_map), _p(mask_u8), _p(occlusion),
+                    _p(metallic_map) if use_metallic else None, None, _p(diffuse), int(diffuse.shape[1]), len(specular),
+                    spec_ptr, spec_res, _p(lut), int(lut.shape[-2]), int(lut.shape[-3]), int(bool(cfg["tone"])),
+                    int(bool(cfg["gamma"])), _p(render_direct), None, None, None, C.addressof(ext), s), "shade_fwd_ex")
             metallic_f = metallic_map if use_metallic else torch.zeros_like(rough_f)
             # Gaussian_SSR (train.py:370-379); its backward is closed-form (grad_albedo = grad * abd)
             IRR, abd = _ops.SSR(W, H, cfg["focal_x"], cfg["focal_y"], gi["radius"], gi["bias"], gi["thick"], gi["delta"],
@@ -81,9 +95,17 @@ class _Stage2Fused(torch.autograd.Function):
             # the loss and, in the same pass over the image, its gradients w.r.t. render_direct / IRR for a unit upstream
             # gradient (the backward then has no loss kernel: gigs_shade_bwd_ex scales them and forms the lamb terms)
             d_direct_u, d_irr_u = new(3, H, W), new(3, H, W)
-            gigs_lib.check(_lib.gigs_stage2_loss_fwd_grad(H, W, _p(render_direct), _p(IRR), _p(gt_image), _p(mask_f),
-                                                          _p(rough_f), _p(metallic_f), _p(render_rgb), _p(acc4), _p(loss),
-                                                          _p(d_direct_u), _p(d_irr_u), s), "stage2_loss_fwd_grad")
+            if _switch("GIGS_STAGE2_GATHER"):
+                # gathered: no atomics, no cleared buffers; the workgroups' partial sums go through `rows`
+                rows = torch.empty(max(int(_lib.gigs_stage2_loss_gather_scratch_bytes(H, W)) // 4, 4), dtype=torch.float32, device=dev)
+                gigs_lib.check(_lib.gigs_stage2_loss_gather(H, W, _p(render_direct), _p(IRR), _p(gt_image), _p(mask_f),
+                                                            _p(rough_f), _p(metallic_f), _p(render_rgb), _p(acc4), _p(loss),
+                                                            _p(d_direct_u), _p(d_irr_u), _p(rows), rows.numel() * 4, s),
+                               "stage2_loss_gather")
+            else:
+                gigs_lib.check(_lib.gigs_stage2_loss_fwd_grad(H, W, _p(render_direct), _p(IRR), _p(gt_image), _p(mask_f),
+                                                              _p(rough_f), _p(metallic_f), _p(render_rgb), _p(acc4), _p(loss),
+                                                              _p(d_direct_u), _p(d_irr_u), s), "stage2_loss_fwd_grad")
         ctx.save_for_backward(normals_view, view_dirs, albedo_map, roughness_map, mask_u8, mask_f, occlusion,
                               metallic_map if use_metallic else None, lut, diffuse, d_direct_u, d_irr_u, abd,
                               acc4, *specular)

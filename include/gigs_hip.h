@@ -388,6 +388,19 @@ int gigs_shade_fwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
                       int n_levels, const float* const* spec, const int* spec_res, const float* lut,
                       int lut_w, int lut_h, int tone, int gamma, float* render_rgb, float* diffuse_rgb,
                       float* specular_rgb, float* diffuse_light, const gigs_shade_ext* ext, void* stream);
+/* gigs_gbuffer_post followed by gigs_shade_fwd_ex (planar layout: ext->planar must be 1; no background, render_rgb and the
+ * ext outputs only) as ONE launch (gigs-hip extension; the fused stage-2 node): a workgroup normalises its tile of
+ * normal_map / out_normal_view once into LDS, forms the medians, the rotation and the mask from there, stores
+ * normals_view, normal_mask (u8, required), normal_mask_f (may be NULL) and out_normal_view_filtered as
+ * gigs_gbuffer_post does, and shades each pixel from the normal and the mask it holds in registers.  Every output is bit
+ * for bit that of the two calls. */
+int gigs_shade_fwd_post(gigs_ctx* ctx, int H, int W, const float* normal_map, const float* out_normal_view,
+                        const float* viewmatrix, float* normals_view, uint8_t* normal_mask, float* normal_mask_f,
+                        float* out_normal_view_filtered, const float* view_dirs, const float* albedo,
+                        const float* roughness, const float* occlusion, const float* metallic, const float* diffuse,
+                        int diffuse_res, int n_levels, const float* const* spec, const int* spec_res, const float* lut,
+                        int lut_w, int lut_h, int tone, int gamma, float* render_rgb, const gigs_shade_ext* ext,
+                        void* stream);
 /* gigs_shade_fwd_ex in the planar layout (ext->planar = 1, rough_scale 1, bias 0, no background) under K lights at once
  * (gigs-hip extension): diffuse[k] is light k's diffuse map, spec[k * n_levels + l] its level l; all lights share
  * diffuse_res, n_levels and spec_res.  The light-independent terms (vectors, cube taps, BRDF LUT, mip level, F0) are
@@ -462,6 +475,22 @@ int gigs_stage2_loss_fwd_grad(int height, int width, const float* render_direct,
                               const float* gt_image, const float* normal_mask_f, const float* roughness,
                               const float* metallic, float* render_rgb, float* acc4, float* loss,
                               float* d_render_direct_unit, float* d_irr_linear_unit, void* stream);
+/* gigs_stage2_loss_fwd_grad without global atomics and without cleared buffers (the fused stage-2 node's loss): the
+ * median's gradient is GATHERED -- a workgroup evaluates median, sign and selected tap for its tile and the ring around
+ * it, and each texel of d_irr_linear_unit adds, in a fixed order, the terms of the neighbours that selected it and is
+ * written once (no zeroing; the same bits on every run).  render_rgb and d_render_direct_unit equal
+ * gigs_stage2_loss_fwd_grad's bit for bit, d_irr_linear_unit up to the order of a texel's <= 9 terms.  The four sums go
+ * through `scratch` (gigs_stage2_loss_gather_scratch_bytes(height, width) bytes, 16-byte aligned, need not be cleared),
+ * one row of doubles per workgroup (64 x 8 pixels), added in a fixed order: they are accumulated in double throughout and
+ * rounded to fp32 once.  acc4 here is the four totals only (4 floats), with gigs_stage2_loss_fwd's meaning; the loss is its
+ * formula evaluated in double on those sums and rounded once (it can differ from gigs_stage2_loss_fwd_grad's in the last
+ * bits: that entry adds in fp32 in the order its atomics arrive). */
+size_t gigs_stage2_loss_gather_scratch_bytes(int height, int width);
+int gigs_stage2_loss_gather(int height, int width, const float* render_direct, const float* irr_linear,
+                            const float* gt_image, const float* normal_mask_f, const float* roughness,
+                            const float* metallic, float* render_rgb, float* acc4, float* loss,
+                            float* d_render_direct_unit, float* d_irr_linear_unit, void* scratch, size_t scratch_bytes,
+                            void* stream);
 
 /* dr.texture(cubemap[None], dirs[None], filter_mode="linear", boundary_mode="cube") (train.py:409-417, render.py:80,
  * relight.py:108) for n directions [n,3], sampled as the shade kernel samples light.diffuse (face by largest |axis|,
