@@ -135,6 +135,11 @@ SIGNATURES = {
     "gigs_tsdf_integrate": (_i, [C.c_void_p, _i, C.c_void_p, C.c_void_p]),
     "gigs_mesh_count": (_i, [C.c_void_p, _fl, _f, _f, C.c_void_p]),
     "gigs_mesh_write": (_i, [C.c_void_p, _fl, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_project": (_i, [_i, _f, _f, _fl, _fl, _i, _i, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_raster_scratch_bytes": (C.c_size_t, [_i]),
+    "gigs_mesh_raster": (_i, [_i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, C.c_void_p]),
+    "gigs_mesh_resolve": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f,
+                               _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_fwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_bwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_masked_l1_fwd": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
@@ -250,6 +255,7 @@ class TsdfView(C.Structure):
 
 TSDF_MAX_VIEWS = 8  # GIGS_TSDF_MAX_VIEWS
 TSDF_MAX_AXIS = 1024  # GIGS_TSDF_MAX_AXIS
+MESH_SMALL_MAX = 64  # GIGS_MESH_SMALL_MAX
 SPEC_SPARSE_STATE_INTS = 32  # GIGS_SPEC_SPARSE_STATE_INTS
 MAX_IMAGES = 4096  # GIGS_MAX_IMAGES
 MINMAX_SCRATCH_FLOATS = 512  # GIGS_MINMAX_SCRATCH_FLOATS

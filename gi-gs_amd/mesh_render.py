@@ -1,0 +1,275 @@
+"""Rendering and relighting a triangle mesh with per-vertex materials (mesh.Mesh, the PLY of extract_mesh.py): a
+visibility-buffer rasterizer fills the G-buffer planes the blend kernel writes in inference mode, and the deferred chain
+behind them is the existing one, unchanged.
+
+    mesh_arrays(mesh)                 a mesh.Mesh, a dict of scene_io.read_mesh_ply or a path -> checked numpy arrays
+    MeshRasterizer(mesh)(cam)         gigs_mesh_project, gigs_mesh_raster, gigs_mesh_resolve -> opacity, depth, pos, normal,
+                                      normal_view, albedo, roughness, metallic ([C,H,W]) and tri_id [H,W] (-1 = background)
+    mesh_planes(rast, cam, gi)        those planes plus the derived normals (gigs_derive_normal) and SSAO with the GI
+                                      settings: the rasterizer's twelve outputs, by name
+    MeshRelighter / MeshMultiRelighter / MeshTurntableRelighter   relight.py's three relighters with the mesh in the place of
+                                      the Gaussians: rl(cam, rast, view_dirs).  Only the G-buffer differs; shade, SSR march,
+                                      sRGB / median finish and the reference's F0 quirk are the parents'
+
+The arithmetic is stated in include/gigs_hip.h and restated in numpy by tests/mesh_raster_ref.py.  There is no clipping:
+a triangle with a vertex behind the near cull (view z <= 0.2) or outside the guard band of 16384 pixels is dropped whole.
+There is no CPU path, and no hipGraph replay (relight.py's replay is keyed on the Gaussian tensors and asynchronous
+binning): graphs=True raises.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+import gigs_lib
+import relight
+from diff_gaussian_rasterization import _C as _ops, _derive_normal
+
+_lib = gigs_lib.lib()
+
+MESH_KEYS = ("vertices", "faces", "normals", "albedo", "roughness", "metallic")
+PLANES = {"opacity": 1, "depth": 1, "pos": 3, "normal": 3, "normal_view": 3, "albedo": 3, "roughness": 1, "metallic": 1}
+
+
+def mesh_arrays(mesh) -> Dict[str, np.ndarray]:
+    """{vertices [V,3], faces [F,3] int32, normals, albedo [V,3], roughness, metallic [V]} as contiguous numpy arrays, from a
+    mesh.Mesh (or any sequence in its field order), a dict with MESH_KEYS (scene_io.read_mesh_ply's) or the path of a PLY
+    written by scene_io.save_mesh_ply.  Face indices are NOT checked here: the kernels drop a face with a bad index."""
+    if isinstance(mesh, str):
+        import scene_io
+        mesh = scene_io.read_mesh_ply(mesh)
+    if not isinstance(mesh, dict):
+        mesh = dict(zip(MESH_KEYS, mesh))
+    missing = [k for k in MESH_KEYS if k not in mesh]
+    if missing:
+        raise ValueError("mesh_arrays: the mesh lacks %s" % ", ".join(missing))
+    a = {k: (mesh[k].detach().cpu().numpy() if isinstance(mesh[k], torch.Tensor) else np.asarray(mesh[k])) for k in MESH_KEYS}
+    out = {"faces": np.ascontiguousarray(a["faces"], dtype=np.int32).reshape(-1, 3)}
+    for k in ("vertices", "normals", "albedo"):
+        out[k] = np.ascontiguousarray(a[k], dtype=np.float32).reshape(-1, 3)
+    for k in ("roughness", "metallic"):
+        out[k] = np.ascontiguousarray(a[k], dtype=np.float32).reshape(-1)
+    V = out["vertices"].shape[0]
+    for k in ("normals", "albedo", "roughness", "metallic"):
+        if out[k].shape[0] != V:
+            raise ValueError("mesh_arrays: %s has %d rows for %d vertices" % (k, out[k].shape[0], V))
+    return out
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _p(t):
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+class MeshRasterizer:
+    """The mesh on the device and the scratch a view needs (projected vertices, the key plane, the list of large
+    triangles), reused from view to view.  small_max: the largest box, in pixels, a triangle's own thread walks (None =
+    gigs_lib.MESH_SMALL_MAX); the result does not depend on it."""
+
+    def __init__(self, mesh, device="cuda", small_max: Optional[int] = None):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("MeshRasterizer: the mesh must live on a CUDA/HIP device: gigs-hip has no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        arrays = mesh_arrays(mesh)
+        self.V, self.F = int(arrays["vertices"].shape[0]), int(arrays["faces"].shape[0])
+        self.small_max = small_max
+        self._mesh = {k: torch.from_numpy(v).to(self.device) for k, v in arrays.items()}
+        dev = self.device
+        self._view_pos = torch.empty((self.V, 3), dtype=torch.float32, device=dev)
+        self._screen = torch.empty((self.V, 2), dtype=torch.int32, device=dev)
+        self._flags = torch.empty((self.V,), dtype=torch.uint8, device=dev)
+        self._list = torch.empty(int(_lib.gigs_mesh_raster_scratch_bytes(self.F)), dtype=torch.uint8, device=dev)
+        self._vis = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        self._mesh = self._view_pos = self._screen = self._flags = self._list = self._vis = None
+
+    def _check(self):
+        if self._mesh is None:
+            raise RuntimeError("MeshRasterizer: closed")
+
+    @staticmethod
+    def _viewmatrix(cam, dev) -> torch.Tensor:
+        vm = cam["viewmatrix"]
+        vm = vm if isinstance(vm, torch.Tensor) else torch.as_tensor(np.asarray(vm, dtype=np.float32))
+        return vm.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+    def project(self, cam: Dict):
+        """gigs_mesh_project -> (view_pos [V,3], screen [V,2] int32, flags [V] uint8): the rasterizer's own buffers,
+        overwritten by the next view."""
+        self._check()
+        W, H = int(cam["image_width"]), int(cam["image_height"])
+        vm = self._viewmatrix(cam, self.device)
+        with torch.cuda.device(self.device):
+            gigs_lib.check(_lib.gigs_mesh_project(self.V, _p(self._mesh["vertices"]), vm.data_ptr(), float(cam["tanfovx"]),
+                                                  float(cam["tanfovy"]), W, H, _p(self._view_pos), _p(self._screen),
+                                                  _p(self._flags), _stream()), "mesh_project")
+        return self._view_pos, self._screen, self._flags
+
+    def raster(self, width: int, height: int, view_pos=None, screen=None, flags=None, small_max: Optional[int] = None,
+               faces=None) -> torch.Tensor:
+        """gigs_mesh_raster on the projected arrays (by default the last project()'s) -> the key plane [H,W] as int64 (the
+        kernel's uint64 bits; -1 = empty), overwritten by the next view."""
+        self._check()
+        W, H = int(width), int(height)
+        dev = self.device
+        view_pos = self._view_pos if view_pos is None else view_pos
+        screen = self._screen if screen is None else screen
+        flags = self._flags if flags is None else flags
+        faces = self._mesh["faces"] if faces is None else faces
+        F = int(faces.shape[0])
+        scratch = self._list
+        if F != self.F:
+            scratch = torch.empty(int(_lib.gigs_mesh_raster_scratch_bytes(F)), dtype=torch.uint8, device=dev)
+        if self._vis is None or tuple(self._vis.shape) != (H, W):
+            self._vis = torch.empty((H, W), dtype=torch.int64, device=dev)
+        sm = self.small_max if small_max is None else small_max
+        with torch.cuda.device(dev):
+            self._vis.fill_(-1)
+            gigs_lib.check(_lib.gigs_mesh_raster(int(flags.shape[0]), F, _p(faces), _p(view_pos), _p(screen), _p(flags), W, H,
+                                                 -1 if sm is None else int(sm), self._vis.data_ptr(), scratch.data_ptr(),
+                                                 _stream()), "mesh_raster")
+        return self._vis
+
+    def resolve(self, cam: Dict, vis: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """gigs_mesh_resolve of a key plane (by default the last raster()'s) with the last project()'s arrays -> fresh
+        planes."""
+        self._check()
+        W, H = int(cam["image_width"]), int(cam["image_height"])
+        dev = self.device
+        vis = self._vis if vis is None else vis
+        if vis is None or tuple(vis.shape) != (H, W):
+            raise ValueError("MeshRasterizer.resolve: no key plane of %d x %d" % (H, W))
+        vm = self._viewmatrix(cam, dev)
+        out = {k: torch.empty((c, H, W), dtype=torch.float32, device=dev) for k, c in PLANES.items()}
+        out["tri_id"] = torch.empty((H, W), dtype=torch.int32, device=dev)
+        m = self._mesh
+        with torch.cuda.device(dev):
+            gigs_lib.check(_lib.gigs_mesh_resolve(
+                self.V, self.F, _p(m["faces"]), _p(self._view_pos), _p(self._screen), _p(self._flags), _p(m["normals"]),
+                _p(m["albedo"]), _p(m["roughness"]), _p(m["metallic"]), vm.data_ptr(), W, H, vis.data_ptr(),
+                *(out[k].data_ptr() for k in PLANES), out["tri_id"].data_ptr(), _stream()), "mesh_resolve")
+        return out
+
+    @torch.no_grad()
+    def __call__(self, cam: Dict, small_max: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        self.project(cam)
+        self.raster(cam["image_width"], cam["image_height"], small_max=small_max)
+        return self.resolve(cam)
+
+
+@torch.no_grad()
+def mesh_planes(rast: MeshRasterizer, cam: Dict, gi: Dict) -> Dict[str, torch.Tensor]:
+    """What GaussianRasterizer.forward returns for the Gaussians (inference, derive_normal), for the mesh and by name:
+    the resolve's planes, normal_from_depth and depth_pos (gigs_derive_normal of the depth plane: 3x3 median, depth to
+    normal, bilateral filter, median of the positions) and occlusion (SSAO of normal_view over depth_pos)."""
+    W, H = int(cam["image_width"]), int(cam["image_height"])
+    if W < 2 or H < 2:
+        raise ValueError("mesh_planes: the derived normals need an image of at least 2 x 2")
+    o = rast(cam)
+    fx, fy = W / (2.0 * cam["tanfovx"]), H / (2.0 * cam["tanfovy"])
+    vm = rast._viewmatrix(cam, rast.device)
+    with torch.cuda.device(rast.device):
+        normal_from_depth, depth_pos = _derive_normal(W, H, fx, fy, vm, o["depth"])
+        occlusion = _ops.SSAO(W, H, fx, fy, gi["radius"], gi["bias"], gi["thick"], gi["delta"], gi["step"], gi["start"],
+                              o["normal_view"], depth_pos)
+    return dict(opacity_map=o["opacity"], depth_map=o["depth"], normal_map_from_depth=normal_from_depth,
+                normal_map=o["normal"], occlusion_map=occlusion, albedo_map=o["albedo"], roughness_map=o["roughness"],
+                metallic_map=o["metallic"], out_normal_view=o["normal_view"], depth_pos=depth_pos, pos=o["pos"],
+                tri_id=o["tri_id"], viewmatrix=vm)
+
+
+class _MeshView:
+    """The mesh in the place of the Gaussians: relight._ViewGraph._gbuffer over mesh_planes.  The parents hand their `g`
+    argument to _gbuffer and nowhere else (graphs off), so it is the MeshRasterizer; their `radii` entry is None and the
+    result gains tri_id, opacity_map, albedo_map, roughness_map and metallic_map."""
+
+    @staticmethod
+    def _no_graphs(graphs) -> None:
+        if graphs:
+            raise ValueError("mesh relighters replay no hipGraph (the replay is keyed on Gaussian tensors): graphs=False only")
+
+    def _gbuffer(self, cam, rast):
+        if not isinstance(rast, MeshRasterizer):
+            raise TypeError("%s: the second argument is a MeshRasterizer" % type(self).__name__)
+        r = mesh_planes(rast, cam, self.gi)
+        dev = rast.device
+        H, W = int(cam["image_height"]), int(cam["image_width"])
+        new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
+        normals_view, onv = new("normals_view", 3, H, W), new("onv", 3, H, W)
+        mask_u8 = self._buf("mask_u8", (H, W), torch.uint8, dev)
+        mask_f = new("mask_f", 1, H, W)
+        albedo_map, roughness_map, metallic_map = r["albedo_map"], r["roughness_map"], r["metallic_map"]
+        p = lambda t: t.data_ptr()  # noqa: E731
+        with torch.cuda.device(dev):
+            gigs_lib.check(_lib.gigs_gbuffer_post(H, W, p(r["normal_map"]), p(r["out_normal_view"]), p(r["viewmatrix"]),
+                                                  p(normals_view), p(mask_u8), p(mask_f), p(onv), _stream()), "gbuffer_post")
+            if self.metallic:  # relight.py:236-240, as written (see relight._ViewGraph._gbuffer)
+                F0 = torch.full_like(albedo_map, 0.04)
+                metallic_in = torch.zeros_like(roughness_map)
+            else:
+                F0 = torch.addcmul(torch.full_like(albedo_map, (1.0 - float(self.metallic)) * 0.04), albedo_map, metallic_map)
+                metallic_in = metallic_map
+        self._mesh_extra = dict(tri_id=r["tri_id"], opacity_map=r["opacity_map"], albedo_map=albedo_map,
+                                roughness_map=roughness_map, metallic_map=metallic_map)
+        return dict(radii=None, depth_map=r["depth_map"], occlusion=r["occlusion_map"], albedo_map=albedo_map,
+                    roughness_map=roughness_map, metallic_map=metallic_map, depth_pos=r["depth_pos"],
+                    normals_view=normals_view, onv=onv, mask_u8=mask_u8, mask_f=mask_f, F0=F0, metallic_in=metallic_in)
+
+    def _with_extra(self, out: Dict) -> Dict:
+        out.update(self._mesh_extra)
+        return out
+
+
+class MeshRelighter(_MeshView, relight.Relighter):
+    """relight.Relighter(fused=True) on a mesh: rl(cam, rast, view_dirs, alpha_mask=None, albedo_ratio=None)."""
+
+    def __init__(self, light, gi: Dict, metallic: bool = False, tone: bool = False, gamma: bool = False,
+                 brdf_lut: Optional[torch.Tensor] = None, graphs: bool = False):
+        self._no_graphs(graphs)
+        relight.Relighter.__init__(self, light, gi, 0, metallic=metallic, tone=tone, gamma=gamma, fused=True,
+                                   brdf_lut=brdf_lut, graphs=False)
+
+    @torch.no_grad()
+    def __call__(self, cam, rast, view_dirs, alpha_mask=None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        return self._with_extra(self._fused(cam, rast, view_dirs, alpha_mask, albedo_ratio))
+
+
+class MeshMultiRelighter(_MeshView, relight.MultiRelighter):
+    """relight.MultiRelighter on a mesh: up to relight.MAX_LIGHTS lights over one G-buffer."""
+
+    def __init__(self, lights, gi: Dict, metallic: bool = False, tone: bool = False, gamma: bool = False,
+                 graphs: bool = False, brdf_lut: Optional[torch.Tensor] = None):
+        self._no_graphs(graphs)
+        relight.MultiRelighter.__init__(self, lights, gi, 0, metallic=metallic, tone=tone, gamma=gamma, graphs=False,
+                                        brdf_lut=brdf_lut)
+
+    @torch.no_grad()
+    def __call__(self, cam, rast, view_dirs, alpha_mask=None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        return self._with_extra(self._fused(cam, rast, view_dirs, alpha_mask, albedo_ratio))
+
+
+class MeshTurntableRelighter(_MeshView, relight.TurntableRelighter):
+    """relight.TurntableRelighter on a mesh: any number of lights, the SSR march recorded once."""
+
+    def __init__(self, lights, gi: Dict, metallic: bool = False, tone: bool = False, gamma: bool = False,
+                 brdf_lut: Optional[torch.Tensor] = None, graphs: bool = False):
+        self._no_graphs(graphs)
+        relight.TurntableRelighter.__init__(self, lights, gi, 0, metallic=metallic, tone=tone, gamma=gamma, brdf_lut=brdf_lut)
+
+    @torch.no_grad()
+    def __call__(self, cam, rast, view_dirs, alpha_mask=None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        return self._with_extra(relight.TurntableRelighter.__call__(self, cam, rast, view_dirs, alpha_mask, albedo_ratio))

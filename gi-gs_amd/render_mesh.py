@@ -1,0 +1,231 @@
+"""An exported mesh (extract_mesh.py's PLY) rendered and relit from the cameras of its scene (mesh_render.py), and compared
+with the splat render it came from.
+
+    python gi-gs_amd/render_mesh.py -m <out> --mesh mesh.ply [--checkpoint <out>/chkpntN.pth] [--hdri a.hdr b.hdr ...]
+                                    [--rotations N] [--compare] [--split test] [--metallic --tone --gamma]        (CLI)
+    render_mesh(args) -> {...}                                                                                   (API)
+
+The scene path and the resolution come from <out>/cfg_args as in render_scene.py, command-line values first; a relative
+--mesh is looked up in <out>.  The mesh is lit by the maps of --hdri (.hdr or .npy, each under --rotations N equal turns
+about its up axis if given) or, without --hdri, by the trained light of --checkpoint (rotated the same way).  Per view
+of the split it writes under <out>/mesh_<split>/
+
+    <image_name>_{depth,normal,albedo,roughness,metallic,occlusion}.png     depth min-max normalised, normal * 0.5 + 0.5
+    <image_name>_<light>.png                                                one relit image per light
+
+and with --compare (needs --checkpoint) renders the same views from the Gaussians under the first light and writes
+mesh_vs_splat.json: per view and on average the PSNR / SSIM (gigs_image_metrics) of the mesh's relit image and albedo
+against the splats', and the mean absolute depth difference over the pixels both cover.  There is no clipping: triangles
+that reach behind the camera's near cull are dropped (mesh_render.py).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+from argparse import Namespace
+from typing import Dict, List, Optional, Sequence
+
+if __package__ in (None, ""):  # run as a script: make the package's modules importable
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+G_PLANES = ("depth", "normal", "albedo", "roughness", "metallic", "occlusion")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    import render_scene
+    p = argparse.ArgumentParser(description="Mesh rendering parameters")
+    render_scene.add_model_arguments(p)
+    p.add_argument("--mesh", type=str, required=True, help="The PLY written by extract_mesh.py.")
+    p.add_argument("--checkpoint", type=str, default=None, help="The checkpoint: its light, and the Gaussians of --compare.")
+    p.add_argument("--hdri", type=str, nargs="+", default=None, help="Environment maps to light the mesh with (.hdr or .npy).")
+    p.add_argument("--rotations", type=int, default=0, help="light under N equal turns of every map about its up axis")
+    p.add_argument("--compare", action="store_true", help="also render the Gaussians and write mesh_vs_splat.json")
+    p.add_argument("--split", choices=("train", "test"), default="test")
+    for k in ("tone", "gamma", "metallic"):
+        p.add_argument("--" + k, action="store_true")
+    for k, v in render_scene.GI_FLAGS.items():
+        p.add_argument("--" + k, type=type(v), default=v)
+    p.add_argument("--workers", type=int, default=12, help="PNG encoder threads (at most 16)")
+    return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> Namespace:
+    return build_parser().parse_args(argv)
+
+
+def light_names(hdris: Optional[Sequence[str]], n_rot: int) -> List[str]:
+    names = [os.path.splitext(os.path.basename(p))[0] for p in hdris] if hdris else ["trained"]
+    if len(set(names)) != len(names):
+        raise ValueError("--hdri: two maps share the light name %s" % sorted(n for n in names if names.count(n) > 1)[0])
+    if n_rot > 0:
+        names = ["%s_rot%03d" % (n, k) for n in names for k in range(n_rot)]
+    return names
+
+
+def view_paths(out: str, split: str, image_name: str, lights: Sequence[str]) -> Dict:
+    base = os.path.join(out, "mesh_" + split)
+    paths: Dict = {k: os.path.join(base, "%s_%s.png" % (image_name, k)) for k in G_PLANES}
+    paths["relit"] = [os.path.join(base, "%s_%s.png" % (image_name, n)) for n in lights]
+    return paths
+
+
+def _check(args: Namespace) -> int:
+    n_rot = int(args.rotations or 0)
+    if n_rot < 0:
+        raise ValueError("--rotations: a count of turns, got %d" % n_rot)
+    if args.compare and not args.checkpoint:
+        raise ValueError("--compare needs --checkpoint: the Gaussians to compare with")
+    if not args.checkpoint and not args.hdri:
+        raise ValueError("a light is needed: --checkpoint or --hdri")
+    if not args.checkpoint and not args.model_path:
+        raise ValueError("-m is required without --checkpoint")
+    return n_rot
+
+
+def _splat_relighter():
+    import relight
+
+    class SplatRelighter(relight.Relighter):
+        """relight.Relighter that keeps the albedo plane of its last view (the result holds none)."""
+
+        def _gbuffer(self, cam, g):
+            b = super()._gbuffer(cam, g)
+            self.albedo_map = b["albedo_map"]
+            return b
+
+    return SplatRelighter
+
+
+def render_mesh(args) -> Dict:
+    """`args`: a Namespace from parse_args, a dict of overrides or an argv list."""
+    import render_scene as rs
+    args = rs.as_namespace(args, parse_args)
+    n_rot = _check(args)  # before anything is read
+    import torch
+
+    import dataset_readers as dr
+    import evaluate
+    import image_writer
+    import mesh_render
+    import pbr
+    import pipeline
+    import relight
+    import trainer
+    _SplatRelighter = _splat_relighter()
+    checkpoint = args.checkpoint
+    if not checkpoint:  # combine_args takes the output folder from the checkpoint's place where -m is missing: not needed here
+        args = Namespace(**dict(vars(args), checkpoint=os.path.join(args.model_path, "none")))
+    args = rs.combine_args(args)
+    args.checkpoint = checkpoint
+    if not torch.cuda.is_available():
+        raise RuntimeError("render_mesh needs the GPU")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    args.source_path = os.path.abspath(args.source_path)
+    out = args.model_path
+    mesh_path = args.mesh if os.path.isabs(args.mesh) or os.path.exists(args.mesh) else os.path.join(out, args.mesh)
+    t0 = time.perf_counter()
+    g = sh_degree = ck = None
+    if checkpoint:
+        g, sh_degree, ck, cams = rs.load_trained(args, dev)
+        infos = cams[args.split]
+    else:
+        info = trainer._read_scene(args)
+        infos = info["test_cameras" if args.split == "test" else "train_cameras"]
+    if not infos:
+        raise ValueError("render_mesh: the %s split has no views" % args.split)
+    hdris = [args.hdri] if isinstance(args.hdri, str) else (list(args.hdri) if args.hdri else None)
+    names = light_names(hdris, n_rot)
+    turns = relight.yaw_rotations(n_rot) if n_rot else None
+    if hdris:
+        maps = [torch.from_numpy(image_writer.load_latlong(p)).to(dev) for p in hdris]
+        if n_rot:
+            lights = [light for m in maps for light in relight.rotated_lights(m, turns, res=256)]
+        else:
+            lights = [relight.make_light(m, res=256) for m in maps]
+    else:
+        if not ck.get("cubemap"):
+            raise ValueError(f"{checkpoint}: the checkpoint holds no cubemap; give --hdri")
+        light = pbr.CubemapLight(base_res=256, device=dev)
+        light.load_state_dict({k: v.to(dev) for k, v in ck["cubemap"].items()})
+        light.eval()
+        lights = relight.rotate_light(light, turns) if n_rot else [light]
+    gi = {k: getattr(args, k) for k in rs.GI_FLAGS}
+    lut = pbr.get_brdf_lut().to(dev)
+    os.makedirs(os.path.join(out, "mesh_" + args.split), exist_ok=True)
+    res: Dict = {"mesh": mesh_path, "n_views": len(infos), "lights": names}
+    per_view: List[Dict] = []
+    try:
+        with mesh_render.MeshRasterizer(mesh_path, device=dev) as rast, image_writer.ImageWriter(workers=args.workers) as wr, \
+                torch.no_grad():
+            res.update(vertices=rast.V, faces=rast.F)
+            tr = mesh_render.MeshTurntableRelighter(lights, gi, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
+                                                    brdf_lut=lut)
+            splat = _SplatRelighter(lights[0], gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
+                                      brdf_lut=lut) if args.compare else None
+            try:
+                rays = None
+                for ci in infos:
+                    c = dr.camera_from_info(ci, args.resolution, device=dev)
+                    if rays is None:
+                        rays = pipeline.canonical_rays(c, dev)
+                    vd = pipeline.view_dirs_for(c, rays, dev)
+                    o = tr(c, rast, vd)
+                    paths = view_paths(out, args.split, ci.image_name, names)
+                    images = [image_writer.Image(paths["depth"], o["depth_map"], normalize=True),
+                              image_writer.Image(paths["normal"], o["normal_map"] * 0.5 + 0.5),
+                              image_writer.Image(paths["occlusion"], o["occlusion"], bias=0.0)]
+                    images += [image_writer.Image(paths[k], o[k + "_map"]) for k in ("albedo", "roughness", "metallic")]
+                    wr.submit(images)
+                    relit = [(p, o["render_rgb"][k]) for k, p in enumerate(paths["relit"])]
+                    for first in range(0, len(relit), relight.MAX_LIGHTS):
+                        wr.submit(relit[first:first + relight.MAX_LIGHTS])
+                    if splat is not None:
+                        s = splat(c, g, vd)
+                        both = (o["tri_id"] >= 0) & (s["depth_map"][0] > 0)
+                        n_both = both.sum()
+                        ddepth = ((o["depth_map"][0] - s["depth_map"][0]).abs() * both).sum() / n_both.clamp(min=1)
+                        per_view.append(dict(
+                            image_name=ci.image_name,
+                            relit=evaluate.image_metrics(o["render_rgb"][0].nan_to_num().clamp(0, 1),
+                                                         s["render_rgb"].nan_to_num().clamp(0, 1)),
+                            albedo=evaluate.image_metrics(o["albedo_map"], splat.albedo_map), depth=ddepth, both=n_both))
+            finally:
+                tr.close()
+                if splat is not None:
+                    splat.close()
+        res.update(files=wr.files, png_bytes=wr.bytes_written)
+        if args.compare:
+            views = []
+            for v in per_view:
+                relit, albedo = v["relit"].cpu(), v["albedo"].cpu()
+                views.append(dict(image_name=v["image_name"], relit_psnr=float(relit[3]), relit_ssim=float(relit[4]),
+                                  albedo_psnr=float(albedo[3]), albedo_ssim=float(albedo[4]), depth_abs_diff=float(v["depth"]),
+                                  pixels_both_cover=int(v["both"])))
+            keys = ("relit_psnr", "relit_ssim", "albedo_psnr", "albedo_ssim", "depth_abs_diff")
+            cmp = dict(light=names[0], views=views, average={k: sum(v[k] for v in views) / len(views) for k in keys})
+            path = os.path.join(out, "mesh_vs_splat.json")
+            with open(path, "w") as f:
+                json.dump(cmp, f, indent=4)
+            res.update(compare_json=path, compare=cmp["average"])
+    finally:
+        pipeline._collect_idle()
+    res["total_s"] = round(time.perf_counter() - t0, 4)
+    return res
+
+
+def main(argv=None) -> int:
+    res = render_mesh(parse_args(argv))
+    print("views %d, lights %d, vertices %d, faces %d, files %d" % (res["n_views"], len(res["lights"]), res["vertices"],
+                                                                    res["faces"], res["files"]))
+    print(json.dumps(res))
+    return 0
+
+
+if __name__ == "__main__":
+    import importlib
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    importlib.import_module("gi-gs_amd")
+    sys.exit(main())

@@ -688,6 +688,54 @@ int gigs_mesh_count(const gigs_tsdf_grid* grid, float min_weight, int* cell_flag
 int gigs_mesh_write(const gigs_tsdf_grid* grid, float min_weight, const int* cell_offsets, const int* quad_offsets,
                     int vertex_capacity, int face_capacity, float* vertices, float* normals, float* albedo, float* roughness,
                     float* metallic, int* faces, int* overflow, void* stream);
+/* Rendering meshes (gigs-hip extension; the device half of mesh_render.py): a triangle mesh -- vertices [V,3], faces [F,3]
+ * int32 and mesh.py's per-vertex attributes -- as the G-buffer planes the blend kernel writes in inference mode, by a
+ * visibility buffer.  Coverage and visibility are integer decisions, so no result depends on the order of execution and a
+ * restatement (tests/mesh_raster_ref.py) agrees index for index.  All arrays are DEVICE memory, viewmatrix included (the
+ * rasterizer's layout); the calls neither synchronise nor allocate.  Every product and sum is rounded on its own, division
+ * is IEEE.  There is NO clipping: a triangle with a flagged vertex is dropped whole.
+ * gigs_mesh_project, one thread per vertex:
+ *     p = xform_point_4x3(vertex, viewmatrix);  u = p.x / p.z * fx + (W - 1) / 2, v = p.y / p.z * fy + (H - 1) / 2 with
+ *     fx = W / (2 tanfovx), fy = H / (2 tanfovy): gigs_tsdf_integrate's pixel convention, pixel centres at the integers.
+ *     view_pos [V,3] = p;  screen [V,2] = (X, Y) = (rint(256 u), rint(256 v)), round half to even;  flags [V] = 1 where
+ *     p.z <= 0.2 (the rasterizer's near cull), where p.x, p.y, p.z, u or v is not finite, or where |u| or |v| exceeds
+ *     16384 pixels (the guard band), else 0.  A flagged vertex gets screen = (0, 0).
+ * gigs_mesh_raster: vis [H,W] of 64-bit keys, set to all ones by the CALLER, receives per pixel the minimum of
+ *     key = (bits(z) << 32) | triangle index  over the triangles that cover the pixel's centre.
+ *   Dropped, without a memory access through a bad index: a triangle with a vertex index outside [0, V), with a flagged
+ *     vertex, or with doubled area A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) == 0 (int64).  If A < 0, vertices 1 and 2
+ *     swap roles (and A changes sign) in everything below.
+ *   Coverage at the centre q = (256 i, 256 j) of pixel (i, j): the int64 edge functions E0 over the edge 1 -> 2, E1 over
+ *     2 -> 0, E2 over 0 -> 1, each (Xb - Xa)(qy - Ya) - (Yb - Ya)(qx - Xa).  The pixel is covered iff for every edge
+ *     E > 0, or E == 0 and the directed edge (dx, dy) = (Xb - Xa, Yb - Ya) has dy < 0 || (dy == 0 && dx > 0): a centre on
+ *     an edge two triangles share belongs to exactly one of them.
+ *   Depth: b_k = float(E_k) / float(A) (int64 -> fp32 to nearest), w_k = b_k * (1 / z_k) with z_k = view_pos[vertex k].z,
+ *     s = (w0 + w1) + w2, z = 1 / s; a z that is not finite or not above 0 is skipped.
+ *   A triangle whose box of pixel centres, clamped to the image, holds at most small_max pixels (a negative value means
+ *     GIGS_MESH_SMALL_MAX) is walked by its own thread; a larger one is appended to a device list and walked by a second
+ *     launch, one wave per triangle, whose fixed grid strides over the device-side count (no read-back).  Both paths and
+ *     every small_max give the same bits.  scratch: gigs_mesh_raster_scratch_bytes(F) bytes (the counter and the list),
+ *     cleared inside the call.
+ * gigs_mesh_resolve, one thread per pixel: the triangle index of the pixel's key is range-checked against F and the
+ *   triangle set up and sampled again by the same device function, so depth has the bits of the key.  Planes as
+ *   the blend kernel's ([C,H,W]): opacity = 1, depth = z, pos = ((w0 x0 + w1 x1) + w2 x2) / s per component of view_pos,
+ *   normal, albedo, roughness, metallic interpolated the same way (the normal is not renormalised), normal_view =
+ *   normalize3(xform_vec_4x3(normal, viewmatrix)), tri_id [H,W] int32 = the triangle.  A pixel with an empty key gets what
+ *   the blend kernel writes where no Gaussian contributes under a black background with inference = 1: zeros,
+ *   roughness = 1, normal_view = normalize3 of the zero vector (NaN), and tri_id = -1.
+ * Images up to 16384 x 16384. */
+#define GIGS_MESH_SMALL_MAX 64
+int gigs_mesh_project(int n_vertices, const float* vertices, const float* viewmatrix, float tanfovx, float tanfovy, int width,
+                      int height, float* view_pos, int* screen, uint8_t* flags, void* stream);
+size_t gigs_mesh_raster_scratch_bytes(int n_faces);
+int gigs_mesh_raster(int n_vertices, int n_faces, const int* faces, const float* view_pos, const int* screen,
+                     const uint8_t* flags, int width, int height, int small_max, unsigned long long* vis, void* scratch,
+                     void* stream);
+int gigs_mesh_resolve(int n_vertices, int n_faces, const int* faces, const float* view_pos, const int* screen,
+                      const uint8_t* flags, const float* normals, const float* albedo, const float* roughness,
+                      const float* metallic, const float* viewmatrix, int width, int height, const unsigned long long* vis,
+                      float* opacity, float* depth, float* pos, float* normal, float* normal_view, float* albedo_out,
+                      float* roughness_out, float* metallic_out, int* tri_id, void* stream);
 int gigs_tv_loss_fwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
                      const float* mask_f, float* scratch, float* loss, void* stream);
 int gigs_tv_loss_bwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
