@@ -34,8 +34,8 @@ import torch
 import gigs_lib
 import pipeline
 from diff_gaussian_rasterization import Gaussian_SSR, filters
-from pbr import CubemapLight, pbr_shading
-from relight import Relighter
+from pbr import CubemapLight, get_brdf_lut, pbr_shading
+from relight import Scratch, ViewReplay, shade_ssr
 
 _lib = gigs_lib.lib()
 
@@ -75,7 +75,7 @@ def image_metrics(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Ten
     return out
 
 
-class NovelViewEvaluator(Relighter):
+class NovelViewEvaluator:
     """render_set's pbr branch (render.py:115-395) without the file I/O.  graphs=True (the default) replays the whole
     view -- rasterizer under asynchronous binning, G-buffer post, shade, SSR, the saved planes and the metrics -- from one
     hipGraph; camera pose, view_dirs, gt_image and alpha_mask are its inputs.  The planes it returns are the graph's
@@ -87,9 +87,15 @@ class NovelViewEvaluator(Relighter):
                  capacity: int = 1024, lpips=None, extra_planes: bool = False):
         """extra_planes=True adds EXTRA_PLANES to the planes a call returns (the shade also writes its diffuse and
         specular parts); the default returns PLANES, exactly as before."""
-        super().__init__(light, gi, sh_degree, metallic=metallic, tone=tone, gamma=gamma, fused=fused, brdf_lut=brdf_lut,
-                         graphs=graphs)
         dev = light.base.device
+        self.light, self.gi, self.sh_degree = light, gi, sh_degree
+        self.metallic, self.tone, self.gamma, self.fused = bool(metallic), bool(tone), bool(gamma), bool(fused)
+        self.graphs = bool(graphs) and self.fused
+        self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(dev)
+        self._scratch = Scratch()
+        self._view = ViewReplay(sh_degree, "NovelViewEvaluator")
+        with torch.no_grad():
+            light.build_mips()  # render.py:142: once per run
         self.extra_planes = bool(extra_planes)
         self.names = PLANES + EXTRA_PLANES if self.extra_planes else PLANES
         self._cap = int(capacity)
@@ -114,12 +120,12 @@ class NovelViewEvaluator(Relighter):
         out = None
         if self.graphs:
             try:
-                out = self._replay(cam, g, (view_dirs, gt_image, alpha_mask), self._core, self.names,
-                                   on_capture=self._rewind)
+                out = self._view(cam, g, (view_dirs, gt_image, alpha_mask), lambda c, *rest: self._core(c, g, *rest),
+                                 self.names, on_capture=self._rewind)
             except pipeline.DenseScene:
                 self.graphs = False
         if out is None:
-            out = dict(zip(self.names, self._core(cam, view_dirs, gt_image, alpha_mask, g=g)))
+            out = dict(zip(self.names, self._core(cam, g, view_dirs, gt_image, alpha_mask)))
         self._n += 1
         return out
 
@@ -128,8 +134,10 @@ class NovelViewEvaluator(Relighter):
         if self.lpips is not None:
             self._lp_slot.fill_(self._n)
 
-    def _core(self, cam, view_dirs, gt_image, alpha_mask, g=None):
-        g = self._g if g is None else g
+    def close(self) -> None:
+        self._view.close()
+
+    def _core(self, cam, g, view_dirs, gt_image, alpha_mask):
         r = (self._fused_pad if self.fused else self._unfused_pad)(cam, g, view_dirs)
         dev = alpha_mask.device
         background = torch.zeros(3, device=dev)
@@ -145,15 +153,11 @@ class NovelViewEvaluator(Relighter):
         if self.extra_planes:
             part = lambda x: comp(torch.where(mask, x.clamp(0.0, 1.0), bg))  # noqa: E731  (render.py:288-317, :348-349)
             planes.update(diffuse=part(r["diffuse"]), specular=part(r["specular"]), depth=r["depth"])
-        image_metrics(render_rgb, gt, scratch=self._buf("metrics_scratch", (int(_lib.gigs_image_metrics_scratch_bytes(
+        image_metrics(render_rgb, gt, scratch=self._scratch("metrics_scratch", (int(_lib.gigs_image_metrics_scratch_bytes(
             3, *render_rgb.shape[1:])),), torch.uint8, dev), slot=self._slot, out=self._rec)
         if self.lpips is not None:
             self.lpips.record(gt, render_rgb, slot=self._lp_slot, out=self._lp_rec)
         return tuple(planes[n] for n in self.names)
-
-    def _replay(self, cam, g, inputs, core, names, key_extra=None, on_capture=None):
-        self._g = g
-        return super()._replay(cam, g, inputs, core, names, key_extra, on_capture)
 
     def _branch(self, albedo_map, roughness_map, metallic_map):
         """render.py:320-326: (F0, the metallic plane SSR receives and render.py saves)."""
@@ -162,7 +166,7 @@ class NovelViewEvaluator(Relighter):
                                  metallic_map), metallic_map
         return torch.full_like(albedo_map, 0.04), torch.zeros_like(roughness_map)
 
-    # -- the fused sequence: the pad_normal G-buffer post, then Relighter's shade / SSR / sRGB + median launches ------
+    # -- the fused sequence: the pad_normal G-buffer post, then relight.shade_ssr's shade / SSR / sRGB + median launches ----
     def _fused_pad(self, cam, g, view_dirs):
         dev = g["means3D"].device
         background = torch.zeros(3, device=dev)
@@ -170,9 +174,9 @@ class NovelViewEvaluator(Relighter):
         (_, _, opacity_map, depth_map, nfd, normal_map, occlusion, albedo_map, roughness_map, metallic_map, out_normal_view,
          depth_pos) = out
         H, W = cam["image_height"], cam["image_width"]
-        new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
+        new = lambda name, *shape: self._scratch(name, shape, torch.float32, dev)  # noqa: E731
         normals_view, onv, nfd_out = new("normals_view", 3, H, W), new("onv", 3, H, W), new("nfd", 3, H, W)
-        mask_u8 = self._buf("mask_u8", (H, W), torch.uint8, dev)
+        mask_u8 = self._scratch("mask_u8", (H, W), torch.uint8, dev)
         mask_f = new("mask_f", 1, H, W)
         p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         vm = st.viewmatrix.contiguous().float()
@@ -182,8 +186,10 @@ class NovelViewEvaluator(Relighter):
                                                       p(mask_u8), p(mask_f), None, p(normals_view), p(onv), p(nfd_out),
                                                       None, s), "gbuffer_post_pad")
         F0, metallic_in = self._branch(albedo_map, roughness_map, metallic_map)
-        res = self._shade_ssr(cam, view_dirs, normals_view, mask_u8, mask_f, onv, depth_pos, albedo_map, albedo_map,
-                              roughness_map, metallic_map, occlusion, F0, metallic_in, parts=self.extra_planes)
+        b = dict(normals_view=normals_view, mask_u8=mask_u8, mask_f=mask_f, onv=onv, depth_pos=depth_pos, albedo_map=albedo_map,
+                 roughness_map=roughness_map, metallic_map=metallic_map, occlusion=occlusion, F0=F0, metallic_in=metallic_in)
+        res = shade_ssr(self.light, self.brdf_lut, self.gi, self.metallic, self.tone, self.gamma, cam, view_dirs, b, albedo_map,
+                        self._scratch, parts=self.extra_planes)
         IRR, render_rgb = res[1], res[2]
         IRR2 = filters.median_blur(pipeline.linear_to_srgb(IRR)[None, ...], (3, 3))[0]
         out = dict(render_rgb=render_rgb, IRR2=IRR2, normal_mask=mask_u8.bool()[None], albedo=albedo_map,

@@ -7,18 +7,20 @@ behind them is the existing one, unchanged.
                                       normal_view, albedo, roughness, metallic ([C,H,W]) and tri_id [H,W] (-1 = background)
     mesh_planes(rast, cam, gi)        those planes plus the derived normals (gigs_derive_normal) and SSAO with the GI
                                       settings: the rasterizer's twelve outputs, by name
-    MeshRelighter / MeshMultiRelighter / MeshTurntableRelighter   relight.py's three relighters with the mesh in the place of
-                                      the Gaussians: rl(cam, rast, view_dirs).  Only the G-buffer differs; shade, SSR march,
-                                      sRGB / median finish and the reference's F0 quirk are the parents'
+    MeshGBuffer(gi, metallic)(cam, rast)   the G-buffer source of relight.py's relighters: mesh_planes, then
+                                      relight.gbuffer_from_planes (G-buffer post, the reference's F0 quirk)
+    MeshRelighter / MeshMultiRelighter / MeshTurntableRelighter   relight.py's three relighters constructed over that source:
+                                      rl(cam, rast, view_dirs).  Only the G-buffer differs; shade, SSR march and the sRGB /
+                                      median finish are theirs, and the result gains the source's extra planes
 
 The arithmetic is stated in include/gigs_hip.h and restated in numpy by tests/mesh_raster_ref.py.  There is no clipping:
 a triangle with a vertex behind the near cull (view z <= 0.2) or outside the guard band of 16384 pixels is dropped whole.
-There is no CPU path, and no hipGraph replay (relight.py's replay is keyed on the Gaussian tensors and asynchronous
-binning): graphs=True raises.
+There is no CPU path, and no hipGraph replay (the source says so: relight.py's replay is keyed on the Gaussian tensors and
+asynchronous binning): graphs=True raises.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -192,84 +194,50 @@ def mesh_planes(rast: MeshRasterizer, cam: Dict, gi: Dict) -> Dict[str, torch.Te
                 tri_id=o["tri_id"], viewmatrix=vm)
 
 
-class _MeshView:
-    """The mesh in the place of the Gaussians: relight._ViewGraph._gbuffer over mesh_planes.  The parents hand their `g`
-    argument to _gbuffer and nowhere else (graphs off), so it is the MeshRasterizer; their `radii` entry is None and the
-    result gains tri_id, opacity_map, albedo_map, roughness_map and metallic_map."""
+class MeshGBuffer:
+    """The G-buffer of a mesh (relight.py documents its keys): source(cam, rast) runs mesh_planes over a MeshRasterizer and
+    relight.gbuffer_from_planes.  `radii` is None and `extra` holds tri_id, opacity_map and the material planes.  The source
+    owns the scratch planes of its result, which is valid until its next call."""
+    replayable = False  # relight.ViewReplay is keyed on Gaussian tensors and asynchronous binning
 
-    @staticmethod
-    def _no_graphs(graphs) -> None:
-        if graphs:
-            raise ValueError("mesh relighters replay no hipGraph (the replay is keyed on Gaussian tensors): graphs=False only")
+    def __init__(self, gi: Dict, metallic: bool = False):
+        self.gi, self.metallic = gi, bool(metallic)
+        self._scratch = relight.Scratch()
 
-    def _gbuffer(self, cam, rast):
+    @torch.no_grad()
+    def __call__(self, cam: Dict, rast: MeshRasterizer) -> Dict:
         if not isinstance(rast, MeshRasterizer):
-            raise TypeError("%s: the second argument is a MeshRasterizer" % type(self).__name__)
+            raise TypeError("MeshGBuffer: the second argument is a MeshRasterizer")
         r = mesh_planes(rast, cam, self.gi)
-        dev = rast.device
-        H, W = int(cam["image_height"]), int(cam["image_width"])
-        new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
-        normals_view, onv = new("normals_view", 3, H, W), new("onv", 3, H, W)
-        mask_u8 = self._buf("mask_u8", (H, W), torch.uint8, dev)
-        mask_f = new("mask_f", 1, H, W)
-        albedo_map, roughness_map, metallic_map = r["albedo_map"], r["roughness_map"], r["metallic_map"]
-        p = lambda t: t.data_ptr()  # noqa: E731
-        with torch.cuda.device(dev):
-            gigs_lib.check(_lib.gigs_gbuffer_post(H, W, p(r["normal_map"]), p(r["out_normal_view"]), p(r["viewmatrix"]),
-                                                  p(normals_view), p(mask_u8), p(mask_f), p(onv), _stream()), "gbuffer_post")
-            if self.metallic:  # relight.py:236-240, as written (see relight._ViewGraph._gbuffer)
-                F0 = torch.full_like(albedo_map, 0.04)
-                metallic_in = torch.zeros_like(roughness_map)
-            else:
-                F0 = torch.addcmul(torch.full_like(albedo_map, (1.0 - float(self.metallic)) * 0.04), albedo_map, metallic_map)
-                metallic_in = metallic_map
-        self._mesh_extra = dict(tri_id=r["tri_id"], opacity_map=r["opacity_map"], albedo_map=albedo_map,
-                                roughness_map=roughness_map, metallic_map=metallic_map)
-        return dict(radii=None, depth_map=r["depth_map"], occlusion=r["occlusion_map"], albedo_map=albedo_map,
-                    roughness_map=roughness_map, metallic_map=metallic_map, depth_pos=r["depth_pos"],
-                    normals_view=normals_view, onv=onv, mask_u8=mask_u8, mask_f=mask_f, F0=F0, metallic_in=metallic_in)
-
-    def _with_extra(self, out: Dict) -> Dict:
-        out.update(self._mesh_extra)
-        return out
+        b = relight.gbuffer_from_planes(r, r["viewmatrix"], self.metallic, self._scratch)
+        b["extra"] = {k: r[k] for k in ("tri_id", "opacity_map", "albedo_map", "roughness_map", "metallic_map")}
+        return b
 
 
-class MeshRelighter(_MeshView, relight.Relighter):
+class MeshRelighter(relight.Relighter):
     """relight.Relighter(fused=True) on a mesh: rl(cam, rast, view_dirs, alpha_mask=None, albedo_ratio=None)."""
 
     def __init__(self, light, gi: Dict, metallic: bool = False, tone: bool = False, gamma: bool = False,
                  brdf_lut: Optional[torch.Tensor] = None, graphs: bool = False):
-        self._no_graphs(graphs)
-        relight.Relighter.__init__(self, light, gi, 0, metallic=metallic, tone=tone, gamma=gamma, fused=True,
-                                   brdf_lut=brdf_lut, graphs=False)
-
-    @torch.no_grad()
-    def __call__(self, cam, rast, view_dirs, alpha_mask=None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
-        return self._with_extra(self._fused(cam, rast, view_dirs, alpha_mask, albedo_ratio))
+        super().__init__(light, gi, 0, metallic=metallic, tone=tone, gamma=gamma, fused=True, brdf_lut=brdf_lut, graphs=graphs,
+                         source=MeshGBuffer(gi, metallic))
 
 
-class MeshMultiRelighter(_MeshView, relight.MultiRelighter):
+class MeshMultiRelighter(relight.MultiRelighter):
     """relight.MultiRelighter on a mesh: up to relight.MAX_LIGHTS lights over one G-buffer."""
 
     def __init__(self, lights, gi: Dict, metallic: bool = False, tone: bool = False, gamma: bool = False,
                  graphs: bool = False, brdf_lut: Optional[torch.Tensor] = None):
-        self._no_graphs(graphs)
-        relight.MultiRelighter.__init__(self, lights, gi, 0, metallic=metallic, tone=tone, gamma=gamma, graphs=False,
-                                        brdf_lut=brdf_lut)
-
-    @torch.no_grad()
-    def __call__(self, cam, rast, view_dirs, alpha_mask=None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
-        return self._with_extra(self._fused(cam, rast, view_dirs, alpha_mask, albedo_ratio))
+        super().__init__(lights, gi, 0, metallic=metallic, tone=tone, gamma=gamma, graphs=graphs, brdf_lut=brdf_lut,
+                         source=MeshGBuffer(gi, metallic))
 
 
-class MeshTurntableRelighter(_MeshView, relight.TurntableRelighter):
+class MeshTurntableRelighter(relight.TurntableRelighter):
     """relight.TurntableRelighter on a mesh: any number of lights, the SSR march recorded once."""
 
     def __init__(self, lights, gi: Dict, metallic: bool = False, tone: bool = False, gamma: bool = False,
                  brdf_lut: Optional[torch.Tensor] = None, graphs: bool = False):
-        self._no_graphs(graphs)
-        relight.TurntableRelighter.__init__(self, lights, gi, 0, metallic=metallic, tone=tone, gamma=gamma, brdf_lut=brdf_lut)
-
-    @torch.no_grad()
-    def __call__(self, cam, rast, view_dirs, alpha_mask=None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
-        return self._with_extra(relight.TurntableRelighter.__call__(self, cam, rast, view_dirs, alpha_mask, albedo_ratio))
+        if graphs:
+            raise ValueError("MeshTurntableRelighter replays no hipGraph: graphs=False only")
+        super().__init__(lights, gi, 0, metallic=metallic, tone=tone, gamma=gamma, brdf_lut=brdf_lut,
+                         source=MeshGBuffer(gi, metallic))

@@ -13,21 +13,26 @@ ops); `fused=True` (default) runs the same arithmetic as five library launches a
 (gigs_gbuffer_post, gigs_shade_fwd_ex in planar layout with the sRGB->linear epilogue, gigs_ssr,
 gigs_stage2_loss_fwd for linear_to_srgb + median + sum) on the rasterizer's [C,H,W] planes.
 
-    MultiRelighter(lights, ...)(cam, gaussians, ...)   relight_all.bash's loop over target maps, one view at a time:
+The fused paths have two seams.  WHO MAKES THE G-BUFFER: a source, source(cam, scene) -> the dict of planes documented below
+(SplatGBuffer for Gaussians, mesh_render.MeshGBuffer for a mesh; both end in gbuffer_from_planes).  WHAT IS DONE WITH IT:
+a relighter's from_gbuffer(cam, b, view_dirs, ...); rl(cam, scene, ...) is rl.from_gbuffer(cam, rl.source(cam, scene), ...),
+replayed from one hipGraph (ViewReplay) where graphs=True and the source allows it.
+
+    MultiRelighter(lights, ...)               relight_all.bash's loop over target maps, one view at a time, at most 16 lights:
                                               the rasterizer, G-buffer post, SSAO and the SSR march run ONCE, then
                                               K-light launches (gigs_shade_fwd_multi, gigs_ssr_multi) and K finishes
+    TurntableRelighter(lights, ...)           the same light loop under ANY number of lights (a turntable: N rotations of one
+                                              map): the march runs once and records its hit list (gigs_ssr_hits), then every
+                                              chunk of <= 16 lights is a shade, a gather at the recorded hits
+                                              (gigs_ssr_apply_multi) and the per-light finish; eager only
     RelightEvaluator(light_names).add(...)    relight_eval.py without the file I/O: per light the PSNR / SSIM of the
                                               8-bit-quantised prediction against its ground truth, kept on the device
-
-    TurntableRelighter(lights, ...)(cam, gaussians, ...)   one view under ANY number of lights (a turntable: N rotations of
-                                              one map): the march runs once and records its hit list (gigs_ssr_hits), then
-                                              every chunk of <= 16 lights is a shade (gigs_shade_fwd_multi), a gather at the
-                                              recorded hits (gigs_ssr_apply_multi) and the per-light finish
     rotation_about / yaw_rotations / rotated_lights / rotate_light   lights turned in their own frame: the BASE is resampled
                                               under the rotation and then pre-filtered like any other light (DESIGN.md,
                                               "Turntables": the pre-filters are not rotation-covariant)
 
-Reference quirks kept on purpose, by Relighter and MultiRelighter alike: the `metallic` branches for F0 are swapped (relight.py:236-240):
+Reference quirks kept on purpose, by every relighter alike: the `metallic` branches for F0 are swapped
+(relight.py:236-240, fused_f0):
 with metallic=True the shade uses the metallic map but SSR receives F0 = 0.04 and a zero metallic plane; with
 metallic=False (`metallic` is the Python bool) SSR receives F0 = (1 - False) * 0.04 + albedo * metallic_map.  The
 per-channel albedo ratio read from albedo_ratio.json (:203-220) scales the shade's albedo only.  Image I/O
@@ -172,59 +177,104 @@ def rotate_light(light: CubemapLight, rotations) -> List[CubemapLight]:
     return out
 
 
-class _ViewGraph:
-    """What Relighter and MultiRelighter share: reusable scratch planes, the fused rasterizer + G-buffer post, and the
-    replay of a whole view from one hipGraph under asynchronous binning."""
+# ---- the G-buffer ---------------------------------------------------------------------------------------------------------
+# A G-buffer is a dict of planes on one device, made by a source (SplatGBuffer here, mesh_render.MeshGBuffer) and read, never
+# written, by everything behind it.  [C,H,W] float32 unless noted:
+#
+#     radii          [P] int32, the Gaussians' screen radii, or None (a mesh)        the result
+#     depth_map      [1,H,W]                                                        the result
+#     occlusion      [1,H,W] SSAO                                                   shade; the result
+#     albedo_map     [3,H,W]                                                        shade (times the albedo ratio), SSR
+#     roughness_map  [1,H,W]                                                        shade, SSR, finish
+#     metallic_map   [1,H,W]                                                        shade (metallic=True), fused_f0
+#     depth_pos      [3,H,W] view-space positions from the filtered depth           SSR
+#     normals_view   [3,H,W] the shading normal, gigs_gbuffer_post's                shade; the result's normal_map
+#     onv            [3,H,W] the view-space normal the march reflects about         SSR
+#     mask_u8        [H,W] uint8, pixels with a normal                              shade; the result's normal_mask
+#     mask_f         [1,H,W] the same as floats                                     finish
+#     F0             [3,H,W] fused_f0's                                             SSR
+#     metallic_in    [1,H,W] fused_f0's: the metallic plane SSR receives            SSR, finish
+#     extra          {name: plane} copied into every relighter's result unchanged: empty for splats; tri_id, opacity_map,
+#                    albedo_map, roughness_map and metallic_map for a mesh
+class Scratch(dict):
+    """Named planes reused from view to view: scratch(name, shape, dtype, dev) allocates on the first use and when the shape
+    or the device changed."""
 
-    def _init_view(self, gi: Dict, sh_degree: int, metallic: bool, graphs: bool) -> None:
-        self.gi, self.sh_degree, self.metallic = gi, sh_degree, bool(metallic)
-        self.graphs = bool(graphs)
-        self._graph = self._graph_key = self._bin = None
-        self._capacity = 0
-        self._scratch = {}
-
-    def _buf(self, name, shape, dtype, dev):
-        t = self._scratch.get(name)
+    def __call__(self, name, shape, dtype, dev):
+        t = self.get(name)
         if t is None or tuple(t.shape) != tuple(shape) or t.device != dev:
-            t = self._scratch[name] = torch.empty(shape, dtype=dtype, device=dev)
+            t = self[name] = torch.empty(shape, dtype=dtype, device=dev)
         return t
 
-    def _gbuffer(self, cam, g):
-        """The rasterizer (inference, derived normals, SSAO) and gigs_gbuffer_post, then relight.py:236-240's F0 branch."""
-        dev = g["means3D"].device
-        background = torch.zeros(3, device=dev)
+
+def fused_f0(albedo_map, roughness_map, metallic_map, metallic: bool):
+    """relight.py:236-240 as the fused paths form it -> (F0, metallic_in).  The branches are the reference's, swapped as they
+    are there: metallic=True gives F0 = 0.04 and a zero metallic plane."""
+    if metallic:
+        return torch.full_like(albedo_map, 0.04), torch.zeros_like(roughness_map)
+    return torch.addcmul(torch.full_like(albedo_map, (1.0 - float(metallic)) * 0.04), albedo_map, metallic_map), metallic_map
+
+
+def gbuffer_from_planes(planes: Dict, viewmatrix: torch.Tensor, metallic: bool, scratch: Scratch) -> Dict:
+    """The G-buffer of a rasterizer's planes (by mesh_render.mesh_planes' names: depth_map, normal_map, occlusion_map,
+    albedo_map, roughness_map, metallic_map, out_normal_view, depth_pos, and radii where there are any): gigs_gbuffer_post into
+    `scratch`'s planes, then fused_f0.  viewmatrix: [4,4] float32, contiguous, on the planes' device."""
+    albedo_map, roughness_map, metallic_map = planes["albedo_map"], planes["roughness_map"], planes["metallic_map"]
+    if not albedo_map.is_cuda:
+        raise RuntimeError("gbuffer_from_planes needs CUDA/HIP tensors: gigs-hip has no CPU path")
+    dev = albedo_map.device
+    _, H, W = albedo_map.shape
+    normals_view, onv = scratch("normals_view", (3, H, W), torch.float32, dev), scratch("onv", (3, H, W), torch.float32, dev)
+    mask_u8, mask_f = scratch("mask_u8", (H, W), torch.uint8, dev), scratch("mask_f", (1, H, W), torch.float32, dev)
+    with torch.cuda.device(dev):
+        gigs_lib.check(_lib.gigs_gbuffer_post(H, W, planes["normal_map"].data_ptr(), planes["out_normal_view"].data_ptr(),
+                                              viewmatrix.data_ptr(), normals_view.data_ptr(), mask_u8.data_ptr(),
+                                              mask_f.data_ptr(), onv.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                       "gbuffer_post")
+        F0, metallic_in = fused_f0(albedo_map, roughness_map, metallic_map, metallic)
+    return dict(radii=planes.get("radii"), depth_map=planes["depth_map"], occlusion=planes["occlusion_map"],
+                albedo_map=albedo_map, roughness_map=roughness_map, metallic_map=metallic_map, depth_pos=planes["depth_pos"],
+                normals_view=normals_view, onv=onv, mask_u8=mask_u8, mask_f=mask_f, F0=F0, metallic_in=metallic_in, extra={})
+
+
+class SplatGBuffer:
+    """The G-buffer of Gaussians: source(cam, g) runs the rasterizer (inference, derived normals, SSAO) and
+    gbuffer_from_planes.  The source owns the scratch planes of its result, which is valid until its next call."""
+    replayable = True  # a view over it can be captured into a hipGraph (ViewReplay, keyed on the Gaussian tensors)
+
+    def __init__(self, gi: Dict, sh_degree: int, metallic: bool = False):
+        self.gi, self.sh_degree, self.metallic = gi, sh_degree, bool(metallic)
+        self._scratch = Scratch()
+
+    @torch.no_grad()
+    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor]) -> Dict:
+        background = torch.zeros(3, device=g["means3D"].device)
         (out, _, st) = pipeline.rasterize(cam, g, self.sh_degree, background, self.gi, inference=True, derive_normal=True)
         (_, radii, _, depth_map, _, normal_map, occlusion, albedo_map, roughness_map, metallic_map, out_normal_view,
          depth_pos) = out
-        H, W = cam["image_height"], cam["image_width"]
-        new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
-        normals_view, onv = new("normals_view", 3, H, W), new("onv", 3, H, W)
-        mask_u8 = self._buf("mask_u8", (H, W), torch.uint8, dev)
-        mask_f = new("mask_f", 1, H, W)
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        vm = st.viewmatrix.contiguous().float()
-        with torch.cuda.device(dev):
-            s = torch.cuda.current_stream().cuda_stream
-            gigs_lib.check(_lib.gigs_gbuffer_post(H, W, p(normal_map), p(out_normal_view), p(vm), p(normals_view), p(mask_u8),
-                                                  p(mask_f), p(onv), s), "gbuffer_post")
-            if self.metallic:
-                F0 = torch.full_like(albedo_map, 0.04)
-                metallic_in = torch.zeros_like(roughness_map)
-            else:
-                F0 = torch.addcmul(torch.full_like(albedo_map, (1.0 - float(self.metallic)) * 0.04), albedo_map, metallic_map)
-                metallic_in = metallic_map
-        return dict(radii=radii, depth_map=depth_map, occlusion=occlusion, albedo_map=albedo_map,
-                    roughness_map=roughness_map, metallic_map=metallic_map, depth_pos=depth_pos, normals_view=normals_view,
-                    onv=onv, mask_u8=mask_u8, mask_f=mask_f, F0=F0, metallic_in=metallic_in)
+        planes = dict(radii=radii, depth_map=depth_map, normal_map=normal_map, occlusion_map=occlusion, albedo_map=albedo_map,
+                      roughness_map=roughness_map, metallic_map=metallic_map, out_normal_view=out_normal_view,
+                      depth_pos=depth_pos)
+        return gbuffer_from_planes(planes, st.viewmatrix.contiguous().float(), self.metallic, self._scratch)
 
-    def _replay(self, cam, g, inputs, core, names, key_extra=None, on_capture=None):
+
+class ViewReplay:
+    """A whole view of Gaussians replayed from one hipGraph under asynchronous binning; its owner closes it."""
+
+    def __init__(self, sh_degree: int, who: str):
+        self.sh_degree, self.who = sh_degree, who
+        self._graph = self._key = self._bin = None
+        self._capacity = 0
+
+    def __call__(self, cam, g, inputs, core, names, key_extra=None, on_capture=None):
         """Replay the view graph of core(cam, *inputs) -> tuple named `names`, capturing it first (under asynchronous
         binning) when the image, the field of view, the Gaussian tensors or key_extra changed; the camera pose and
-        `inputs` are the graph's inputs.  on_capture() runs after every capture (the warm-up runs are real runs)."""
+        `inputs` are the graph's inputs, and whatever else core needs (the Gaussians) it captures itself.  on_capture() runs
+        after every capture (the warm-up runs are real runs)."""
         from diff_gaussian_rasterization import AsyncBinning, BinningOverflow
         key = (pipeline.camera_model(cam), tuple(sorted((k, v.data_ptr()) for k, v in g.items())), key_extra)
         for _ in range(4):
-            if self._graph is None or self._graph_key != key:
+            if self._graph is None or self._key != key:
                 if self._capacity <= 0:
                     self._capacity = pipeline.first_capacity(cam, g, self.sh_degree, inference=True)
                 self._bin = AsyncBinning(self._capacity, g["means3D"].device)
@@ -236,7 +286,7 @@ class _ViewGraph:
                 with self._bin:
                     self._graph = pipeline._graphed_inference(pose_core, (cam["viewmatrix"], cam["projmatrix"],
                                                                           cam["campos"], *inputs))
-                self._graph_key = key
+                self._key = key
                 if on_capture is not None:
                     on_capture()
             out = dict(zip(names, self._graph(cam["viewmatrix"], cam["projmatrix"], cam["campos"], *inputs)))
@@ -247,68 +297,168 @@ class _ViewGraph:
             except BinningOverflow as ex:
                 self._capacity = pipeline.grown_capacity(ex.needed)
                 self.close()
-        raise RuntimeError(f"{type(self).__name__}: the binning capacity kept overflowing")
+        raise RuntimeError(f"{self.who}: the binning capacity kept overflowing")
 
     def close(self) -> None:
         """Release the view graph with the device idle before and after (see pipeline.WholeStepGraph._drop_graphs)."""
         if self._graph is not None:
             torch.cuda.synchronize()
-            self._graph = self._graph_key = None
+            self._graph = self._key = None
             torch.cuda.synchronize()
 
-    @staticmethod
-    def _albedo_shade(albedo_map, albedo_ratio):
-        """relight.py:203-220: the albedo ratio scales the shade's albedo only."""
-        if albedo_ratio is None:
-            return albedo_map
-        return albedo_map * torch.as_tensor(albedo_ratio, dtype=torch.float32, device=albedo_map.device)[:, None, None]
+
+def _gi_args(cam: Dict, gi: Dict):
+    """(W, H, fx, fy, radius, bias, thick, delta, step, start): the screen-space march's arguments."""
+    H, W = cam["image_height"], cam["image_width"]
+    return (W, H, float(W / (2.0 * cam["tanfovx"])), float(H / (2.0 * cam["tanfovy"])), float(gi["radius"]),
+            float(gi["bias"]), float(gi["thick"]), float(gi["delta"]), int(gi["step"]), int(gi["start"]))
 
 
-class Relighter(_ViewGraph):
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def shade_ssr(light: CubemapLight, brdf_lut, gi: Dict, metallic: bool, tone: bool, gamma: bool, cam: Dict, view_dirs, b: Dict,
+              albedo_shade, scratch: Scratch, parts: bool = False):
+    """The launches behind a G-buffer `b` under one light: shade (planar, with the sRGB->linear epilogue) of albedo_shade, SSR
+    with b's F0 / metallic_in, then render_rgb = render_direct + median3x3(linear_to_srgb(IRR)) -> (render_direct, IRR,
+    render_rgb).  Of `b` it reads the planes that the table above gives to shade, SSR and finish, so
+    evaluate.NovelViewEvaluator hands it its own (the pad_normal post, render.py's F0 branch).  parts=True also has the shade
+    write pbr_shading's diffuse_rgb and specular_rgb [3,H,W] and returns them behind the three planes."""
+    albedo_map, roughness_map = b["albedo_map"], b["roughness_map"]
+    dev = albedo_map.device
+    H, W = cam["image_height"], cam["image_width"]
+    render_direct, linear_rgb = torch.empty((3, H, W), device=dev), scratch("linear_rgb", (3, H, W), torch.float32, dev)
+    render_rgb = torch.empty((3, H, W), device=dev)
+    acc, loss = scratch("acc", (4 + 4 * 256,), torch.float32, dev), scratch("loss", (1,), torch.float32, dev)
+    diffuse_rgb, specular_rgb = (torch.empty((3, H, W), device=dev) for _ in range(2)) if parts else (None, None)
+    spec = [s.contiguous() for s in light.specular]
+    spec_ptr = _ptr_array(spec)
+    spec_res = (C.c_int * len(spec))(*[int(s.shape[1]) for s in spec])
+    lut = brdf_lut
+    ext = gigs_lib.ShadeExt(planar=1, rough_scale=1.0, rough_bias=0.0, out_linear=_p(linear_rgb))
+    vd = view_dirs.contiguous().float()
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream().cuda_stream
+        gigs_lib.check(_lib.gigs_shade_fwd_ex(
+            gigs_lib.ctx_ptr(), H, W, _p(b["normals_view"]), _p(vd), _p(albedo_shade), _p(roughness_map), _p(b["mask_u8"]),
+            _p(b["occlusion"]), _p(b["metallic_map"]) if metallic else None, None, _p(light.diffuse), int(light.diffuse.shape[1]),
+            len(spec), spec_ptr, spec_res, _p(lut), int(lut.shape[-2]), int(lut.shape[-3]), int(tone), int(gamma),
+            _p(render_direct), _p(diffuse_rgb), _p(specular_rgb), None, C.addressof(ext), s), "shade_fwd_ex")
+        IRR, _ = _ops.SSR(W, H, W / (2.0 * cam["tanfovx"]), H / (2.0 * cam["tanfovy"]), gi["radius"], gi["bias"],
+                          gi["thick"], gi["delta"], gi["step"], gi["start"], b["onv"], b["depth_pos"], linear_rgb, albedo_map,
+                          roughness_map, b["metallic_in"], b["F0"])
+        # render_rgb = render_direct + median3x3(linear_to_srgb(IRR)); the loss this entry point also forms is unused
+        gigs_lib.check(_lib.gigs_stage2_loss_fwd(H, W, _p(render_direct), _p(IRR), _p(render_direct), _p(b["mask_f"]),
+                                                 _p(roughness_map), _p(b["metallic_in"]), _p(render_rgb), _p(acc), _p(loss), s),
+                       "stage2_loss_fwd")
+    if parts:
+        return render_direct, IRR, render_rgb, diffuse_rgb, specular_rgb
+    return render_direct, IRR, render_rgb
+
+
+MAX_LIGHTS = 16  # GIGS_MAX_LIGHTS (include/gigs_hip.h)
+RESULT_NAMES = ("render_rgb", "render_direct", "IRR", "occlusion", "depth_map", "normal_map", "normal_mask", "radii")
+
+
+def _albedo_shade(albedo_map, albedo_ratio):
+    """relight.py:203-220: the albedo ratio scales the shade's albedo only."""
+    if albedo_ratio is None:
+        return albedo_map
+    return albedo_map * torch.as_tensor(albedo_ratio, dtype=torch.float32, device=albedo_map.device)[:, None, None]
+
+
+def _result(b: Dict, render_rgb, render_direct, IRR, alpha_mask) -> Dict:
+    """What every relighter returns for the G-buffer `b`: RESULT_NAMES and b's extra planes."""
+    if alpha_mask is not None:
+        render_rgb = render_rgb * alpha_mask
+    return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=b["occlusion"],
+                depth_map=b["depth_map"], normal_map=b["normals_view"], normal_mask=b["mask_u8"].bool()[None],
+                radii=b["radii"], **b.get("extra", {}))
+
+
+def _check_lights(who: str, lights) -> None:
+    res = {tuple(l.base.shape) for l in lights}
+    if len(res) != 1:
+        raise ValueError(f"{who}: the lights differ in base resolution: {sorted(res)}")
+
+
+def _build_lights(who: str, lights) -> None:
+    with torch.no_grad():
+        for light in lights:
+            light.build_mips()  # relight.py:141: once per run and light
+    levels = {tuple(int(s.shape[1]) for s in l.specular) for l in lights}
+    if len(levels) != 1 or len({int(l.diffuse.shape[1]) for l in lights}) != 1:
+        raise ValueError(f"{who}: the lights' mip chains differ in level count or resolution")
+
+
+class _Relighter:
+    """What the relighters share: the shading settings, a G-buffer source (SplatGBuffer unless one is given), scratch planes
+    of their own and a ViewReplay.  rl(cam, scene, ...) is rl.from_gbuffer(cam, rl.source(cam, scene), ...), replayed from one
+    hipGraph with graphs=True; a subclass says in from_gbuffer what is done with a G-buffer."""
+
+    def __init__(self, who, lights, gi, sh_degree, metallic, tone, gamma, brdf_lut, graphs, source):
+        _check_lights(who, lights)
+        self.gi, self.sh_degree, self.metallic = gi, sh_degree, bool(metallic)
+        self.tone, self.gamma = bool(tone), bool(gamma)
+        self.source = SplatGBuffer(gi, sh_degree, metallic) if source is None else source
+        if self.source.metallic != self.metallic:
+            raise ValueError(f"{who}: the source forms F0 for metallic={self.source.metallic}")
+        if graphs and not self.source.replayable:
+            raise ValueError(f"{who}: a view over {type(self.source).__name__} replays no hipGraph (the replay is keyed on "
+                             "Gaussian tensors): graphs=False only")
+        self.graphs = bool(graphs)
+        self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(lights[0].base.device)
+        self._scratch = Scratch()
+        self._view = ViewReplay(sh_degree, who)
+        _build_lights(who, lights)
+
+    def __call__(self, cam: Dict, scene, view_dirs: torch.Tensor, alpha_mask: Optional[torch.Tensor] = None,
+                 albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        """`scene` is what the source takes: the Gaussians' tensors, or a mesh_render.MeshRasterizer.  The source and
+        from_gbuffer run without autograd on their own."""
+        if self.graphs:
+            try:
+                def core(c, vd):  # the graph's inputs are the pose and the view directions; the scene is baked in
+                    o = self.from_gbuffer(c, self.source(c, scene), vd, None, albedo_ratio)
+                    return tuple(o[n] for n in RESULT_NAMES)
+
+                out = self._view(cam, scene, (view_dirs,), core, RESULT_NAMES,
+                                 None if albedo_ratio is None else tuple(albedo_ratio))
+                if alpha_mask is not None:
+                    out["render_rgb"] = out["render_rgb"] * alpha_mask
+                return out
+            except pipeline.DenseScene:
+                self.graphs = False
+        return self.from_gbuffer(cam, self.source(cam, scene), view_dirs, alpha_mask, albedo_ratio)
+
+    def close(self) -> None:
+        self._view.close()
+
+
+class Relighter(_Relighter):
     """render_set (relight.py:113-251) without the file I/O: build_mips once, then one call per view."""
 
     def __init__(self, light: CubemapLight, gi: Dict, sh_degree: int, metallic: bool = False, tone: bool = False,
                  gamma: bool = False, fused: bool = True, pad_normal: bool = False, brdf_lut: Optional[torch.Tensor] = None,
-                 graphs: bool = False):
+                 graphs: bool = False, source=None):
         """graphs=True (with fused): the whole view -- rasterizer under asynchronous binning, filters, SSAO, shade, SSR,
         sRGB / median / sum -- is captured once into ONE hipGraph and replayed per view (camera pose and view
         directions are its inputs; image size, field of view, GI settings and the Gaussian tensors are baked in).  The
         tensors it returns are the graph's static outputs: consume them before the next call."""
         self.light = light
-        self.tone, self.gamma = bool(tone), bool(gamma)
         self.fused, self.pad_normal = bool(fused) and not pad_normal, bool(pad_normal)
-        self._init_view(gi, sh_degree, metallic, bool(graphs) and self.fused)
-        dev = light.base.device
-        self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(dev)
-        with torch.no_grad():
-            light.build_mips()  # relight.py:141: once per run
+        super().__init__("Relighter", [light], gi, sh_degree, metallic, tone, gamma, brdf_lut, bool(graphs) and self.fused,
+                         source)
 
-    @torch.no_grad()
-    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], view_dirs: torch.Tensor,
-                 alpha_mask: Optional[torch.Tensor] = None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
-        if self.graphs:
-            try:
-                return self._graphed(cam, g, view_dirs, alpha_mask, albedo_ratio)
-            except pipeline.DenseScene:
-                self.graphs = False
-        if self.fused:
-            return self._fused(cam, g, view_dirs, alpha_mask, albedo_ratio)
-        return self._unfused(cam, g, view_dirs, alpha_mask, albedo_ratio)
-
-    # -- the fused sequence replayed from one hipGraph --------------------------------------------------------------
-    def _graphed(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
-        names = ("render_rgb", "render_direct", "IRR", "occlusion", "depth_map", "normal_map", "normal_mask", "radii")
-
-        def core(c, vd):
-            o = self._fused(c, g, vd, None, albedo_ratio)
-            return tuple(o[n] for n in names)
-
-        out = self._replay(cam, g, (view_dirs,), core, names, None if albedo_ratio is None else tuple(albedo_ratio))
-        if alpha_mask is not None:
-            out["render_rgb"] = out["render_rgb"] * alpha_mask
-        return out
+    def __call__(self, cam: Dict, scene, view_dirs: torch.Tensor, alpha_mask: Optional[torch.Tensor] = None,
+                 albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        if not self.fused:
+            return self._unfused(cam, scene, view_dirs, alpha_mask, albedo_ratio)
+        return super().__call__(cam, scene, view_dirs, alpha_mask, albedo_ratio)
 
     # -- the reference's op sequence, operator by operator ------------------------------------------------------
+    @torch.no_grad()
     def _unfused(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
         dev = g["means3D"].device
         gi = self.gi
@@ -328,7 +478,7 @@ class Relighter(_ViewGraph):
         render_direct = torch.where(normal_mask, render_direct, background[:, None, None])
         ssr = Gaussian_SSR(cam["tanfovx"], cam["tanfovy"], W, H, gi["radius"], gi["bias"], gi["thick"], gi["delta"],
                            gi["step"], gi["start"])
-        if self.metallic:  # relight.py:236-240, as written
+        if self.metallic:  # relight.py:236-240, as written: the reference's own spelling, which rounds unlike fused_f0's
             F0 = torch.ones_like(albedo_map) * 0.04
             metallic_in = torch.zeros_like(roughness_map)
         else:
@@ -344,201 +494,29 @@ class Relighter(_ViewGraph):
                     depth_map=r["depth_map"], normal_map=r["normal_map"], normal_mask=normal_mask, radii=r["radii"])
 
     # -- the same arithmetic as five launches behind the rasterizer ----------------------------------------------
-    def _fused(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
-        b = self._gbuffer(cam, g)
-        with torch.cuda.device(b["albedo_map"].device):
-            render_direct, IRR, render_rgb = self._shade_ssr(
-                cam, view_dirs, b["normals_view"], b["mask_u8"], b["mask_f"], b["onv"], b["depth_pos"],
-                self._albedo_shade(b["albedo_map"], albedo_ratio), b["albedo_map"], b["roughness_map"], b["metallic_map"],
-                b["occlusion"], b["F0"], b["metallic_in"])
-        if alpha_mask is not None:
-            render_rgb = render_rgb * alpha_mask
-        return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=b["occlusion"],
-                    depth_map=b["depth_map"], normal_map=b["normals_view"], normal_mask=b["mask_u8"].bool()[None],
-                    radii=b["radii"])
-
-    def _shade_ssr(self, cam, view_dirs, normals_view, mask_u8, mask_f, onv, depth_pos, albedo_shade, albedo_map,
-                   roughness_map, metallic_map, occlusion, F0, metallic_in, parts=False):
-        """The launches after the G-buffer post: shade (planar, with the sRGB->linear epilogue), SSR with the caller's
-        F0 / metallic planes, then render_rgb = render_direct + median3x3(linear_to_srgb(IRR)).  Shared with
-        evaluate.NovelViewEvaluator, whose G-buffer post and F0 branch differ.  parts=True also has the shade write
-        pbr_shading's diffuse_rgb and specular_rgb [3,H,W] and returns them behind the three planes."""
-        dev = albedo_map.device
-        gi = self.gi
-        H, W = cam["image_height"], cam["image_width"]
-        new = lambda name, *shape: self._buf(name, shape, torch.float32, dev)  # noqa: E731
-        render_direct, linear_rgb = torch.empty((3, H, W), device=dev), new("linear_rgb", 3, H, W)
-        render_rgb, acc, loss = torch.empty((3, H, W), device=dev), new("acc", 4 + 4 * 256), new("loss", 1)
-        diffuse_rgb, specular_rgb = (torch.empty((3, H, W), device=dev) for _ in range(2)) if parts else (None, None)
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        light = self.light
-        spec = [s.contiguous() for s in light.specular]
-        spec_ptr = _ptr_array(spec)
-        spec_res = (C.c_int * len(spec))(*[int(s.shape[1]) for s in spec])
-        lut = self.brdf_lut
-        ext = gigs_lib.ShadeExt(planar=1, rough_scale=1.0, rough_bias=0.0, out_linear=p(linear_rgb))
-        vd = view_dirs.contiguous().float()
-        with torch.cuda.device(dev):
-            s = torch.cuda.current_stream().cuda_stream
-            gigs_lib.check(_lib.gigs_shade_fwd_ex(
-                gigs_lib.ctx_ptr(), H, W, p(normals_view), p(vd), p(albedo_shade), p(roughness_map), p(mask_u8), p(occlusion),
-                p(metallic_map) if self.metallic else None, None, p(light.diffuse), int(light.diffuse.shape[1]), len(spec),
-                spec_ptr, spec_res, p(lut), int(lut.shape[-2]), int(lut.shape[-3]), int(self.tone), int(self.gamma),
-                p(render_direct), p(diffuse_rgb), p(specular_rgb), None, C.addressof(ext), s), "shade_fwd_ex")
-            IRR, _ = _ops.SSR(W, H, W / (2.0 * cam["tanfovx"]), H / (2.0 * cam["tanfovy"]), gi["radius"], gi["bias"],
-                              gi["thick"], gi["delta"], gi["step"], gi["start"], onv, depth_pos, linear_rgb, albedo_map,
-                              roughness_map, metallic_in, F0)
-            # render_rgb = render_direct + median3x3(linear_to_srgb(IRR)); the loss this entry point also forms is unused
-            gigs_lib.check(_lib.gigs_stage2_loss_fwd(H, W, p(render_direct), p(IRR), p(render_direct), p(mask_f),
-                                                     p(roughness_map), p(metallic_in), p(render_rgb), p(acc), p(loss), s),
-                           "stage2_loss_fwd")
-        if parts:
-            return render_direct, IRR, render_rgb, diffuse_rgb, specular_rgb
-        return render_direct, IRR, render_rgb
-
-
-MAX_LIGHTS = 16  # GIGS_MAX_LIGHTS (include/gigs_hip.h)
-_MULTI_NAMES = ("render_rgb", "render_direct", "IRR", "occlusion", "depth_map", "normal_map", "normal_mask", "radii")
-
-
-class MultiRelighter(_ViewGraph):
-    """One view under K environment maps (relight_all.bash's list of target maps) at the cost of one G-buffer: the
-    rasterizer, G-buffer post, SSAO and the SSR march do not depend on the light, so they run once; the shade samples the
-    K lights at the same cube taps (gigs_shade_fwd_multi), the march gathers the K radiance planes at the same hits
-    (gigs_ssr_multi), and the finish render_rgb = render_direct + median3x3(linear_to_srgb(IRR)) runs per light.
-    Light k's outputs equal Relighter(lights[k], fused=True)'s bit for bit, with the same reference quirks (module
-    docstring).  render_rgb, render_direct and IRR are [K,3,H,W]; the light-independent planes are returned once.
-
-    graphs=True captures the whole K-light view into one hipGraph, as Relighter(graphs=True) does (same replay, binning
-    and DenseScene fallback); its outputs are the graph's static tensors: consume them before the next call."""
-
-    def __init__(self, lights: Sequence[CubemapLight], gi: Dict, sh_degree: int, metallic: bool = False,
-                 tone: bool = False, gamma: bool = False, graphs: bool = False, brdf_lut: Optional[torch.Tensor] = None):
-        lights = list(lights)
-        if not 1 <= len(lights) <= MAX_LIGHTS:
-            raise ValueError(f"MultiRelighter: 1..{MAX_LIGHTS} lights, got {len(lights)}")
-        _check_lights("MultiRelighter", lights)
-        self.lights = lights
-        self.tone, self.gamma = bool(tone), bool(gamma)
-        self._init_view(gi, sh_degree, metallic, graphs)
-        dev = lights[0].base.device
-        self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(dev)
-        _build_lights("MultiRelighter", lights)
-
     @torch.no_grad()
-    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], view_dirs: torch.Tensor,
-                 alpha_mask: Optional[torch.Tensor] = None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
-        if self.graphs:
-            try:
-                def core(c, vd):
-                    o = self._fused(c, g, vd, None, albedo_ratio)
-                    return tuple(o[n] for n in _MULTI_NAMES)
-
-                out = self._replay(cam, g, (view_dirs,), core, _MULTI_NAMES,
-                                   None if albedo_ratio is None else tuple(albedo_ratio))
-                if alpha_mask is not None:
-                    out["render_rgb"] = out["render_rgb"] * alpha_mask
-                return out
-            except pipeline.DenseScene:
-                self.graphs = False
-        return self._fused(cam, g, view_dirs, alpha_mask, albedo_ratio)
-
-    def _fused(self, cam, g, view_dirs, alpha_mask, albedo_ratio):
-        b = self._gbuffer(cam, g)
-        albedo_map = b["albedo_map"]
-        dev = albedo_map.device
-        gi = self.gi
-        K = len(self.lights)
-        H, W = cam["image_height"], cam["image_width"]
-        render_direct, IRR, render_rgb = (torch.empty((K, 3, H, W), device=dev) for _ in range(3))
-        linear_rgb, abd = self._buf("linear_rgb_k", (K, 3, H, W), torch.float32, dev), self._buf("abd_k", (K, 3, H, W),
-                                                                                                 torch.float32, dev)
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        vd = view_dirs.contiguous().float()
-        scratch = _gi_scratch(W, H, dev)
-        with torch.cuda.device(dev):
-            s = torch.cuda.current_stream().cuda_stream
-            _shade_lights(self, self.lights, H, W, b, vd, self._albedo_shade(albedo_map, albedo_ratio), render_direct,
-                          linear_rgb, s)
-            gigs_lib.check(_lib.gigs_ssr_multi(
-                gigs_lib.ctx_ptr(), K, W, H, float(W / (2.0 * cam["tanfovx"])), float(H / (2.0 * cam["tanfovy"])),
-                float(gi["radius"]), float(gi["bias"]), float(gi["thick"]), float(gi["delta"]), int(gi["step"]),
-                int(gi["start"]), p(b["onv"]), p(b["depth_pos"]), p(linear_rgb), p(albedo_map), p(b["roughness_map"]),
-                p(b["metallic_in"]), p(b["F0"]), p(IRR), p(abd), p(scratch), s), "ssr_multi")
-            _finish_lights(self, H, W, b, render_direct, IRR, render_rgb, s)
-        if alpha_mask is not None:
-            render_rgb = render_rgb * alpha_mask
-        return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=b["occlusion"],
-                    depth_map=b["depth_map"], normal_map=b["normals_view"], normal_mask=b["mask_u8"].bool()[None],
-                    radii=b["radii"])
+    def from_gbuffer(self, cam: Dict, b: Dict, view_dirs: torch.Tensor, alpha_mask: Optional[torch.Tensor] = None,
+                     albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        """Everything after the G-buffer `b` (a source's), which it reads and leaves as it is."""
+        render_direct, IRR, render_rgb = shade_ssr(self.light, self.brdf_lut, self.gi, self.metallic, self.tone, self.gamma,
+                                                   cam, view_dirs, b, _albedo_shade(b["albedo_map"], albedo_ratio),
+                                                   self._scratch)
+        return _result(b, render_rgb, render_direct, IRR, alpha_mask)
 
 
-def _check_lights(who: str, lights) -> None:
-    res = {tuple(l.base.shape) for l in lights}
-    if len(res) != 1:
-        raise ValueError(f"{who}: the lights differ in base resolution: {sorted(res)}")
+class _LightsRelighter(_Relighter):
+    """One view under several lights of equal base resolution: the rasterizer, G-buffer post, SSAO and the SSR march do not
+    depend on the light.  from_gbuffer runs every chunk of up to MAX_LIGHTS lights as one gigs_shade_fwd_multi (the K lights
+    sampled at the same cube taps), one gather of the chunk's radiance -- gigs_ssr_apply_multi at the hits of a march recorded
+    once per view, or gigs_ssr_multi, which marches itself -- and the finish render_rgb = render_direct +
+    median3x3(linear_to_srgb(IRR)) per light.  Light k's outputs equal Relighter(lights[k], fused=True)'s bit for bit, with
+    the same reference quirks (module docstring).  render_rgb, render_direct and IRR are [K,3,H,W]; the light-independent
+    planes are returned once.  `records` (the subclass's) says whether the march is recorded."""
+    records = False
 
-
-def _build_lights(who: str, lights) -> None:
-    with torch.no_grad():
-        for light in lights:
-            light.build_mips()  # relight.py:141: once per run and light
-    levels = {tuple(int(s.shape[1]) for s in l.specular) for l in lights}
-    if len(levels) != 1 or len({int(l.diffuse.shape[1]) for l in lights}) != 1:
-        raise ValueError(f"{who}: the lights' mip chains differ in level count or resolution")
-
-
-def _shade_lights(view, lights, H, W, b, vd, albedo_shade, render_direct, linear_rgb, s) -> None:
-    """gigs_shade_fwd_multi of the G-buffer `b` under `lights` (at most MAX_LIGHTS) into render_direct / linear_rgb [K,3,H,W]."""
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    spec = [[x.contiguous() for x in light.specular] for light in lights]
-    L = len(spec[0])
-    diffuse_ptr = _ptr_array([light.diffuse for light in lights])
-    spec_ptr = _ptr_array([x for chain in spec for x in chain])
-    spec_res = (C.c_int * L)(*[int(x.shape[1]) for x in spec[0]])
-    lut = view.brdf_lut
-    gigs_lib.check(_lib.gigs_shade_fwd_multi(
-        gigs_lib.ctx_ptr(), len(lights), H, W, p(b["normals_view"]), p(vd), p(albedo_shade), p(b["roughness_map"]),
-        p(b["mask_u8"]), p(b["occlusion"]), p(b["metallic_map"]) if view.metallic else None, diffuse_ptr,
-        int(lights[0].diffuse.shape[1]), L, spec_ptr, spec_res, p(lut), int(lut.shape[-2]), int(lut.shape[-3]),
-        int(view.tone), int(view.gamma), p(render_direct), p(linear_rgb), s), "shade_fwd_multi")
-
-
-def _finish_lights(view, H, W, b, render_direct, IRR, render_rgb, s) -> None:
-    """render_rgb[k] = render_direct[k] + median3x3(linear_to_srgb(IRR[k])); the loss gigs_stage2_loss_fwd also forms is unused."""
-    dev = render_direct.device
-    acc, loss = view._buf("acc", (4 + 4 * 256,), torch.float32, dev), view._buf("loss", (1,), torch.float32, dev)
-    p = lambda t: t.data_ptr()  # noqa: E731
-    for k in range(int(render_direct.shape[0])):
-        gigs_lib.check(_lib.gigs_stage2_loss_fwd(H, W, p(render_direct[k]), p(IRR[k]), p(render_direct[k]), p(b["mask_f"]),
-                                                 p(b["roughness_map"]), p(b["metallic_in"]), p(render_rgb[k]), p(acc), p(loss),
-                                                 s), "stage2_loss_fwd")
-
-
-class TurntableRelighter(_ViewGraph):
-    """One view under any number of lights of equal base resolution -- usually rotated_lights(...) of one map, a turntable or
-    a lighting sweep, but any list: only the shade samples and the radiance gathered at the march's hits depend on the light.
-    Per call the rasterizer, G-buffer post and SSAO run once and the SSR march runs once as a recording (gigs_ssr_hits: count,
-    prefix sum, one read-back of the total to size the entries, fill); then every chunk of up to MAX_LIGHTS lights is one
-    gigs_shade_fwd_multi, one gigs_ssr_apply_multi over the recorded hits (the chunk's radiance packed pixel-major first) and the per-light finish.  Outputs are
-    MultiRelighter's with K = len(lights); light k equals Relighter(lights[k], fused=True) bit for bit, quirks included.
-
-    The gather is only launched with a complete list: the total read back is compared with the entries' capacity, and a
-    mismatch (a total beyond 2^31 - 1 wraps the 32-bit prefix) sends the view through gigs_ssr_multi instead.  The hit list
-    exists for the default march only (gi_march = proj, start < step); any other march also takes gigs_ssr_multi per chunk,
-    with the same results.  Eager only (the read-back sizes a buffer): no hipGraph."""
-
-    def __init__(self, lights: Sequence[CubemapLight], gi: Dict, sh_degree: int, metallic: bool = False,
-                 tone: bool = False, gamma: bool = False, brdf_lut: Optional[torch.Tensor] = None):
-        lights = list(lights)
-        if not lights:
-            raise ValueError("TurntableRelighter: no lights")
-        _check_lights("TurntableRelighter", lights)
+    def __init__(self, who, lights, gi, sh_degree, metallic, tone, gamma, brdf_lut, graphs, source):
+        super().__init__(who, lights, gi, sh_degree, metallic, tone, gamma, brdf_lut, graphs, source)
         self.lights = lights
-        self.tone, self.gamma = bool(tone), bool(gamma)
-        self._init_view(gi, sh_degree, metallic, False)
-        self.brdf_lut = (brdf_lut if brdf_lut is not None else get_brdf_lut()).to(lights[0].base.device)
-        _build_lights("TurntableRelighter", lights)
         self._entries = None  # the hit list's {hit pixel, ray} pairs, grown on demand
         self.last_hits = None  # hits of the last view's list, None where it took the march
 
@@ -550,25 +528,23 @@ class TurntableRelighter(_ViewGraph):
 
     def close(self) -> None:
         self._entries = None
-        self._scratch = {}
+        self._scratch.clear()
         super().close()
 
-    def _record_hits(self, cam, b, a, scratch, s):
+    def _record_hits(self, b, a, scratch, s):
         """The march as a recording -> (offsets, entries) of a complete list, or None where there is none to be had."""
-        gi = self.gi
-        if gigs_lib.current().option("gi_march") != 4 or not int(gi["start"]) < int(gi["step"]):
+        if gigs_lib.current().option("gi_march") != 4 or not int(self.gi["start"]) < int(self.gi["step"]):
             return None
         dev = b["albedo_map"].device
-        H, W = cam["image_height"], cam["image_width"]
+        W, H = a[:2]
         n = H * W
-        counts = self._buf("hit_counts", (4 * n,), torch.int32, dev)
-        offsets = self._buf("hit_offsets", (4 * n + 1,), torch.int32, dev)
-        color, abd = self._buf("hit_color", (3, H, W), torch.float32, dev), self._buf("hit_abd", (3, H, W), torch.float32, dev)
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        counts = self._scratch("hit_counts", (4 * n,), torch.int32, dev)
+        offsets = self._scratch("hit_offsets", (4 * n + 1,), torch.int32, dev)
+        color, abd = (self._scratch(name, (3, H, W), torch.float32, dev) for name in ("hit_color", "hit_abd"))
         # which pixel a ray hits does not depend on the radiance: any plane serves the recording passes, their outputs are unused
-        planes = (p(b["onv"]), p(b["depth_pos"]), p(b["albedo_map"]), p(b["albedo_map"]), p(b["roughness_map"]),
-                  p(b["metallic_in"]), p(b["F0"]), p(color), p(abd))
-        if _lib.gigs_ssr_hits(gigs_lib.ctx_ptr(), *a, *planes, 1, p(counts), None, None, 0, p(scratch), s) != 0:
+        planes = (_p(b["onv"]), _p(b["depth_pos"]), _p(b["albedo_map"]), _p(b["albedo_map"]), _p(b["roughness_map"]),
+                  _p(b["metallic_in"]), _p(b["F0"]), _p(color), _p(abd))
+        if _lib.gigs_ssr_hits(gigs_lib.ctx_ptr(), *a, *planes, 1, _p(counts), None, None, 0, _p(scratch), s) != 0:
             return None  # a march without a hit list (more steps than the projective march's table holds)
         offsets[:1].zero_()
         torch.cumsum(counts, 0, dtype=torch.int32, out=offsets[1:])
@@ -580,54 +556,100 @@ class TurntableRelighter(_ViewGraph):
         capacity = int(self._entries.shape[0])
         if total > capacity:
             return None
-        gigs_lib.check(_lib.gigs_ssr_hits(gigs_lib.ctx_ptr(), *a, *planes, 2, None, p(offsets), p(self._entries), capacity,
-                                          p(scratch), s), "ssr_hits (fill)")
+        gigs_lib.check(_lib.gigs_ssr_hits(gigs_lib.ctx_ptr(), *a, *planes, 2, None, _p(offsets), _p(self._entries), capacity,
+                                          _p(scratch), s), "ssr_hits (fill)")
         self.last_hits = total
         return offsets, self._entries
 
     @torch.no_grad()
-    def __call__(self, cam: Dict, g: Dict[str, torch.Tensor], view_dirs: torch.Tensor,
-                 alpha_mask: Optional[torch.Tensor] = None, albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
-        b = self._gbuffer(cam, g)
+    def from_gbuffer(self, cam: Dict, b: Dict, view_dirs: torch.Tensor, alpha_mask: Optional[torch.Tensor] = None,
+                     albedo_ratio: Optional[Sequence[float]] = None) -> Dict:
+        """Everything after the G-buffer `b` (a source's), which it reads and leaves as it is."""
         albedo_map = b["albedo_map"]
         dev = albedo_map.device
-        gi = self.gi
         N = len(self.lights)
         H, W = cam["image_height"], cam["image_width"]
         render_direct, IRR, render_rgb = (torch.empty((N, 3, H, W), device=dev) for _ in range(3))
         Kmax = min(N, MAX_LIGHTS)
-        linear_rgb = self._buf("linear_rgb_k", (Kmax, 3, H, W), torch.float32, dev)
-        abd = self._buf("abd_k", (Kmax, 3, H, W), torch.float32, dev)
-        packed = self._buf("packed_rgb", (max(16, int(_lib.gigs_ssr_apply_multi_scratch_bytes(Kmax, W, H))),), torch.uint8, dev)
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        linear_rgb = self._scratch("linear_rgb_k", (Kmax, 3, H, W), torch.float32, dev)
+        abd = self._scratch("abd_k", (Kmax, 3, H, W), torch.float32, dev)
+        acc, loss = self._scratch("acc", (4 + 4 * 256,), torch.float32, dev), self._scratch("loss", (1,), torch.float32, dev)
         vd = view_dirs.contiguous().float()
-        albedo_shade = self._albedo_shade(albedo_map, albedo_ratio)
+        albedo_shade = _albedo_shade(albedo_map, albedo_ratio)
         scratch = _gi_scratch(W, H, dev)
-        a = (W, H, float(W / (2.0 * cam["tanfovx"])), float(H / (2.0 * cam["tanfovy"])), float(gi["radius"]),
-             float(gi["bias"]), float(gi["thick"]), float(gi["delta"]), int(gi["step"]), int(gi["start"]))
+        a = _gi_args(cam, self.gi)
+        lut = self.brdf_lut
         self.last_hits = None
         with torch.cuda.device(dev):
             s = torch.cuda.current_stream().cuda_stream
-            hits = self._record_hits(cam, b, a, scratch, s)
+            hits = packed = None
+            if self.records:
+                hits = self._record_hits(b, a, scratch, s)
+            if hits is not None:
+                packed = self._scratch("packed_rgb", (max(16, int(_lib.gigs_ssr_apply_multi_scratch_bytes(Kmax, W, H))),),
+                                       torch.uint8, dev)
             for first in range(0, N, MAX_LIGHTS):
                 chunk = self.lights[first:first + MAX_LIGHTS]
                 K = len(chunk)
-                rd, irr = render_direct[first:first + K], IRR[first:first + K]
-                _shade_lights(self, chunk, H, W, b, vd, albedo_shade, rd, linear_rgb[:K], s)
+                rd, irr, rgb = render_direct[first:first + K], IRR[first:first + K], render_rgb[first:first + K]
+                spec = [[x.contiguous() for x in light.specular] for light in chunk]
+                L = len(spec[0])
+                gigs_lib.check(_lib.gigs_shade_fwd_multi(
+                    gigs_lib.ctx_ptr(), K, H, W, _p(b["normals_view"]), _p(vd), _p(albedo_shade), _p(b["roughness_map"]),
+                    _p(b["mask_u8"]), _p(b["occlusion"]), _p(b["metallic_map"]) if self.metallic else None,
+                    _ptr_array([light.diffuse for light in chunk]), int(chunk[0].diffuse.shape[1]), L,
+                    _ptr_array([x for chain in spec for x in chain]), (C.c_int * L)(*[int(x.shape[1]) for x in spec[0]]),
+                    _p(lut), int(lut.shape[-2]), int(lut.shape[-3]), int(self.tone), int(self.gamma), _p(rd), _p(linear_rgb), s),
+                    "shade_fwd_multi")
                 if hits is not None:
                     gigs_lib.check(_lib.gigs_ssr_apply_multi(
-                        K, W, H, float(gi["delta"]), p(hits[0]), p(hits[1]), p(b["onv"]), p(b["depth_pos"]), p(linear_rgb),
-                        p(albedo_map), p(b["metallic_in"]), p(b["F0"]), p(irr), p(abd), p(packed), s), "ssr_apply_multi")
+                        K, W, H, float(self.gi["delta"]), _p(hits[0]), _p(hits[1]), _p(b["onv"]), _p(b["depth_pos"]), _p(linear_rgb), _p(albedo_map),
+                        _p(b["metallic_in"]), _p(b["F0"]), _p(irr), _p(abd), _p(packed), s), "ssr_apply_multi")
                 else:
                     gigs_lib.check(_lib.gigs_ssr_multi(
-                        gigs_lib.ctx_ptr(), K, *a, p(b["onv"]), p(b["depth_pos"]), p(linear_rgb), p(albedo_map),
-                        p(b["roughness_map"]), p(b["metallic_in"]), p(b["F0"]), p(irr), p(abd), p(scratch), s), "ssr_multi")
-                _finish_lights(self, H, W, b, rd, irr, render_rgb[first:first + K], s)
-        if alpha_mask is not None:
-            render_rgb = render_rgb * alpha_mask
-        return dict(render_rgb=render_rgb, render_direct=render_direct, IRR=IRR, occlusion=b["occlusion"],
-                    depth_map=b["depth_map"], normal_map=b["normals_view"], normal_mask=b["mask_u8"].bool()[None],
-                    radii=b["radii"])
+                        gigs_lib.ctx_ptr(), K, *a, _p(b["onv"]), _p(b["depth_pos"]), _p(linear_rgb), _p(albedo_map),
+                        _p(b["roughness_map"]), _p(b["metallic_in"]), _p(b["F0"]), _p(irr), _p(abd), _p(scratch), s), "ssr_multi")
+                for k in range(K):  # the finish; the loss gigs_stage2_loss_fwd also forms is unused
+                    gigs_lib.check(_lib.gigs_stage2_loss_fwd(H, W, _p(rd[k]), _p(irr[k]), _p(rd[k]), _p(b["mask_f"]),
+                                                             _p(b["roughness_map"]), _p(b["metallic_in"]), _p(rgb[k]), _p(acc),
+                                                             _p(loss), s), "stage2_loss_fwd")
+        return _result(b, render_rgb, render_direct, IRR, alpha_mask)
+
+
+class MultiRelighter(_LightsRelighter):
+    """One view under K <= MAX_LIGHTS environment maps (relight_all.bash's list of target maps) at the cost of one G-buffer
+    and one march (gigs_ssr_multi gathers the K radiance planes at the same hits); see _LightsRelighter.
+
+    graphs=True captures the whole K-light view into one hipGraph, as Relighter(graphs=True) does (same replay, binning
+    and DenseScene fallback); its outputs are the graph's static tensors: consume them before the next call."""
+
+    def __init__(self, lights: Sequence[CubemapLight], gi: Dict, sh_degree: int, metallic: bool = False,
+                 tone: bool = False, gamma: bool = False, graphs: bool = False, brdf_lut: Optional[torch.Tensor] = None,
+                 source=None):
+        lights = list(lights)
+        if not 1 <= len(lights) <= MAX_LIGHTS:
+            raise ValueError(f"MultiRelighter: 1..{MAX_LIGHTS} lights, got {len(lights)}")
+        super().__init__("MultiRelighter", lights, gi, sh_degree, metallic, tone, gamma, brdf_lut, graphs, source)
+
+
+class TurntableRelighter(_LightsRelighter):
+    """One view under any number of lights -- usually rotated_lights(...) of one map, a turntable or a lighting sweep, but any
+    list: only the shade samples and the radiance gathered at the march's hits depend on the light.  Per call the SSR march
+    runs once as a recording (gigs_ssr_hits: count, prefix sum, one read-back of the total to size the entries, fill) and
+    every chunk gathers at the recorded hits (the chunk's radiance packed pixel-major first); see _LightsRelighter.
+
+    The gather is only launched with a complete list: the total read back is compared with the entries' capacity, and a
+    mismatch (a total beyond 2^31 - 1 wraps the 32-bit prefix) sends the view through gigs_ssr_multi instead.  The hit list
+    exists for the default march only (gi_march = proj, start < step); any other march also takes gigs_ssr_multi per chunk,
+    with the same results.  Eager only (the read-back sizes a buffer): no hipGraph."""
+    records = True
+
+    def __init__(self, lights: Sequence[CubemapLight], gi: Dict, sh_degree: int, metallic: bool = False,
+                 tone: bool = False, gamma: bool = False, brdf_lut: Optional[torch.Tensor] = None, source=None):
+        lights = list(lights)
+        if not lights:
+            raise ValueError("TurntableRelighter: no lights")
+        super().__init__("TurntableRelighter", lights, gi, sh_degree, metallic, tone, gamma, brdf_lut, False, source)
 
 
 def quantize_8bit(x: torch.Tensor) -> torch.Tensor:

@@ -42,8 +42,6 @@ if __package__ in (None, ""):  # run as a script: make the package's modules imp
 
 import render_scene as rs  # noqa: E402
 
-MAX_LIGHTS = 16  # relight.MAX_LIGHTS
-
 
 def rotated_names(names: Sequence[str], rotations: int) -> List[str]:
     """The light names of a run: the maps' own, or <light>_r000 .. per map with --rotations N."""
@@ -133,6 +131,7 @@ def relight_split(args: Namespace, split: str, infos, g, sh_degree: int, lights,
     gi = {k: getattr(args, k) for k in rs.GI_FLAGS}
     lut = pbr.get_brdf_lut().to(dev)
     res: Dict = {"n_views": len(infos), "lights": list(names)}
+    MAX_LIGHTS = relight.MAX_LIGHTS
     t0 = time.perf_counter()
     with image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
         tr = relight.TurntableRelighter(lights, gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,

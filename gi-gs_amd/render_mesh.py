@@ -85,20 +85,6 @@ def _check(args: Namespace) -> int:
     return n_rot
 
 
-def _splat_relighter():
-    import relight
-
-    class SplatRelighter(relight.Relighter):
-        """relight.Relighter that keeps the albedo plane of its last view (the result holds none)."""
-
-        def _gbuffer(self, cam, g):
-            b = super()._gbuffer(cam, g)
-            self.albedo_map = b["albedo_map"]
-            return b
-
-    return SplatRelighter
-
-
 def render_mesh(args) -> Dict:
     """`args`: a Namespace from parse_args, a dict of overrides or an argv list."""
     import render_scene as rs
@@ -114,7 +100,6 @@ def render_mesh(args) -> Dict:
     import pipeline
     import relight
     import trainer
-    _SplatRelighter = _splat_relighter()
     checkpoint = args.checkpoint
     if not checkpoint:  # combine_args takes the output folder from the checkpoint's place where -m is missing: not needed here
         args = Namespace(**dict(vars(args), checkpoint=os.path.join(args.model_path, "none")))
@@ -163,7 +148,7 @@ def render_mesh(args) -> Dict:
             res.update(vertices=rast.V, faces=rast.F)
             tr = mesh_render.MeshTurntableRelighter(lights, gi, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
                                                     brdf_lut=lut)
-            splat = _SplatRelighter(lights[0], gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
+            splat = relight.Relighter(lights[0], gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
                                       brdf_lut=lut) if args.compare else None
             try:
                 rays = None
@@ -183,7 +168,8 @@ def render_mesh(args) -> Dict:
                     for first in range(0, len(relit), relight.MAX_LIGHTS):
                         wr.submit(relit[first:first + relight.MAX_LIGHTS])
                     if splat is not None:
-                        s = splat(c, g, vd)
+                        b = splat.source(c, g)  # the relighter's result holds no albedo plane: the G-buffer does
+                        s = splat.from_gbuffer(c, b, vd)
                         both = (o["tri_id"] >= 0) & (s["depth_map"][0] > 0)
                         n_both = both.sum()
                         ddepth = ((o["depth_map"][0] - s["depth_map"][0]).abs() * both).sum() / n_both.clamp(min=1)
@@ -191,7 +177,7 @@ def render_mesh(args) -> Dict:
                             image_name=ci.image_name,
                             relit=evaluate.image_metrics(o["render_rgb"][0].nan_to_num().clamp(0, 1),
                                                          s["render_rgb"].nan_to_num().clamp(0, 1)),
-                            albedo=evaluate.image_metrics(o["albedo_map"], splat.albedo_map), depth=ddepth, both=n_both))
+                            albedo=evaluate.image_metrics(o["albedo_map"], b["albedo_map"]), depth=ddepth, both=n_both))
             finally:
                 tr.close()
                 if splat is not None:

@@ -51,7 +51,7 @@ def gbuf():
     import relight
     sc, cam, envs, lights, g = _case(1)
     rl = relight.Relighter(lights[0], scenes.GI_DEFAULTS, 2)
-    b = rl._gbuffer(cam_t(cam), g)
+    b = rl.source(cam_t(cam), g)
     torch.cuda.synchronize()
     return cam, b, lights[0], rl
 

@@ -124,8 +124,7 @@ def gbuf():
     import relight
     sc, _, envs, lights, g = _case(1)
     cam = _camera()
-    rl = relight.Relighter(lights[0], scenes.GI_DEFAULTS, 2)
-    b = rl._gbuffer(cam_t(cam), g)
+    b = relight.SplatGBuffer(scenes.GI_DEFAULTS, 2)(cam_t(cam), g)
     torch.cuda.synchronize()
     return cam, b
 

@@ -57,3 +57,35 @@ def test_multi_relighter_rejects_mismatched_lights_on_cpu():
     with pytest.raises(ValueError):
         relight.MultiRelighter([a] * 17, {}, 2)
     assert not hasattr(a, "specular") and not hasattr(b, "specular")  # no mips were built
+
+
+def _planes(seed=0):
+    gen = torch.Generator().manual_seed(seed)
+    return torch.rand((3, 5, 7), generator=gen), torch.rand((1, 5, 7), generator=gen), torch.rand((1, 5, 7), generator=gen)
+
+
+def test_gbuffer_from_planes_refuses_cpu_tensors():
+    import relight
+    a, r, m = _planes()
+    three = torch.zeros(3, 5, 7)
+    planes = dict(depth_map=r, normal_map=three, occlusion_map=r, albedo_map=a, roughness_map=r, metallic_map=m,
+                  out_normal_view=three, depth_pos=three)
+    scratch = relight.Scratch()
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        relight.gbuffer_from_planes(planes, torch.eye(4), False, scratch)
+    assert not scratch  # refused before anything was allocated
+
+
+@pytest.mark.parametrize("metallic", [False, True])
+def test_fused_f0_is_the_reference_branch_written_out(metallic):
+    """relight.py:236-240 in the spelling of the fused paths: metallic=False -> F0 = 0.04 + albedo * metallic_map and the
+    metallic map; metallic=True -> the 0.04 / zero-plane pair."""
+    import relight
+    a, r, m = _planes(1)
+    F0, metallic_in = relight.fused_f0(a, r, m, metallic)
+    assert F0.shape == a.shape and metallic_in.shape == r.shape and F0.dtype == metallic_in.dtype == torch.float32
+    if metallic:
+        assert torch.equal(F0, torch.full((3, 5, 7), 0.04)) and torch.equal(metallic_in, torch.zeros(1, 5, 7))
+    else:
+        assert torch.equal(F0, torch.addcmul(torch.full_like(a, 0.04), a, m)) and metallic_in is m
+        assert float((F0 - 0.04).abs().max()) > 0.1

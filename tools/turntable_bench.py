@@ -67,10 +67,8 @@ def gather_only(args, g, views):
     lib = gigs_lib.lib()
     W = H = args.size
     gi = scenes.GI_DEFAULTS
-    light = relight.make_light(tt(scenes.synthetic_envmap(512, 1024, seed=1)), res=args.light)
-    rl = relight.Relighter(light, gi, 2)
     ct, _ = views[0]
-    b = rl._gbuffer(ct, g)
+    b = relight.SplatGBuffer(gi, 2)(ct, g)
     p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     a = (W, H, float(W / (2.0 * ct["tanfovx"])), float(H / (2.0 * ct["tanfovy"])), float(gi["radius"]), float(gi["bias"]),
          float(gi["thick"]), float(gi["delta"]), int(gi["step"]), int(gi["start"]))
