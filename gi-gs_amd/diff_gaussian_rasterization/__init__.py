@@ -560,8 +560,9 @@ def _SSR(width, height, focal_x, focal_y, radius, bias, thick, delta, step, star
     sp = None if scratch is None else scratch.data_ptr()
     W, H = int(width), int(height)
     a = (W, H, float(focal_x), float(focal_y), float(radius), float(bias), float(thick), float(delta), int(step), int(start))
-    hit_list = (_st.view is not None and gigs_lib.current().option("gi_march") == 4 and int(start) < int(step)
-                and os.environ.get("GIGS_SSR_HIT_LIST", "1") == "1")
+    # the ssr_hit_list switch is the view's owner's decision (pipeline.GeometryCache): without it no view reaches "replay_rec"
+    # and no slot holds a hit list
+    hit_list = _st.view is not None and gigs_lib.current().option("gi_march") == 4 and int(start) < int(step)
     with torch.cuda.device(dev):
         if hit_list and _st.view[1] == "replay" and _st.view[0].ssr_loaded:
             # frozen geometry: gather the radiance at the recorded hits instead of marching (gigs_ssr_apply)
@@ -867,7 +868,7 @@ class GaussianRasterizer(nn.Module):
         focal_x = raster_settings.image_width / (2.0 * raster_settings.tanfovx)
         focal_y = raster_settings.image_height / (2.0 * raster_settings.tanfovy)
         W_, H_ = int(raster_settings.image_width), int(raster_settings.image_height)
-        if derive_normal and W_ > 1 and H_ > 1 and os.environ.get("GIGS_FUSED_DERIVE", "1") == "1":
+        if derive_normal and W_ > 1 and H_ > 1 and gigs_lib.current().switch("fused_derive"):
             # the four passes below as one launch (gigs_derive_normal; bit-identical, tests/test_gpu_parity.py)
             normal_from_depth, depth_pos_filter = _derive_normal(W_, H_, focal_x, focal_y, raster_settings.viewmatrix,
                                                                  depth.detach())

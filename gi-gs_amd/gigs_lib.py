@@ -197,6 +197,26 @@ OPTION_NAMES = tuple(n for n, _ in Options._fields_ if n != "struct_bytes")
 GI_MARCHES = {0: "exact", 4: "proj"}  # gigs_options.gi_march: value -> name
 _GI_MARCH_VALUES = {name: value for value, name in GI_MARCHES.items()}
 
+# The A/B switches of the Python host code: name -> environment variable of its default.  A switch is on iff the variable is
+# unset or equals "1".  They travel with the context like the gigs_options do (Context.switch) and never reach the native
+# gigs_ctx.
+SWITCHES = {
+    "step_graph": "GIGS_STEP_GRAPH",
+    "light_prefetch": "GIGS_LIGHT_PREFETCH",
+    "mip_chain": "GIGS_MIP_CHAIN",
+    "spec_multi": "GIGS_SPEC_MULTI",
+    "spec_prescaled": "GIGS_SPEC_PRESCALED",
+    "cube_bwd_gather": "GIGS_CUBE_BWD_GATHER",
+    "ssr_hit_list": "GIGS_SSR_HIT_LIST",
+    "declared_grads": "GIGS_MATERIALS_ONLY",  # `materials_only` is derive's keyword for the counter tensor
+    "split_sh": "GIGS_SPLIT_SH",
+    "fused_derive": "GIGS_FUSED_DERIVE",
+    "stage2_gather": "GIGS_STAGE2_GATHER",
+    "shade_post_fused": "GIGS_SHADE_POST_FUSED",
+}
+SWITCH_NAMES = tuple(SWITCHES)
+_KEEP = object()  # Context.derive: "leave this setting as it is" where None already means "off"
+
 
 class SpecLevel(C.Structure):
     """gigs_spec_level of include/gigs_hip.h."""
@@ -314,17 +334,18 @@ class profile:
 # contexts (gigs_ctx): per-instance state of the library -- options, asynchronous binning, scheduling event
 # ------------------------------------------------------------------------------------------
 class Context:
-    """An immutable gigs_ctx.  Contexts are interned by their complete settings (`Context.get`): asking twice for the same
-    options / asynchronous-binning buffer / event yields the same native object, so deriving one per call costs a
-    dictionary lookup.  `ptr` is what the C entry points take first (None = the library's default context)."""
+    """An immutable gigs_ctx and the Python-side switches (SWITCHES) that go with it.  Contexts are interned by their complete
+    settings (`Context.get`): asking twice for the same options / switches / asynchronous-binning buffer / event yields the
+    same native object, so deriving one per call costs a dictionary lookup.  `ptr` is what the C entry points take first
+    (None = the library's default context).  A captured graph bakes the options and switches that were current at capture."""
 
     _cache: dict = {}
     _lock = threading.Lock()
 
-    def __init__(self, opts: tuple, async_capacity: int, async_counters, blend_event, reuse_binning: bool = False,
-                 materials_only=None, sh_rest=None):
+    def __init__(self, opts: tuple, switches: tuple, async_capacity: int, async_counters, blend_event,
+                 reuse_binning: bool = False, materials_only=None, sh_rest=None):
         l = lib()
-        self.opts, self.async_capacity = tuple(opts), int(async_capacity)
+        self.opts, self.switches, self.async_capacity = tuple(opts), tuple(switches), int(async_capacity)
         self.async_counters, self.blend_event = async_counters, blend_event  # kept alive with the context
         self.reuse_binning = bool(reuse_binning)
         self.materials_only = materials_only  # device int32[1] violation counter (gigs_ctx_set_materials_only), kept alive
@@ -359,9 +380,10 @@ class Context:
             pass
 
     @classmethod
-    def get(cls, opts: tuple, async_capacity: int = 0, async_counters=None, blend_event=None, reuse_binning=False,
-            materials_only=None, sh_rest=None) -> "Context":
-        key = (tuple(int(v) for v in opts), int(async_capacity),
+    def get(cls, opts: tuple, switches: tuple, async_capacity: int = 0, async_counters=None, blend_event=None,
+            reuse_binning=False, materials_only=None, sh_rest=None) -> "Context":
+        # opts / switches: tuples of int / bool, as default_options(), default_switches() and derive() build them
+        key = (opts, switches, int(async_capacity),
                None if async_counters is None else async_counters.data_ptr(), None if blend_event is None else id(blend_event),
                bool(reuse_binning), None if materials_only is None else materials_only.data_ptr(),
                None if sh_rest is None else (sh_rest.data_ptr(), tuple(sh_rest.shape)))
@@ -370,7 +392,7 @@ class Context:
             if c is None:
                 if len(cls._cache) > 512:  # contexts of long-gone buffers: start over (live ones are re-created on demand)
                     cls._cache.clear()
-                c = cls._cache[key] = cls(key[0], async_capacity, async_counters, blend_event, reuse_binning, materials_only, sh_rest)
+                c = cls._cache[key] = cls(key[0], key[1], async_capacity, async_counters, blend_event, reuse_binning, materials_only, sh_rest)
         return c
 
     @classmethod
@@ -384,14 +406,20 @@ class Context:
                       if any(id(t) in ids for t in (c.async_counters, c.materials_only, c.sh_rest) if t is not None)]:
                 del cls._cache[k]
 
-    def derive(self, async_binning=None, blend_event="keep", reuse_binning=None, materials_only="keep", sh_rest="keep",
+    def derive(self, async_binning=None, blend_event=_KEEP, reuse_binning=None, materials_only=_KEEP, sh_rest=_KEEP,
                **options) -> "Context":
-        """The context with some settings changed: option names of gigs_options (gi_march also by name), `async_binning` =
-        (capacity, counters tensor) or False to switch it off, `blend_event` = a torch.cuda.Event or None, `reuse_binning`
-        = True / False (gigs_ctx_set_reuse_binning), `materials_only` = a device int32[1] violation counter or None
-        (gigs_ctx_set_materials_only), `sh_rest` = the optimizer's _features_rest tensor or None (gigs_ctx_set_split_sh)."""
-        opts = list(self.opts)
-        for k, v in options.items():
+        """The context with some settings changed: option names of gigs_options (gi_march also by name) and switch names of
+        SWITCHES (0 / 1), `async_binning` = (capacity, counters tensor) or False to switch it off, `blend_event` = a
+        torch.cuda.Event or None, `reuse_binning` = True / False (gigs_ctx_set_reuse_binning), `materials_only` = a device
+        int32[1] violation counter or None (gigs_ctx_set_materials_only), `sh_rest` = the optimizer's _features_rest tensor
+        or None (gigs_ctx_set_split_sh)."""
+        opts, switches = list(self.opts), list(self.switches)
+        for k, v in options.items():  # values are normalised here: Context.get keys on them as they are
+            if k in SWITCHES:
+                switches[SWITCH_NAMES.index(k)] = bool(int(v))
+                continue
+            if k not in OPTION_NAMES:
+                raise ValueError(f"unknown setting {k!r}: one of {sorted(OPTION_NAMES + SWITCH_NAMES)}")
             if k == "gi_march" and isinstance(v, str):
                 if v not in _GI_MARCH_VALUES:
                     raise ValueError(f"gi_march {v!r}: one of {sorted(_GI_MARCH_VALUES)}")
@@ -402,16 +430,21 @@ class Context:
             cap, cnt = 0, None
         elif async_binning is not None:
             cap, cnt = async_binning
-        ev = self.blend_event if isinstance(blend_event, str) else blend_event
-        mo = self.materials_only if isinstance(materials_only, str) else materials_only
-        rest = self.sh_rest if isinstance(sh_rest, str) else sh_rest
-        return Context.get(tuple(opts), cap, cnt, ev, self.reuse_binning if reuse_binning is None else reuse_binning, mo, rest)
+        ev = self.blend_event if blend_event is _KEEP else blend_event
+        mo = self.materials_only if materials_only is _KEEP else materials_only
+        rest = self.sh_rest if sh_rest is _KEEP else sh_rest
+        return Context.get(tuple(opts), tuple(switches), cap, cnt, ev,
+                           self.reuse_binning if reuse_binning is None else reuse_binning, mo, rest)
 
     def option(self, name: str) -> int:
         return self.opts[OPTION_NAMES.index(name)]
 
+    def switch(self, name: str) -> bool:
+        return self.switches[SWITCH_NAMES.index(name)]
+
 
 _default_opts = None
+_default_switches = None
 _tls = threading.local()
 
 # Objects with independent work the rasterizer's forward may start beside its blend kernel (pbr.light.CubemapLight registers
@@ -433,11 +466,19 @@ def default_options() -> tuple:
     return _default_opts
 
 
+def default_switches() -> tuple:
+    """The switches' defaults, in SWITCHES' order: the GIGS_* environment as it was at the first call."""
+    global _default_switches
+    if _default_switches is None:
+        _default_switches = tuple(os.environ.get(var, "1") == "1" for var in SWITCHES.values())
+    return _default_switches
+
+
 def current() -> Context:
     """The context the Python operators of this thread pass to the library."""
     c = getattr(_tls, "ctx", None)
     if c is None:
-        c = _tls.ctx = Context.get(default_options())
+        c = _tls.ctx = Context.get(default_options(), default_switches())
     return c
 
 
@@ -462,7 +503,8 @@ class use:
 
 
 def options(**kw) -> use:
-    """`with options(gi_march="exact", blend_cull=0):` -- the current context with these gigs_options changed."""
+    """`with options(gi_march="exact", blend_cull=0, step_graph=0):` -- the current context with these gigs_options and
+    switches changed."""
     return use(current().derive(**kw))
 
 

@@ -4,7 +4,6 @@ write needs cv2, imported only when a filename is given.  load_envmap and split_
 of scope."""
 from __future__ import annotations
 
-import os
 import threading
 import math
 from typing import List, Optional
@@ -204,7 +203,7 @@ class CubemapLight(nn.Module):
             t.record_stream(main)
         self.specular, self.diffuse = pre["specular"], pre["diffuse"]
 
-    # ---- drop-in overlap (gigs-hip extension; GIGS_LIGHT_PREFETCH=0 switches it off) ------------------------------------
+    # ---- drop-in overlap (gigs-hip extension; the switch light_prefetch = 0 turns it off) ------------------
     # train.py:330-345 calls render() (the rasterizer, with its SSAO march) and THEN cubemap.build_mips(): op by op, the
     # 0.3 ms GGX pre-filter and its 0.3 ms backward sit on the step's critical path.  They depend on `base` alone, which only
     # the optimizer step changes, so the rasterizer's forward starts the filter the caller is about to ask for on this light's
@@ -235,7 +234,7 @@ class CubemapLight(nn.Module):
 
     def wants_prefetch(self) -> bool:
         return (self._wanted and self._prefetch_ok and self._pre is None and self.base.is_cuda
-                and os.environ.get("GIGS_LIGHT_PREFETCH", "1") == "1")
+                and gigs_lib.current().switch("light_prefetch"))
 
     def prefetch(self, step_event, blend_event, cutoff: float = 0.99) -> None:
         self._wanted = False
@@ -248,7 +247,7 @@ class CubemapLight(nn.Module):
     def _build(self, cutoff: float = 0.99):
         specular = [self.base]
         diffuse_in = None
-        if os.environ.get("GIGS_MIP_CHAIN", "1") == "1" and self.base.shape[3] == 3:
+        if gigs_lib.current().switch("mip_chain") and self.base.shape[3] == 3:
             n_levels, r = 0, self.base.shape[1]
             while r > self.LIGHT_MIN_RES:
                 n_levels, r = n_levels + 1, r // 2

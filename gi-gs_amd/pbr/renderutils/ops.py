@@ -281,7 +281,7 @@ def spec_sparse_report(shapes, device=None):
 def specular_cubemap_levels(mips, roughnesses, cutoff=0.99):
     """[specular_cubemap(m, r, cutoff) for m, r in zip(mips, roughnesses)] as one launch each way, or None if a level
     lacks its cached tables (then the caller filters level by level)."""
-    if os.environ.get("GIGS_SPEC_MULTI", "1") != "1" or torch.is_anomaly_enabled() or not mips[0].is_cuda:
+    if not gigs_lib.current().switch("spec_multi") or torch.is_anomaly_enabled() or not mips[0].is_cuda:
         return None
     meta = []
     for m, r in zip(mips, roughnesses):
@@ -322,7 +322,7 @@ def _weight_tables(res, roughness, cutoff, device):
                                    "specular_weights")
                     tabs.append(wt)
             scaled = wsum = None
-            if os.environ.get("GIGS_SPEC_PRESCALED", "1") == "1" and used + total * 12 <= _TABLE_MAX_BYTES:
+            if gigs_lib.current().switch("spec_prescaled") and used + total * 12 <= _TABLE_MAX_BYTES:
                 # weight sums of the forward (independent of the cubemap's values), then the backward table divided by them
                 with torch.cuda.device(device):
                     ones = torch.ones((6, res, res, 3), dtype=torch.float32, device=device)

@@ -12,7 +12,7 @@ _lib = gigs_lib.lib()
 
 # Gather plans of the lookup's backward for direction sets that come back every iteration (the envmap TV's panorama grid):
 # taps sorted by texel into a CSR list, built once per (directions tensor, resolution) outside any graph capture.
-# GIGS_CUBE_BWD_GATHER=0 keeps the atomic scatter.
+# The switch cube_bwd_gather = 0 (GIGS_CUBE_BWD_GATHER=0) keeps the atomic scatter.
 _PLAN_MIN_DIRS = 1 << 14
 _HEAVY = 64
 _plans = {}
@@ -25,8 +25,7 @@ def release_plans(d: torch.Tensor) -> None:
 
 
 def _gather_plan(d: torch.Tensor, res: int, n: int, build: bool):
-    import os
-    if os.environ.get("GIGS_CUBE_BWD_GATHER", "1") != "1" or n < _PLAN_MIN_DIRS:
+    if not gigs_lib.current().switch("cube_bwd_gather") or n < _PLAN_MIN_DIRS:
         return None
     key = (d.data_ptr(), d._version, res, n, str(d.device))
     hit = _plans.get(key)
@@ -79,15 +78,15 @@ class _CubeTexture(torch.autograd.Function):
                                                       torch.cuda.current_stream().cuda_stream), "cube_texture_fwd")
         ctx.save_for_backward(d)
         ctx.res, ctx.planar, ctx.n = int(cubemap.shape[1]), bool(planar), n
-        if cubemap.requires_grad or ctx.needs_input_grad[0]:
-            _gather_plan(d, ctx.res, n, build=True)  # built on the first (eager) call, found again by the backward
+        # built on the first (eager) call; the backward follows the forward's decision, whatever context it runs under
+        ctx.plan = _gather_plan(d, ctx.res, n, build=True) if cubemap.requires_grad or ctx.needs_input_grad[0] else None
         return out
 
     @staticmethod
     def backward(ctx, g_out):
         (d,) = ctx.saved_tensors
         g = g_out.contiguous().float()
-        plan = _gather_plan(d, ctx.res, ctx.n, build=False)
+        plan = ctx.plan
         if plan is not None:
             d_tex = torch.empty((6, ctx.res, ctx.res, 3), dtype=torch.float32, device=g.device)  # every texel is written
             with torch.cuda.device(g.device):

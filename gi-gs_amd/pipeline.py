@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import contextlib
 import math
-import os
 import weakref
 from typing import Dict, Optional
 
@@ -330,7 +329,7 @@ class GeometryCache:
         self.stats = dict(recorded=0, replayed=0, repeated=0, invalidated=0, hit_lists=0)
         self.recorded_R: Dict = {}
         # the hit list of the indirect-light march is recorded by the default march only (gigs_ssr_hits)
-        self.hit_lists = os.environ.get("GIGS_SSR_HIT_LIST", "1") == "1" and gigs_lib.current().option("gi_march") == 4
+        self.hit_lists = gigs_lib.current().switch("ssr_hit_list") and gigs_lib.current().option("gi_march") == 4
 
     @staticmethod
     def view_key(cam: Dict):
@@ -420,7 +419,10 @@ class WholeStepGraph:
     Binning runs under AsyncBinning (fixed capacity, nothing read back inside the step); the counters are copied to
     pinned memory by a node at the end of the forward graph and examined after the backward has been queued, so the
     host waits for the forward only.  On overflow the capacity grows, both graphs are re-captured and the step is
-    repeated; its gradients are never handed out."""
+    repeated; its gradients are never handed out.
+
+    The graphs bake the library context of the capture: the gigs_options and the Python-side switches (gigs_lib.SWITCHES)
+    that were current then, whatever is current at a replay."""
 
     def __init__(self, owner: "Stage2Step", cam: Dict, g: Dict[str, torch.Tensor], cache: Optional["GeometryCache"] = None,
                  mode: Optional[str] = None):
@@ -519,7 +521,7 @@ class WholeStepGraph:
                 "WholeStepGraph: %d wave(s) of the rasterizer's backward found a gradient outside the declared stage-2 set "
                 "(albedo / roughness / metallic / light) -- the loss reaches colour, opacity, depth, normal or geometry.  "
                 "The updates since then were withheld on the device (gigs_adam_step_guarded), the parameters are those of "
-                "the last valid step.  Build the stepper / trainer with materials_only=False (GIGS_MATERIALS_ONLY=0)." % n)
+                "the last valid step.  Build the stepper / trainer with materials_only=False (or switch declared_grads off: GIGS_MATERIALS_ONLY=0)." % n)
 
     def _into_slab(self, g, grads):
         """Inside the backward capture: every gradient ends up in its slab view (most were born there; the light's is
@@ -567,14 +569,14 @@ class WholeStepGraph:
         # Declared stage-2 gradient set (complete iterations only: the gradients are consumed inside the step, by an Adam
         # launch that takes an absent gradient as g = 0)
         self.viol_dev = self.viol_host = self.split_rest = None
-        if o.optimizers and getattr(o, "materials_only", False) and os.environ.get("GIGS_MATERIALS_ONLY", "1") == "1":
+        if o.optimizers and getattr(o, "materials_only", False) and gigs_lib.current().switch("declared_grads"):
             self.viol_dev = torch.zeros(1, dtype=torch.int32, device=self.dev)
             self.viol_host = torch.zeros(1, dtype=torch.int32).pin_memory()
             # with it, the SH block is never concatenated: the rasterizer reads the optimizer's two tensors (gigs_ctx_set_split_sh;
             # its materials-only backward does not touch SH)
             rest = g.get("f_rest") if o.prepare is not None else None
             if (rest is not None and rest.dim() == 3 and rest.shape[1] > 0 and rest.is_contiguous()
-                    and os.environ.get("GIGS_SPLIT_SH", "1") == "1"):
+                    and gigs_lib.current().switch("split_sh")):
                 self.split_rest = rest
         self.inner = o._make_inner()  # the eager step that is captured: returns its attached loss instead of differentiating
         self.inner._defer_backward = True
@@ -855,9 +857,9 @@ class _Stepper:
         self._dense = False  # declined as dense (DenseScene): synchronous binning with the global radix sort from then on
 
     def _graph_step(self, cam, raw, gt_image, view_dirs, update=True):
-        """The step from the whole-step graphs, or None: the caller's eager path runs instead (GIGS_STEP_GRAPH=0, more
+        """The step from the whole-step graphs, or None: the caller's eager path runs instead (step_graph off, more
         camera models than graphs, or a scene declined as dense -- then for good)."""
-        if os.environ.get("GIGS_STEP_GRAPH", "1") != "1" or self._dense:
+        if not gigs_lib.current().switch("step_graph") or self._dense:
             return None
         try:
             return self._replay_whole(cam, raw, gt_image, view_dirs, update=update)

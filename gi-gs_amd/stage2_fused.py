@@ -15,7 +15,6 @@ tests/test_gpu_pbr.py::test_stage2_fused_matches_unfused compares the two formul
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict
 
 import torch
@@ -33,11 +32,6 @@ def _p(t):
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
-
-
-def _switch(name: str) -> bool:
-    """A/B switch of the node: "0" goes back to the previous kernel sequence."""
-    return os.environ.get(name, "1") == "1"
 
 
 class _Stage2Fused(torch.autograd.Function):
@@ -73,7 +67,7 @@ class _Stage2Fused(torch.autograd.Function):
         gi = cfg["gi"]
         with torch.cuda.device(dev):
             s = _stream()
-            if _switch("GIGS_SHADE_POST_FUSED"):
+            if gigs_lib.current().switch("shade_post_fused"):  # A/B switch: off = the previous kernel sequence
                 gigs_lib.check(_lib.gigs_shade_fwd_post(
                     gigs_lib.ctx_ptr(), H, W, _p(normal_map), _p(out_normal_view), _p(viewmatrix), _p(normals_view), _p(mask_u8),
                     _p(mask_f), _p(onv), _p(view_dirs), _p(albedo_map), _p(roughness_map), _p(occlusion),
@@ -95,7 +89,7 @@ class _Stage2Fused(torch.autograd.Function):
             # the loss and, in the same pass over the image, its gradients w.r.t. render_direct / IRR for a unit upstream
             # gradient (the backward then has no loss kernel: gigs_shade_bwd_ex scales them and forms the lamb terms)
             d_direct_u, d_irr_u = new(3, H, W), new(3, H, W)
-            if _switch("GIGS_STAGE2_GATHER"):
+            if gigs_lib.current().switch("stage2_gather"):
                 # gathered: no atomics, no cleared buffers; the workgroups' partial sums go through `rows`
                 rows = torch.empty(max(int(_lib.gigs_stage2_loss_gather_scratch_bytes(H, W)) // 4, 4), dtype=torch.float32, device=dev)
                 gigs_lib.check(_lib.gigs_stage2_loss_gather(H, W, _p(render_direct), _p(IRR), _p(gt_image), _p(mask_f),

@@ -38,8 +38,9 @@ def small_scene(P=300, sh_degree=1, seed=3, W=64, H=48, scale_mu=0.08, view=0):
 
 
 def set_options(monkeypatch, **kw):
-    """Switch gigs_options for the rest of the test: the current library context of this thread is replaced by a derived
-    one (gigs_lib.Context.derive) and restored by monkeypatch at teardown.  Option names are gigs_options members
-    (include/gigs_hip.h); `async_binning=(capacity, counters)` / `False` and `blend_event=` are accepted too."""
+    """Switch gigs_options and Python-side switches for the rest of the test: the current library context of this thread is
+    replaced by a derived one (gigs_lib.Context.derive) and restored by monkeypatch at teardown.  Names are gigs_options
+    members (include/gigs_hip.h) or keys of gigs_lib.SWITCHES; `async_binning=(capacity, counters)` / `False` and
+    `blend_event=` are accepted too."""
     import gigs_lib
     monkeypatch.setattr(gigs_lib._tls, "ctx", gigs_lib.current().derive(**kw))

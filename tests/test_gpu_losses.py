@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import set_options
+
 pytestmark = pytest.mark.gpu
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "ref_loss.npz"))
@@ -262,10 +264,46 @@ def test_env_tv_loss_matches_restatement(size, monkeypatch):
         b2 = base.to(dev).requires_grad_(True)
         losses.env_tv_loss(b2, d_dev).backward()
         assert torch.equal(b1.grad, b2.grad)  # reproducible
-        monkeypatch.setenv("GIGS_CUBE_BWD_GATHER", "0")
+        set_options(monkeypatch, cube_bwd_gather=0)
         b3 = base.to(dev).requires_grad_(True)
         losses.env_tv_loss(b3, d_dev).backward()
         assert (b3.grad - b1.grad).abs().max().item() <= 1e-5 * b1.grad.abs().max().item()
+
+
+def test_cube_texture_backward_follows_its_forward():
+    """The lookup's backward takes the path its forward chose under the cube_bwd_gather switch, whatever context is current
+    when it runs: (a) forward with the switch off, backward outside -> the atomic scatter, no plan is built; (b) forward
+    with defaults, backward with the switch off -> the gather, bit-equal to a default run (it is reproducible)."""
+    import gigs_lib
+    import losses
+    import pbr.texture as tex
+    from oracle import train_glue_ref as ref
+    dev = _dev()
+    size = (128, 256)
+    n = size[0] * size[1]
+    g = torch.Generator().manual_seed(22)
+    base = (0.5 + 0.25 * torch.randn(6, 32, 32, 3, generator=g)).abs()
+    dirs = ref.envmap_dirs_ref(size).float()
+    # (a) before anything builds a plan for these directions
+    d_a = dirs.to(dev).contiguous()
+    ba = base.to(dev).requires_grad_(True)
+    with gigs_lib.options(cube_bwd_gather=0):
+        loss = losses.env_tv_loss(ba, d_a)
+    loss.backward()
+    assert tex._gather_plan(d_a, 32, n, build=False) is None
+    # the default run: the gather
+    d_b = dirs.to(dev).contiguous()
+    b0 = base.to(dev).requires_grad_(True)
+    losses.env_tv_loss(b0, d_b).backward()
+    assert tex._gather_plan(d_b, 32, n, build=False) is not None
+    assert (ba.grad - b0.grad).abs().max().item() <= 1e-5 * b0.grad.abs().max().item()
+    # (b)
+    bb = base.to(dev).requires_grad_(True)
+    loss = losses.env_tv_loss(bb, d_b)
+    with gigs_lib.options(cube_bwd_gather=0):
+        loss.backward()
+    assert torch.equal(bb.grad, b0.grad)
+    tex.release_plans(d_b)
 
 
 @pytest.mark.parametrize("P,K,misalign", [(1003, 9, False), (1003, 9, True), (130, 16, False), (64, 4, False), (77, 1, False)])

@@ -579,7 +579,7 @@ def test_fused_derive_normal_is_bit_identical_to_the_four_kernel_chain(W, H, mon
     t = {k: tt(sc[k]) for k in GAUSS_KEYS}
     outs = []
     for fused in ("0", "1"):
-        monkeypatch.setenv("GIGS_FUSED_DERIVE", fused)
+        set_options(monkeypatch, fused_derive=fused)
         st = settings(dgr, cam, 1)
         out = dgr.GaussianRasterizer(st)(t["means3D"], torch.zeros_like(t["means3D"]), t["opacities"], t["normal"],
                                          t["albedo"], t["roughness"], t["metallic"], shs=t["shs"], scales=t["scales"],

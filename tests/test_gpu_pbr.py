@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import scenes
-from helpers import GAUSS_KEYS, focal, oracle_forward
+from helpers import GAUSS_KEYS, focal, oracle_forward, set_options
 from oracle import torch_pbr_ref as tp
 from test_pbr_cpu import light_levels, make_gbuffer, make_light
 
@@ -231,6 +231,7 @@ def test_stage2_fused_matches_unfused(orc, metallic):
     """stage2_fused (gbuffer_post + shade_ex + SSR + loss as one autograd node, 6 kernels) against the
     op-by-op torch formulation of train.py:293-402 in pipeline.Stage2Front / stage2_loss: same loss, image
     and gradients, eagerly and replayed from a hipGraph on a second view."""
+    import gigs_lib
     import pbr
     import pipeline
     sc = scenes.surface_scene(P=10_000, sh_degree=2, seed=9, scale_mu=0.025)
@@ -250,21 +251,20 @@ def test_stage2_fused_matches_unfused(orc, metallic):
         g = {k: tt(sc[k], grad=True) for k in GAUSS_KEYS}
         # fused_step_graph: the whole iteration as two hand-captured hipGraphs (pipeline.WholeStepGraph, the default);
         # fused_graph: glue replayed from hipGraphs, rasterizer launched eagerly with asynchronous binning
-        os.environ["GIGS_STEP_GRAPH"] = "1" if mode == "fused_step_graph" else "0"
-        step = pipeline.Stage2Step(light, lut, gi, 2, metallic=metallic, fused=mode != "unfused",
-                                   graphs=mode in ("fused_graph", "fused_step_graph"))
-        outs = []
-        for ci in (0, 1, 0):
-            for t in list(g.values()) + [light.base]:
-                t.grad = None
-            o = step(camts[ci], g, gt, vds[ci])
-            torch.cuda.synchronize()
-            outs.append((float(o["loss"]), {k: g[k].grad.clone() for k in ("albedo", "roughness", "metallic")},
-                         light.base.grad.clone(), o["render_rgb"].clone(), o["IRR"].clone()))
+        with gigs_lib.options(step_graph=int(mode == "fused_step_graph")):
+            step = pipeline.Stage2Step(light, lut, gi, 2, metallic=metallic, fused=mode != "unfused",
+                                       graphs=mode in ("fused_graph", "fused_step_graph"))
+            outs = []
+            for ci in (0, 1, 0):
+                for t in list(g.values()) + [light.base]:
+                    t.grad = None
+                o = step(camts[ci], g, gt, vds[ci])
+                torch.cuda.synchronize()
+                outs.append((float(o["loss"]), {k: g[k].grad.clone() for k in ("albedo", "roughness", "metallic")},
+                             light.base.grad.clone(), o["render_rgb"].clone(), o["IRR"].clone()))
         if mode == "fused_step_graph":
             assert step.whole is not None and step.whole.recaptures == 1  # three views, one capture
         results[mode] = outs
-    os.environ.pop("GIGS_STEP_GRAPH", None)
     for mode in ("fused", "fused_graph", "fused_step_graph"):
         for (lu, gu, bu, ru, iu), (lf, gf, bf, rf, irf) in zip(results["unfused"], results[mode]):
             assert abs(lu - lf) <= 2e-6 * max(1.0, abs(lu)), (mode, lu, lf)
@@ -286,7 +286,7 @@ def test_graphed_step_survives_a_binning_overflow(raster, monkeypatch):
     import pbr
     import pipeline
     from diff_gaussian_rasterization import AsyncBinning
-    monkeypatch.setenv("GIGS_STEP_GRAPH", "1" if raster == "step_graph" else "0")
+    set_options(monkeypatch, step_graph=int(raster == "step_graph"))
     sc = scenes.surface_scene(P=20_000, sh_degree=2, seed=4, scale_mu=0.03)
     gi = scenes.GI_DEFAULTS
     H, W = 160, 208
@@ -367,8 +367,7 @@ def test_build_mips_fused_chain_and_prescaled_tables_match_op_by_op(monkeypatch)
     ws = None
     results = []
     for chain, prescaled in (("0", "0"), ("1", "1")):
-        monkeypatch.setenv("GIGS_MIP_CHAIN", chain)
-        monkeypatch.setenv("GIGS_SPEC_PRESCALED", prescaled)
+        set_options(monkeypatch, mip_chain=chain, spec_prescaled=prescaled)
         ops._weightTables.clear()
         light = pbr.CubemapLight(base_res=64, device=dev)
         with torch.no_grad():
@@ -395,7 +394,7 @@ def test_merged_level_filter_equals_per_level(base, monkeypatch):
     import pbr
     res = {}
     for multi in ("1", "0"):
-        monkeypatch.setenv("GIGS_SPEC_MULTI", multi)
+        set_options(monkeypatch, spec_multi=multi)
         torch.manual_seed(11)
         light = pbr.CubemapLight(base_res=base, device=DEV)
         light.build_mips()
@@ -415,7 +414,7 @@ def test_whole_step_graph_gradient_semantics_and_recapture(monkeypatch):
     -> old + new; (3) a parameter tensor replaced by another one (densification) -> one re-capture, results as eager."""
     import pbr
     import pipeline
-    monkeypatch.setenv("GIGS_STEP_GRAPH", "1")
+    set_options(monkeypatch, step_graph=1)
     sc = scenes.surface_scene(P=8000, sh_degree=2, seed=21, scale_mu=0.025)
     gi = scenes.GI_DEFAULTS
     H, W = 176, 224
@@ -555,7 +554,7 @@ def test_whole_step_graph_writes_gradients_into_the_all_reduce_slab(monkeypatch)
     import dp
     import pbr
     import pipeline
-    monkeypatch.setenv("GIGS_STEP_GRAPH", "1")
+    set_options(monkeypatch, step_graph=1)
     sc = scenes.surface_scene(P=6000, sh_degree=2, seed=31, scale_mu=0.025)
     gi = scenes.GI_DEFAULTS
     H, W = 160, 208
@@ -656,7 +655,7 @@ def test_hipgraph_lifetime_is_deterministic(monkeypatch):
     import pbr
     import pipeline
     import train_iteration
-    monkeypatch.setenv("GIGS_STEP_GRAPH", "1")
+    set_options(monkeypatch, step_graph=1)
     sc = scenes.surface_scene(P=6000, sh_degree=2, seed=21, scale_mu=0.03)
     gi = scenes.GI_DEFAULTS
     H, W = 112, 144
@@ -748,7 +747,7 @@ def test_drop_in_light_prefetch_is_adopted_and_changes_nothing(monkeypatch):
     vds = [pipeline.view_dirs_for(c, rays, DEV) for c in camts]
 
     def run(prefetch):
-        monkeypatch.setenv("GIGS_LIGHT_PREFETCH", "1" if prefetch else "0")
+        set_options(monkeypatch, light_prefetch=int(prefetch))
         torch.manual_seed(2)
         light = pbr.CubemapLight(base_res=64, device=DEV)
         g = {k: tt(sc[k], grad=True) for k in GAUSS_KEYS}
@@ -776,7 +775,7 @@ def test_drop_in_light_prefetch_is_adopted_and_changes_nothing(monkeypatch):
     assert abs(ref[0][0] - ref[2][0]) > 1e-7  # the optimizer did change the light / albedo between iterations
 
     # a caller that touches the light between the rasterizer's forward and build_mips(): the stale prefetch is dropped
-    monkeypatch.setenv("GIGS_LIGHT_PREFETCH", "1")
+    set_options(monkeypatch, light_prefetch=1)
     torch.manual_seed(2)
     light = pbr.CubemapLight(base_res=64, device=DEV)
     g = {k: tt(sc[k], grad=True) for k in GAUSS_KEYS}

@@ -4,7 +4,7 @@
     and without cleared buffers) against gigs_stage2_loss_fwd_grad on the same inputs;
   * gigs_shade_fwd_post (csrc/pbr.hip: the G-buffer post-processing inside the shade forward) against gigs_gbuffer_post
     followed by gigs_shade_fwd_ex;
-  * stage2_fused._Stage2Fused with the switches GIGS_STAGE2_GATHER / GIGS_SHADE_POST_FUSED on and off.
+  * stage2_fused._Stage2Fused with the switches stage2_gather / shade_post_fused on and off.
 
 Sizes: 5 x 7 (smaller than any tile: every pixel at a border), 9 x 70 (ragged both ways, across the 64-pixel tile edge and a
 tile-row edge), 40 x 130 (a few tiles).
@@ -27,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 import scenes  # noqa: F401  (the package path)
+from helpers import set_options
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -312,8 +313,7 @@ def test_fused_node_with_the_switches_on_and_off(light, monkeypatch):
     cfg = dict(H=H, W=W, gi=scenes.GI_DEFAULTS, focal_x=fx, focal_y=fy, metallic=True, indirect=True, gamma=True, tone=False)
 
     def run(on):
-        for name in ("GIGS_STAGE2_GATHER", "GIGS_SHADE_POST_FUSED"):
-            monkeypatch.setenv(name, "1" if on else "0")
+        set_options(monkeypatch, stage2_gather=int(on), shade_post_fused=int(on))
         leaves = [x["albedo"].clone().requires_grad_(True), x["rough"].clone().requires_grad_(True),
                   x["metal"].clone().requires_grad_(True), diffuse.clone().requires_grad_(True)]
         sp = [s.clone().requires_grad_(True) for s in spec]
