@@ -1,0 +1,71 @@
+"""A mesh PLY already on disk (extract_mesh.py's) without its debris: mesh.clean drops the connected components of fewer
+faces than max(--min_faces, the --keep_largest-th largest, 1), the invalid faces and the vertices nothing references.
+
+    python gi-gs_amd/clean_mesh.py IN.ply -o OUT.ply [--keep_largest K] [--min_faces M]          (CLI)
+    clean_mesh(args) -> {...}                                                                     (API)
+
+Reads with scene_io.read_mesh_ply and writes with scene_io.save_mesh_ply, so the colour makes one more trip through the
+PLY's 8 bits (x / 255 -> trunc(x * 255 + 0.5): the same byte).  Prints the report as JSON: mesh.clean's, the sizes before
+and after and the time.  Both flags 0 still removes unreferenced vertices.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+from argparse import Namespace
+from typing import Dict, List, Optional
+
+if __package__ in (None, ""):  # run as a script: make the package's modules importable
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Mesh cleaning parameters")
+    p.add_argument("input", type=str, help="a PLY written by extract_mesh.py")
+    p.add_argument("-o", "--output", type=str, required=True)
+    p.add_argument("--keep_largest", type=int, default=0, help="keep the components with at least as many faces as the K-th largest")
+    p.add_argument("--min_faces", type=int, default=0, help="drop the components with fewer faces")
+    return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> Namespace:
+    return build_parser().parse_args(argv)
+
+
+def clean_mesh(args) -> Dict:
+    """`args`: a Namespace from parse_args or an argv list."""
+    import torch
+
+    import mesh
+    import mesh_render
+    import scene_io
+    if not isinstance(args, Namespace):
+        args = parse_args(list(args))
+    if not torch.cuda.is_available():
+        raise RuntimeError("clean_mesh needs the GPU")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    arrays = mesh_render.mesh_arrays(scene_io.read_mesh_ply(args.input))
+    m = mesh.Mesh(*(torch.from_numpy(arrays[k]).to(dev) for k in mesh.Mesh._fields))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out, report = mesh.clean(m, args.keep_largest, args.min_faces)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    scene_io.save_mesh_ply(args.output, *out)
+    return dict(report, path=args.output, vertices_in=int(m.vertices.shape[0]), faces_in=int(m.faces.shape[0]),
+                vertices=int(out.vertices.shape[0]), faces=int(out.faces.shape[0]), clean_s=round(t1 - t0, 4))
+
+
+def main(argv=None) -> int:
+    print(json.dumps(clean_mesh(parse_args(argv))))
+    return 0
+
+
+if __name__ == "__main__":
+    import importlib
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    importlib.import_module("gi-gs_amd")
+    sys.exit(main())

@@ -135,6 +135,12 @@ SIGNATURES = {
     "gigs_tsdf_integrate": (_i, [C.c_void_p, _i, C.c_void_p, C.c_void_p]),
     "gigs_mesh_count": (_i, [C.c_void_p, _fl, _f, _f, C.c_void_p]),
     "gigs_mesh_write": (_i, [C.c_void_p, _fl, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_cc_hook": (_i, [_i, _i, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_cc_flatten": (_i, [_i, _f, C.c_void_p]),
+    "gigs_mesh_cc_count": (_i, [_i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_mark": (_i, [_i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_compact": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f,
+                               C.c_void_p]),
     "gigs_mesh_project": (_i, [_i, _f, _f, _fl, _fl, _i, _i, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_raster_scratch_bytes": (C.c_size_t, [_i]),
     "gigs_mesh_raster": (_i, [_i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, C.c_void_p]),

@@ -6,6 +6,11 @@
     auto_bounds(g)                       a box around the opaque Gaussians
     fuse_views(g, sh_degree, cams, gi, volume)   rasterizes each view (pipeline.rasterize, inference=True) and integrates
                                          its opacity, depth, world normal, albedo, roughness and metallic planes
+    components(mesh)                     the connected components of a mesh's faces (gigs_mesh_cc_hook / _flatten until a
+                                         pass changes nothing, gigs_mesh_cc_count)
+    keep_threshold(counts, K, M)         the face count a component needs to be kept (host arithmetic)
+    clean(mesh, keep_largest, min_faces) drops the components below that count, the invalid faces and the vertices no
+                                         kept face references (gigs_mesh_mark, two scans, gigs_mesh_compact)
 
 The route is the one of 2DGS and GOF: depth and material planes of the training views go into a truncated signed
 distance volume, and the mesh is its zero level set.  The arithmetic of both halves is stated in include/gigs_hip.h and
@@ -14,7 +19,7 @@ restated in numpy by tests/mesh_ref.py.  There is no CPU path: the volume lives 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, NamedTuple, Sequence
+from typing import Dict, List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -36,6 +41,19 @@ class Mesh(NamedTuple):
 
 class MeshOverflow(RuntimeError):
     """The writing pass met an index outside its outputs: the volume changed between the counting and the writing pass."""
+
+
+class MeshComponents(NamedTuple):
+    labels: torch.Tensor       # [V] int32: the smallest vertex index of the vertex's component
+    face_labels: torch.Tensor  # [F] int32: labels[faces[f,0]], -1 for an invalid face
+    roots: torch.Tensor        # [C] int32: the components (roots with at least one face), ascending
+    counts: torch.Tensor       # [C] int32: their valid faces
+    invalid_faces: int
+    rounds: int                # hook passes, the confirming one included
+
+
+class ComponentsNotConverged(RuntimeError):
+    """The labelling reached its cap on hook passes (cc_round_cap) with faces still joining trees: no labels are returned."""
 
 
 def _stream():
@@ -224,3 +242,137 @@ def fuse_views(g: Dict[str, torch.Tensor], sh_degree: int, cams: Sequence[Dict],
             if keep_planes:
                 kept.extend(planes)
     return kept
+
+
+# ---- cleaning: connected components, the keep rule, compaction (include/gigs_hip.h, "Cleaning meshes") -----------------------
+def cc_round_cap(n_vertices: int) -> int:
+    """The most hook passes components() runs: 2 ceil(log2 V) + 8.  In every pass and under every schedule, a tree that a
+    face joins to a tree with a smaller root stops being a root: only the local minima among the trees survive a pass.
+    In the synchronous model of a pass (every face reads the forest the last pass left) a tree that survives two passes
+    in a row has taken every neighbouring tree into itself -- had one of them gone elsewhere, it went under a smaller
+    root, which the survivor then touches -- so it absorbed at least one tree, and that tree is its alone: the trees of a
+    component at least halve every two passes, 2 ceil(log2 V) passes plus the confirming one.  (One pass does not halve
+    them: a star whose centre has the largest root loses only the centre.)  The asynchronous schedule differs from the
+    model in that a root may be offered a vertex further down its neighbour's chain, or overtaken; it is not proved to keep
+    the factor, hence the margin of 7 passes, and hence an error and no labels at the cap ("Cleaning meshes",
+    has the observed counts).  Progress never depends on the cap: a pass that changes something removes a root."""
+    return 2 * max(int(n_vertices) - 1, 0).bit_length() + 8
+
+
+def _mesh_tensors(mesh, what: str) -> Mesh:
+    m = mesh if isinstance(mesh, Mesh) else Mesh(*mesh)
+    dev = m.vertices.device if isinstance(m.vertices, torch.Tensor) else None
+    for name, t in zip(Mesh._fields, m):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.device != dev:
+            raise RuntimeError("%s: %s must be a tensor on one CUDA/HIP device: gigs-hip has no CPU path" % (what, name))
+    V = int(m.vertices.shape[0])
+    if m.faces.dtype != torch.int32 or m.faces.dim() != 2 or m.faces.shape[1] != 3:
+        raise ValueError("%s: faces must be [F,3] int32, got %s %s" % (what, tuple(m.faces.shape), m.faces.dtype))
+    for name, shape in (("vertices", (V, 3)), ("normals", (V, 3)), ("albedo", (V, 3)), ("roughness", (V,)), ("metallic", (V,))):
+        t = getattr(m, name)
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be %s float32, got %s %s" % (what, name, shape, tuple(t.shape), t.dtype))
+    return Mesh(*(t.contiguous() for t in m))
+
+
+def _p(t):
+    return t.data_ptr() if t.numel() else None
+
+
+def _label(m: Mesh):
+    """-> (labels [V], face_labels [F], count [V] per root, invalid (device int [1]), rounds)."""
+    dev = m.vertices.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
+    lib = gigs_lib.lib()
+    parent = torch.arange(V, **i32)
+    face_labels, count = torch.empty(F, **i32), torch.empty(V, **i32)
+    flag = torch.zeros(2, **i32)  # changed, invalid faces
+    rounds = 0
+    if V and F:
+        cap = cc_round_cap(V)
+        while True:
+            gigs_lib.check(lib.gigs_mesh_cc_hook(V, F, _p(m.faces), _p(parent), flag.data_ptr(), _stream()), "mesh_cc_hook")
+            rounds += 1
+            if int(flag[0].item()) == 0:  # the one read-back of a round
+                break
+            if rounds >= cap:
+                raise ComponentsNotConverged("components: %d hook passes over %d vertices and faces still join trees" % (rounds, V))
+            gigs_lib.check(lib.gigs_mesh_cc_flatten(V, _p(parent), _stream()), "mesh_cc_flatten")
+    gigs_lib.check(lib.gigs_mesh_cc_count(V, F, _p(m.faces), _p(parent), _p(face_labels), _p(count), flag[1:].data_ptr(),
+                                          _stream()), "mesh_cc_count")
+    return parent, face_labels, count, flag[1:], rounds
+
+
+def components(mesh) -> MeshComponents:
+    """The connected components of the valid faces of `mesh` (a Mesh on the device), by vertex connectivity: two shells that
+    share one vertex are one component.  V == 0 or F == 0 launches nothing."""
+    m = _mesh_tensors(mesh, "components")
+    dev = m.vertices.device
+    V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
+    i32 = dict(dtype=torch.int32, device=dev)
+    if V == 0 or F == 0:
+        return MeshComponents(torch.arange(V, **i32), torch.full((F,), -1, **i32), torch.empty(0, **i32), torch.empty(0, **i32),
+                              F, 0)
+    with torch.cuda.device(dev):
+        labels, face_labels, count, invalid, rounds = _label(m)
+        roots = torch.nonzero(count > 0).reshape(-1).to(torch.int32)  # a face's label is a root: count > 0 only at roots
+        counts = count[roots.long()]
+        return MeshComponents(labels, face_labels, roots, counts, int(invalid.item()), rounds)
+
+
+def keep_threshold(counts, keep_largest: int = 0, min_faces: int = 0) -> int:
+    """The face count a component needs: max(min_faces, c_K, 1) with c_K the keep_largest-th largest of `counts` (the face
+    counts of the components, each >= 1; a tensor, an array or a list), 0 for keep_largest <= 0 and the smallest count for
+    keep_largest >= len(counts).  Components tied with the K-th reach it too.  Sorts where the counts live."""
+    c = torch.as_tensor(counts).reshape(-1)
+    K, n = int(keep_largest), int(c.numel())
+    c_k = 0
+    if K > 0 and n > 0:
+        c_k = int(torch.sort(c, descending=True).values[min(K, n) - 1].item())
+    return max(int(min_faces), c_k, 1)
+
+
+def clean(mesh, keep_largest: int = 0, min_faces: int = 0) -> Tuple[Mesh, Dict]:
+    """(the mesh without the components of fewer than keep_threshold faces, a report).  Invalid faces and the vertices no
+    kept face references go too; with keep_largest = min_faces = 0 nothing else does.  Kept vertices and faces stay in
+    their order, values are copied bit for bit.  Report: components, components_kept, faces_removed, vertices_removed,
+    invalid_faces, rounds, threshold."""
+    m = _mesh_tensors(mesh, "clean")
+    dev = m.vertices.device
+    V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+
+    def sized(v, f):
+        return Mesh(torch.empty((v, 3), **f32), torch.empty((f, 3), **i32), torch.empty((v, 3), **f32),
+                    torch.empty((v, 3), **f32), torch.empty((v,), **f32), torch.empty((v,), **f32))
+
+    if V == 0 or F == 0:
+        return sized(0, 0), dict(components=0, components_kept=0, faces_removed=F, vertices_removed=V, invalid_faces=F,
+                                 rounds=0, threshold=keep_threshold([], keep_largest, min_faces))
+    lib = gigs_lib.lib()
+    with torch.cuda.device(dev):
+        labels, face_labels, count, invalid, rounds = _label(m)
+        comp = count > 0
+        thr = keep_threshold(count[comp], keep_largest, min_faces)
+        root_keep = (count >= thr).to(torch.uint8)
+        face_keep, vertex_keep = torch.empty(F, **i32), torch.empty(V, **i32)
+        gigs_lib.check(lib.gigs_mesh_mark(V, F, _p(m.faces), _p(face_labels), _p(root_keep), _p(face_keep), _p(vertex_keep),
+                                          _stream()), "mesh_mark")
+        v_incl = torch.cumsum(vertex_keep, 0, dtype=torch.int32)
+        f_incl = torch.cumsum(face_keep, 0, dtype=torch.int32)
+        V2, F2, n_comp, n_kept, n_invalid = (int(x) for x in torch.stack(
+            (v_incl[-1], f_incl[-1], comp.sum().to(torch.int32), root_keep.sum().to(torch.int32), invalid[0])).cpu())
+        out = sized(V2, F2)
+        v_off, f_off = v_incl - vertex_keep, f_incl - face_keep
+        if V2 and F2:
+            overflow = torch.zeros(1, **i32)
+            gigs_lib.check(lib.gigs_mesh_compact(
+                V, F, _p(m.vertices), _p(m.normals), _p(m.albedo), _p(m.roughness), _p(m.metallic), _p(m.faces), _p(vertex_keep),
+                _p(v_off), _p(face_keep), _p(f_off), V2, F2, _p(out.vertices), _p(out.normals),
+                _p(out.albedo), _p(out.roughness), _p(out.metallic), _p(out.faces), overflow.data_ptr(), _stream()),
+                "mesh_compact")
+            if int(overflow.item()) != 0:
+                raise MeshOverflow("clean: an index left the outputs (%d vertices, %d faces)" % (V2, F2))
+    return out, dict(components=n_comp, components_kept=n_kept, faces_removed=F - F2, vertices_removed=V - V2,
+                     invalid_faces=n_invalid, rounds=rounds, threshold=thr)

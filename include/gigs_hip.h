@@ -688,6 +688,55 @@ int gigs_mesh_count(const gigs_tsdf_grid* grid, float min_weight, int* cell_flag
 int gigs_mesh_write(const gigs_tsdf_grid* grid, float min_weight, const int* cell_offsets, const int* quad_offsets,
                     int vertex_capacity, int face_capacity, float* vertices, float* normals, float* albedo, float* roughness,
                     float* metallic, int* faces, int* overflow, void* stream);
+/* Cleaning meshes (gigs-hip extension; the device half of mesh.components / mesh.clean): the connected components of a
+ * triangle mesh, a keep flag per component, and the compaction of what is kept.  The mesh: V vertices, faces [F,3] int32,
+ * and mesh.py's per-vertex arrays.  All arrays are DEVICE memory; the calls neither synchronise nor allocate.  Every
+ * quantity below is an integer that does not depend on the order of execution (tests/mesh_clean_ref.py restates them).
+ *   Valid face: all three indices lie in [0, V).  An invalid face is never dereferenced and belongs to no component:
+ *     face_label = -1, never kept, counted in *invalid_faces.
+ *   Connectivity: two vertices are connected if a chain of valid faces joins them, consecutive faces sharing AT LEAST ONE
+ *     VERTEX.  This is vertex connectivity, not edge connectivity: two shells that touch in a single vertex are one
+ *     component (the cheaper rule, and the conservative one for a filter: it never splits what an edge rule joins).  A
+ *     degenerate face (a, a, b) is valid and connects a and b.
+ *   label[v] = the smallest vertex index of v's component; a vertex no valid face references is a component of its own
+ *     with zero faces (label[v] = v).  face_label[f] = label[faces[f,0]].  count[r] = the number of valid faces with
+ *     face_label == r.  The components are the roots (label[v] == v) with count >= 1, in ascending root order.
+ *   Keep rule (mesh.keep_threshold; the 2DGS post-processing threshold with keep_largest = K, min_faces = M): c_K = the K-th
+ *     largest count among the components, 0 when K <= 0, the smallest count when K >= their number; a component is kept
+ *     iff count >= max(M, c_K, 1), so components tied with the K-th are all kept.
+ *   Compaction: a vertex is kept iff a kept face references it, its new index is the number of kept vertices with a
+ *     smaller index; kept faces stay in their order with remapped indices and unchanged winding; positions and the five
+ *     attribute arrays are copied bit for bit.
+ * gigs_mesh_cc_hook, one thread per face: `parent` [V] int32 with 0 <= parent[x] <= x, set to parent[x] = x by the CALLER
+ *   before the first call.  The three roots of a valid face by walking parent (a walk down a strictly decreasing chain:
+ *   it ends by itself, and a value outside [0, x) ends it too), m = their minimum, atomicMin(parent[r], m) for each root
+ *   r > m.  *changed (device int, cleared inside the call) becomes 1 if some face saw different roots.
+ * gigs_mesh_cc_flatten, one thread per vertex: parent[v] = root(v).
+ *   The caller alternates hook and flatten until a hook leaves *changed == 0; parent is then label.  That confirming pass
+ *   stored nothing, so every face was seen under one root of a static forest; a link that a stale read overwrote in an
+ *   earlier pass is re-made by the pass after it (gi-gs_amd/csrc/mesh_clean.hip has the argument).  No call waits on
+ *   another thread: there is no retry, spin or ticket loop.
+ * gigs_mesh_cc_count, one thread per face, parent = label: face_label [F]; count [V] and *invalid_faces (cleared inside
+ *   the call) by integer atomics, one per wave for the lanes that share the label of the wave's first valid lane.
+ * gigs_mesh_mark, one thread per face: face_keep [F] int32 = 1 for a valid face with root_keep[face_label] != 0
+ *   (root_keep [V] uint8), else 0; vertex_keep [V] int32 (cleared inside the call) = 1 for the vertices of those faces.
+ * gigs_mesh_compact: vertex_offsets / face_offsets = the exclusive prefix sums of vertex_keep / face_keep.  Kept vertex v
+ *   goes to row vertex_offsets[v] of out_vertices, out_normals, out_albedo [vertex_capacity,3], out_roughness,
+ *   out_metallic [vertex_capacity]; kept face f to row face_offsets[f] of out_faces [face_capacity,3] with its indices
+ *   replaced by vertex_offsets.  A row outside a capacity, a new index outside [0, vertex_capacity), or a kept face with
+ *   an index outside [0, V) or on a vertex that is not kept sets *overflow (device int, cleared by the caller) to 1 and
+ *   stores nothing: gigs_mesh_write's guard. */
+int gigs_mesh_cc_hook(int n_vertices, int n_faces, const int* faces, int* parent, int* changed, void* stream);
+int gigs_mesh_cc_flatten(int n_vertices, int* parent, void* stream);
+int gigs_mesh_cc_count(int n_vertices, int n_faces, const int* faces, const int* parent, int* face_label, int* count,
+                       int* invalid_faces, void* stream);
+int gigs_mesh_mark(int n_vertices, int n_faces, const int* faces, const int* face_label, const uint8_t* root_keep,
+                   int* face_keep, int* vertex_keep, void* stream);
+int gigs_mesh_compact(int n_vertices, int n_faces, const float* vertices, const float* normals, const float* albedo,
+                      const float* roughness, const float* metallic, const int* faces, const int* vertex_keep,
+                      const int* vertex_offsets, const int* face_keep, const int* face_offsets, int vertex_capacity,
+                      int face_capacity, float* out_vertices, float* out_normals, float* out_albedo, float* out_roughness,
+                      float* out_metallic, int* out_faces, int* overflow, void* stream);
 /* Rendering meshes (gigs-hip extension; the device half of mesh_render.py): a triangle mesh -- vertices [V,3], faces [F,3]
  * int32 and mesh.py's per-vertex attributes -- as the G-buffer planes the blend kernel writes in inference mode, by a
  * visibility buffer.  Coverage and visibility are integer decisions, so no result depends on the order of execution and a
