@@ -8,6 +8,7 @@ library (see csrc/gigs_common.h), not an optimisation knob.
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -28,8 +29,7 @@ FLAGS = [
 
 def _deps(src: str):
     yield os.path.join(CSRC, src)
-    yield os.path.join(CSRC, "gigs_common.h")
-    yield os.path.join(CSRC, "pixel_ops.h")
+    yield from sorted(glob.glob(os.path.join(CSRC, "*.h")))
     yield os.path.join(HERE, "..", "include", "gigs_hip.h")
 
 

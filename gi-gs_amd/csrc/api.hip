@@ -10,12 +10,12 @@
 #include <cstring>
 #include <map>
 #include <algorithm>
+#include <atomic>
 #include <new>
 #include <mutex>
 #include <vector>
 
-#include "../../include/gigs_hip.h"
-#include "gigs_common.h"
+#include "gigs_internal.h"
 
 namespace {
 
@@ -84,23 +84,6 @@ uint32_t higher_msb(uint32_t n) {
   return msb;
 }
 
-// ---- in-library per-stage timing --------------------------------------------------------
-// A "profile session" records one hipEvent pair per kernel stage on the stream the stage is
-// launched on, WITHOUT synchronising; gigs_profile_end() synchronises once and sums the
-// elapsed times.  bench.py uses it to measure kernel durations live over its timed region.
-enum Stage {
-  kPreprocess = 0, kScan, kDuplicate, kSort, kRanges, kBlendFwd, kBlendBwd, kPreprocessBwd,
-  kDepthToNormal, kSsao, kSsr, kMedian, kBilateral, kMedianBwd, kShadeFwd, kShadeBwd,
-  kCubemapFwd, kCubemapBwd, kGbufferPost, kLossFwd, kLossBwd, kL1SsimFwd, kL1SsimBwd, kTvFwd, kTvBwd,
-  kMaskedL1, kAdam, kDensifyStats, kGatherRows, kDist2, kActivateFwd, kActivateBwd, kNumStages
-};
-const char* kStageNames[kNumStages] = {
-  "preprocess_fwd", "scan", "duplicate", "sort", "tile_ranges", "blend_fwd", "blend_bwd",
-  "preprocess_bwd", "depth_to_normal", "ssao", "ssr", "median3x3", "bilateral3x3",
-  "median3x3_bwd", "shade_fwd", "shade_bwd", "cubemap_fwd", "cubemap_bwd", "gbuffer_post",
-  "stage2_loss_fwd", "stage2_loss_bwd", "l1_ssim_fwd", "l1_ssim_bwd", "tv_loss_fwd", "tv_loss_bwd", "masked_l1",
-  "adam_step", "densify_stats", "gather_rows", "dist2", "activate_fwd", "activate_bwd"};
-
 // ---- contexts (include/gigs_hip.h) -------------------------------------------------------------------------------
 int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -108,6 +91,7 @@ int env_int(const char* name, int dflt) {
 }
 gigs::Options options_from_env() {
   gigs::Options o;
+  o.struct_bytes = (int)sizeof(gigs_options);
   const char* b = getenv("GIGS_BINNING");
   o.binning_legacy = (b && strcmp(b, "legacy") == 0) ? 1 : 0;
   o.bucket_max_mean = env_int("GIGS_BUCKET_MAX_MEAN", gigs::kBucketMaxMeanList);
@@ -138,9 +122,13 @@ gigs::Options options_from_env() {
 }
 const gigs::Ctx& ctx_of(const gigs_ctx* c) { return c ? *reinterpret_cast<const gigs::Ctx*>(c) : gigs::default_ctx(); }
 
-struct ProfRec { int stage; hipEvent_t a, b; };
+// ---- in-library per-stage timing --------------------------------------------------------
+// A "profile session" records one hipEvent pair per kernel stage (gigs::StageTimer, gigs_internal.h) on the stream
+// the stage is launched on, WITHOUT synchronising; gigs_profile_end() synchronises once and sums the elapsed
+// times.  bench.py uses it to measure kernel durations live over its timed region.
+struct ProfRec { gigs::Stage stage; hipEvent_t a, b; };
 std::mutex g_prof_mu;
-bool g_prof_on = false;
+std::atomic<bool> g_prof_on{false};  // written under g_prof_mu; the timers look at it before they take the mutex
 std::vector<ProfRec> g_prof_recs;
 std::vector<hipEvent_t> g_prof_pool;
 
@@ -155,31 +143,25 @@ hipEvent_t prof_event() {
   return e;
 }
 
-// RAII: records start at construction and stop at destruction when a session is active.
-struct StageScope {
-  hipStream_t s;
-  int stage;
-  bool on;
-  hipEvent_t a, b;
-  StageScope(int stage_, hipStream_t s_) : s(s_), stage(stage_), on(false) {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    if (!g_prof_on) return;
-    on = true;
-    a = prof_event();
-    b = prof_event();
-    hipEventRecord(a, s);
-  }
-  ~StageScope() {
-    if (!on) return;
-    hipEventRecord(b, s);
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof_recs.push_back({stage, a, b});
-  }
-};
-
 }  // namespace
 
 namespace gigs {
+StageTimer::StageTimer(Stage stage, void* stream) : s_((hipStream_t)stream), stage_(stage), on_(false) {
+  if (!g_prof_on.load(std::memory_order_relaxed)) return;
+  std::lock_guard<std::mutex> lk(g_prof_mu);
+  if (!g_prof_on.load(std::memory_order_relaxed)) return;
+  on_ = true;
+  a_ = prof_event();
+  b_ = prof_event();
+  hipEventRecord(a_, s_);
+}
+StageTimer::~StageTimer() {
+  if (!on_) return;
+  hipEventRecord(b_, s_);
+  std::lock_guard<std::mutex> lk(g_prof_mu);
+  g_prof_recs.push_back({stage_, a_, b_});
+}
+
 const Options& default_options() {
   static const Options o = options_from_env();  // the environment is read here, once
   return o;
@@ -190,14 +172,14 @@ const Ctx& default_ctx() {
 }
 }  // namespace gigs
 
-// helpers for the other translation units of the library (not part of the ABI)
+// helpers for the translation units of the library (gigs_internal.h; not part of the ABI)
 extern "C" {
-__attribute__((visibility("hidden"))) const gigs::Options* gigs_internal_options(const gigs_ctx* ctx) { return &ctx_of(ctx).opt; }
-__attribute__((visibility("hidden"))) int gigs_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
-__attribute__((visibility("hidden"))) void gigs_internal_stage_begin(int stage, void* stream, void** token) {
-  *token = new StageScope(stage, (hipStream_t)stream);
+const gigs::Options* gigs_internal_options(const gigs_ctx* ctx) { return &ctx_of(ctx).opt; }
+int gigs_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
+int gigs_internal_check_launch(const char* entry) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(GIGS_ERR_HIP, "%s: launch failed: %s", entry, hipGetErrorString(e));
 }
-__attribute__((visibility("hidden"))) void gigs_internal_stage_end(void* token) { delete (StageScope*)token; }
 }
 
 extern "C" {
@@ -256,14 +238,7 @@ void gigs_ctx_destroy(gigs_ctx* ctx) { delete reinterpret_cast<gigs::Ctx*>(ctx);
 
 int gigs_ctx_get_options(const gigs_ctx* ctx, gigs_options* out) {
   if (!out || out->struct_bytes < (int)sizeof(gigs_options)) return fail(GIGS_ERR_INVALID, "gigs_ctx_get_options: set struct_bytes = sizeof(gigs_options)");
-  const gigs::Options& o = ctx_of(ctx).opt;
-  out->struct_bytes = (int)sizeof(gigs_options);
-  out->binning_legacy = o.binning_legacy; out->bucket_max_mean = o.bucket_max_mean; out->long_lists = o.long_lists;
-  out->bucket_target = o.bucket_target; out->bin_bands = o.bin_bands; out->blend_cull = o.blend_cull; out->pre_bwd_sh_skip = o.pre_bwd_sh_skip;
-  out->gi_march = o.gi_march; out->gi_cert = o.gi_cert; out->gi_interleave = o.gi_interleave;
-  out->gi_tile_log2w = o.gi_tile_log2w; out->gi_zero_rays = o.gi_zero_rays; out->spec_max8 = o.spec_max8;
-  out->spec_max16 = o.spec_max16; out->shade_lds_floats = o.shade_lds_floats; out->shade_bwd_blocks = o.shade_bwd_blocks;
-  out->shade_bwd_rows = o.shade_bwd_rows; out->spec_sparse = o.spec_sparse; out->spec_sparse_permille = o.spec_sparse_permille;
+  *out = ctx_of(ctx).opt;
   return 0;
 }
 int gigs_ctx_set_options(gigs_ctx* ctx, const gigs_options* in) {
@@ -278,12 +253,11 @@ int gigs_ctx_set_options(gigs_ctx* ctx, const gigs_options* in) {
   if (in->shade_lds_floats < 0 || in->shade_bwd_blocks < 0) return fail(GIGS_ERR_INVALID, "shade_lds_floats, shade_bwd_blocks >= 0");
   if (in->spec_sparse_permille < 0 || in->spec_sparse_permille > 1000) return fail(GIGS_ERR_INVALID, "0 <= spec_sparse_permille <= 1000");
   gigs::Options& o = reinterpret_cast<gigs::Ctx*>(ctx)->opt;
-  o.binning_legacy = in->binning_legacy != 0; o.bucket_max_mean = in->bucket_max_mean; o.long_lists = in->long_lists;
-  o.bucket_target = in->bucket_target; o.bin_bands = in->bin_bands; o.blend_cull = in->blend_cull != 0; o.pre_bwd_sh_skip = in->pre_bwd_sh_skip != 0;
-  o.gi_march = in->gi_march; o.gi_cert = in->gi_cert != 0; o.gi_interleave = in->gi_interleave != 0;
-  o.gi_tile_log2w = in->gi_tile_log2w; o.gi_zero_rays = in->gi_zero_rays != 0; o.spec_max8 = in->spec_max8;
-  o.spec_max16 = in->spec_max16; o.shade_lds_floats = in->shade_lds_floats; o.shade_bwd_blocks = in->shade_bwd_blocks;
-  o.shade_bwd_rows = in->shade_bwd_rows != 0; o.spec_sparse = in->spec_sparse != 0; o.spec_sparse_permille = in->spec_sparse_permille;
+  static_cast<gigs_options&>(o) = *in;
+  o.struct_bytes = (int)sizeof(gigs_options);
+  for (int* sw : {&o.binning_legacy, &o.blend_cull, &o.pre_bwd_sh_skip, &o.gi_cert, &o.gi_interleave, &o.gi_zero_rays,
+                  &o.shade_bwd_rows, &o.spec_sparse})
+    *sw = *sw != 0;  // the on / off members
   return 0;
 }
 int gigs_ctx_set_reuse_binning(gigs_ctx* ctx, int on) {
@@ -317,7 +291,7 @@ int gigs_stream_delay(unsigned nanoseconds, void* stream) {
   if (nanoseconds == 0) return 0;
   const unsigned ns = nanoseconds > 1000000u ? 1000000u : nanoseconds;
   hipLaunchKernelGGL(stream_delay_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (ns + 9u) / 10u);
-  return hipGetLastError() == hipSuccess ? 0 : gigs_internal_fail(GIGS_ERR_HIP, "stream_delay: launch failed");
+  return gigs_internal_check_launch("stream_delay");
 }
 
 int gigs_ctx_set_async_binning(gigs_ctx* ctx, int r_capacity, unsigned* device_counters) {
@@ -346,18 +320,18 @@ int gigs_profile_end(float* total_ms, int* launches, int n) {
   for (auto& r : recs) {
     hipEventSynchronize(r.b);
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess && r.stage < n) {
-      total_ms[r.stage] += ms;
-      launches[r.stage] += 1;
+    if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess && (int)r.stage < n) {
+      total_ms[(int)r.stage] += ms;
+      launches[(int)r.stage] += 1;
     }
   }
   std::lock_guard<std::mutex> lk(g_prof_mu);
   for (auto& r : recs) { g_prof_pool.push_back(r.a); g_prof_pool.push_back(r.b); }
-  return kNumStages;
+  return (int)gigs::Stage::kCount;
 }
 
 const char* gigs_profile_stage_name(int stage) {
-  return (stage >= 0 && stage < kNumStages) ? kStageNames[stage] : "";
+  return (stage >= 0 && stage < (int)gigs::Stage::kCount) ? gigs::kStageNames[stage] : "";
 }
 
 int gigs_forward(gigs_ctx* ctx, gigs_alloc_fn geometryBuffer, void* geom_user, gigs_alloc_fn binningBuffer,
@@ -414,7 +388,7 @@ int gigs_forward(gigs_ctx* ctx, gigs_alloc_fn geometryBuffer, void* geom_user, g
   gigs::ImageState img = gigs::ImageState::fromChunk(img_chunk, N, T);
 
   {
-    StageScope sc(kPreprocess, s);
+    gigs::StageTimer timer(gigs::Stage::kPreprocess, s);
     gigs::launch_preprocess_fwd(a, geom, radii, s);
   }
   STAGE_CHECK("preprocess");
@@ -448,7 +422,7 @@ int gigs_forward(gigs_ctx* ctx, gigs_alloc_fn geometryBuffer, void* geom_user, g
     // to size the binning chunk exactly; with gigs_set_async_binning the chunk has the caller's capacity and nothing
     // is read back (the caller sizes it at twice a probed instance count: the density is judged from that).
     {
-      StageScope sc(kDuplicate, s);
+      gigs::StageTimer timer(gigs::Stage::kDuplicate, s);
       gigs::launch_bin_count(P, radii, a.gx, a.gy, geom, img, s);
       gigs::launch_bin_prefix(P, (int)T, async_cap > 0 ? async_cap : 0x7fffffffu, img, cx.async_counters, s);
     }
@@ -470,11 +444,11 @@ int gigs_forward(gigs_ctx* ctx, gigs_alloc_fn geometryBuffer, void* geom_user, g
     if (!bin_chunk) return fail(GIGS_ERR_ALLOC, "binning buffer allocation of %zu bytes failed", bin_bytes);
     bin = gigs::BinningState::fromChunk(bin_chunk, (size_t)num_rendered, sort_sz);
     {
-      StageScope sc(kRanges, s);
+      gigs::StageTimer timer(gigs::Stage::kRanges, s);
       gigs::launch_tile_order((int)T, img.ranges, img.tile_order, s);
     }
     {
-      StageScope sc(kSort, s);
+      gigs::StageTimer timer(gigs::Stage::kSort, s);
       // dense scenes scatter in bands of tile rows (binning.hip::bin_scatter_kernel); options.bin_bands overrides
       const unsigned bands = opt.bin_bands > 0 ? (unsigned)opt.bin_bands : (dense ? 4u : 1u);
       gigs::launch_bin_scatter(P, radii, a.gx, a.gy, (unsigned)num_rendered, bands, geom, bin, img, s);
@@ -484,7 +458,7 @@ int gigs_forward(gigs_ctx* ctx, gigs_alloc_fn geometryBuffer, void* geom_user, g
     STAGE_CHECK("bin scatter / sort");
   } else {
   {
-    StageScope sc(kScan, s);
+    gigs::StageTimer timer(gigs::Stage::kScan, s);
     HIP_TRY(gigs::scan_tiles(geom, P, s));
   }
   STAGE_CHECK("scan");
@@ -502,18 +476,18 @@ int gigs_forward(gigs_ctx* ctx, gigs_alloc_fn geometryBuffer, void* geom_user, g
   bin = gigs::BinningState::fromChunk(bin_chunk, (size_t)num_rendered, sort_sz);
 
   {
-    StageScope sc(kDuplicate, s);
+    gigs::StageTimer timer(gigs::Stage::kDuplicate, s);
     gigs::launch_duplicate(P, radii, a.gx, a.gy, geom, bin, s);
   }
   STAGE_CHECK("duplicateWithKeys");
   const int bit = (int)higher_msb(a.gx * a.gy);
   if (num_rendered > 0) {
-    StageScope sc(kSort, s);
+    gigs::StageTimer timer(gigs::Stage::kSort, s);
     HIP_TRY(gigs::sort_pairs(bin, num_rendered, 32 + bit, s));
   }
   STAGE_CHECK("sort");
   {
-    StageScope sc(kRanges, s);
+    gigs::StageTimer timer(gigs::Stage::kRanges, s);
     HIP_TRY(hipMemsetAsync(img.ranges, 0, T * sizeof(uint2), s));
     gigs::launch_tile_ranges(num_rendered, bin, img.ranges, s);
     gigs::launch_tile_order((int)T, img.ranges, img.tile_order, s);
@@ -522,7 +496,7 @@ int gigs_forward(gigs_ctx* ctx, gigs_alloc_fn geometryBuffer, void* geom_user, g
   }
   if (void* ev = cx.blend_begin_event) HIP_TRY(hipEventRecord((hipEvent_t)ev, s));
   {
-    StageScope sc(kBlendFwd, s);
+    gigs::StageTimer timer(gigs::Stage::kBlendFwd, s);
     gigs::launch_blend_fwd(a, geom, bin, img, out_color, out_opacity, out_depth, out_normal,
                            out_normal_view, out_pos, out_albedo, out_roughness, out_metallic, opt.blend_cull,
                            (size_t)num_rendered, s, cx.reuse_binning != 0);
@@ -631,13 +605,13 @@ int gigs_backward(gigs_ctx* ctx, int P, int D, int M, int R, const float* backgr
   a.radii = radii ? radii : geom.internal_radii;
 
   {
-    StageScope sc(kBlendBwd, s);
+    gigs::StageTimer timer(gigs::Stage::kBlendBwd, s);
     // geom.grec is zero here: preprocess_fwd clears it and preprocess_bwd clears it again after reading (no fill launch)
     gigs::launch_blend_bwd(a, geom, bin, img, s);
   }
   STAGE_CHECK("render backward");
   {
-    StageScope sc(kPreprocessBwd, s);
+    gigs::StageTimer timer(gigs::Stage::kPreprocessBwd, s);
     gigs::launch_preprocess_bwd(a, geom, ctx_of(ctx).opt.pre_bwd_sh_skip, s, materials_only);
   }
   STAGE_CHECK("preprocess backward");
@@ -650,8 +624,7 @@ int gigs_mark_visible(int P, const float* means3D, const float* viewmatrix,
   if (P == 0) return 0;
   if (P < 0 || !means3D || !viewmatrix || !present) return fail(GIGS_ERR_INVALID, "bad argument");
   gigs::launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gigs_internal_check_launch("mark_visible");
 }
 
 int gigs_depth_to_normal(int width, int height, float focal_x, float focal_y,
@@ -659,10 +632,9 @@ int gigs_depth_to_normal(int width, int height, float focal_x, float focal_y,
                          float* depth_pos, void* stream) {
   if (width <= 0 || height <= 0 || !viewmatrix || !depth || !normal || !depth_pos)
     return fail(GIGS_ERR_INVALID, "bad argument");
-  StageScope sc(kDepthToNormal, (hipStream_t)stream);
+  gigs::StageTimer timer(gigs::Stage::kDepthToNormal, (hipStream_t)stream);
   gigs::launch_depth_to_normal(width, height, focal_x, focal_y, viewmatrix, depth, normal, depth_pos, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gigs_internal_check_launch("depth_to_normal");
 }
 
 int gigs_derive_normal(int width, int height, float focal_x, float focal_y, const float* viewmatrix, const float* depth,
@@ -670,12 +642,34 @@ int gigs_derive_normal(int width, int height, float focal_x, float focal_y, cons
                        void* stream) {
   if (width <= 1 || height <= 1 || !viewmatrix || !depth || !normal_from_depth || !depth_pos_filter)
     return fail(GIGS_ERR_INVALID, "derive_normal: bad argument (images must be larger than 1x1)");
-  StageScope sc(kDepthToNormal, (hipStream_t)stream);
+  gigs::StageTimer timer(gigs::Stage::kDepthToNormal, (hipStream_t)stream);
   gigs::launch_derive_normal_fused(width, height, focal_x, focal_y, viewmatrix, sigma_color, sigma_x, sigma_y, depth,
                                    normal_from_depth, depth_pos_filter, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
+  return gigs_internal_check_launch("derive_normal");
+}
+
+}  // extern "C"
+
+namespace {
+// What the SSR entry points test in front of their launch: sizes and required pointers, and -- where rays are marched --
+// the side limit of the packed pixel coordinates.
+int ssr_check_args(int width, int height, std::initializer_list<const void*> required, bool marches) {
+  bool bad = width <= 0 || height <= 0;
+  for (const void* p : required) bad = bad || !p;
+  if (bad) return fail(GIGS_ERR_INVALID, "bad argument");
+  if (marches && (width >= (1 << 15) || height >= (1 << 15))) return fail(GIGS_ERR_INVALID, "image side above 32767 pixels");
   return 0;
 }
+// ...and what the SSAO / SSR entry points return after it: the launcher's status (gi.hip) as an error, or the launch check.
+int gi_status(const char* entry, int rc, float delta) {
+  if (rc == -1) return fail(GIGS_ERR_INVALID, "delta=%g gives an unbounded or oversized ray set", (double)delta);
+  if (rc == -3) return fail(GIGS_ERR_INVALID, "ssr_hits: the hit list is recorded by the default march only (gi_march = proj, start < step)");
+  if (rc) return fail(GIGS_ERR_HIP, "ray table upload failed");
+  return gigs_internal_check_launch(entry);
+}
+}  // namespace
+
+extern "C" {
 
 size_t gigs_gi_scratch_bytes(int width, int height) {
   if (width <= 0 || height <= 0) return 0;
@@ -687,13 +681,10 @@ int gigs_ssao_ex(gigs_ctx* ctx, int width, int height, float focal_x, float foca
                  const float* pos, float* occlusion, void* scratch, void* stream) {
   if (width <= 0 || height <= 0 || !normal_view || !pos || !occlusion) return fail(GIGS_ERR_INVALID, "bad argument");
   if (width >= (1 << 15) || height >= (1 << 15)) return fail(GIGS_ERR_INVALID, "image side above 32767 pixels");
-  StageScope sc(kSsao, (hipStream_t)stream);
+  gigs::StageTimer timer(gigs::Stage::kSsao, (hipStream_t)stream);
   const int rc = gigs::launch_ssao(ctx_of(ctx).opt, width, height, focal_x, focal_y, radius, bias, thick, delta, step, start,
                                    normal_view, pos, occlusion, scratch, (hipStream_t)stream);
-  if (rc == -1) return fail(GIGS_ERR_INVALID, "delta=%g gives an unbounded or oversized ray set", (double)delta);
-  if (rc) return fail(GIGS_ERR_HIP, "ray table upload failed");
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gi_status("ssao", rc, delta);
 }
 int gigs_ssao(int width, int height, float focal_x, float focal_y, float radius, float bias,
               float thick, float delta, int step, int start, const float* normal_view,
@@ -706,17 +697,12 @@ int gigs_ssr_ex(gigs_ctx* ctx, int width, int height, float focal_x, float focal
                 float thick, float delta, int step, int start, const float* normal_view,
                 const float* pos, const float* rgb, const float* albedo, const float* roughness,
                 const float* metallic, const float* F0, float* color, float* abd, void* scratch, void* stream) {
-  if (width <= 0 || height <= 0 || !normal_view || !pos || !rgb || !albedo || !metallic || !F0 || !color || !abd)
-    return fail(GIGS_ERR_INVALID, "bad argument");
-  if (width >= (1 << 15) || height >= (1 << 15)) return fail(GIGS_ERR_INVALID, "image side above 32767 pixels");
-  StageScope sc(kSsr, (hipStream_t)stream);
+  if (int rc = ssr_check_args(width, height, {normal_view, pos, rgb, albedo, metallic, F0, color, abd}, true)) return rc;
+  gigs::StageTimer timer(gigs::Stage::kSsr, (hipStream_t)stream);
   const int rc = gigs::launch_ssr(ctx_of(ctx).opt, width, height, focal_x, focal_y, radius, bias, thick, delta, step, start,
                                   normal_view, pos, rgb, albedo, roughness, metallic, F0, color, abd, scratch,
                                   (hipStream_t)stream);
-  if (rc == -1) return fail(GIGS_ERR_INVALID, "delta=%g gives an unbounded or oversized ray set", (double)delta);
-  if (rc) return fail(GIGS_ERR_HIP, "ray table upload failed");
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gi_status("ssr", rc, delta);
 }
 int gigs_ssr_multi(gigs_ctx* ctx, int n_lights, int width, int height, float focal_x, float focal_y, float radius, float bias,
                    float thick, float delta, int step, int start, const float* normal_view, const float* pos, const float* rgb,
@@ -724,52 +710,37 @@ int gigs_ssr_multi(gigs_ctx* ctx, int n_lights, int width, int height, float foc
                    float* abd, void* scratch, void* stream) {
   if (n_lights < 1 || n_lights > GIGS_MAX_LIGHTS)
     return fail(GIGS_ERR_INVALID, "ssr_multi: n_lights=%d outside 1..%d", n_lights, GIGS_MAX_LIGHTS);
-  if (width <= 0 || height <= 0 || !normal_view || !pos || !rgb || !albedo || !metallic || !F0 || !color || !abd)
-    return fail(GIGS_ERR_INVALID, "bad argument");
-  if (width >= (1 << 15) || height >= (1 << 15)) return fail(GIGS_ERR_INVALID, "image side above 32767 pixels");
-  StageScope sc(kSsr, (hipStream_t)stream);
+  if (int rc = ssr_check_args(width, height, {normal_view, pos, rgb, albedo, metallic, F0, color, abd}, true)) return rc;
+  gigs::StageTimer timer(gigs::Stage::kSsr, (hipStream_t)stream);
   (void)roughness;  // as gigs_ssr_ex: the reference's SSR reads no roughness
   const int rc = gigs::launch_ssr_multi(ctx_of(ctx).opt, n_lights, width, height, focal_x, focal_y, radius, bias, thick, delta,
                                         step, start, normal_view, pos, rgb, albedo, metallic, F0, color, abd, scratch,
                                         (hipStream_t)stream);
-  if (rc == -1) return fail(GIGS_ERR_INVALID, "delta=%g gives an unbounded or oversized ray set", (double)delta);
-  if (rc) return fail(GIGS_ERR_HIP, "ray table upload failed");
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gi_status("ssr_multi", rc, delta);
 }
 int gigs_ssr_hits(gigs_ctx* ctx, int width, int height, float focal_x, float focal_y, float radius, float bias, float thick,
                   float delta, int step, int start, const float* normal_view, const float* pos, const float* rgb,
                   const float* albedo, const float* roughness, const float* metallic, const float* F0, float* color, float* abd,
                   int mode, unsigned* counts, const unsigned* offsets, void* entries, unsigned capacity, void* scratch,
                   void* stream) {
-  if (width <= 0 || height <= 0 || !normal_view || !pos || !rgb || !albedo || !metallic || !F0 || !color || !abd)
-    return fail(GIGS_ERR_INVALID, "bad argument");
-  if (width >= (1 << 15) || height >= (1 << 15)) return fail(GIGS_ERR_INVALID, "image side above 32767 pixels");
+  if (int rc = ssr_check_args(width, height, {normal_view, pos, rgb, albedo, metallic, F0, color, abd}, true)) return rc;
   if ((mode != 1 && mode != 2) || (mode == 1 && !counts) || (mode == 2 && (!offsets || (!entries && capacity > 0))))
     return fail(GIGS_ERR_INVALID, "ssr_hits: mode 1 needs counts, mode 2 offsets and entries");
-  StageScope sc(kSsr, (hipStream_t)stream);
+  gigs::StageTimer timer(gigs::Stage::kSsr, (hipStream_t)stream);
   const int rc = gigs::launch_ssr(ctx_of(ctx).opt, width, height, focal_x, focal_y, radius, bias, thick, delta, step, start,
                                   normal_view, pos, rgb, albedo, roughness, metallic, F0, color, abd, scratch,
                                   (hipStream_t)stream, mode, counts, offsets, entries, capacity);
-  if (rc == -1) return fail(GIGS_ERR_INVALID, "delta=%g gives an unbounded or oversized ray set", (double)delta);
-  if (rc == -3) return fail(GIGS_ERR_INVALID, "ssr_hits: the hit list is recorded by the default march only (gi_march = proj, start < step)");
-  if (rc) return fail(GIGS_ERR_HIP, "ray table upload failed");
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gi_status("ssr_hits", rc, delta);
 }
 
 int gigs_ssr_apply(int width, int height, float delta, const unsigned* offsets, const void* entries, const float* normal_view,
                    const float* pos, const float* rgb, const float* albedo, const float* metallic, const float* F0,
                    float* color, float* abd, void* stream) {
-  if (width <= 0 || height <= 0 || !offsets || !normal_view || !pos || !rgb || !albedo || !metallic || !F0 || !color || !abd)
-    return fail(GIGS_ERR_INVALID, "bad argument");
-  StageScope sc(kSsr, (hipStream_t)stream);
+  if (int rc = ssr_check_args(width, height, {offsets, normal_view, pos, rgb, albedo, metallic, F0, color, abd}, false)) return rc;
+  gigs::StageTimer timer(gigs::Stage::kSsr, (hipStream_t)stream);
   const int rc = gigs::launch_ssr_apply(width, height, delta, offsets, entries, normal_view, pos, rgb, albedo, metallic, F0, color,
                                         abd, (hipStream_t)stream);
-  if (rc == -1) return fail(GIGS_ERR_INVALID, "delta=%g gives an unbounded or oversized ray set", (double)delta);
-  if (rc) return fail(GIGS_ERR_HIP, "ray table upload failed");
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gi_status("ssr_apply", rc, delta);
 }
 
 size_t gigs_ssr_apply_multi_scratch_bytes(int n_lights, int width, int height) {
@@ -781,19 +752,15 @@ int gigs_ssr_apply_multi(int n_lights, int width, int height, float delta, const
                          const float* metallic, const float* F0, float* color, float* abd, void* scratch, void* stream) {
   if (n_lights < 1 || n_lights > GIGS_MAX_LIGHTS)
     return fail(GIGS_ERR_INVALID, "ssr_apply_multi: n_lights=%d outside 1..%d", n_lights, GIGS_MAX_LIGHTS);
-  if (width <= 0 || height <= 0 || !offsets || !normal_view || !pos || !rgb || !albedo || !metallic || !F0 || !color || !abd)
-    return fail(GIGS_ERR_INVALID, "bad argument");
+  if (int rc = ssr_check_args(width, height, {offsets, normal_view, pos, rgb, albedo, metallic, F0, color, abd}, false)) return rc;
   if ((size_t)offsets % 16 != 0 || (size_t)scratch % 16 != 0)
     return fail(GIGS_ERR_INVALID, "ssr_apply_multi: offsets and scratch must be 16-byte aligned");
   if (n_lights > 1 && !scratch)
     return fail(GIGS_ERR_INVALID, "ssr_apply_multi: %d lights need gigs_ssr_apply_multi_scratch_bytes of scratch", n_lights);
-  StageScope sc(kSsr, (hipStream_t)stream);
+  gigs::StageTimer timer(gigs::Stage::kSsr, (hipStream_t)stream);
   const int rc = gigs::launch_ssr_apply_multi(n_lights, width, height, delta, offsets, entries, normal_view, pos, rgb, albedo,
                                               metallic, F0, color, abd, scratch, (hipStream_t)stream);
-  if (rc == -1) return fail(GIGS_ERR_INVALID, "delta=%g gives an unbounded or oversized ray set", (double)delta);
-  if (rc) return fail(GIGS_ERR_HIP, "ray table upload failed");
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gi_status("ssr_apply_multi", rc, delta);
 }
 
 int gigs_ssr(int width, int height, float focal_x, float focal_y, float radius, float bias,
@@ -819,35 +786,31 @@ int gigs_ssr_backward(int width, int height, const float* grad_color, const floa
   const size_t n = 3 * (size_t)width * height;
   hipLaunchKernelGGL(gigs::ssr_backward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, grad_color,
                      abd, grad_albedo);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gigs_internal_check_launch("ssr_backward");
 }
 
 int gigs_median3x3(int channels, int height, int width, const float* in, float* out, void* stream) {
   if (channels <= 0 || width <= 0 || height <= 0 || !in || !out) return fail(GIGS_ERR_INVALID, "bad argument");
-  StageScope sc(kMedian, (hipStream_t)stream);
+  gigs::StageTimer timer(gigs::Stage::kMedian, (hipStream_t)stream);
   gigs::launch_median3x3(channels, height, width, in, out, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gigs_internal_check_launch("median3x3");
 }
 
 int gigs_median3x3_backward(int channels, int height, int width, const float* in,
                             const float* grad_out, float* grad_in, void* stream) {
   if (channels <= 0 || width <= 0 || height <= 0 || !in || !grad_out || !grad_in) return fail(GIGS_ERR_INVALID, "bad argument");
-  StageScope sc(kMedianBwd, (hipStream_t)stream);
+  gigs::StageTimer timer(gigs::Stage::kMedianBwd, (hipStream_t)stream);
   gigs::launch_median3x3_bwd(channels, height, width, in, grad_out, grad_in, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gigs_internal_check_launch("median3x3_backward");
 }
 
 int gigs_bilateral3x3(int channels, int height, int width, float sigma_color, float sigma_x,
                       float sigma_y, const float* in, float* out, void* stream) {
   if ((channels != 1 && channels != 3) || width <= 1 || height <= 1 || !in || !out)
     return fail(GIGS_ERR_INVALID, "bilateral3x3 supports 1 or 3 channels and images larger than 1x1");
-  StageScope sc(kBilateral, (hipStream_t)stream);
+  gigs::StageTimer timer(gigs::Stage::kBilateral, (hipStream_t)stream);
   gigs::launch_bilateral3x3(channels, height, width, sigma_color, sigma_x, sigma_y, in, out, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return gigs_internal_check_launch("bilateral3x3");
 }
 
 }  // extern "C"

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/gigs_hip.h"
+
 #define GIGS_BLOCK_X 16  // reference tile: R/cuda_rasterizer/config.h:15-17
 #define GIGS_BLOCK_Y 16
 #define GIGS_TILE (GIGS_BLOCK_X * GIGS_BLOCK_Y)
@@ -233,26 +235,8 @@ inline size_t required_bytes(A... a) {
 // Every switch a launch path reads lives here: the library itself keeps no mutable process-wide state besides
 // immutable caches (ray tables, texel tables, rocPRIM temp sizes) and the diagnostic profile session.  The
 // default options are the environment, parsed ONCE (first use); a context starts as a copy of them.
-struct Options {
-  int binning_legacy;    // GIGS_BINNING=legacy
-  int bucket_max_mean;   // GIGS_BUCKET_MAX_MEAN
-  int long_lists;        // GIGS_LONG_LISTS: -1 auto, 0 never, 1 always
-  int bucket_target;     // GIGS_BUCKET_TARGET
-  int bin_bands;         // GIGS_BIN_BANDS: passes of the by-tile scatter over bands of tile rows (0 = by density: 1 / 4)
-  int blend_cull;        // GIGS_BLEND_CULL
-  int pre_bwd_sh_skip;   // GIGS_PRE_BWD_SH_SKIP
-  int gi_march;          // GIGS_GI_MARCH: 0 exact, 4 proj
-  int gi_cert;           // GIGS_GI_CERT
-  int gi_interleave;     // GIGS_GI_INTERLEAVE
-  int gi_tile_log2w;     // GIGS_GI_TILE_LOG2W
-  int gi_zero_rays;      // GIGS_GI_ZERO_RAYS: 1 = march the zero-weight rays too (diagnostic; same bits)
-  int spec_max8, spec_max16;  // GIGS_SPEC_MAX8 / _MAX16
-  int shade_lds_floats;  // GIGS_SHADE_LDS_FLOATS
-  int shade_bwd_blocks;  // GIGS_SHADE_BWD_BLOCKS (0 = one workgroup per CU)
-  int shade_bwd_rows;    // GIGS_SHADE_BWD_ROWS: 1 = the shade backward's row-major chunks and 16-lane runs (same per-pixel bits)
-  int spec_sparse;       // GIGS_SPEC_SPARSE: 1 = the GGX backward scatters levels with few nonzero gradient texels
-  int spec_sparse_permille;  // GIGS_SPEC_SPARSE_PERMILLE: list capacity of a level, in thousandths of its texels
-};
+// The options ARE the ABI's struct (include/gigs_hip.h, where each member is documented): one list of members.
+struct Options : ::gigs_options {};
 struct Ctx {
   Options opt;
   unsigned async_capacity;  // gigs_ctx_set_async_binning

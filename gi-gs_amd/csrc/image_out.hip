@@ -18,8 +18,7 @@
 //                   aligned dwords; only the dwords a row shares with its neighbours are stored byte by byte.
 // Descriptor tables live in device memory: the launches read no host state but n, so a captured graph stays valid
 // while the tables are rewritten between replays.  A descriptor that is not well-formed is skipped.
-#include "../../include/gigs_hip.h"
-#include "gigs_common.h"
+#include "gigs_internal.h"
 
 namespace gigs {
 namespace img {
@@ -295,14 +294,12 @@ __global__ __launch_bounds__(256) void filter_kernel(int n, const gigs_filter_de
 }  // namespace gigs
 
 extern "C" {
-int gigs_internal_fail(int code, const char* msg);  // api.hip
 
 int gigs_pack_images(int n, const gigs_pack_desc* desc, void* stream) {
   if (n == 0) return 0;
   if (n < 0 || n > GIGS_MAX_IMAGES || !desc) return gigs_internal_fail(GIGS_ERR_INVALID, "pack_images: bad argument");
   hipLaunchKernelGGL(gigs::img::pack_kernel, dim3(gigs::img::kPackBlocks, n), dim3(256), 0, (hipStream_t)stream, n, desc);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "pack_images: launch failed");
-  return 0;
+  return gigs_internal_check_launch("pack_images");
 }
 
 int gigs_plane_minmax(long long count, const float* src, float* scratch, float* out2, void* stream) {
@@ -310,15 +307,13 @@ int gigs_plane_minmax(long long count, const float* src, float* scratch, float* 
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(gigs::img::minmax_kernel, dim3(gigs::img::kMinMaxBlocks), dim3(256), 0, s, count, src, scratch);
   hipLaunchKernelGGL(gigs::img::minmax_finish_kernel, dim3(1), dim3(256), 0, s, scratch, out2);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "plane_minmax: launch failed");
-  return 0;
+  return gigs_internal_check_launch("plane_minmax");
 }
 
 int gigs_png_filter(int n, const gigs_filter_desc* desc, void* stream) {
   if (n == 0) return 0;
   if (n < 0 || n > GIGS_MAX_IMAGES || !desc) return gigs_internal_fail(GIGS_ERR_INVALID, "png_filter: bad argument");
   hipLaunchKernelGGL(gigs::img::filter_kernel, dim3(gigs::img::kFilterBlocks, n), dim3(256), 0, (hipStream_t)stream, n, desc);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "png_filter: launch failed");
-  return 0;
+  return gigs_internal_check_launch("png_filter");
 }
 }  // extern "C"

@@ -16,8 +16,7 @@
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "../../include/gigs_hip.h"
-#include "gigs_common.h"
+#include "gigs_internal.h"
 
 namespace gigs {
 
@@ -243,9 +242,6 @@ static KnnScratch knn_carve(char* base, int P) {
 }  // namespace gigs
 
 extern "C" {
-int gigs_internal_fail(int code, const char* fmt, ...);
-void gigs_internal_stage_begin(int stage, void* stream, void** token);
-void gigs_internal_stage_end(void* token);
 
 size_t gigs_dist2_scratch_bytes(int P) {
   if (P <= 0) return 0;
@@ -259,7 +255,7 @@ int gigs_dist2(int P, const float* points, float* mean_dists, void* scratch, siz
   gigs::KnnScratch k = gigs::knn_carve((char*)scratch, P);
   if (scratch_bytes < k.total) return gigs_internal_fail(GIGS_ERR_INVALID, "dist2: scratch too small");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(29, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kDist2, stream);
   const int nb = (P + gigs::kKnnBox - 1) / gigs::kKnnBox, ns = (nb + gigs::kKnnSuper - 1) / gigs::kKnnSuper;
   const int pblocks = (P + 255) / 256;
   hipLaunchKernelGGL(gigs::knn_init_kernel, dim3(1), dim3(64), 0, s, k.ext);
@@ -267,18 +263,14 @@ int gigs_dist2(int P, const float* points, float* mean_dists, void* scratch, siz
   hipLaunchKernelGGL(gigs::knn_morton_kernel, dim3(pblocks), dim3(256), 0, s, P, points, k.ext, k.codes, k.index);
   size_t bytes = k.sort_bytes;
   if (rocprim::radix_sort_pairs(k.sort_temp, bytes, k.codes, k.codes_sorted, k.index, k.order, (size_t)P, 0, 30, s) !=
-      hipSuccess) {
-    gigs_internal_stage_end(tok);
+      hipSuccess)
     return gigs_internal_fail(GIGS_ERR_HIP, "dist2: sort failed");
-  }
   hipLaunchKernelGGL(gigs::knn_gather_kernel, dim3((nb * 64 + 255) / 256), dim3(256), 0, s, P, points, k.order, k.sorted,
                      k.boxes);
   hipLaunchKernelGGL(gigs::knn_super_kernel, dim3((ns * 64 + 255) / 256), dim3(256), 0, s, nb, k.boxes, k.supers);
   hipLaunchKernelGGL(gigs::knn_search_kernel, dim3((nb + 3) / 4), dim3(256), 0, s, P, nb, ns, k.sorted, k.boxes, k.supers,
                      mean_dists);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "dist2: launch failed");
-  return 0;
+  return gigs_internal_check_launch("dist2");
 }
 
 }  // extern "C"

@@ -21,8 +21,7 @@
 // same bits alone, inside a batch, in either argument order (the head is symmetric) and on every call.
 #include <cmath>
 
-#include "../../include/gigs_hip.h"
-#include "gigs_common.h"
+#include "gigs_internal.h"
 
 namespace gigs {
 namespace lp {
@@ -374,7 +373,6 @@ inline Sizes sizes(int n, int H, int W) {
 }  // namespace gigs
 
 extern "C" {
-int gigs_internal_fail(int code, const char* msg);  // api.hip
 
 size_t gigs_lpips_vgg_weight_floats(void) { return gigs::lp::kWeightFloats; }
 
@@ -398,8 +396,7 @@ int gigs_lpips_vgg_pack(const float* const* conv_w, const float* const* conv_b, 
     if (hipMemcpyAsync(packed + lin_offset(t), lin_w[t], kTapC[t] * sizeof(float), hipMemcpyDeviceToDevice, s) !=
         hipSuccess)
       return gigs_internal_fail(GIGS_ERR_HIP, "lpips_vgg_pack: copy failed");
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "lpips_vgg_pack: launch failed");
-  return 0;
+  return gigs_internal_check_launch("lpips_vgg_pack");
 }
 
 size_t gigs_lpips_vgg_scratch_bytes(int n, int height, int width) {
@@ -460,7 +457,6 @@ int gigs_lpips_vgg(int n, int height, int width, const float* in0, const float* 
                          kTapC[tap], cur, taps[tap], taps[kTaps + tap]);
   }
   hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, n, part, z.g, slot, out);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "lpips_vgg: launch failed");
-  return 0;
+  return gigs_internal_check_launch("lpips_vgg");
 }
 }  // extern "C"

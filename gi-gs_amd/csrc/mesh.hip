@@ -20,8 +20,7 @@
 //                        arrays (the caller's): one vertex per active cell in ascending cell index, two triangles per
 //                        quad ordered by (sample index, axis).  Both take the capacities of their outputs: an index
 //                        beyond a capacity sets *overflow and stores nothing.
-#include "../../include/gigs_hip.h"
-#include "gigs_common.h"
+#include "gigs_internal.h"
 
 namespace gigs {
 namespace mesh {
@@ -303,7 +302,6 @@ inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace gigs
 
 extern "C" {
-int gigs_internal_fail(int code, const char* msg);  // api.hip
 
 int gigs_tsdf_integrate(const gigs_tsdf_grid* grid, int n_views, const gigs_tsdf_view* views, void* stream) {
   using namespace gigs::mesh;
@@ -332,8 +330,7 @@ int gigs_tsdf_integrate(const gigs_tsdf_grid* grid, int n_views, const gigs_tsdf
   const size_t total = (size_t)g.Gx * g.Gy * g.Gz;
   hipLaunchKernelGGL(integrate_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, g, n_views, vk, grid->tsdf,
                      grid->weight, grid->attr_weight, grid->attr);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "tsdf_integrate: launch failed");
-  return 0;
+  return gigs_internal_check_launch("tsdf_integrate");
 }
 
 int gigs_mesh_count(const gigs_tsdf_grid* grid, float min_weight, int* cell_flags, int* sample_quads, void* stream) {
@@ -347,8 +344,7 @@ int gigs_mesh_count(const gigs_tsdf_grid* grid, float min_weight, int* cell_flag
                      cell_flags);
   hipLaunchKernelGGL(count_quads_kernel, dim3(blocks_for((size_t)D.Gx * D.Gy * D.Gz)), dim3(256), 0, s, D, min_weight,
                      grid->tsdf, grid->weight, sample_quads);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_count: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_count");
 }
 
 int gigs_mesh_write(const gigs_tsdf_grid* grid, float min_weight, const int* cell_offsets, const int* quad_offsets,
@@ -369,7 +365,6 @@ int gigs_mesh_write(const gigs_tsdf_grid* grid, float min_weight, const int* cel
                      vertex_capacity, vertices, normals, albedo, roughness, metallic, overflow);
   hipLaunchKernelGGL(write_faces_kernel, dim3(blocks_for((size_t)D.Gx * D.Gy * D.Gz)), dim3(256), 0, s, D, min_weight,
                      grid->tsdf, grid->weight, cell_offsets, quad_offsets, vertex_capacity, face_capacity, faces, overflow);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_write: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_write");
 }
 }  // extern "C"

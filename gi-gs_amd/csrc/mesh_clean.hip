@@ -27,8 +27,7 @@
 //   progress    A pass that sets *changed lowers the parent of at least one vertex that was a root, so the number of
 //               roots falls: at most V passes in any schedule.  The host's cap is far lower (mesh.py, DESIGN.md
 //               "Cleaning meshes") and reaching it is an error, never a result.
-#include "../../include/gigs_hip.h"
-#include "gigs_common.h"
+#include "gigs_internal.h"
 
 namespace gigs {
 namespace mesh_clean {
@@ -180,7 +179,6 @@ inline unsigned blocks_for(int n) { return ((unsigned)n + 255u) / 256u; }
 }  // namespace gigs
 
 extern "C" {
-int gigs_internal_fail(int code, const char* msg);  // api.hip
 
 int gigs_mesh_cc_hook(int n_vertices, int n_faces, const int* faces, int* parent, int* changed, void* stream) {
   using namespace gigs::mesh_clean;
@@ -190,8 +188,7 @@ int gigs_mesh_cc_hook(int n_vertices, int n_faces, const int* faces, int* parent
   if (hipMemsetAsync(changed, 0, sizeof(int), s) != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_cc_hook: clear failed");
   if (n_faces == 0 || n_vertices == 0) return 0;
   hipLaunchKernelGGL(hook_kernel, dim3(blocks_for(n_faces)), dim3(256), 0, s, n_vertices, n_faces, faces, parent, changed);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_cc_hook: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_cc_hook");
 }
 
 int gigs_mesh_cc_flatten(int n_vertices, int* parent, void* stream) {
@@ -199,8 +196,7 @@ int gigs_mesh_cc_flatten(int n_vertices, int* parent, void* stream) {
   if (n_vertices < 0 || (n_vertices > 0 && !parent)) return gigs_internal_fail(GIGS_ERR_INVALID, "mesh_cc_flatten: bad argument");
   if (n_vertices == 0) return 0;
   hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(n_vertices)), dim3(256), 0, (hipStream_t)stream, n_vertices, parent);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_cc_flatten: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_cc_flatten");
 }
 
 int gigs_mesh_cc_count(int n_vertices, int n_faces, const int* faces, const int* parent, int* face_label, int* count,
@@ -216,8 +212,7 @@ int gigs_mesh_cc_count(int n_vertices, int n_faces, const int* faces, const int*
   if (n_faces == 0) return 0;
   hipLaunchKernelGGL(count_kernel, dim3(blocks_for(n_faces)), dim3(256), 0, s, n_vertices, n_faces, faces, parent, face_label,
                      count, invalid_faces);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_cc_count: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_cc_count");
 }
 
 int gigs_mesh_mark(int n_vertices, int n_faces, const int* faces, const int* face_label, const uint8_t* root_keep,
@@ -232,8 +227,7 @@ int gigs_mesh_mark(int n_vertices, int n_faces, const int* faces, const int* fac
   if (n_faces == 0) return 0;
   hipLaunchKernelGGL(mark_kernel, dim3(blocks_for(n_faces)), dim3(256), 0, s, n_vertices, n_faces, faces, face_label, root_keep,
                      face_keep, vertex_keep);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_mark: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_mark");
 }
 
 int gigs_mesh_compact(int n_vertices, int n_faces, const float* vertices, const float* normals, const float* albedo,
@@ -259,7 +253,6 @@ int gigs_mesh_compact(int n_vertices, int n_faces, const float* vertices, const 
   if (n_faces > 0 && n_vertices > 0)
     hipLaunchKernelGGL(compact_faces_kernel, dim3(blocks_for(n_faces)), dim3(256), 0, s, n_vertices, n_faces, faces, vertex_keep,
                        vertex_offsets, face_keep, face_offsets, vertex_capacity, face_capacity, out_faces, overflow);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_compact: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_compact");
 }
 }  // extern "C"

@@ -12,8 +12,7 @@
 // Both raster kernels and the resolve go through tri_setup / tri_sample, so the depth in a key and the depth plane have the
 // same bits, and both paths and any small_max give the same visibility buffer.  No clipping: a triangle with a vertex
 // behind the near cull (or outside the guard band) is dropped whole.
-#include "../../include/gigs_hip.h"
-#include "gigs_common.h"
+#include "gigs_internal.h"
 
 namespace gigs {
 namespace mesh_raster {
@@ -243,7 +242,6 @@ inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace gigs
 
 extern "C" {
-int gigs_internal_fail(int code, const char* msg);  // api.hip
 
 int gigs_mesh_project(int n_vertices, const float* vertices, const float* viewmatrix, float tanfovx, float tanfovy, int width,
                       int height, float* view_pos, int* screen, uint8_t* flags, void* stream) {
@@ -256,8 +254,7 @@ int gigs_mesh_project(int n_vertices, const float* vertices, const float* viewma
                    (float)(height - 1) / 2.0f};
   hipLaunchKernelGGL(project_kernel, dim3(blocks_for((size_t)n_vertices)), dim3(256), 0, (hipStream_t)stream, n_vertices, k,
                      vertices, viewmatrix, view_pos, screen, flags);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_project: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_project");
 }
 
 size_t gigs_mesh_raster_scratch_bytes(int n_faces) { return sizeof(unsigned) * ((size_t)(n_faces > 0 ? n_faces : 0) + 4); }
@@ -280,8 +277,7 @@ int gigs_mesh_raster(int n_vertices, int n_faces, const int* faces, const float*
   hipLaunchKernelGGL(raster_small_kernel, dim3(blocks_for((size_t)n_faces)), dim3(256), 0, s, m,
                      (long long)(small_max < 0 ? GIGS_MESH_SMALL_MAX : small_max), vis, counter, list);
   hipLaunchKernelGGL(raster_large_kernel, dim3(kLargeBlocks), dim3(256), 0, s, m, vis, counter, list);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_raster: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_raster");
 }
 
 int gigs_mesh_resolve(int n_vertices, int n_faces, const int* faces, const float* view_pos, const int* screen,
@@ -300,7 +296,6 @@ int gigs_mesh_resolve(int n_vertices, int n_faces, const int* faces, const float
   const AttrK a = {normals, albedo, roughness, metallic, viewmatrix};
   const PlanesK o = {opacity, depth, pos, normal, normal_view, albedo_out, roughness_out, metallic_out, tri_id};
   hipLaunchKernelGGL(resolve_kernel, dim3(blocks_for((size_t)width * height)), dim3(256), 0, (hipStream_t)stream, m, a, vis, o);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "mesh_resolve: launch failed");
-  return 0;
+  return gigs_internal_check_launch("mesh_resolve");
 }
 }  // extern "C"

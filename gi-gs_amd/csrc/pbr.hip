@@ -1852,30 +1852,18 @@ shade_bwd_kernel(ShadeArgs A) {
 // ------------------------------------------------------------------------------------------
 // C ABI (declared in include/gigs_hip.h)
 // ------------------------------------------------------------------------------------------
-#include "../../include/gigs_hip.h"
+#include "gigs_internal.h"
 
 extern "C" {
-
-int gigs_internal_fail(int code, const char* msg);  // api.hip
-void gigs_internal_stage_begin(int stage, void* stream, void** token);
-void gigs_internal_stage_end(void* token);
-const gigs::Options* gigs_internal_options(const gigs_ctx* ctx);  // the context's options (NULL = the defaults)
-
-#define PBR_CHECK_LAUNCH()                                        \
-  do {                                                            \
-    if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "pbr kernel launch failed"); \
-  } while (0)
 
 int gigs_diffuse_cubemap_fwd(int res, const float* cubemap, float* out, void* stream) {
   if (res <= 0 || !cubemap || !out) return gigs_internal_fail(GIGS_ERR_INVALID, "diffuse_cubemap_fwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
   const float4* table = gigs::texel_table(res, s);
   if (!table) return gigs_internal_fail(GIGS_ERR_HIP, "texel table");
-  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapFwd, stream);
   hipLaunchKernelGGL(gigs::diffuse_cubemap_kernel<false>, dim3((6 * res * res + 3) / 4), dim3(256), 0, s, res, table, cubemap, out);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("diffuse_cubemap_fwd");
 }
 
 int gigs_diffuse_cubemap_bwd(int res, const float* grad_out, float* grad_cubemap, void* stream) {
@@ -1883,18 +1871,15 @@ int gigs_diffuse_cubemap_bwd(int res, const float* grad_out, float* grad_cubemap
   hipStream_t s = (hipStream_t)stream;
   const float4* table = gigs::texel_table(res, s);
   if (!table) return gigs_internal_fail(GIGS_ERR_HIP, "texel table");
-  void* tok; gigs_internal_stage_begin(17, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
   hipLaunchKernelGGL(gigs::diffuse_cubemap_kernel<true>, dim3((6 * res * res + 3) / 4), dim3(256), 0, s, res, table, grad_out, grad_cubemap);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("diffuse_cubemap_bwd");
 }
 
 int gigs_specular_bounds(int res, float costheta_cutoff, float* bounds, void* stream) {
   if (res <= 0 || !bounds) return gigs_internal_fail(GIGS_ERR_INVALID, "specular_bounds: bad argument");
   hipLaunchKernelGGL(gigs::specular_bounds_kernel, dim3((6 * res * res + 63) / 64), dim3(64), 0, (hipStream_t)stream, res, costheta_cutoff, bounds);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("specular_bounds");
 }
 
 int gigs_specular_cubemap_fwd(int res, const float* cubemap, const float* bounds, float roughness,
@@ -1903,11 +1888,9 @@ int gigs_specular_cubemap_fwd(int res, const float* cubemap, const float* bounds
   hipStream_t s = (hipStream_t)stream;
   const float4* table = gigs::texel_table(res, s);
   if (!table) return gigs_internal_fail(GIGS_ERR_HIP, "texel table");
-  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapFwd, stream);
   hipLaunchKernelGGL(gigs::specular_cubemap_kernel<false>, dim3((6 * res * res + 3) / 4), dim3(256), 0, s, res, table, cubemap, bounds, roughness, costheta_cutoff, out);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("specular_cubemap_fwd");
 }
 
 int gigs_specular_cubemap_bwd(int res, const float* bounds, const float* grad_out, float roughness,
@@ -1916,11 +1899,9 @@ int gigs_specular_cubemap_bwd(int res, const float* bounds, const float* grad_ou
   hipStream_t s = (hipStream_t)stream;
   const float4* table = gigs::texel_table(res, s);
   if (!table) return gigs_internal_fail(GIGS_ERR_HIP, "texel table");
-  void* tok; gigs_internal_stage_begin(17, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
   hipLaunchKernelGGL(gigs::specular_cubemap_kernel<true>, dim3((6 * res * res + 3) / 4), dim3(256), 0, s, res, table, grad_out, bounds, roughness, costheta_cutoff, grad_cubemap);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("specular_cubemap_bwd");
 }
 
 int gigs_specular_weights(int res, const float* bounds, const uint32_t* offsets, float roughness,
@@ -1934,8 +1915,7 @@ int gigs_specular_weights(int res, const float* bounds, const uint32_t* offsets,
     hipLaunchKernelGGL(gigs::specular_weights_kernel<true>, grid, dim3(256), 0, s, res, table, bounds, offsets, roughness, costheta_cutoff, weights);
   else
     hipLaunchKernelGGL(gigs::specular_weights_kernel<false>, grid, dim3(256), 0, s, res, table, bounds, offsets, roughness, costheta_cutoff, weights);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("specular_weights");
 }
 
 int gigs_specular_weights_divide(int res, const float* bounds, const uint32_t* offsets, const float* weights,
@@ -1944,8 +1924,7 @@ int gigs_specular_weights_divide(int res, const float* bounds, const uint32_t* o
     return gigs_internal_fail(GIGS_ERR_INVALID, "specular_weights_divide: bad argument");
   hipLaunchKernelGGL(gigs::specular_divide_weights_kernel, dim3((6 * res * res + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                      res, bounds, offsets, weights, texel_divisor, out_weights);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("specular_weights_divide");
 }
 
 int gigs_specular_cubemap_fwd_w(gigs_ctx* ctx, int res, const float* cubemap, const float* bounds, const uint32_t* offsets,
@@ -1953,14 +1932,12 @@ int gigs_specular_cubemap_fwd_w(gigs_ctx* ctx, int res, const float* cubemap, co
   const gigs::Options& o = *gigs_internal_options(ctx);
   if (res <= 0 || !cubemap || !bounds || !offsets || !weights || !out) return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_fwd_w: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapFwd, stream);
   if (wsum_out)
     gigs::launch_specular_apply<false, true>(o, res, avg_window, cubemap, bounds, offsets, weights, out, wsum_out, s);
   else
     gigs::launch_specular_apply<false, false>(o, res, avg_window, cubemap, bounds, offsets, weights, out, nullptr, s);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("specular_cubemap_fwd_w");
 }
 
 int gigs_specular_cubemap_bwd_w(gigs_ctx* ctx, int res, const float* bounds, const uint32_t* offsets, const float* weights_swapped,
@@ -1968,14 +1945,23 @@ int gigs_specular_cubemap_bwd_w(gigs_ctx* ctx, int res, const float* bounds, con
   const gigs::Options& o = *gigs_internal_options(ctx);
   if (res <= 0 || !bounds || !offsets || !weights_swapped || !grad_out || !grad_cubemap) return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_bwd_w: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(17, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
   if (grad_is_rgb)
     gigs::launch_specular_apply<true, true>(o, res, avg_window, grad_out, bounds, offsets, weights_swapped, grad_cubemap, nullptr, s);
   else
     gigs::launch_specular_apply<true, false>(o, res, avg_window, grad_out, bounds, offsets, weights_swapped, grad_cubemap, nullptr, s);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("specular_cubemap_bwd_w");
+}
+
+// One level of a multi-level apply launch: its arrays, its lane group and its first workgroup; `blocks` advances past
+// the level.  Returns the level's texel count.
+static int fill_spec_level(const gigs::Options& o, const gigs_spec_level& a, gigs::SpecLevel& v, int& blocks) {
+  v.N = a.res; v.lanes = gigs::spec_lanes_for(o, a.avg_window); v.block_begin = blocks;
+  v.src = a.src; v.bounds = a.bounds; v.offsets = a.offsets; v.W = a.weights; v.dst = a.dst; v.wsum_out = a.wsum;
+  const int total = 6 * a.res * a.res;
+  const int waves = v.lanes == 64 ? total : (total + (64 / v.lanes) - 1) / (64 / v.lanes);
+  blocks += (waves + 3) / 4;
+  return total;
 }
 
 int gigs_specular_cubemap_multi_w(gigs_ctx* ctx, int n_levels, const gigs_spec_level* levels, int backward, void* stream) {
@@ -1988,19 +1974,12 @@ int gigs_specular_cubemap_multi_w(gigs_ctx* ctx, int n_levels, const gigs_spec_l
     const gigs_spec_level& a = levels[i];
     if (a.res <= 0 || !a.src || !a.bounds || !a.offsets || !a.weights || !a.dst || (!backward && !a.wsum))
       return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_multi_w: bad level");
-    gigs::SpecLevel& v = L.lv[i];
-    v.N = a.res; v.lanes = gigs::spec_lanes_for(o, a.avg_window); v.block_begin = blocks;
-    v.src = a.src; v.bounds = a.bounds; v.offsets = a.offsets; v.W = a.weights; v.dst = a.dst; v.wsum_out = a.wsum;
-    const int total = 6 * a.res * a.res;
-    const int waves = v.lanes == 64 ? total : (total + (64 / v.lanes) - 1) / (64 / v.lanes);
-    blocks += (waves + 3) / 4;
+    fill_spec_level(o, a, L.lv[i], blocks);
   }
-  void* tok; gigs_internal_stage_begin(backward ? 17 : 16, stream, &tok);
+  gigs::StageTimer timer(backward ? gigs::Stage::kCubemapBwd : gigs::Stage::kCubemapFwd, stream);
   if (backward) hipLaunchKernelGGL(gigs::specular_apply_multi_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
   else hipLaunchKernelGGL(gigs::specular_apply_multi_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("specular_cubemap_multi_w");
 }
 
 int gigs_spec_sparse_capacity(const gigs_ctx* ctx, int res) {
@@ -2024,12 +2003,7 @@ int gigs_specular_cubemap_multi_bwd_sparse(gigs_ctx* ctx, int n_levels, const gi
     const gigs_spec_level& a = levels[i];
     if (a.res <= 0 || a.res > 4096 || !a.src || !a.bounds || !a.offsets || !a.weights || !a.dst || !weights_fwd[i] || !wsum[i])
       return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_multi_bwd_sparse: bad level");
-    gigs::SpecLevel& v = L.lv[i];
-    v.N = a.res; v.lanes = gigs::spec_lanes_for(o, a.avg_window); v.block_begin = blocks;
-    v.src = a.src; v.bounds = a.bounds; v.offsets = a.offsets; v.W = a.weights; v.dst = a.dst; v.wsum_out = a.wsum;
-    const int total = 6 * a.res * a.res;
-    const int waves = v.lanes == 64 ? total : (total + (64 / v.lanes) - 1) / (64 / v.lanes);
-    blocks += (waves + 3) / 4;
+    const int total = fill_spec_level(o, a, L.lv[i], blocks);
     gigs::SparseLevel& q = S.lv[i];
     q.total = total; q.cap = gigs::spec_sparse_capacity(o, a.res); q.block_begin = census_blocks; q.group_begin = groups; q.N = a.res;
     q.vec = ((((uintptr_t)a.src) | ((uintptr_t)a.dst)) & 15) == 0;
@@ -2045,55 +2019,43 @@ int gigs_specular_cubemap_multi_bwd_sparse(gigs_ctx* ctx, int n_levels, const gi
     list_begin += (size_t)q.cap;
   }
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(17, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
   hipLaunchKernelGGL(gigs::specular_census_kernel, dim3(census_blocks), dim3(256), 0, s, S, state);
   hipLaunchKernelGGL(gigs::specular_scatter_kernel, dim3(std::max(1, (groups + 3) / 4)), dim3(256), 0, s, S, state);
   hipLaunchKernelGGL(gigs::specular_apply_multi_bwd_sparse_kernel, dim3(blocks), dim3(256), 0, s, L, state);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("specular_cubemap_multi_bwd_sparse");
 }
 
 int gigs_cubemap_mip_fwd(int res_out, int channels, const float* in, float* out, void* stream) {
   if (res_out <= 0 || channels <= 0 || !in || !out) return gigs_internal_fail(GIGS_ERR_INVALID, "cubemap_mip_fwd: bad argument");
-  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapFwd, stream);
   hipLaunchKernelGGL(gigs::cubemap_mip_fwd_kernel, dim3((6 * res_out * res_out * channels + 255) / 256), dim3(256), 0, (hipStream_t)stream, res_out, channels, in, out);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("cubemap_mip_fwd");
+}
+
+// din = 2x2 box backward of dout (+ dout2) (+ add): the three entry points differ in which addends they pass
+static int cubemap_mip_bwd(const char* entry, int res_out, const float* dout, const float* dout2, const float* add, float* din,
+                           void* stream) {
+  const int res = 2 * res_out;
+  gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
+  hipLaunchKernelGGL(gigs::cubemap_mip_bwd_kernel, dim3((6 * res * res + 255) / 256), dim3(256), 0, (hipStream_t)stream, res_out, dout, din, add,
+                     dout2);
+  return gigs_internal_check_launch(entry);
 }
 
 int gigs_cubemap_mip_bwd(int res_out, const float* dout, float* din, void* stream) {
   if (res_out <= 0 || !dout || !din) return gigs_internal_fail(GIGS_ERR_INVALID, "cubemap_mip_bwd: bad argument");
-  const int res = 2 * res_out;
-  void* tok; gigs_internal_stage_begin(17, stream, &tok);
-  hipLaunchKernelGGL(gigs::cubemap_mip_bwd_kernel, dim3((6 * res * res + 255) / 256), dim3(256), 0, (hipStream_t)stream, res_out, dout, din, (const float*)nullptr,
-                     (const float*)nullptr);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return cubemap_mip_bwd("cubemap_mip_bwd", res_out, dout, nullptr, nullptr, din, stream);
 }
 
 int gigs_cubemap_mip_bwd_add(int res_out, const float* dout, const float* add, float* din, void* stream) {
   if (res_out <= 0 || !dout || !add || !din) return gigs_internal_fail(GIGS_ERR_INVALID, "cubemap_mip_bwd_add: bad argument");
-  const int res = 2 * res_out;
-  void* tok; gigs_internal_stage_begin(17, stream, &tok);
-  hipLaunchKernelGGL(gigs::cubemap_mip_bwd_kernel, dim3((6 * res * res + 255) / 256), dim3(256), 0, (hipStream_t)stream, res_out, dout, din, add,
-                     (const float*)nullptr);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return cubemap_mip_bwd("cubemap_mip_bwd_add", res_out, dout, nullptr, add, din, stream);
 }
 
 int gigs_cubemap_mip_bwd_add2(int res_out, const float* dout, const float* dout2, const float* add, float* din, void* stream) {
   if (res_out <= 0 || !dout || !din) return gigs_internal_fail(GIGS_ERR_INVALID, "cubemap_mip_bwd_add2: bad argument");
-  const int res = 2 * res_out;
-  void* tok; gigs_internal_stage_begin(17, stream, &tok);
-  hipLaunchKernelGGL(gigs::cubemap_mip_bwd_kernel, dim3((6 * res * res + 255) / 256), dim3(256), 0, (hipStream_t)stream, res_out, dout, din, add,
-                     dout2);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return cubemap_mip_bwd("cubemap_mip_bwd_add2", res_out, dout, dout2, add, din, stream);
 }
 
 int gigs_cube_texture_fwd(int res, const float* cubemap, int n, const float* dirs, float* out, int planar,
@@ -2101,24 +2063,20 @@ int gigs_cube_texture_fwd(int res, const float* cubemap, int n, const float* dir
   if (res <= 0 || n < 0 || !cubemap || (n > 0 && (!dirs || !out)))
     return gigs_internal_fail(GIGS_ERR_INVALID, "cube_texture_fwd: bad argument");
   if (n == 0) return 0;
-  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapFwd, stream);
   hipLaunchKernelGGL(gigs::cube_texture_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, res,
                      cubemap, n, dirs, out, planar);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("cube_texture_fwd");
 }
 
 int gigs_cube_texture_fwd_precise(int res, const float* cubemap, int n, const float* dirs, float* out, void* stream) {
   if (res <= 0 || n < 0 || !cubemap || (n > 0 && (!dirs || !out)))
     return gigs_internal_fail(GIGS_ERR_INVALID, "cube_texture_fwd_precise: bad argument");
   if (n == 0) return 0;
-  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapFwd, stream);
   hipLaunchKernelGGL(gigs::cube_texture_fwd_precise_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, res,
                      cubemap, n, dirs, out);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("cube_texture_fwd_precise");
 }
 
 int gigs_latlong_to_cubemap(int res_y, int res_x, int lat_h, int lat_w, int channels, const float* latlong, float* cubemap,
@@ -2126,12 +2084,10 @@ int gigs_latlong_to_cubemap(int res_y, int res_x, int lat_h, int lat_w, int chan
   if (res_y <= 0 || res_x <= 0 || lat_h <= 0 || lat_w <= 0 || channels <= 0 || !latlong || !cubemap)
     return gigs_internal_fail(GIGS_ERR_INVALID, "latlong_to_cubemap: bad argument");
   const int n = 6 * res_y * res_x;
-  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapFwd, stream);
   hipLaunchKernelGGL(gigs::latlong_to_cubemap_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, res_y, res_x,
                      lat_h, lat_w, channels, latlong, cubemap);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("latlong_to_cubemap");
 }
 
 int gigs_latlong_to_cubemap_rot(int res_y, int res_x, int lat_h, int lat_w, int channels, const float* latlong, int n_rot,
@@ -2141,12 +2097,10 @@ int gigs_latlong_to_cubemap_rot(int res_y, int res_x, int lat_h, int lat_w, int 
   if (res_y <= 0 || res_x <= 0 || lat_h <= 0 || lat_w <= 0 || channels <= 0 || !latlong || !rotations || !cubemap)
     return gigs_internal_fail(GIGS_ERR_INVALID, "latlong_to_cubemap_rot: bad argument");
   const int n = 6 * res_y * res_x;
-  void* tok; gigs_internal_stage_begin(16, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapFwd, stream);
   hipLaunchKernelGGL(gigs::latlong_to_cubemap_rot_kernel, dim3((n + 255) / 256, n_rot), dim3(256), 0, (hipStream_t)stream,
                      res_y, res_x, lat_h, lat_w, channels, latlong, rotations, cubemap);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("latlong_to_cubemap_rot");
 }
 
 int gigs_cube_texture_bwd(int res, int n, const float* dirs, const float* g_out, float* d_cubemap, int planar,
@@ -2154,20 +2108,17 @@ int gigs_cube_texture_bwd(int res, int n, const float* dirs, const float* g_out,
   if (res <= 0 || n < 0 || !d_cubemap || (n > 0 && (!dirs || !g_out)))
     return gigs_internal_fail(GIGS_ERR_INVALID, "cube_texture_bwd: bad argument");
   if (n == 0) return 0;
-  void* tok; gigs_internal_stage_begin(17, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
   hipLaunchKernelGGL(gigs::cube_texture_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, res, n,
                      dirs, g_out, d_cubemap, planar);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("cube_texture_bwd");
 }
 
 int gigs_cube_taps(int res, int n, const float* dirs, int* idx, float* w, void* stream) {
   if (res <= 0 || n < 0 || (n > 0 && (!dirs || !idx || !w))) return gigs_internal_fail(GIGS_ERR_INVALID, "cube_taps: bad argument");
   if (n == 0) return 0;
   hipLaunchKernelGGL(gigs::cube_taps_export_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, res, n, dirs, idx, w);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("cube_taps");
 }
 
 int gigs_cube_texture_bwd_gather(int res, int n, int planar, const int* offsets, const int* ent_sample, const float* ent_w,
@@ -2178,12 +2129,10 @@ int gigs_cube_texture_bwd_gather(int res, int n, int planar, const int* offsets,
     return gigs_internal_fail(GIGS_ERR_INVALID, "cube_texture_bwd_gather: bad argument");
   const int n_tex = 6 * res * res;
   const int light_blocks = (n_tex + 255) / 256, heavy_blocks = (n_heavy + 3) / 4;
-  void* tok; gigs_internal_stage_begin(17, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
   hipLaunchKernelGGL(gigs::cube_texture_bwd_gather_kernel, dim3(light_blocks + heavy_blocks), dim3(256), 0, (hipStream_t)stream,
                      n_tex, offsets, ent_sample, ent_w, g_out, n, planar, d_cubemap, heavy, light_blocks, heavy_ids, n_heavy);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("cube_texture_bwd_gather");
 }
 
 static int fill_shade(gigs::ShadeArgs& A, int H, int W, const float* normals, const float* view_dirs,
@@ -2257,11 +2206,9 @@ int gigs_shade_fwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
     return gigs_internal_fail(GIGS_ERR_INVALID, "shade_fwd: null output");
   if (apply_shade_ext(A, ext, false)) return GIGS_ERR_INVALID;
   A.render_rgb = render_rgb; A.diffuse_rgb = diffuse_rgb; A.specular_rgb = specular_rgb; A.diffuse_light = diffuse_light;
-  void* tok; gigs_internal_stage_begin(14, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kShadeFwd, stream);
   hipLaunchKernelGGL(gigs::shade_fwd_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, A);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("shade_fwd");
 }
 
 int gigs_shade_fwd_post(gigs_ctx* ctx, int H, int W, const float* normal_map, const float* out_normal_view,
@@ -2284,12 +2231,10 @@ int gigs_shade_fwd_post(gigs_ctx* ctx, int H, int W, const float* normal_map, co
   A.render_rgb = render_rgb;
   const gigs::ShadePostArgs P{normal_map, out_normal_view, viewmatrix, normals_view, normal_mask, normal_mask_f,
                               out_normal_view_filtered};
-  void* tok; gigs_internal_stage_begin(14, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kShadeFwd, stream);
   hipLaunchKernelGGL(gigs::shade_fwd_post_kernel, dim3((W + gigs::kPostW - 1) / gigs::kPostW, (H + gigs::kPostH - 1) / gigs::kPostH),
                      dim3(256), 0, (hipStream_t)stream, A, P);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("shade_fwd_post");
 }
 
 int gigs_shade_fwd_multi(gigs_ctx* ctx, int n_lights, int H, int W, const float* normals, const float* view_dirs,
@@ -2319,11 +2264,9 @@ int gigs_shade_fwd_multi(gigs_ctx* ctx, int n_lights, int H, int W, const float*
   }
   A.ps = 1; A.cs = H * W;  // planar, rough_scale 1, rough_bias 0 (fill_shade)
   A.render_rgb = render_rgb; A.out_linear = out_linear;
-  void* tok; gigs_internal_stage_begin(14, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kShadeFwd, stream);
   hipLaunchKernelGGL(gigs::shade_fwd_multi_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, A, Ls);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("shade_fwd_multi");
 }
 
 int gigs_shade_bwd(int H, int W, const float* normals, const float* view_dirs, const float* albedo,
@@ -2381,7 +2324,7 @@ int gigs_shade_bwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
       return gigs_internal_fail(GIGS_ERR_HIP, "shade_bwd: cannot raise the dynamic LDS limit");
     attr_set[rows] = true;
   }
-  void* tok; gigs_internal_stage_begin(15, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kShadeBwd, stream);
   const int n_chunks = rows ? (H * W + gigs::kShadeBwdBlock - 1) / gigs::kShadeBwdBlock : ((W + 31) / 32) * ((H + 31) / 32);
   static const int n_cus = [] {  // one workgroup per CU (120 KB of LDS each); gigs_options.shade_bwd_blocks overrides
     int dev = 0, cus = 256;
@@ -2396,9 +2339,7 @@ int gigs_shade_bwd_ex(gigs_ctx* ctx, int H, int W, const float* normals, const f
   else
     hipLaunchKernelGGL(gigs::shade_bwd_kernel<true>, dim3(blocks), dim3(gigs::kShadeBwdBlock), (size_t)used * sizeof(float),
                        (hipStream_t)stream, A);
-  gigs_internal_stage_end(tok);
-  PBR_CHECK_LAUNCH();
-  return 0;
+  return gigs_internal_check_launch("shade_bwd");
 }
 
 }  // extern "C"

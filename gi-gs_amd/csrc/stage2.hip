@@ -16,8 +16,7 @@
 // All planes are [C,H,W] fp32, the rasterizer's layout.  HBM-bound streaming kernels.
 #include <cstdint>
 
-#include "../../include/gigs_hip.h"
-#include "gigs_common.h"
+#include "gigs_internal.h"
 #include "pixel_ops.h"
 
 namespace gigs {
@@ -564,9 +563,6 @@ static void launch_zero2(float* a, size_t na, float* b, size_t nb, hipStream_t s
 }  // namespace gigs
 
 extern "C" {
-int gigs_internal_fail(int code, const char* fmt, ...);
-void gigs_internal_stage_begin(int stage, void* stream, void** token);
-void gigs_internal_stage_end(void* token);
 
 int gigs_gbuffer_post(int height, int width, const float* normal_map, const float* out_normal_view,
                       const float* viewmatrix, float* normals_view, uint8_t* normal_mask, float* normal_mask_f,
@@ -574,13 +570,11 @@ int gigs_gbuffer_post(int height, int width, const float* normal_map, const floa
   if (height <= 0 || width <= 0 || !normal_map || !out_normal_view || !viewmatrix || !normals_view ||
       !out_normal_view_filtered)
     return gigs_internal_fail(GIGS_ERR_INVALID, "gbuffer_post: bad argument");
-  void* tok; gigs_internal_stage_begin(18, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kGbufferPost, stream);
   hipLaunchKernelGGL(gigs::gbuffer_post_kernel<false>, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, height, width, normal_map, out_normal_view, viewmatrix, normals_view,
                      normal_mask, normal_mask_f, out_normal_view_filtered, gigs::GbufferPad{});
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "gbuffer_post: launch failed");
-  return 0;
+  return gigs_internal_check_launch("gbuffer_post");
 }
 
 int gigs_gbuffer_post_pad(int height, int width, const float* normal_map, const float* normal_map_from_depth,
@@ -592,13 +586,11 @@ int gigs_gbuffer_post_pad(int height, int width, const float* normal_map, const 
       !out_normal_view_filtered || (normal_map_from_depth_out && !normal_map_from_depth))
     return gigs_internal_fail(GIGS_ERR_INVALID, "gbuffer_post_pad: bad argument");
   const gigs::GbufferPad pad{opacity_map, normal_map_from_depth, normal_world, normal_map_from_depth_out, opacity_out};
-  void* tok; gigs_internal_stage_begin(18, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kGbufferPost, stream);
   hipLaunchKernelGGL(gigs::gbuffer_post_kernel<true>, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, height, width, normal_map, out_normal_view, viewmatrix, normals_view,
                      normal_mask, normal_mask_f, out_normal_view_filtered, pad);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "gbuffer_post_pad: launch failed");
-  return 0;
+  return gigs_internal_check_launch("gbuffer_post_pad");
 }
 
 int gigs_gbuffer_post_bwd(int height, int width, const float* normal_map, const float* viewmatrix,
@@ -607,34 +599,29 @@ int gigs_gbuffer_post_bwd(int height, int width, const float* normal_map, const 
     return gigs_internal_fail(GIGS_ERR_INVALID, "gbuffer_post_bwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
   const size_t HW = (size_t)height * width;
-  void* tok; gigs_internal_stage_begin(18, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kGbufferPost, stream);
   gigs::launch_zero(scratch3, 3 * HW, s);
   hipLaunchKernelGGL(gigs::gbuffer_post_bwd_scatter_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, s,
                      height, width, normal_map, viewmatrix, g_normals_view, scratch3);
   hipLaunchKernelGGL(gigs::gbuffer_post_bwd_finish_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, s, HW,
                      normal_map, scratch3, g_normal_map);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "gbuffer_post_bwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("gbuffer_post_bwd");
 }
 
 int gigs_normalize_mask(int height, int width, const float* in, float* out, uint8_t* mask, void* stream) {
   if (height <= 0 || width <= 0 || !in || !out) return gigs_internal_fail(GIGS_ERR_INVALID, "normalize_mask: bad argument");
   const size_t HW = (size_t)height * width;
-  void* tok; gigs_internal_stage_begin(18, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kGbufferPost, stream);
   hipLaunchKernelGGL(gigs::normalize_mask_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, (hipStream_t)stream, HW,
                      in, out, mask);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "normalize_mask: launch failed");
-  return 0;
+  return gigs_internal_check_launch("normalize_mask");
 }
 
 int gigs_nonzero_mask(int height, int width, const float* in, float* mask, void* stream) {
   if (height <= 0 || width <= 0 || !in || !mask) return gigs_internal_fail(GIGS_ERR_INVALID, "nonzero_mask: bad argument");
   const size_t HW = (size_t)height * width;
   hipLaunchKernelGGL(gigs::nonzero_mask_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, (hipStream_t)stream, HW, in, mask);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "nonzero_mask: launch failed");
-  return 0;
+  return gigs_internal_check_launch("nonzero_mask");
 }
 
 int gigs_stage2_loss_fwd(int height, int width, const float* render_direct, const float* irr_linear,
@@ -644,16 +631,14 @@ int gigs_stage2_loss_fwd(int height, int width, const float* render_direct, cons
       !metallic || !acc4 || !loss)
     return gigs_internal_fail(GIGS_ERR_INVALID, "stage2_loss_fwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(19, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kLossFwd, stream);
   float* rows = acc4 + 4;  // [kAccSlots][4] partial sums behind the four totals
   gigs::launch_zero(rows, 4 * gigs::kAccSlots, s);
   hipLaunchKernelGGL(gigs::stage2_loss_fwd_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, s, height,
                      width, render_direct, irr_linear, gt_image, normal_mask_f, roughness, metallic, render_rgb, rows,
                      (float*)nullptr, (float*)nullptr);
   hipLaunchKernelGGL(gigs::stage2_loss_finish_kernel, dim3(1), dim3(64), 0, s, height, width, rows, acc4, loss);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "stage2_loss_fwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("stage2_loss_fwd");
 }
 
 int gigs_stage2_loss_fwd_grad(int height, int width, const float* render_direct, const float* irr_linear,
@@ -664,16 +649,14 @@ int gigs_stage2_loss_fwd_grad(int height, int width, const float* render_direct,
       !metallic || !acc4 || !loss || !d_render_direct_unit || !d_irr_linear_unit)
     return gigs_internal_fail(GIGS_ERR_INVALID, "stage2_loss_fwd_grad: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(19, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kLossFwd, stream);
   float* rows = acc4 + 4;
   gigs::launch_zero2(rows, 4 * gigs::kAccSlots, d_irr_linear_unit, 3 * (size_t)height * width, s);
   hipLaunchKernelGGL(gigs::stage2_loss_fwd_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, s, height,
                      width, render_direct, irr_linear, gt_image, normal_mask_f, roughness, metallic, render_rgb, rows,
                      d_render_direct_unit, d_irr_linear_unit);
   hipLaunchKernelGGL(gigs::stage2_loss_finish_kernel, dim3(1), dim3(64), 0, s, height, width, rows, acc4, loss);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "stage2_loss_fwd_grad: launch failed");
-  return 0;
+  return gigs_internal_check_launch("stage2_loss_fwd_grad");
 }
 
 // rows of the gather's scratch: one per workgroup
@@ -699,15 +682,13 @@ int gigs_stage2_loss_gather(int height, int width, const float* render_direct, c
   hipStream_t s = (hipStream_t)stream;
   double* rows = (double*)scratch;
   const dim3 grid((width + gigs::kGatherW - 1) / gigs::kGatherW, (height + gigs::kGatherH - 1) / gigs::kGatherH);
-  void* tok; gigs_internal_stage_begin(19, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kLossFwd, stream);
   hipLaunchKernelGGL(gigs::stage2_loss_gather_kernel, grid, dim3(256), 0, s, height, width, render_direct, irr_linear,
                      gt_image, normal_mask_f, roughness, metallic, render_rgb, rows, d_render_direct_unit,
                      d_irr_linear_unit);
   hipLaunchKernelGGL(gigs::stage2_loss_gather_finish_kernel, dim3(1), dim3(256), 0, s, height, width,
                      (int)(grid.x * grid.y), rows, acc4, loss);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "stage2_loss_gather: launch failed");
-  return 0;
+  return gigs_internal_check_launch("stage2_loss_gather");
 }
 
 int gigs_stage2_loss_bwd(int height, int width, const float* render_direct, const float* irr_linear,
@@ -718,14 +699,12 @@ int gigs_stage2_loss_bwd(int height, int width, const float* render_direct, cons
       !d_render_direct || !d_irr_linear || !d_roughness || !d_metallic)
     return gigs_internal_fail(GIGS_ERR_INVALID, "stage2_loss_bwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(20, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kLossBwd, stream);
   gigs::launch_zero(d_irr_linear, 3 * (size_t)height * width, s);
   hipLaunchKernelGGL(gigs::stage2_loss_bwd_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, s, height,
                      width, render_direct, irr_linear, gt_image, normal_mask_f, acc4, g_loss, d_render_direct,
                      d_irr_linear, d_roughness, d_metallic);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "stage2_loss_bwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("stage2_loss_bwd");
 }
 
 }  // extern "C"

@@ -17,8 +17,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "../../include/gigs_hip.h"
-#include "gigs_common.h"
+#include "gigs_internal.h"
 
 namespace gigs {
 
@@ -847,9 +846,6 @@ static inline unsigned stream_blocks(size_t HW) {
 }  // namespace gigs
 
 extern "C" {
-int gigs_internal_fail(int code, const char* fmt, ...);
-void gigs_internal_stage_begin(int stage, void* stream, void** token);
-void gigs_internal_stage_end(void* token);
 
 size_t gigs_loss_scratch_floats(int channels, int height, int width) {
   if (channels <= 0 || height <= 0 || width <= 0) return 0;
@@ -867,16 +863,14 @@ int gigs_l1_ssim_fwd(int channels, int height, int width, const float* image, co
       ((d_mu1 != nullptr) != (d_e11 != nullptr)) || ((d_mu1 != nullptr) != (d_e12 != nullptr)))
     return gigs_internal_fail(GIGS_ERR_INVALID, "l1_ssim_fwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(21, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kL1SsimFwd, stream);
   const dim3 grid((width + gigs::kSsimTile - 1) / gigs::kSsimTile, (height + gigs::kSsimTile - 1) / gigs::kSsimTile,
                   channels);
   hipLaunchKernelGGL(gigs::l1_ssim_fwd_kernel<false>, grid, dim3(256), 0, s, height, width, image, gt,
                      gigs::make_window(), d_mu1, d_e11, d_e12, scratch, nullptr, nullptr);
   hipLaunchKernelGGL(gigs::l1_ssim_finish_kernel, dim3(1), dim3(256), 0, s, scratch, (int)(grid.x * grid.y * grid.z),
                      (float)channels * (float)height * (float)width, lambda_dssim, out3);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "l1_ssim_fwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("l1_ssim_fwd");
 }
 
 size_t gigs_image_metrics_scratch_bytes(int channels, int height, int width) {
@@ -893,14 +887,12 @@ int gigs_image_metrics(int channels, int height, int width, const float* pred, c
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((width + gigs::kSsimTile - 1) / gigs::kSsimTile, (height + gigs::kSsimTile - 1) / gigs::kSsimTile,
                   channels);
-  void* tok; gigs_internal_stage_begin(21, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kL1SsimFwd, stream);
   hipLaunchKernelGGL(gigs::l1_ssim_fwd_kernel<true>, grid, dim3(256), 0, s, height, width, pred, gt, gigs::make_window(),
                      nullptr, nullptr, nullptr, nullptr, mask, (double*)scratch);
   hipLaunchKernelGGL(gigs::image_metrics_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)scratch, channels,
                      (int)(grid.x * grid.y), (double)height * (double)width, slot, out);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "image_metrics: launch failed");
-  return 0;
+  return gigs_internal_check_launch("image_metrics");
 }
 
 int gigs_normal_angular_error(int height, int width, const float* pred, const uint8_t* gt, int gt_channels,
@@ -911,14 +903,12 @@ int gigs_normal_angular_error(int height, int width, const float* pred, const ui
   const size_t HW = (size_t)height * width;
   if (HW > 0x7fffffff) return gigs_internal_fail(GIGS_ERR_INVALID, "normal_angular_error: image too large");
   const unsigned blocks = gigs::mae_blocks(HW);
-  void* tok; gigs_internal_stage_begin(21, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kL1SsimFwd, stream);
   hipLaunchKernelGGL(gigs::normal_angular_error_kernel, dim3(blocks), dim3(256), 0, s, (int)HW, pred, gt, gt_channels,
                      (double*)scratch);
   hipLaunchKernelGGL(gigs::normal_angular_error_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)scratch,
                      (int)blocks, (double)HW, slot, out);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "normal_angular_error: launch failed");
-  return 0;
+  return gigs_internal_check_launch("normal_angular_error");
 }
 
 int gigs_l1_ssim_bwd(int channels, int height, int width, const float* image, const float* gt, float lambda_dssim,
@@ -927,15 +917,13 @@ int gigs_l1_ssim_bwd(int channels, int height, int width, const float* image, co
   if (channels <= 0 || height <= 0 || width <= 0 || !image || !gt || !d_mu1 || !d_e11 || !d_e12 || !g_image)
     return gigs_internal_fail(GIGS_ERR_INVALID, "l1_ssim_bwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(22, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kL1SsimBwd, stream);
   const dim3 grid((width + gigs::kSsimTile - 1) / gigs::kSsimTile, (height + gigs::kSsimTile - 1) / gigs::kSsimTile,
                   channels);
   const float count = (float)channels * (float)height * (float)width;
   hipLaunchKernelGGL(gigs::l1_ssim_bwd_kernel, grid, dim3(256), 0, s, height, width, image, gt, gigs::make_window(),
                      d_mu1, d_e11, d_e12, g_loss, (1.0f - lambda_dssim) / count, -lambda_dssim / count, g_image);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "l1_ssim_bwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("l1_ssim_bwd");
 }
 
 int gigs_tv_loss_fwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
@@ -944,14 +932,12 @@ int gigs_tv_loss_fwd(int channels, int height, int width, int step, const float*
       !prediction || !scratch || !loss)
     return gigs_internal_fail(GIGS_ERR_INVALID, "tv_loss_fwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(23, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kTvFwd, stream);
   const dim3 grid((width + 63) / 64, (height + 3) / 4);
   hipLaunchKernelGGL(gigs::tv_fwd_kernel, grid, dim3(256), 0, s, channels, height, width, step, gt, prediction,
                      mask_f, scratch);
   hipLaunchKernelGGL(gigs::sum_finish_kernel, dim3(1), dim3(256), 0, s, scratch, (int)(grid.x * grid.y), loss);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "tv_loss_fwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("tv_loss_fwd");
 }
 
 int gigs_tv_loss_bwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
@@ -960,12 +946,10 @@ int gigs_tv_loss_bwd(int channels, int height, int width, int step, const float*
       !prediction || !g_prediction)
     return gigs_internal_fail(GIGS_ERR_INVALID, "tv_loss_bwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(24, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kTvBwd, stream);
   hipLaunchKernelGGL(gigs::tv_bwd_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, s, channels,
                      height, width, step, gt, prediction, mask_f, g_loss, g_prediction);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "tv_loss_bwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("tv_loss_bwd");
 }
 
 int gigs_masked_l1_fwd(int channels, int height, int width, const float* a, const float* b, const uint8_t* mask,
@@ -973,15 +957,13 @@ int gigs_masked_l1_fwd(int channels, int height, int width, const float* a, cons
   if (channels <= 0 || height <= 0 || width <= 0 || !a || !b || !mask || !scratch || !loss_count)
     return gigs_internal_fail(GIGS_ERR_INVALID, "masked_l1_fwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(25, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kMaskedL1, stream);
   const size_t HW = (size_t)height * width;
   const unsigned blocks = gigs::stream_blocks(HW);
   hipLaunchKernelGGL(gigs::masked_l1_fwd_kernel, dim3(blocks), dim3(256), 0, s, channels, HW, a, b, mask, scratch);
   hipLaunchKernelGGL(gigs::masked_l1_finish_kernel, dim3(1), dim3(256), 0, s, scratch, (int)blocks, channels,
                      loss_count);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "masked_l1_fwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("masked_l1_fwd");
 }
 
 int gigs_masked_l1_bwd(int channels, int height, int width, const float* a, const float* b, const uint8_t* mask,
@@ -989,13 +971,11 @@ int gigs_masked_l1_bwd(int channels, int height, int width, const float* a, cons
   if (channels <= 0 || height <= 0 || width <= 0 || !a || !b || !mask || !loss_count || (!g_a && !g_b))
     return gigs_internal_fail(GIGS_ERR_INVALID, "masked_l1_bwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(25, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kMaskedL1, stream);
   const size_t HW = (size_t)height * width;
   hipLaunchKernelGGL(gigs::masked_l1_bwd_kernel, dim3(gigs::stream_blocks(HW)), dim3(256), 0, s, channels, HW, a, b,
                      mask, loss_count, g_loss, g_a, g_b);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "masked_l1_bwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("masked_l1_bwd");
 }
 
 int gigs_adam_step(int n_groups, const gigs_adam_group* groups, double beta1, double beta2, double eps, int zero_grad,
@@ -1024,7 +1004,7 @@ int gigs_adam_step_guarded(int n_groups, const gigs_adam_group* groups, double b
                            const float* dyn, const unsigned char* watch, unsigned* changed, const unsigned* guard, void* stream) {
   if (n_groups < 0 || (n_groups > 0 && !groups)) return gigs_internal_fail(GIGS_ERR_INVALID, "adam_step: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  void* tok; gigs_internal_stage_begin(26, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kAdam, stream);
   int done = 0;
   while (done < n_groups) {
     gigs::AdamGroups G;
@@ -1033,10 +1013,8 @@ int gigs_adam_step_guarded(int n_groups, const gigs_adam_group* groups, double b
     int k = 0;
     for (; done < n_groups && k < gigs::kAdamMaxGroups; done++) {
       const gigs_adam_group& g = groups[done];
-      if (g.n < 0 || (!dyn && g.step < 1) || (g.n > 0 && (!g.param || !g.exp_avg || !g.exp_avg_sq))) {  // grad == NULL: an exact-zero gradient, not materialised
-        gigs_internal_stage_end(tok);
+      if (g.n < 0 || (!dyn && g.step < 1) || (g.n > 0 && (!g.param || !g.exp_avg || !g.exp_avg_sq)))  // grad == NULL: an exact-zero gradient, not materialised
         return gigs_internal_fail(GIGS_ERR_INVALID, "adam_step: bad group");
-      }
       if (g.n == 0) {
         if (dyn && k > 0) break;  // keep the (dyn_base + k) <-> group index correspondence: close this launch
         if (dyn) { G.dyn_base = done + 1; }
@@ -1065,10 +1043,8 @@ int gigs_adam_step_guarded(int n_groups, const gigs_adam_group* groups, double b
     G.guard = guard;
     G.first_chunk[k] = chunks;
     if (k == 0 || chunks == 0) {
-      if (k == 0 && done < n_groups) {  // a single group too large for one grid
-        gigs_internal_stage_end(tok);
+      if (k == 0 && done < n_groups)  // a single group too large for one grid
         return gigs_internal_fail(GIGS_ERR_INVALID, "adam_step: group too large");
-      }
       continue;
     }
     const gigs::AdamConsts K = {(float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps};
@@ -1076,9 +1052,7 @@ int gigs_adam_step_guarded(int n_groups, const gigs_adam_group* groups, double b
     if (zero_grad & 0x100) hipLaunchKernelGGL(gigs::adam_kernel<false>, dim3(chunks), dim3(256), 0, s, G, K, zero_grad & 0xff);
     else hipLaunchKernelGGL(gigs::adam_kernel<true>, dim3(chunks), dim3(256), 0, s, G, K, zero_grad & 0xff);
   }
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "adam_step: launch failed");
-  return 0;
+  return gigs_internal_check_launch("adam_step");
 }
 
 int gigs_densify_stats_guarded(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum,
@@ -1088,13 +1062,11 @@ int gigs_densify_stats_guarded(int P, const float* viewspace_grad, const int* ra
                           !xyz_gradient_accum_abs_max || !denom || !max_radii2D)))
     return gigs_internal_fail(GIGS_ERR_INVALID, "densify_stats: bad argument");
   if (P == 0) return 0;
-  void* tok; gigs_internal_stage_begin(27, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kDensifyStats, stream);
   hipLaunchKernelGGL(gigs::densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P,
                      viewspace_grad, radii, xyz_gradient_accum, xyz_gradient_accum_abs, xyz_gradient_accum_abs_max,
                      denom, max_radii2D, skip);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "densify_stats: launch failed");
-  return 0;
+  return gigs_internal_check_launch("densify_stats");
 }
 
 int gigs_densify_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum,
@@ -1109,7 +1081,7 @@ int gigs_gather_rows(int n_tensors, const gigs_gather_tensor* tensors, long long
   if (n_tensors < 0 || n_rows_out < 0 || n_rows_in < 0 || (n_tensors > 0 && !tensors) || (n_rows_out > 0 && !src_index))
     return gigs_internal_fail(GIGS_ERR_INVALID, "gather_rows: bad argument");
   if (n_rows_out == 0 || n_tensors == 0) return 0;
-  void* tok; gigs_internal_stage_begin(28, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kGatherRows, stream);
   int done = 0;
   while (done < n_tensors) {
     gigs::GatherTable T;
@@ -1118,17 +1090,13 @@ int gigs_gather_rows(int n_tensors, const gigs_gather_tensor* tensors, long long
     int k = 0;
     for (; done < n_tensors && k < gigs::kGatherMaxTensors; done++) {
       const gigs_gather_tensor& g = tensors[done];
-      if (g.row_floats <= 0 || !g.dst || (n_rows_in > 0 && !g.src)) {
-        gigs_internal_stage_end(tok);
+      if (g.row_floats <= 0 || !g.dst || (n_rows_in > 0 && !g.src))
         return gigs_internal_fail(GIGS_ERR_INVALID, "gather_rows: bad tensor");
-      }
       const unsigned long long c =
           (unsigned long long)((n_rows_out * g.row_floats + gigs::kGatherChunk - 1) / gigs::kGatherChunk);
       if (chunks + c > 0x7fffffffull) {
-        if (k == 0) {
-          gigs_internal_stage_end(tok);
+        if (k == 0)
           return gigs_internal_fail(GIGS_ERR_INVALID, "gather_rows: tensor too large");
-        }
         break;
       }
       T.src[k] = g.src; T.dst[k] = g.dst; T.row_floats[k] = g.row_floats; T.zero_new[k] = g.zero_new;
@@ -1141,9 +1109,7 @@ int gigs_gather_rows(int n_tensors, const gigs_gather_tensor* tensors, long long
     hipLaunchKernelGGL(gigs::gather_rows_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream, T, n_rows_out,
                        src_index, zero_row);
   }
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "gather_rows: launch failed");
-  return 0;
+  return gigs_internal_check_launch("gather_rows");
 }
 
 static bool act_raw_ok(const gigs_activation_raw* r, int K) {
@@ -1165,13 +1131,11 @@ int gigs_activate_fwd(int P, int K, const gigs_activation_raw* raw, const gigs_a
   act_fill_raw(A, raw);
   A.shs = out->shs; A.o_opacity = out->opacities; A.o_normal = out->normal; A.o_albedo = out->albedo;
   A.o_roughness = out->roughness; A.o_metallic = out->metallic; A.o_scales = out->scales; A.o_rotations = out->rotations;
-  void* tok; gigs_internal_stage_begin(30, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kActivateFwd, stream);
   const int sh_tiles = A.shs ? (P + gigs::kActRows - 1) / gigs::kActRows : 0;  // no concatenation without an output for it
   hipLaunchKernelGGL(gigs::activate_fwd_kernel, dim3((unsigned)(sh_tiles + (P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, K,
                      A, sh_tiles);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "activate_fwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("activate_fwd");
 }
 
 int gigs_activate_bwd(int P, int K, const gigs_activation_raw* raw, const gigs_activation_out* grad_out,
@@ -1188,14 +1152,12 @@ int gigs_activate_bwd(int P, int K, const gigs_activation_raw* raw, const gigs_a
   A.d_f_dc = grad_raw->f_dc; A.d_f_rest = grad_raw->f_rest; A.d_opacity = grad_raw->opacity; A.d_normal = grad_raw->normal;
   A.d_albedo = grad_raw->albedo; A.d_roughness = grad_raw->roughness; A.d_metallic = grad_raw->metallic;
   A.d_scaling = grad_raw->scaling; A.d_rotation = grad_raw->rotation;
-  void* tok; gigs_internal_stage_begin(31, stream, &tok);
+  gigs::StageTimer timer(gigs::Stage::kActivateBwd, stream);
   // no SH tile when neither SH gradient is wanted
   const int sh_tiles = (A.d_f_dc || A.d_f_rest) ? (P + gigs::kActRows - 1) / gigs::kActRows : 0;
   hipLaunchKernelGGL(gigs::activate_bwd_kernel, dim3((unsigned)(sh_tiles + (P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, K,
                      A, sh_tiles);
-  gigs_internal_stage_end(tok);
-  if (hipGetLastError() != hipSuccess) return gigs_internal_fail(GIGS_ERR_HIP, "activate_bwd: launch failed");
-  return 0;
+  return gigs_internal_check_launch("activate_bwd");
 }
 
 }  // extern "C"

@@ -115,6 +115,81 @@ def test_contexts_are_independent_and_validated():
             base.derive(gi_march=name)
 
 
+def test_options_round_trip_member_by_member():
+    """gigs_ctx_set_options / gigs_ctx_get_options copy the struct: every member of gigs_options comes back as written, and
+    neither a second context nor the defaults see it.  The values are valid, differ from the defaults and -- where the member
+    is not an on / off one -- from each other, so a member copied into its neighbour shows."""
+    import ctypes as C
+    import gigs_lib
+    gl = gigs_lib.lib()
+    values = dict(binning_legacy=1, bucket_max_mean=2501, long_lists=1, bucket_target=1537, bin_bands=3, blend_cull=0,
+                  pre_bwd_sh_skip=0, gi_march=0, gi_cert=0, gi_interleave=0, gi_tile_log2w=5, gi_zero_rays=1, spec_max8=129,
+                  spec_max16=1501, shade_lds_floats=30001, shade_bwd_blocks=7, shade_bwd_rows=1, spec_sparse=0,
+                  spec_sparse_permille=41)
+    assert sorted(values) == sorted(gigs_lib.OPTION_NAMES)
+
+    def read(ctx):
+        o = gigs_lib.Options()
+        o.struct_bytes = C.sizeof(gigs_lib.Options)
+        assert gl.gigs_ctx_get_options(ctx, C.byref(o)) == 0
+        assert o.struct_bytes == C.sizeof(gigs_lib.Options)
+        return {n: getattr(o, n) for n in gigs_lib.OPTION_NAMES}
+
+    defaults = read(None)
+    assert all(values[n] != defaults[n] for n in values), "a round trip of the default value checks nothing"
+    a, b = gl.gigs_ctx_create(), gl.gigs_ctx_create()
+    try:
+        o = gigs_lib.Options()
+        o.struct_bytes = C.sizeof(gigs_lib.Options)
+        for n, v in values.items():
+            setattr(o, n, v)
+        assert gl.gigs_ctx_set_options(a, C.byref(o)) == 0, gl.gigs_last_error()
+        assert read(a) == values
+        assert read(b) == defaults and read(None) == defaults
+    finally:
+        gl.gigs_ctx_destroy(a)
+        gl.gigs_ctx_destroy(b)
+
+
+def test_profile_stage_names_are_the_recorded_ones():
+    """The stage table (csrc/gigs_internal.h): gigs_profile_end(n = 0) returns the stage count, every stage below it has a
+    distinct non-empty name, outside it the name is empty -- and the list is the one the library had before the table moved
+    (tests/golden/profile_stages.json, written by tests/test_gpu_profile_stages.py from that library): tools key on the names."""
+    import ctypes as C
+    import json
+    import gigs_lib
+    gl = gigs_lib.lib()
+    count = gl.gigs_profile_end((C.c_float * 1)(), (C.c_int * 1)(), 0)
+    names = [gl.gigs_profile_stage_name(i) for i in range(count)]
+    assert count > 0 and all(names) and len(set(names)) == count
+    assert gl.gigs_profile_stage_name(count) == b"" and gl.gigs_profile_stage_name(-1) == b""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "profile_stages.json")))
+    assert [n.decode() for n in names] == golden["stages"]
+
+
+def test_internal_helpers_are_declared_in_one_header_only():
+    """csrc/gigs_internal.h is the only declaration of the gigs_internal_* helpers: a prototype repeated in a .hip file can
+    drift from the definition without any compiler seeing both (three units once declared gigs_internal_fail variadic)."""
+    csrc = os.path.join(ROOT, "gi-gs_amd", "csrc")
+    prototype = re.compile(r"(?:^|[;{}])\s*(?:(?!return\b)[\w:]+[\s*&]+)+(gigs_internal_\w+)\s*\([^;{}]*\)\s*;", re.M)
+
+    def code(f):
+        txt = open(os.path.join(csrc, f)).read()
+        txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+        return "\n".join(l.split("//")[0] for l in txt.splitlines())
+
+    assert prototype.findall("extern \"C\" {\nint gigs_internal_fail(int code, const char* fmt, ...);\n}") == ["gigs_internal_fail"]
+    assert not prototype.findall("  return gigs_internal_check_launch(\"x\");\n  if (a) return gigs_internal_fail(1, \"y\");")
+    used = set()
+    for f in sorted(os.listdir(csrc)):
+        if f == "gigs_internal.h":
+            continue
+        assert not prototype.findall(code(f)), f"{f} declares a gigs_internal_* helper itself"
+        used |= set(re.findall(r"\bgigs_internal_\w+", code(f)))
+    declared = set(prototype.findall(re.sub(r"\bGIGS_HIDDEN\b", "", code("gigs_internal.h"))))
+    assert used and used <= declared, sorted(used - declared)
+
+
 def test_no_launch_path_reads_the_environment():
     """the library is re-entrant per stream -- switches live in gigs_ctx; getenv appears only where the default
     options are built (api.hip::options_from_env) and in -DGIGS_DIAG code."""
