@@ -4,7 +4,8 @@ their depth and material planes fused into a truncated signed distance volume, a
 
     python gi-gs_amd/extract_mesh.py -m <out> --checkpoint <out>/chkpntN.pth [--grid 256] [--bounds x0 y0 z0 x1 y1 z1]
                                      [--trunc_voxels 4] [--min_weight 2] [--opacity_min 0.5] [--no_carve]
-                                     [--split train] [--keep_largest K] [--min_faces M] -o mesh.ply         (CLI)
+                                     [--split train] [--keep_largest K] [--min_faces M] [--simplify R]
+                                     -o mesh.ply                                                           (CLI)
     extract_mesh(args) -> {...}                                                                            (API)
 
 The scene path, the SH degree and the resolution come from <out>/cfg_args as in render_scene.py, command-line values
@@ -12,7 +13,10 @@ first.  --grid is the number of samples along the longest axis of the box; witho
 mesh.auto_bounds of the Gaussians.  A relative -o lands in <out>.  Prints the counts of views, samples, vertices and
 faces and the time of each phase.  --keep_largest K and --min_faces M (both 0: the raw level set, as before) run
 mesh.clean on the extracted mesh: the connected components of fewer faces than max(M, the K-th largest, 1) are dropped,
-and the result gains components, components_kept, faces_removed and clean_s.
+and the result gains components, components_kept, faces_removed and clean_s.  --simplify R (0: off, as before) then runs
+mesh.simplify with cells of R voxels that start at the volume's corner, so that a cell holds R^3 voxels of the fusion
+grid: the face count falls by about R^2 while the volume keeps its resolution.  The result gains clusters,
+faces_collapsed, faces_duplicate and simplify_s.
 """
 from __future__ import annotations
 
@@ -44,6 +48,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--split", choices=("train", "test"), default="train")
     p.add_argument("--keep_largest", type=int, default=0, help="keep the components with at least as many faces as the K-th largest")
     p.add_argument("--min_faces", type=int, default=0, help="drop the components with fewer faces")
+    p.add_argument("--simplify", type=float, default=0.0, help="cluster the vertices in cells of this many voxels (0: off)")
     p.add_argument("-o", "--output", type=str, default="mesh.ply")
     return p
 
@@ -96,6 +101,11 @@ def extract_mesh(args) -> Dict:
             m, report = mesh.clean(m, args.keep_largest, args.min_faces)
             sync()
         t4c = time.perf_counter()
+        simplified = None
+        if args.simplify > 0:
+            m, simplified = mesh.simplify(m, args.simplify * voxel, origin=vol.lo)
+            sync()
+        t4s = time.perf_counter()
         path = args.output if os.path.isabs(args.output) else os.path.join(args.model_path, args.output)
         scene_io.save_mesh_ply(path, *m)
         t5 = time.perf_counter()
@@ -104,10 +114,13 @@ def extract_mesh(args) -> Dict:
     res = dict(path=path, views=len(views), samples=vol.n_samples, dims=list(dims), voxel=voxel,
                lo=[float(v) for v in lo], hi=[float(v) for v in hi], vertices=int(m.vertices.shape[0]),
                faces=int(m.faces.shape[0]), load_s=round(t1 - t0, 4), cameras_s=round(t2 - t1, 4),
-               fuse_s=round(t3 - t2, 4), extract_s=round(t4 - t3, 4), write_s=round(t5 - t4c, 4))
+               fuse_s=round(t3 - t2, 4), extract_s=round(t4 - t3, 4), write_s=round(t5 - t4s, 4))
     if report is not None:
         res.update(components=report["components"], components_kept=report["components_kept"],
                    faces_removed=report["faces_removed"], clean_s=round(t4c - t4, 4))
+    if simplified is not None:
+        res.update(clusters=simplified["clusters"], faces_collapsed=simplified["faces_collapsed"],
+                   faces_duplicate=simplified["faces_duplicate"], simplify_s=round(t4s - t4c, 4))
     return res
 
 
@@ -120,6 +133,9 @@ def main(argv=None) -> int:
     if "components" in res:
         print("clean %.3f s: %d of %d components kept, %d faces removed" % (res["clean_s"], res["components_kept"],
                                                                           res["components"], res["faces_removed"]))
+    if "clusters" in res:
+        print("simplify %.3f s: %d clusters, %d faces collapsed, %d duplicates" % (res["simplify_s"], res["clusters"],
+                                                                                  res["faces_collapsed"], res["faces_duplicate"]))
     print(json.dumps(res))
     return 0
 

@@ -141,6 +141,11 @@ SIGNATURES = {
     "gigs_mesh_mark": (_i, [_i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_compact": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f,
                                C.c_void_p]),
+    "gigs_mesh_cluster_keys": (_i, [_i, _f, C.POINTER(_fl), _fl, _f, C.c_void_p]),  # origin: three floats on the host
+    "gigs_mesh_cluster_faces": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_face_dedupe": (_i, [_i, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_cluster_solve": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.POINTER(_fl), _fl,
+                                     C.c_double, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_project": (_i, [_i, _f, _f, _fl, _fl, _i, _i, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_raster_scratch_bytes": (C.c_size_t, [_i]),
     "gigs_mesh_raster": (_i, [_i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, C.c_void_p]),

@@ -11,6 +11,10 @@
     keep_threshold(counts, K, M)         the face count a component needs to be kept (host arithmetic)
     clean(mesh, keep_largest, min_faces) drops the components below that count, the invalid faces and the vertices no
                                          kept face references (gigs_mesh_mark, two scans, gigs_mesh_compact)
+    cluster_map(mesh, cell, origin)      the cell cluster of every vertex (gigs_mesh_cluster_keys, a stable sort, a scan)
+    simplify(mesh, cell, origin, reg)    one vertex per occupied cell, placed by the plane quadrics of its faces; collapsed
+                                         and duplicate faces go (gigs_mesh_cluster_faces, gigs_mesh_cluster_solve,
+                                         gigs_mesh_face_dedupe, then the mark / compact pair of clean)
 
 The route is the one of 2DGS and GOF: depth and material planes of the training views go into a truncated signed
 distance volume, and the mesh is its zero level set.  The arithmetic of both halves is stated in include/gigs_hip.h and
@@ -279,6 +283,12 @@ def _p(t):
     return t.data_ptr() if t.numel() else None
 
 
+def _sized(dev, v: int, f: int) -> Mesh:
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    return Mesh(torch.empty((v, 3), **f32), torch.empty((f, 3), **i32), torch.empty((v, 3), **f32),
+                torch.empty((v, 3), **f32), torch.empty((v,), **f32), torch.empty((v,), **f32))
+
+
 def _label(m: Mesh):
     """-> (labels [V], face_labels [F], count [V] per root, invalid (device int [1]), rounds)."""
     dev = m.vertices.device
@@ -343,10 +353,7 @@ def clean(mesh, keep_largest: int = 0, min_faces: int = 0) -> Tuple[Mesh, Dict]:
     V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
     f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
 
-    def sized(v, f):
-        return Mesh(torch.empty((v, 3), **f32), torch.empty((f, 3), **i32), torch.empty((v, 3), **f32),
-                    torch.empty((v, 3), **f32), torch.empty((v,), **f32), torch.empty((v,), **f32))
-
+    sized = lambda v, f: _sized(dev, v, f)  # noqa: E731
     if V == 0 or F == 0:
         return sized(0, 0), dict(components=0, components_kept=0, faces_removed=F, vertices_removed=V, invalid_faces=F,
                                  rounds=0, threshold=keep_threshold([], keep_largest, min_faces))
@@ -376,3 +383,180 @@ def clean(mesh, keep_largest: int = 0, min_faces: int = 0) -> Tuple[Mesh, Dict]:
                 raise MeshOverflow("clean: an index left the outputs (%d vertices, %d faces)" % (V2, F2))
     return out, dict(components=n_comp, components_kept=n_kept, faces_removed=F - F2, vertices_removed=V - V2,
                      invalid_faces=n_invalid, rounds=rounds, threshold=thr)
+
+
+# ---- simplifying: vertex clustering with quadric placement (include/gigs_hip.h, "Simplifying meshes") ------------------------
+CELL_AXIS = 1 << 21  # cell coordinates per axis: three of them share an int64 key
+
+
+def cluster_grid(lo, hi, cell, origin=None):
+    """(origin float32 [3], inv float32) of the cell grid over vertices with the finite extent lo .. hi (float32 [3] each;
+    lo = +inf where no vertex is finite).  Host arithmetic.  ValueError for a cell that is not positive (or whose
+    reciprocal is not finite in float32), an origin that is not finite, or an extent that needs a cell coordinate of 2^21
+    or more on some axis."""
+    cell32 = np.float32(cell)
+    if not (np.isfinite(cell32) and cell32 > 0):
+        raise ValueError("simplify: cell must be positive, got %r" % (cell,))
+    with np.errstate(over="ignore", invalid="ignore"):
+        inv = np.float32(1) / cell32
+        if not np.isfinite(inv):
+            raise ValueError("simplify: 1 / cell is not finite in float32 (cell = %r)" % (cell,))
+        lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        some = bool(np.isfinite(lo).all() and np.isfinite(hi).all())
+        if some:
+            top = np.floor((hi - lo) * inv)
+            if not bool((top < CELL_AXIS).all()):
+                raise ValueError("simplify: the extent %s at cell %g needs more than 2^21 cells on an axis"
+                                 % ((hi.astype(np.float64) - lo).tolist(), float(cell32)))
+    if origin is None:
+        org = lo.copy() if some else np.zeros(3, np.float32)
+    else:
+        org = np.asarray(origin, np.float32).reshape(3).copy()
+        if not np.isfinite(org).all():
+            raise ValueError("simplify: origin must be finite, got %r" % (origin,))
+    return org, inv
+
+
+class _Clusters(NamedTuple):
+    cluster_of: torch.Tensor    # [V] int32, -1 for an unclustered vertex
+    n: int                      # C
+    order: torch.Tensor         # [V] int64: the vertices sorted by (key, index), the unclustered ones first
+    member_start: torch.Tensor  # [C+1] int64: the first row of every cluster in `order`, then V
+    keys: torch.Tensor          # [C] int64
+    unclustered: torch.Tensor   # [] the number of unclustered vertices, on the device
+    origin: np.ndarray
+    inv: np.float32
+
+
+def _c_origin(org):
+    return (C.c_float * 3)(*(float(x) for x in org))
+
+
+def _cluster(m: Mesh, cell, origin) -> _Clusters:
+    """Two read-backs: the extent and C."""
+    dev = m.vertices.device
+    V = int(m.vertices.shape[0])
+    v = m.vertices
+    finite = torch.isfinite(v).all(1, keepdim=True)
+    ext = torch.stack((v.masked_fill(~finite, float("inf")).amin(0), v.masked_fill(~finite, float("-inf")).amax(0))).cpu().numpy()
+    org, inv = cluster_grid(ext[0], ext[1], cell, origin)
+    keys = torch.empty(V, dtype=torch.int64, device=dev)
+    gigs_lib.check(gigs_lib.lib().gigs_mesh_cluster_keys(V, _p(v), _c_origin(org), float(inv), _p(keys), _stream()),
+                   "mesh_cluster_keys")
+    skeys, order = torch.sort(keys, stable=True)
+    head = torch.ones(V, dtype=torch.bool, device=dev)
+    head[1:] = skeys[1:] != skeys[:-1]
+    head &= skeys >= 0
+    ids = torch.cumsum(head, 0, dtype=torch.int32) - 1  # -1 on the unclustered rows: they sort first
+    cluster_of = torch.empty(V, dtype=torch.int32, device=dev)
+    cluster_of[order] = ids
+    starts = torch.nonzero(head).reshape(-1)  # its length is C: the read-back
+    member_start = torch.cat((starts, starts.new_tensor([V])))
+    return _Clusters(cluster_of, int(starts.numel()), order, member_start, skeys[starts], (skeys < 0).sum(), org, inv)
+
+
+def _check_cell(cell, reg=1e-3):
+    if not (float(cell) > 0):
+        raise ValueError("simplify: cell must be positive, got %r" % (cell,))
+    if not (0 < float(reg) <= 1):
+        raise ValueError("simplify: reg must lie in (0, 1], got %r" % (reg,))
+
+
+def cluster_map(mesh, cell, origin=None) -> Tuple[torch.Tensor, int]:
+    """(cluster_of [V] int32, C): the cluster of every vertex of `mesh` on the grid of `cell`-sized cells from `origin`
+    (default: the minimum of the finite vertices), -1 for a vertex that is not finite or lies outside the 2^21 cells of an
+    axis.  Clusters are numbered in ascending key order (x fastest)."""
+    _check_cell(cell)
+    m = _mesh_tensors(mesh, "cluster_map")
+    if int(m.vertices.shape[0]) == 0:
+        return torch.empty(0, dtype=torch.int32, device=m.vertices.device), 0
+    with torch.cuda.device(m.vertices.device):
+        cl = _cluster(m, cell, origin)
+    return cl.cluster_of, cl.n
+
+
+def median_edge(mesh) -> float:
+    """The (lower) median length of the 3 F' edges of the F' valid faces of `mesh`, computed where the mesh lives; 0.0
+    without a valid face with finite edges."""
+    m = _mesh_tensors(mesh, "median_edge")
+    V = int(m.vertices.shape[0])
+    f = m.faces.long()
+    f = f[((f >= 0) & (f < V)).all(1)]
+    if f.numel() == 0:
+        return 0.0
+    p = m.vertices[f]  # [F',3,3]
+    e = (p - p.roll(-1, 1)).double().norm(dim=2).reshape(-1)
+    e = e[torch.isfinite(e)]
+    return float(e.median().item()) if e.numel() else 0.0
+
+
+def simplify(mesh, cell, origin=None, reg: float = 1e-3) -> Tuple[Mesh, Dict]:
+    """(the mesh with one vertex per occupied cell of the `cell`-sized grid from `origin`, a report).  The vertex of a cell
+    minimises the area-weighted plane quadrics of the faces that touch the cell, regularised towards the member mean by
+    `reg` and clamped to the cell; its attributes are the member means (the normal: the normalised member sum).  Faces
+    with two vertices in one cell, faces that repeat an earlier face's cluster triple and invalid faces go, then the
+    clusters nothing references.  Report: clusters, vertices, faces, faces_in, vertices_in, faces_collapsed,
+    faces_duplicate, faces_invalid, vertices_unclustered, cell, origin.  V == 0 or F == 0 launches nothing."""
+    _check_cell(cell, reg)
+    m = _mesh_tensors(mesh, "simplify")
+    dev = m.vertices.device
+    V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+
+    def report(org, **kw):
+        r = dict(clusters=0, vertices=0, faces=0, faces_in=F, vertices_in=V, faces_collapsed=0, faces_duplicate=0,
+                 faces_invalid=0, vertices_unclustered=0, cell=float(np.float32(cell)), origin=[float(x) for x in org])
+        r.update(kw)
+        return r
+
+    if V == 0 or F == 0:
+        org = np.zeros(3, np.float32) if origin is None else np.asarray(origin, np.float32).reshape(3)
+        return _sized(dev, 0, 0), report(org, faces_invalid=F if V == 0 else 0)
+    lib = gigs_lib.lib()
+    with torch.cuda.device(dev):
+        cl = _cluster(m, cell, origin)
+        Cn = cl.n
+        if Cn == 0:
+            return _sized(dev, 0, 0), report(cl.origin, faces_invalid=F, vertices_unclustered=V)
+        triples, pairs, counts = torch.empty((F, 3), **i32), torch.empty(3 * F, **i64), torch.empty(2, **i32)
+        gigs_lib.check(lib.gigs_mesh_cluster_faces(V, F, Cn, _p(m.faces), _p(cl.cluster_of), _p(triples), _p(pairs), _p(counts),
+                                                   _stream()), "mesh_cluster_faces")
+        pairs = torch.sort(pairs).values  # (cluster, face) ascending; the sentinels last
+        pair_start = torch.searchsorted(pairs, torch.arange(Cn + 1, **i64) << 32)
+        cv = _sized(dev, Cn, 0)
+        flags = torch.zeros(2, **i32)  # overflow, duplicates
+        gigs_lib.check(lib.gigs_mesh_cluster_solve(
+            V, F, Cn, _p(m.vertices), _p(m.normals), _p(m.albedo), _p(m.roughness), _p(m.metallic), _p(m.faces), _p(cl.order),
+            _p(cl.member_start), _p(pairs), _p(pair_start), _p(cl.keys), _c_origin(cl.origin), float(np.float32(cell)), float(reg),
+            _p(cv.vertices), _p(cv.normals), _p(cv.albedo), _p(cv.roughness), _p(cv.metallic), flags.data_ptr(), _stream()),
+            "mesh_cluster_solve")
+        # the faces in the order of their triples, ties in ascending face index: two stable sorts, last column first
+        t = triples.long()
+        by_last = torch.sort(t[:, 2], stable=True).indices
+        order = by_last[torch.sort(((t[:, 0] << 32) | t[:, 1])[by_last], stable=True).indices]
+        faces = torch.empty((F, 3), **i32)
+        gigs_lib.check(lib.gigs_mesh_face_dedupe(F, _p(triples), _p(order), _p(faces), flags[1:].data_ptr(), flags.data_ptr(),
+                                                 _stream()), "mesh_face_dedupe")
+        # clean(.., 0, 0)'s compaction without its labelling: every face that is still a triple is kept
+        face_keep, vertex_keep = torch.empty(F, **i32), torch.empty(Cn, **i32)
+        label, root_keep = torch.zeros(F, **i32), torch.ones(Cn, dtype=torch.uint8, device=dev)
+        gigs_lib.check(lib.gigs_mesh_mark(Cn, F, _p(faces), _p(label), _p(root_keep), _p(face_keep), _p(vertex_keep), _stream()),
+                       "mesh_mark")
+        v_incl = torch.cumsum(vertex_keep, 0, dtype=torch.int32)
+        f_incl = torch.cumsum(face_keep, 0, dtype=torch.int32)
+        V2, F2, n_invalid, n_collapsed, overflow, n_dup, n_unclustered = (int(x) for x in torch.cat(
+            (torch.stack((v_incl[-1], f_incl[-1])), counts, flags, cl.unclustered.to(torch.int32).reshape(1))).cpu())
+        if overflow != 0:
+            raise MeshOverflow("simplify: an index left its range (%d clusters, %d faces)" % (Cn, F))
+        out = _sized(dev, V2, F2)
+        if V2 and F2:
+            v_off, f_off = v_incl - vertex_keep, f_incl - face_keep
+            flag = torch.zeros(1, **i32)
+            gigs_lib.check(lib.gigs_mesh_compact(
+                Cn, F, _p(cv.vertices), _p(cv.normals), _p(cv.albedo), _p(cv.roughness), _p(cv.metallic), _p(faces),
+                _p(vertex_keep), _p(v_off), _p(face_keep), _p(f_off), V2, F2, _p(out.vertices), _p(out.normals), _p(out.albedo),
+                _p(out.roughness), _p(out.metallic), _p(out.faces), flag.data_ptr(), _stream()), "mesh_compact")
+            if int(flag.item()) != 0:
+                raise MeshOverflow("simplify: an index left the outputs (%d vertices, %d faces)" % (V2, F2))
+    return out, report(cl.origin, clusters=Cn, vertices=V2, faces=F2, faces_collapsed=n_collapsed, faces_duplicate=n_dup,
+                       faces_invalid=n_invalid, vertices_unclustered=n_unclustered)

@@ -737,6 +737,65 @@ int gigs_mesh_compact(int n_vertices, int n_faces, const float* vertices, const 
                       const int* vertex_offsets, const int* face_keep, const int* face_offsets, int vertex_capacity,
                       int face_capacity, float* out_vertices, float* out_normals, float* out_albedo, float* out_roughness,
                       float* out_metallic, int* out_faces, int* overflow, void* stream);
+/* Simplifying meshes (gigs-hip extension; the device half of mesh.cluster_map / mesh.simplify): vertex clustering on a
+ * uniform grid of cells (Rossignac-Borrel) with one representative vertex per cell placed by its faces' plane quadrics
+ * (Lindstrom).  simplify(mesh, cell, origin = NULL, reg = 1e-3); cell > 0 in world units.  All arrays are DEVICE memory
+ * except `origin` (three floats on the host, read during the call); the calls neither synchronise nor allocate; the sorts
+ * and scans between them are the caller's.  No float atomics and no thread waits on another: the output bits do not
+ * depend on the order of execution (tests/mesh_simplify_ref.py restates everything below in numpy).
+ *   1 Cells.  origin defaults to the per-axis minimum over the finite vertices (float32).  inv = float32(1) / float32(cell).
+ *     A vertex v has the cell c = floor((v - origin) * inv) per axis: one float32 subtraction, one float32 product (no
+ *     contraction: __fsub_rn, __fmul_rn), floorf.  key = cx | cy << 21 | cz << 42 (int64).  A vertex with a non-finite
+ *     coordinate, or with a cell coordinate outside [0, 2^21) (possible only under an explicit origin), is UNCLUSTERED:
+ *     key = -1, cluster -1, it joins no cluster.  The host reads the extent of the finite vertices back once and refuses
+ *     (ValueError) a mesh whose extent, measured from its own minimum, needs a cell coordinate >= 2^21 on some axis.
+ *   2 Clusters.  The distinct keys >= 0 in ascending order are the clusters 0 .. C-1; the members of a cluster are taken in
+ *     ascending vertex index (a stable sort of the keys gives both orders).  cluster_of [V] int32.
+ *   3 Faces.  A face is VALID if its three indices lie in [0, V) and its three vertices are clustered.  A valid face whose
+ *     three clusters are pairwise different SURVIVES as the triple of its clusters, rotated so that the smallest comes first
+ *     (winding unchanged); every other face becomes (-1, -1, -1).  Among surviving faces with the same rotated triple only
+ *     the one with the lowest face index stays, the others become (-1, -1, -1).  Faces on the same three clusters with
+ *     OPPOSITE winding have different triples and both stay (the two sides of a collapsed thin part).
+ *   4 Attributes of a cluster.  albedo, roughness, metallic: the float64 sum of the members' values in ascending vertex
+ *     index, divided by the member count, rounded once to float32.  normal: the float64 member sum s divided by
+ *     sqrt(s . s) component by component, or zero if that length is zero.
+ *   5 Position of a cluster, in float64 and in coordinates local to the cell centre g = origin + (c + 1/2) cell: every
+ *     valid face, surviving or not, contributes once to each distinct cluster among its three, in ascending face index,
+ *     its area-weighted plane quadric: n = (p1 - p0) x (p2 - p0), u = n / |n|, w = |n| / 2, d = -(u . p0); A += w u u^T,
+ *     b += w d u; faces with |n| = 0 add nothing.  m = the member mean (local), lam = reg (A00 + A11 + A22) / 3.  If
+ *     lam > 0 is false (no area), x = m; else x solves (A + lam I) x = lam m - b (symmetric positive definite, condition
+ *     <= 3 / reg + 1; by cofactors).  x is clamped per axis to [-cell / 2, cell / 2]; the position is float32(g + x).  The
+ *     clamp is continuous: there is no accept-or-fall-back decision that two implementations could take differently.
+ *   6 Compaction.  The C cluster vertices and the rewritten faces go through gigs_mesh_mark (every face label 0,
+ *     root_keep[0] = 1) and gigs_mesh_compact: the (-1, -1, -1) rows and the clusters no kept face references go, order
+ *     is kept.
+ * gigs_mesh_cluster_keys, one thread per vertex: keys [V] int64 as in 1, inv_cell = inv.
+ * gigs_mesh_cluster_faces, one thread per face: triples [F,3] int32 as in 3 before the removal of duplicates; pair_keys
+ *   [3 F] int64: slot j of face f holds cluster << 32 | f if the face is valid and the cluster of its j-th vertex differs
+ *   from those of the earlier slots, else 2^63 - 1, so the sorted array lists every cluster's faces in ascending face
+ *   index and the sentinels last.  cluster_of entries outside [0, n_clusters) count as unclustered.  counts [2] (cleared
+ *   inside the call; integer atomics): the invalid faces, and the valid faces with a repeated cluster.
+ * gigs_mesh_face_dedupe, one thread per row of `order` [F] int64 (the faces sorted by triple, ties in ascending face
+ *   index): out_faces [F,3] (set to -1 inside the call) receives the triple of every surviving face that differs from its
+ *   predecessor's; *duplicates (cleared inside the call) counts the others.
+ * gigs_mesh_cluster_solve, one thread per cluster: member_order [V] int64 = the vertices sorted by (key, index),
+ *   member_start [C + 1] int64 = the first row of every cluster in it and the end of the last, pair_keys [3 F] SORTED,
+ *   pair_start [C + 1] int64 = the first row of every cluster in it (the first key >= k << 32), cluster_keys [C] int64.
+ *   Writes 4 and 5 into out_vertices, out_normals, out_albedo [C,3], out_roughness, out_metallic [C].
+ * An order row, an offset, a pair key or a face index outside its range sets *overflow (device int, cleared by the
+ *   caller) to 1 and the thread stores nothing: gigs_mesh_compact's convention. */
+int gigs_mesh_cluster_keys(int n_vertices, const float* vertices, const float* origin, float inv_cell, long long* keys,
+                           void* stream);
+int gigs_mesh_cluster_faces(int n_vertices, int n_faces, int n_clusters, const int* faces, const int* cluster_of, int* triples,
+                            long long* pair_keys, int* counts, void* stream);
+int gigs_mesh_face_dedupe(int n_faces, const int* triples, const long long* order, int* out_faces, int* duplicates,
+                          int* overflow, void* stream);
+int gigs_mesh_cluster_solve(int n_vertices, int n_faces, int n_clusters, const float* vertices, const float* normals,
+                            const float* albedo, const float* roughness, const float* metallic, const int* faces,
+                            const long long* member_order, const long long* member_start, const long long* pair_keys,
+                            const long long* pair_start, const long long* cluster_keys, const float* origin, float cell,
+                            double reg, float* out_vertices, float* out_normals, float* out_albedo, float* out_roughness,
+                            float* out_metallic, int* overflow, void* stream);
 /* Rendering meshes (gigs-hip extension; the device half of mesh_render.py): a triangle mesh -- vertices [V,3], faces [F,3]
  * int32 and mesh.py's per-vertex attributes -- as the G-buffer planes the blend kernel writes in inference mode, by a
  * visibility buffer.  Coverage and visibility are integer decisions, so no result depends on the order of execution and a
