@@ -146,6 +146,13 @@ SIGNATURES = {
     "gigs_mesh_face_dedupe": (_i, [_i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_cluster_solve": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.POINTER(_fl), _fl,
                                      C.c_double, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_face_areas": (_i, [_i, _i, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_sample_surface": (_i, [_i, _i, _f, _f, _f, _i, C.c_ulonglong, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_grid_count": (_i, [_i, _i, _f, _f, _f, C.POINTER(_fl), C.c_double, C.POINTER(_i), _f, C.c_void_p]),  # lo, dims: host
+    "gigs_mesh_grid_pairs": (_i, [_i, _i, _f, _f, _f, C.POINTER(_fl), C.c_double, C.POINTER(_i), _f, C.c_longlong, _f, _f,
+                                  C.c_void_p]),
+    "gigs_mesh_closest": (_i, [_i, _i, _f, _f, C.POINTER(_fl), C.c_double, C.POINTER(_i), _f, _f, C.c_longlong, _i, _f, _f,
+                               C.c_double, _f, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_project": (_i, [_i, _f, _f, _fl, _fl, _i, _i, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_raster_scratch_bytes": (C.c_size_t, [_i]),
     "gigs_mesh_raster": (_i, [_i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, C.c_void_p]),

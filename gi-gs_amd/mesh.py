@@ -15,6 +15,14 @@
     simplify(mesh, cell, origin, reg)    one vertex per occupied cell, placed by the plane quadrics of its faces; collapsed
                                          and duplicate faces go (gigs_mesh_cluster_faces, gigs_mesh_cluster_solve,
                                          gigs_mesh_face_dedupe, then the mark / compact pair of clean)
+    sample_surface(mesh, n, seed)        n stratified, area-weighted surface samples from a counter hash
+                                         (gigs_mesh_face_areas, a scan, gigs_mesh_sample_surface)
+    triangle_grid(mesh, cell)            a uniform grid of triangle lists (gigs_mesh_grid_count, a scan, gigs_mesh_grid_pairs,
+                                         a sort)
+    closest_point(points, mesh_b, ...)   the exact closest triangle of every point by an expanding-shell search of that grid
+                                         (gigs_mesh_closest)
+    distance(a, b, samples, ...)         both surfaces sampled and searched both ways: Chamfer, Hausdorff, one-sided
+                                         statistics, precision / recall / F-score per threshold
 
 The route is the one of 2DGS and GOF: depth and material planes of the training views go into a truncated signed
 distance volume, and the mesh is its zero level set.  The arithmetic of both halves is stated in include/gigs_hip.h and
@@ -560,3 +568,237 @@ def simplify(mesh, cell, origin=None, reg: float = 1e-3) -> Tuple[Mesh, Dict]:
                 raise MeshOverflow("simplify: an index left the outputs (%d vertices, %d faces)" % (V2, F2))
     return out, report(cl.origin, clusters=Cn, vertices=V2, faces=F2, faces_collapsed=n_collapsed, faces_duplicate=n_dup,
                        faces_invalid=n_invalid, vertices_unclustered=n_unclustered)
+
+
+# ---- comparing: surface samples, the triangle grid, the closest triangle (include/gigs_hip.h, "Comparing meshes") ------------
+GRID_AXIS = 256  # cells per axis of the triangle grid
+
+
+class _Areas(NamedTuple):
+    areas: torch.Tensor  # [F] float64, 0 for an unusable face
+    skipped: torch.Tensor  # [1] int32 on the device
+
+
+def _face_areas(m: Mesh) -> _Areas:
+    dev = m.vertices.device
+    F = int(m.faces.shape[0])
+    areas, skipped = torch.empty(F, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    gigs_lib.check(gigs_lib.lib().gigs_mesh_face_areas(int(m.vertices.shape[0]), F, _p(m.vertices), _p(m.faces), _p(areas),
+                                                       skipped.data_ptr(), _stream()), "mesh_face_areas")
+    return _Areas(areas, skipped)
+
+
+def sample_surface(mesh, n: int, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(points [n,3] float32, face [n] int32, bary [n,2] float32): n stratified, area-weighted samples of the usable faces
+    of `mesh` (indices in range, finite corners, area > 0), a pure function of (mesh, n, seed): sample i takes the i-th of n
+    equal slices of the cumulative area and its random numbers from a counter hash of (seed, i).  A mesh without area, or
+    n == 0, gives empty tensors and launches nothing."""
+    m = _mesh_tensors(mesh, "sample_surface")
+    dev = m.vertices.device
+    n, seed = int(n), int(seed)
+    if n < 0 or n >= 2 ** 31:
+        raise ValueError("sample_surface: n must lie in [0, 2^31), got %d" % n)
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    empty = (torch.empty((0, 3), **f32), torch.empty((0,), **i32), torch.empty((0, 2), **f32))
+    V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
+    if n == 0 or V == 0 or F == 0:
+        return empty
+    with torch.cuda.device(dev):
+        cum = torch.cumsum(_face_areas(m).areas, 0)
+        A = float(cum[-1].item())  # the one read-back
+        if not (A > 0 and np.isfinite(A)):
+            return empty
+        points, face, bary = torch.empty((n, 3), **f32), torch.empty(n, **i32), torch.empty((n, 2), **f32)
+        overflow = torch.zeros(1, **i32)
+        gigs_lib.check(gigs_lib.lib().gigs_mesh_sample_surface(V, F, _p(m.vertices), _p(m.faces), _p(cum), n,
+                                                               seed & 0xFFFFFFFFFFFFFFFF, _p(points), _p(face), _p(bary),
+                                                               overflow.data_ptr(), _stream()), "mesh_sample_surface")
+        if int(overflow.item()) != 0:
+            raise MeshOverflow("sample_surface: a sample fell on a face with an index outside the %d vertices" % V)
+    return points, face, bary
+
+
+class TriangleGrid(NamedTuple):
+    lo: np.ndarray             # [3] float32: the minimum corner of the usable faces
+    cell: float
+    dims: Tuple[int, int, int]
+    cell_start: torch.Tensor   # [cells + 1] int64
+    pairs: torch.Tensor        # [n_pairs] int64, sorted: cell << 32 | face
+    faces_skipped: int
+
+
+def grid_dims(lo, hi, cell) -> Tuple[float, Tuple[int, int, int]]:
+    """(cell, (Gx, Gy, Gz)): `cell` as a float32 value, raised if the longest axis of lo .. hi would need more than 256 of
+    them; G = clamp(ceil(extent / cell), 1, 256) per axis.  Host arithmetic."""
+    ext = np.asarray(hi, np.float32).astype(np.float64) - np.asarray(lo, np.float32).astype(np.float64)
+    cell = float(np.float32(cell))
+    need = float(ext.max()) / GRID_AXIS
+    if cell < need:
+        cell = float(np.nextafter(np.float32(need), np.float32(np.inf)))
+    return cell, tuple(int(min(max(np.ceil(e / cell), 1), GRID_AXIS)) for e in ext)
+
+
+def _c_grid(lo, dims):
+    return (C.c_float * 3)(*(float(x) for x in lo)), (C.c_int * 3)(*(int(d) for d in dims))
+
+
+def triangle_grid(mesh, cell=None):
+    """The uniform grid of triangle lists over the usable faces of `mesh`, or None if it has none.  `cell` defaults to twice
+    median_edge(mesh); it is doubled while the lists would hold more than 8 F + 4096 (cell, face) pairs.  Read-backs: the
+    box (with the skipped faces), and the pair total of every attempt."""
+    m = _mesh_tensors(mesh, "triangle_grid")
+    dev = m.vertices.device
+    V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
+    if V == 0 or F == 0:
+        return None
+    if cell is not None and not (float(cell) > 0 and np.isfinite(float(cell))):
+        raise ValueError("triangle_grid: cell must be positive and finite, got %r" % (cell,))
+    lib = gigs_lib.lib()
+    with torch.cuda.device(dev):
+        ar = _face_areas(m)
+        usable = ar.areas > 0
+        corners = m.vertices[m.faces[usable].long().reshape(-1)]
+        if corners.shape[0] == 0:  # a shape: the mask was read back by the indexing
+            return None
+        box = torch.cat((corners.amin(0), corners.amax(0), ar.skipped.float())).cpu().numpy()
+        lo, hi, skipped = box[:3].astype(np.float32), box[3:6].astype(np.float32), int(box[6])
+        if cell is None:
+            cell = 2.0 * median_edge(m)
+            if not (cell > 0 and np.isfinite(cell)):
+                cell = float((hi.astype(np.float64) - lo).max())
+        counts = torch.empty(F, dtype=torch.int32, device=dev)
+        while True:
+            cell, dims = grid_dims(lo, hi, cell)
+            c_lo, c_dims = _c_grid(lo, dims)
+            gigs_lib.check(lib.gigs_mesh_grid_count(V, F, _p(m.vertices), _p(m.faces), _p(ar.areas), c_lo, cell, c_dims,
+                                                    _p(counts), _stream()), "mesh_grid_count")
+            incl = torch.cumsum(counts, 0, dtype=torch.int64)
+            total = int(incl[-1].item())
+            if total <= 8 * F + 4096:
+                break
+            cell = 2.0 * cell
+        pairs = torch.empty(total, dtype=torch.int64, device=dev)
+        overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        gigs_lib.check(lib.gigs_mesh_grid_pairs(V, F, _p(m.vertices), _p(m.faces), _p(ar.areas), c_lo, cell, c_dims,
+                                                _p(incl - counts), total, _p(pairs), overflow.data_ptr(), _stream()),
+                       "mesh_grid_pairs")
+        pairs = torch.sort(pairs).values
+        cells = dims[0] * dims[1] * dims[2]
+        cell_start = torch.searchsorted(pairs, torch.arange(cells + 1, dtype=torch.int64, device=dev) << 32)
+        if int(overflow.item()) != 0:
+            raise MeshOverflow("triangle_grid: a face's cells left the %d pairs counted for them" % total)
+    return TriangleGrid(lo, cell, dims, cell_start, pairs, skipped)
+
+
+def _closest(points: torch.Tensor, m: Mesh, grid, max_distance):
+    """-> (distance [N] float32, face [N] int32, flags [3] int32 on the device: far, invalid, overflow)."""
+    dev = m.vertices.device
+    N = int(points.shape[0])
+    distance = torch.full((N,), float("inf"), dtype=torch.float32, device=dev)
+    face = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    flags = torch.zeros(3, dtype=torch.int32, device=dev)
+    if N == 0:
+        return distance, face, flags
+    if grid is None:  # no usable face: nothing is launched
+        flags[1] = (~torch.isfinite(points).all(1)).sum()
+        return distance, face, flags
+    lo = torch.from_numpy(grid.lo.astype(np.float64)).to(dev)
+    G = torch.tensor(grid.dims, dtype=torch.float64, device=dev)
+    c = torch.nan_to_num(((points.double() - lo) / grid.cell).floor(), nan=0.0).clamp_(min=0).minimum(G - 1).long()
+    order = torch.sort((c[:, 2] * grid.dims[1] + c[:, 1]) * grid.dims[0] + c[:, 0]).indices  # lanes of a wave share lists
+    c_lo, c_dims = _c_grid(grid.lo, grid.dims)
+    gigs_lib.check(gigs_lib.lib().gigs_mesh_closest(
+        int(m.vertices.shape[0]), int(m.faces.shape[0]), _p(m.vertices), _p(m.faces), c_lo, grid.cell, c_dims,
+        _p(grid.cell_start), _p(grid.pairs), int(grid.pairs.shape[0]), N, _p(points), _p(order),
+        float("inf") if max_distance is None else float(max_distance), _p(distance), _p(face), flags.data_ptr(),
+        flags[2:].data_ptr(), _stream()), "mesh_closest")
+    return distance, face, flags
+
+
+def _check_max_distance(max_distance):
+    if max_distance is not None and not (float(max_distance) >= 0):
+        raise ValueError("max_distance must be >= 0 or None, got %r" % (max_distance,))
+
+
+def closest_point(points, mesh_b, cell=None, max_distance=None, grid=None) -> Tuple[torch.Tensor, torch.Tensor, Dict]:
+    """(distance [N] float32, face [N] int32, report): for every point of `points` ([N,3] float32 on the mesh's device) the
+    distance to the closest usable triangle of `mesh_b` and its index (the smallest among equally close ones).  With
+    `max_distance`, a point with no triangle within it gets that distance and face -1 (report: far), and the search stops
+    there: without it a point far from the mesh walks O(G^3) cell headers alone.  A point with a non-finite coordinate
+    gets +inf and -1 (queries_invalid), as does every point if the mesh has no usable face.  `cell`: the grid's cell
+    (triangle_grid), or pass a `grid` built before.  Report: n, far, queries_invalid, faces_skipped, cell, dims, pairs."""
+    _check_max_distance(max_distance)
+    m = _mesh_tensors(mesh_b, "closest_point")
+    dev = m.vertices.device
+    if not isinstance(points, torch.Tensor) or points.device != dev:
+        raise RuntimeError("closest_point: points must be a tensor on the mesh's device: gigs-hip has no CPU path")
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("closest_point: points must be [N,3] float32, got %s %s" % (tuple(points.shape), points.dtype))
+    points = points.contiguous()
+    N = int(points.shape[0])
+    if N == 0:  # nothing is launched, so nothing is known about the faces either
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        return torch.empty(0, **f32), torch.empty(0, **i32), dict(n=0, far=0, queries_invalid=0, faces_skipped=None, cell=0.0,
+                                                                  dims=[0, 0, 0], pairs=0)
+    with torch.cuda.device(dev):
+        if grid is None:
+            grid = triangle_grid(m, cell)
+        distance, face, flags = _closest(points, m, grid, max_distance)
+        flags = [int(x) for x in flags.cpu()]  # the one read-back
+        if flags[2] != 0:
+            raise MeshOverflow("closest_point: an index left its range (%d faces, %d queries)" % (int(m.faces.shape[0]), N))
+    report = dict(n=N, far=flags[0], queries_invalid=flags[1],
+                  faces_skipped=grid.faces_skipped if grid is not None else int(m.faces.shape[0]),
+                  cell=grid.cell if grid is not None else 0.0, dims=list(grid.dims) if grid is not None else [0, 0, 0],
+                  pairs=int(grid.pairs.shape[0]) if grid is not None else 0)
+    return distance, face, report
+
+
+def distance(a, b, samples: int = 100000, seed: int = 0, taus=(), max_distance=None) -> Dict:
+    """How far two meshes are apart: `samples` surface samples of each (sample_surface, `seed`) against the other
+    (closest_point).  Per direction (a_to_b, b_to_a): n, far, mean, rms, median (the lower one), max; chamfer = the mean of
+    the two means, hausdorff = the larger max; per tau: precision (the share of a's samples within tau of b), recall (b's
+    within tau of a) and fscore = 2 P R / (P + R), 0 when both are 0.  A sample farther than `max_distance` counts with that
+    distance.  Also faces_skipped, cell and dims of both grids, samples and seed.  Float64 reductions where the distances
+    live, one read-back for them."""
+    _check_max_distance(max_distance)
+    ma, mb = _mesh_tensors(a, "distance"), _mesh_tensors(b, "distance")
+    if ma.vertices.device != mb.vertices.device:
+        raise RuntimeError("distance: the two meshes must live on one device")
+    taus = [float(t) for t in taus]
+    dev = ma.vertices.device
+    rows, grids, ns = [], [], []
+    with torch.cuda.device(dev):
+        t = torch.tensor(taus, dtype=torch.float64, device=dev)
+        for src, dst in ((ma, mb), (mb, ma)):
+            pts = sample_surface(src, samples, seed)[0]
+            grid = triangle_grid(dst)
+            d, _, flags = _closest(pts, dst, grid, max_distance)
+            grids.append(grid)
+            ns.append(int(d.shape[0]))
+            d64 = d.double()
+            if ns[-1]:
+                stats = torch.stack((d64.mean(), (d64 * d64).mean().sqrt(), d.median().double(), d64.max()))
+                within = (d64[None, :] <= t[:, None]).double().mean(1)
+            else:
+                stats, within = torch.zeros(4, dtype=torch.float64, device=dev), torch.zeros_like(t)
+            rows.append(torch.cat((stats, flags.double(), within)))
+        got = torch.stack(rows).cpu().numpy()  # the one read-back of the reductions
+    if got[:, 6].any():
+        raise MeshOverflow("distance: an index left its range")
+    out = {}
+    for name, row, n in (("a_to_b", got[0], ns[0]), ("b_to_a", got[1], ns[1])):
+        out[name] = dict(n=n, far=int(row[4]), mean=float(row[0]), rms=float(row[1]), median=float(row[2]), max=float(row[3]))
+    out["chamfer"] = 0.5 * (out["a_to_b"]["mean"] + out["b_to_a"]["mean"])
+    out["hausdorff"] = max(out["a_to_b"]["max"], out["b_to_a"]["max"])
+    out["taus"] = []
+    for k, tau in enumerate(taus):
+        P, R = float(got[0, 7 + k]), float(got[1, 7 + k])
+        out["taus"].append(dict(tau=tau, precision=P, recall=R, fscore=2.0 * P * R / (P + R) if P + R > 0 else 0.0))
+    gb, ga = grids  # the first direction searched b's grid
+    out["faces_skipped"] = dict(a=ga.faces_skipped if ga is not None else int(ma.faces.shape[0]),
+                                b=gb.faces_skipped if gb is not None else int(mb.faces.shape[0]))
+    out["grid"] = dict(a=dict(cell=ga.cell, dims=list(ga.dims)) if ga is not None else None,
+                       b=dict(cell=gb.cell, dims=list(gb.dims)) if gb is not None else None)
+    out["samples"], out["seed"] = int(samples), int(seed)
+    return out

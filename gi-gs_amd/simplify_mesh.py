@@ -1,7 +1,8 @@
 """A mesh PLY already on disk (extract_mesh.py's) with fewer faces: mesh.simplify puts one vertex into every occupied cell
 of a uniform grid, placed by the plane quadrics of the faces that touch the cell, and drops the faces that collapse.
 
-    python gi-gs_amd/simplify_mesh.py IN.ply -o OUT.ply (--cell X | --cell_edges R) [--keep_largest K] [--min_faces M]   (CLI)
+    python gi-gs_amd/simplify_mesh.py IN.ply -o OUT.ply (--cell X | --cell_edges R) [--keep_largest K] [--min_faces M]
+                                      [--distance N]                                              (CLI)
     simplify_mesh(args) -> {...}                                                                  (API)
 
 --cell is the cell size in world units; --cell_edges R makes it R times the median edge length of the valid faces
@@ -9,7 +10,8 @@ of a uniform grid, placed by the plane quadrics of the faces that touch the cell
 minimum of the vertices.  --keep_largest / --min_faces run mesh.clean AFTER the simplification (clustering can join what
 were separate components, and cleaning first would spend the labelling on faces that go anyway).  Reads with
 scene_io.read_mesh_ply and writes with scene_io.save_mesh_ply, as clean_mesh.py does.  Prints the report as JSON:
-mesh.simplify's, the clean's if it ran, and the times.
+mesh.simplify's, the clean's if it ran, and the times.  --distance N adds `distance`: mesh.distance of the input against
+the output with N surface samples each (Chamfer, Hausdorff, one-sided means); the PLY written is the same with and without.
 """
 from __future__ import annotations
 
@@ -34,6 +36,7 @@ def build_parser() -> argparse.ArgumentParser:
     size.add_argument("--cell_edges", type=float, default=None, help="cell size in median edge lengths")
     p.add_argument("--keep_largest", type=int, default=0, help="afterwards keep the components with at least as many faces as the K-th largest")
     p.add_argument("--min_faces", type=int, default=0, help="afterwards drop the components with fewer faces")
+    p.add_argument("--distance", type=int, default=0, help="report mesh.distance of the input against the output, N samples each")
     return p
 
 
@@ -74,6 +77,8 @@ def simplify_mesh(args) -> Dict:
         extra.update(components=cleaned["components"], components_kept=cleaned["components_kept"],
                      faces_removed=cleaned["faces_removed"], clean_s=round(time.perf_counter() - t1, 4))
         report = dict(report, vertices=int(out.vertices.shape[0]), faces=int(out.faces.shape[0]))
+    if args.distance > 0:  # a: the input, b: what is written
+        extra["distance"] = mesh.distance(m, out, samples=args.distance)
     scene_io.save_mesh_ply(args.output, *out)
     return dict(report, path=args.output, **extra)
 

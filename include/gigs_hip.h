@@ -796,6 +796,68 @@ int gigs_mesh_cluster_solve(int n_vertices, int n_faces, int n_clusters, const f
                             const long long* pair_start, const long long* cluster_keys, const float* origin, float cell,
                             double reg, float* out_vertices, float* out_normals, float* out_albedo, float* out_roughness,
                             float* out_metallic, int* overflow, void* stream);
+/* Comparing meshes (gigs-hip extension; the device half of mesh.sample_surface / mesh.closest_point / mesh.distance):
+ * area-weighted samples of a surface and, for every query point, the exact closest triangle of a mesh through a uniform
+ * grid of triangle lists.  All arrays are DEVICE memory except `lo` (three floats) and `dims` (three ints) on the host,
+ * read during the call; the calls neither synchronise nor allocate; the sorts and scans between them are the caller's.  One
+ * independent thread per face, sample or query, no float atomics, no thread waits on another: the output bits do not
+ * depend on the order of execution (tests/mesh_distance_ref.py restates everything below in numpy).  All arithmetic below
+ * is float64 on the float32 inputs, every product and sum rounded on its own; dot(a, b) = (a0 b0 + a1 b1) + a2 b2,
+ * cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0).
+ *   1 Usable faces.  A face is USABLE if its three indices lie in [0, V), its nine coordinates are finite and |n| > 0 with
+ *     n = cross(p1 - p0, p2 - p0), |n| = sqrt(dot(n, n)).  area = |n| / 2; an unusable face has area 0, gets no sample, is
+ *     in no grid cell and is counted in *skipped.
+ *   2 Random numbers.  mix(z): z = (z ^ z >> 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) 0x94D049BB133111EB; z ^ z >> 31 (the
+ *     splitmix64 finaliser, uint64).  u(i, k) = (mix((seed 2^32 + i) 4 + k) >> 11) 2^-53, in [0, 1).
+ *   3 Samples.  cum [F] = the inclusive cumulative sum of the areas, A = cum[F - 1] > 0.  Sample i of n: t = ((i + u(i, 0))
+ *     / n) A; its face is the first f with cum[f] > t, and if there is none (t rounded up to A) the first f with
+ *     cum[f] >= A: the last usable face.  (a, b) = (u(i, 1), u(i, 2)), replaced by (1 - a, 1 - b) if a + b > 1.
+ *     point = float32((p0 + a (p1 - p0)) + b (p2 - p0)) per component; bary = (float32(a), float32(b)).
+ *   4 Grid.  lo = the minimum corner of the usable faces (float32), cell > 0, dims = (Gx, Gy, Gz) each in [1, 256].  The
+ *     cell coordinate of x on axis a is c(x) = clamp(floor((x - lo_a) / cell), 0, G_a - 1); the cell planes are
+ *     plane_a(k) = lo_a + k cell; cell index = (z Gy + y) Gx + x.  A usable face is listed in every cell of the box
+ *     [c(min corner), c(max corner)] per axis.  pair key = cell << 32 | face (int64); the caller sorts the keys, and
+ *     cell_start [Gx Gy Gz + 1] int64 = the first row of every cell (the first key >= cell << 32), so every list ascends
+ *     in face index.
+ *   5 Point-triangle.  seg(p; a, b): ab = b - a, ap = p - a, t = dot(ap, ab), den = dot(ab, ab); t <= 0: dot(ap, ap);
+ *     t >= den: dot(p - b, p - b); else q = ap - (t / den) ab, dot(q, q).  The three edges are each walked from the
+ *     vertex with the lower INDEX, so two faces that share an edge get the same bits from it.  d^2 = the minimum of the
+ *     three; if the edge functions dot(cross(b - a, p - a), n) over (p0,p1), (p1,p2), (p2,p0) are all >= 0, the plane
+ *     term dot(p - p0, n)^2 / dot(n, n) enters the minimum too.  On the border between the cases the candidates coincide.
+ *     distance = float32(sqrt(d^2)).  Among faces with equal d^2 the smallest face index wins.
+ *   6 Search.  c0 = the clamped cell of the query.  Round r = 0, 1, .. visits the cells of the grid at Chebyshev distance
+ *     r from c0.  After it, L(r) = the minimum, over the sides of the block [c0 - r, c0 + r] that have cells behind them
+ *     (c0_a - r > 0: p_a - plane_a(c0_a - r); c0_a + r < G_a - 1: plane_a(c0_a + r + 1) - p_a), of max(0, that distance);
+ *     L' = (L - 2^-45 M)(1 - 2^-40) with M = the largest |lo_a| or |plane_a(G_a)|.  The search ends when no side has cells
+ *     behind it, when L' > 0 and best d^2 <= L'^2, or when L' > max_distance; at most max(G) rounds.
+ *   7 Results.  A query with a non-finite coordinate: distance +inf, face -1, counts[1] += 1.  A query whose best d^2 exceeds
+ *     max_distance^2 (max_distance = +inf for no limit), or that met no face: distance float32(max_distance), face -1,
+ *     counts[0] += 1.
+ * gigs_mesh_face_areas, one thread per face: areas [F] float64 and *skipped (cleared inside the call) as in 1.
+ * gigs_mesh_sample_surface, one thread per sample (a binary search over cum_areas): points [n,3], face [n], bary [n,2] as
+ *   in 3.  n_samples == 0 launches nothing; with samples asked of no face the call fails.
+ * gigs_mesh_grid_count, one thread per face: counts [F] int32 = the cells of the face's box, 0 for areas[f] <= 0.
+ * gigs_mesh_grid_pairs, one thread per face: offsets [F] int64 = the exclusive cumulative sum of counts; the face's keys go
+ *   to pair_keys[offsets[f] ..].  A range outside [0, n_pairs] sets *overflow and stores nothing.
+ * gigs_mesh_closest, one thread per row of `order` [N] int64 (the queries sorted by cell, or NULL for the identity): query
+ *   order[i] gets distance and face as in 5 - 7; counts [2] (cleared inside the call; integer atomics) = far, invalid.
+ * An order row, a cell_start entry, a pair key (its cell is not the cell visited, its face >= F) or a face index outside its
+ *   range sets *overflow (device int, cleared by the caller) to 1 and the thread stores nothing: gigs_mesh_compact's
+ *   convention. */
+int gigs_mesh_face_areas(int n_vertices, int n_faces, const float* vertices, const int* faces, double* areas, int* skipped,
+                         void* stream);
+int gigs_mesh_sample_surface(int n_vertices, int n_faces, const float* vertices, const int* faces, const double* cum_areas,
+                             int n_samples, unsigned long long seed, float* points, int* face, float* bary, int* overflow,
+                             void* stream);
+int gigs_mesh_grid_count(int n_vertices, int n_faces, const float* vertices, const int* faces, const double* areas,
+                         const float* lo, double cell, const int* dims, int* counts, void* stream);
+int gigs_mesh_grid_pairs(int n_vertices, int n_faces, const float* vertices, const int* faces, const double* areas,
+                         const float* lo, double cell, const int* dims, const long long* offsets, long long n_pairs,
+                         long long* pair_keys, int* overflow, void* stream);
+int gigs_mesh_closest(int n_vertices, int n_faces, const float* vertices, const int* faces, const float* lo, double cell,
+                      const int* dims, const long long* cell_start, const long long* pair_keys, long long n_pairs,
+                      int n_points, const float* points, const long long* order, double max_distance, float* distance,
+                      int* face, int* counts, int* overflow, void* stream);
 /* Rendering meshes (gigs-hip extension; the device half of mesh_render.py): a triangle mesh -- vertices [V,3], faces [F,3]
  * int32 and mesh.py's per-vertex attributes -- as the G-buffer planes the blend kernel writes in inference mode, by a
  * visibility buffer.  Coverage and visibility are integer decisions, so no result depends on the order of execution and a
