@@ -24,7 +24,7 @@ if __package__ in (None, ""):  # run as a script: make the package's modules imp
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Mesh cleaning parameters")
-    p.add_argument("input", type=str, help="a PLY written by extract_mesh.py")
+    p.add_argument("input", type=str, help="a PLY written by extract_mesh.py (an occlusion channel of bake_mesh.py is read and dropped)")
     p.add_argument("-o", "--output", type=str, required=True)
     p.add_argument("--keep_largest", type=int, default=0, help="keep the components with at least as many faces as the K-th largest")
     p.add_argument("--min_faces", type=int, default=0, help="drop the components with fewer faces")

@@ -25,7 +25,8 @@ if __package__ in (None, ""):  # run as a script: make the package's modules imp
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Mesh comparison parameters")
-    p.add_argument("a", type=str, help="a PLY written by extract_mesh.py, clean_mesh.py or simplify_mesh.py")
+    p.add_argument("a", type=str, help="a PLY written by extract_mesh.py, clean_mesh.py, simplify_mesh.py or bake_mesh.py (an occlusion channel is "
+                                      "read and dropped)")
     p.add_argument("b", type=str, help="the PLY to compare it with")
     p.add_argument("--samples", type=int, default=100000, help="surface samples per mesh")
     p.add_argument("--seed", type=int, default=0)

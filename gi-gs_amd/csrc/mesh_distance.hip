@@ -16,58 +16,12 @@
 //                 A lane group per query would share one query's faces among its lanes, but the lists hold a dozen faces
 //                 where a group wants 16 or 64, and the (d^2, index) minimum would need a cross-lane reduction per shell.
 //                 One-wave blocks: a block retires with its slowest wave, and an outlier query keeps only its own wave.
-#include <cfloat>
-#include <cmath>
-
-#include "gigs_internal.h"
+#include "mesh_grid.h"  // the vector helpers, the hash and the grid arithmetic, shared with mesh_raycast.hip
 
 namespace gigs {
 namespace mesh_distance {
 
-constexpr int kGridAxis = 256;
 constexpr double kShrink = 1.0 - 0x1p-40;  // the relative part of the slack on L(r)
-
-template <unsigned kBlock>
-__device__ __forceinline__ int item(int n) {
-  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-  return i < (unsigned)n ? (int)i : -1;
-}
-
-__device__ __forceinline__ bool in_range(int a, int b, int c, int n) {
-  return a >= 0 && a < n && b >= 0 && b < n && c >= 0 && c < n;
-}
-
-__device__ __forceinline__ bool finite3(const double* p) {
-  return fabs(p[0]) <= DBL_MAX && fabs(p[1]) <= DBL_MAX && fabs(p[2]) <= DBL_MAX;
-}
-
-__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* n) {
-  n[0] = a[1] * b[2] - a[2] * b[1];
-  n[1] = a[2] * b[0] - a[0] * b[2];
-  n[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-__device__ __forceinline__ void load3(const float* v, int i, double* p) {
-  p[0] = (double)v[3 * (size_t)i];
-  p[1] = (double)v[3 * (size_t)i + 1];
-  p[2] = (double)v[3 * (size_t)i + 2];
-}
-
-struct Grid {
-  double lo[3], cell;
-  int G[3];
-};
-
-// the clamped cell coordinate of x on axis a; a NaN goes to 0
-__device__ __forceinline__ int cell_of(const Grid& g, int a, double x) {
-  const double t = floor((x - g.lo[a]) / g.cell);
-  const double top = (double)(g.G[a] - 1);
-  return !(t >= 0.0) ? 0 : (t > top ? g.G[a] - 1 : (int)t);
-}
-
-__device__ __forceinline__ double plane_of(const Grid& g, int a, int k) { return g.lo[a] + (double)k * g.cell; }
 
 // ---- areas -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void areas_kernel(int V, int F, const float* __restrict__ vertices,
@@ -94,12 +48,6 @@ __global__ __launch_bounds__(256) void areas_kernel(int V, int F, const float* _
 }
 
 // ---- samples ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
-}
-
 __device__ __forceinline__ double uniform(unsigned long long seed, unsigned i, unsigned k) {
   return (double)(mix64(((seed << 32) + i) * 4ULL + k) >> 11) * 0x1p-53;
 }
@@ -358,20 +306,6 @@ __global__ __launch_bounds__(kClosestBlock) void closest_kernel(ClosestArgs a) {
   }
   a.distance[q] = (float)sqrt(best2);
   a.face[q] = bestf;
-}
-
-inline unsigned blocks_for(int n, unsigned block = 256u) { return ((unsigned)n + block - 1u) / block; }
-
-// the grid of a call, or false
-inline bool make_grid(const float* lo, double cell, const int* dims, Grid* g) {
-  if (!lo || !dims || !(cell > 0.0 && cell <= DBL_MAX)) return false;
-  for (int a = 0; a < 3; a++) {
-    if (!(std::fabs(lo[a]) <= FLT_MAX) || dims[a] < 1 || dims[a] > kGridAxis) return false;
-    g->lo[a] = (double)lo[a];
-    g->G[a] = dims[a];
-  }
-  g->cell = cell;
-  return true;
 }
 
 }  // namespace mesh_distance

@@ -5,6 +5,7 @@ their depth and material planes fused into a truncated signed distance volume, a
     python gi-gs_amd/extract_mesh.py -m <out> --checkpoint <out>/chkpntN.pth [--grid 256] [--bounds x0 y0 z0 x1 y1 z1]
                                      [--trunc_voxels 4] [--min_weight 2] [--opacity_min 0.5] [--no_carve]
                                      [--split train] [--keep_largest K] [--min_faces M] [--simplify R]
+                                     [--bake_occlusion RAYS] [--ao_distance D]
                                      -o mesh.ply                                                           (CLI)
     extract_mesh(args) -> {...}                                                                            (API)
 
@@ -16,7 +17,10 @@ mesh.clean on the extracted mesh: the connected components of fewer faces than m
 and the result gains components, components_kept, faces_removed and clean_s.  --simplify R (0: off, as before) then runs
 mesh.simplify with cells of R voxels that start at the volume's corner, so that a cell holds R^3 voxels of the fusion
 grid: the face count falls by about R^2 while the volume keeps its resolution.  The result gains clusters,
-faces_collapsed, faces_duplicate and simplify_s.
+faces_collapsed, faces_duplicate and simplify_s.  --bake_occlusion RAYS (0: off, as before, byte for byte) runs
+mesh.bake_occlusion with RAYS rays per vertex (a multiple of 64) on the mesh that is written -- after cleaning and
+simplifying -- and the PLY gains `property float occlusion` (1 = open); --ao_distance D is its max_distance (default: 0.1 of
+the longest axis of the mesh's grid).  The result gains occlusion (the bake's report) and bake_s.
 """
 from __future__ import annotations
 
@@ -49,6 +53,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--keep_largest", type=int, default=0, help="keep the components with at least as many faces as the K-th largest")
     p.add_argument("--min_faces", type=int, default=0, help="drop the components with fewer faces")
     p.add_argument("--simplify", type=float, default=0.0, help="cluster the vertices in cells of this many voxels (0: off)")
+    p.add_argument("--bake_occlusion", type=int, default=0, help="rays per vertex of the occlusion bake, a multiple of 64 (0: off)")
+    p.add_argument("--ao_distance", type=float, default=None, help="how far an occluder counts (default: 0.1 of the longest axis)")
     p.add_argument("-o", "--output", type=str, default="mesh.ply")
     return p
 
@@ -106,21 +112,28 @@ def extract_mesh(args) -> Dict:
             m, simplified = mesh.simplify(m, args.simplify * voxel, origin=vol.lo)
             sync()
         t4s = time.perf_counter()
+        occlusion = baked = None
+        if args.bake_occlusion > 0:
+            occlusion, baked = mesh.bake_occlusion(m, rays=args.bake_occlusion, max_distance=args.ao_distance)
+            sync()
+        t4b = time.perf_counter()
         path = args.output if os.path.isabs(args.output) else os.path.join(args.model_path, args.output)
-        scene_io.save_mesh_ply(path, *m)
+        scene_io.save_mesh_ply(path, *m, occlusion=occlusion)
         t5 = time.perf_counter()
     finally:
         pipeline._collect_idle()
     res = dict(path=path, views=len(views), samples=vol.n_samples, dims=list(dims), voxel=voxel,
                lo=[float(v) for v in lo], hi=[float(v) for v in hi], vertices=int(m.vertices.shape[0]),
                faces=int(m.faces.shape[0]), load_s=round(t1 - t0, 4), cameras_s=round(t2 - t1, 4),
-               fuse_s=round(t3 - t2, 4), extract_s=round(t4 - t3, 4), write_s=round(t5 - t4s, 4))
+               fuse_s=round(t3 - t2, 4), extract_s=round(t4 - t3, 4), write_s=round(t5 - t4b, 4))
     if report is not None:
         res.update(components=report["components"], components_kept=report["components_kept"],
                    faces_removed=report["faces_removed"], clean_s=round(t4c - t4, 4))
     if simplified is not None:
         res.update(clusters=simplified["clusters"], faces_collapsed=simplified["faces_collapsed"],
                    faces_duplicate=simplified["faces_duplicate"], simplify_s=round(t4s - t4c, 4))
+    if baked is not None:
+        res.update(occlusion=baked, bake_s=round(t4b - t4s, 4))
     return res
 
 
@@ -136,6 +149,9 @@ def main(argv=None) -> int:
     if "clusters" in res:
         print("simplify %.3f s: %d clusters, %d faces collapsed, %d duplicates" % (res["simplify_s"], res["clusters"],
                                                                                   res["faces_collapsed"], res["faces_duplicate"]))
+    if "occlusion" in res:
+        print("bake %.3f s: %d rays per vertex, %d hits, %d vertices without a normal" % (
+            res["bake_s"], res["occlusion"]["rays"], res["occlusion"]["hits_total"], res["occlusion"]["no_normal"]))
     print(json.dumps(res))
     return 0
 

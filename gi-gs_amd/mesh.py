@@ -23,6 +23,11 @@
                                          (gigs_mesh_closest)
     distance(a, b, samples, ...)         both surfaces sampled and searched both ways: Chamfer, Hausdorff, one-sided
                                          statistics, precision / recall / F-score per threshold
+    raycast(origins, directions, mesh)   the nearest usable face every ray hits, by a slab traversal of that grid
+                                         (gigs_mesh_raycast)
+    occlusion_directions(rays, rotations)   the bake's default direction table: a cosine-weighted spiral lattice (host)
+    bake_occlusion(mesh, rays, ...)      per-vertex ambient occlusion, 1 = open: a wave per vertex casts `rays`
+                                         cosine-distributed rays and counts the hits (gigs_mesh_bake_occlusion)
 
 The route is the one of 2DGS and GOF: depth and material planes of the training views go into a truncated signed
 distance volume, and the mesh is its zero level set.  The arithmetic of both halves is stated in include/gigs_hip.h and
@@ -625,6 +630,7 @@ class TriangleGrid(NamedTuple):
     cell_start: torch.Tensor   # [cells + 1] int64
     pairs: torch.Tensor        # [n_pairs] int64, sorted: cell << 32 | face
     faces_skipped: int
+    hi: np.ndarray = None      # [3] float32: the maximum corner of the usable faces
 
 
 def grid_dims(lo, hi, cell) -> Tuple[float, Tuple[int, int, int]]:
@@ -687,7 +693,7 @@ def triangle_grid(mesh, cell=None):
         cell_start = torch.searchsorted(pairs, torch.arange(cells + 1, dtype=torch.int64, device=dev) << 32)
         if int(overflow.item()) != 0:
             raise MeshOverflow("triangle_grid: a face's cells left the %d pairs counted for them" % total)
-    return TriangleGrid(lo, cell, dims, cell_start, pairs, skipped)
+    return TriangleGrid(lo, cell, dims, cell_start, pairs, skipped, hi)
 
 
 def _closest(points: torch.Tensor, m: Mesh, grid, max_distance):
@@ -802,3 +808,193 @@ def distance(a, b, samples: int = 100000, seed: int = 0, taus=(), max_distance=N
                        b=dict(cell=gb.cell, dims=list(gb.dims)) if gb is not None else None)
     out["samples"], out["seed"] = int(samples), int(seed)
     return out
+
+
+# ---- baking occlusion: what a ray hits, the occlusion of every vertex (include/gigs_hip.h, "Baking occlusion") ---------------
+BAKE_MAX_RAYS, BAKE_MAX_ROTATIONS = 1024, 64
+
+
+def _cell_order(p64: torch.Tensor, grid: TriangleGrid) -> torch.Tensor:
+    """The rows of p64 [N,3] (float64) sorted by the grid cell they fall in (clamped; a NaN goes to 0)."""
+    dev = p64.device
+    lo = torch.from_numpy(grid.lo.astype(np.float64)).to(dev)
+    G = torch.tensor(grid.dims, dtype=torch.float64, device=dev)
+    c = torch.nan_to_num(((p64 - lo) / grid.cell).floor(), nan=0.0).clamp_(min=0).minimum(G - 1).long()
+    return torch.sort((c[:, 2] * grid.dims[1] + c[:, 1]) * grid.dims[0] + c[:, 0]).indices
+
+
+def _entry_order(origins: torch.Tensor, directions: torch.Tensor, grid: TriangleGrid) -> torch.Tensor:
+    """The rays sorted by the cell of the point where they enter the grid's box (their origin if it lies inside, the
+    clamped cell for a ray that misses the box): the lanes of a wave start on the same lists."""
+    dev = origins.device
+    o, d = origins.double(), directions.double()
+    lo = torch.from_numpy(grid.lo.astype(np.float64)).to(dev)
+    hi = lo + torch.tensor(grid.dims, dtype=torch.float64, device=dev) * grid.cell
+    t0, t1 = (lo - o) / d, (hi - o) / d
+    near = torch.nan_to_num(torch.minimum(t0, t1), nan=float("-inf"), neginf=float("-inf"), posinf=float("inf"))
+    t = torch.nan_to_num(near.amax(1).clamp_(min=0.0), posinf=0.0)
+    return _cell_order(o + t[:, None] * d, grid)
+
+
+def _raycast(origins: torch.Tensor, directions: torch.Tensor, m: Mesh, grid, t_max, sort: bool = True):
+    """-> (t [N] float32, face [N] int32, bary [N,2] float32, flags [3] int32 on the device: hits, invalid, overflow)."""
+    dev = m.vertices.device
+    N = int(origins.shape[0])
+    t = torch.full((N,), float("inf"), dtype=torch.float32, device=dev)
+    face = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    bary = torch.zeros((N, 2), dtype=torch.float32, device=dev)
+    flags = torch.zeros(3, dtype=torch.int32, device=dev)
+    if N == 0:
+        return t, face, bary, flags
+    if grid is None:  # no usable face: nothing is launched
+        valid = torch.isfinite(origins).all(1) & torch.isfinite(directions).all(1) & (directions != 0).any(1)
+        flags[1] = (~valid).sum()
+        return t, face, bary, flags
+    order = _entry_order(origins, directions, grid) if sort else None
+    c_lo, c_dims = _c_grid(grid.lo, grid.dims)
+    gigs_lib.check(gigs_lib.lib().gigs_mesh_raycast(
+        int(m.vertices.shape[0]), int(m.faces.shape[0]), _p(m.vertices), _p(m.faces), c_lo, grid.cell, c_dims,
+        _p(grid.cell_start), _p(grid.pairs), int(grid.pairs.shape[0]), _scale(grid), N, _p(origins), _p(directions),
+        _p(order) if order is not None else None, float("inf") if t_max is None else float(t_max), _p(t), _p(face), _p(bary),
+        flags.data_ptr(), flags[2:].data_ptr(), _stream()), "mesh_raycast")
+    return t, face, bary, flags
+
+
+def _scale(grid: TriangleGrid) -> float:
+    """M of sigma: the largest |coordinate| of a corner of a usable face."""
+    if grid.hi is None:
+        raise ValueError("the grid carries no `hi`: build it with triangle_grid")
+    return float(max(np.abs(grid.lo.astype(np.float64)).max(), np.abs(grid.hi.astype(np.float64)).max()))
+
+
+def _grid_report(grid, F: int) -> Dict:
+    return dict(faces_skipped=grid.faces_skipped if grid is not None else F, cell=grid.cell if grid is not None else 0.0,
+                dims=list(grid.dims) if grid is not None else [0, 0, 0], pairs=int(grid.pairs.shape[0]) if grid is not None else 0)
+
+
+def raycast(origins, directions, mesh, t_max=None, cell=None, grid=None):
+    """(t [N] float32, face [N] int32, bary [N,2] float32, report): for every ray origins[i] + t directions[i] ([N,3] float32
+    each, on the mesh's device; the direction need not be a unit vector and t is in its units) the nearest usable face of
+    `mesh` it hits within 0 <= t <= t_max (None: no limit) and the barycentric weights of the face's second and third
+    vertex at the hit.  Faces are two-sided; of faces hit at the same t the smallest index wins; a ray within about 1e-6
+    rad of a face's plane misses that face by definition (include/gigs_hip.h, "Baking occlusion").  A miss gives +inf,
+    -1, (0, 0), as does a ray with a non-finite component or a zero direction (rays_invalid) and every ray if the mesh has
+    no usable face.  The result does not depend on the grid: `cell` (triangle_grid) or a `grid` built before only change
+    the time.  Report: n, hits, rays_invalid, faces_skipped, cell, dims, pairs.  One read-back."""
+    if t_max is not None and not (float(t_max) >= 0):
+        raise ValueError("raycast: t_max must be >= 0 or None, got %r" % (t_max,))
+    m = _mesh_tensors(mesh, "raycast")
+    dev = m.vertices.device
+    for name, r in (("origins", origins), ("directions", directions)):
+        if not isinstance(r, torch.Tensor) or r.device != dev:
+            raise RuntimeError("raycast: %s must be a tensor on the mesh's device: gigs-hip has no CPU path" % name)
+        if r.dtype != torch.float32 or r.dim() != 2 or r.shape[1] != 3:
+            raise ValueError("raycast: %s must be [N,3] float32, got %s %s" % (name, tuple(r.shape), r.dtype))
+    if origins.shape[0] != directions.shape[0]:
+        raise ValueError("raycast: %d origins, %d directions" % (origins.shape[0], directions.shape[0]))
+    origins, directions = origins.contiguous(), directions.contiguous()
+    N = int(origins.shape[0])
+    if N == 0:  # nothing is launched, so nothing is known about the faces either
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        return torch.empty(0, **f32), torch.empty(0, **i32), torch.empty((0, 2), **f32), dict(
+            n=0, hits=0, rays_invalid=0, faces_skipped=None, cell=0.0, dims=[0, 0, 0], pairs=0)
+    with torch.cuda.device(dev):
+        if grid is None:
+            grid = triangle_grid(m, cell)
+        t, face, bary, flags = _raycast(origins, directions, m, grid, t_max)
+        flags = [int(x) for x in flags.cpu()]  # the one read-back
+        if flags[2] != 0:
+            raise MeshOverflow("raycast: an index left its range (%d faces, %d rays)" % (int(m.faces.shape[0]), N))
+    report = dict(n=N, hits=flags[0], rays_invalid=flags[1])
+    report.update(_grid_report(grid, int(m.faces.shape[0])))
+    return t, face, bary, report
+
+
+def occlusion_directions(rays: int = 256, rotations: int = 16) -> np.ndarray:
+    """[rotations, rays, 3] float32: a cosine-weighted spiral lattice on the hemisphere z >= 0 -- point i of R has
+    u = (i + 1/2) / R, radius sqrt(u), azimuth i times the golden angle and z = sqrt(1 - u) -- turned about z by
+    2 pi k / K for the k-th of K rotations.  numpy float64 on the host: the device does no trigonometry."""
+    R, K = int(rays), int(rotations)
+    i = np.arange(R, dtype=np.float64)
+    u = (i + 0.5) / R
+    r, z = np.sqrt(u), np.sqrt(1.0 - u)
+    golden = np.pi * (3.0 - np.sqrt(5.0))
+    phi = i[None, :] * golden + (2.0 * np.pi * np.arange(K, dtype=np.float64) / K)[:, None]
+    return np.stack([r[None] * np.cos(phi), r[None] * np.sin(phi), np.broadcast_to(z, phi.shape)], -1).astype(np.float32)
+
+
+def _bake_occlusion(mesh, rays=256, max_distance=None, bias=None, seed=0, rotations=16, directions=None, cell=None, grid=None,
+                    sort: bool = True):
+    """bake_occlusion with the per-vertex hit counts: -> (occlusion [V] float32, hits [V] int32, report)."""
+    m = _mesh_tensors(mesh, "bake_occlusion")
+    dev = m.vertices.device
+    if directions is None:
+        R, K = int(rays), int(rotations)
+    else:
+        directions = np.ascontiguousarray(directions, dtype=np.float32)
+        if directions.ndim != 3 or directions.shape[2] != 3:
+            raise ValueError("bake_occlusion: directions must be [K,R,3], got %s" % (directions.shape,))
+        K, R = int(directions.shape[0]), int(directions.shape[1])
+    if R < 64 or R > BAKE_MAX_RAYS or R % 64 != 0:
+        raise ValueError("bake_occlusion: rays must be a multiple of 64 in [64, %d], got %d" % (BAKE_MAX_RAYS, R))
+    if K < 1 or K > BAKE_MAX_ROTATIONS:
+        raise ValueError("bake_occlusion: rotations must lie in [1, %d], got %d" % (BAKE_MAX_ROTATIONS, K))
+    if directions is None:
+        directions = occlusion_directions(R, K)
+    elif not (np.isfinite(directions).all() and (directions[..., 2] >= 0).all()):
+        raise ValueError("bake_occlusion: directions must be finite with z >= 0")
+    for name, x in (("max_distance", max_distance), ("bias", bias)):
+        if x is not None and not (float(x) >= 0 and np.isfinite(float(x))):
+            raise ValueError("bake_occlusion: %s must be finite and >= 0 or None, got %r" % (name, x))
+    V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    occlusion = torch.ones(V, dtype=torch.float32, device=dev)
+    hits = torch.zeros(V, dtype=torch.int32, device=dev)
+    report = dict(n=V, hits_total=0, no_normal=0, rays=R, rotations=K, seed=seed,
+                  max_distance=0.0 if max_distance is None else float(max_distance), bias=0.0 if bias is None else float(bias))
+    if V == 0:
+        report.update(_grid_report(None, F))
+        return occlusion, hits, report
+    with torch.cuda.device(dev):
+        if grid is None:
+            grid = triangle_grid(m, cell)
+        report.update(_grid_report(grid, F))
+        if grid is None:  # no usable face: every vertex is open and nothing is launched
+            n2 = (m.normals.double() ** 2).sum(1)
+            ok = torch.isfinite(m.vertices).all(1) & (n2 >= 1.0 - 2.0 ** -10) & (n2 <= 1.0 + 2.0 ** -10)
+            report["no_normal"] = int((~ok).sum().item())
+            return occlusion, hits, report
+        if max_distance is None:
+            max_distance = 0.1 * (max(grid.dims) * grid.cell)
+        if bias is None:
+            bias = 1e-3 * float(max_distance)
+        report["max_distance"], report["bias"] = float(max_distance), float(bias)
+        order = _cell_order(m.vertices.double(), grid) if sort else None
+        table = torch.from_numpy(directions).to(dev)
+        counts = torch.zeros(3, dtype=torch.int64, device=dev)  # hits in all, no normal; overflow (an int32 in its low half)
+        c_lo, c_dims = _c_grid(grid.lo, grid.dims)
+        gigs_lib.check(gigs_lib.lib().gigs_mesh_bake_occlusion(
+            V, F, _p(m.vertices), _p(m.normals), _p(m.faces), c_lo, grid.cell, c_dims, _p(grid.cell_start), _p(grid.pairs),
+            int(grid.pairs.shape[0]), _scale(grid), _p(order) if order is not None else None, _p(table), R, K, seed, float(max_distance),
+            float(bias), _p(occlusion), _p(hits), counts.data_ptr(), counts[2:].data_ptr(), _stream()), "mesh_bake_occlusion")
+        got = [int(x) for x in counts.cpu()]  # the one read-back
+        if got[2] != 0:
+            raise MeshOverflow("bake_occlusion: an index left its range (%d vertices, %d faces)" % (V, F))
+        report["hits_total"], report["no_normal"] = got[0], got[1]
+    return occlusion, hits, report
+
+
+def bake_occlusion(mesh, rays=256, max_distance=None, bias=None, seed=0, rotations=16, directions=None, cell=None, grid=None):
+    """(occlusion [V] float32, report): for every vertex the cosine-weighted share of the hemisphere about its stored normal
+    that is open within `max_distance` -- 1 means open, the convention of the SSAO `occlusion` plane and of the shade's
+    `occlusion` input.  A wave per vertex casts `rays` rays (a multiple of 64 in [64, 1024]) from vertex + bias normal and
+    counts the ones that hit a usable face (mesh.raycast's rule) within max_distance: occlusion = (rays - hits) / rays,
+    a plain count because the directions are cosine-distributed.  They come from a table [rotations, rays, 3] in the local
+    frame (default: occlusion_directions; `directions` overrides it, and then sets rays and rotations); vertex v uses the
+    rotation mix64(seed 2^32 + v) mod rotations, so the result is a pure function of the arguments.  The stored normal is
+    used as it is; a vertex whose normal is not of unit length within 2^-10 (the zero normals the extraction can leave) or
+    whose position is not finite gets 1 and counts as no_normal.  max_distance defaults to 0.1 of the longest axis of the
+    grid's box and bias to 1e-3 max_distance: conventions, not measurements.  Report: n, hits_total, no_normal, rays,
+    rotations, seed, max_distance, bias, faces_skipped, cell, dims, pairs.  One read-back."""
+    occlusion, _, report = _bake_occlusion(mesh, rays, max_distance, bias, seed, rotations, directions, cell, grid)
+    return occlusion, report

@@ -9,7 +9,8 @@
                                    state_dict, "light_optimizer": state_dict, "iteration"} (train.py:466-490,
                                    scene/gaussian_model.py:82-176)
     save_mesh_ply / read_mesh_ply  a triangle mesh with per-vertex materials (mesh.Mesh; not a reference format): position,
-                                   world normal, albedo as 8-bit colour, roughness, metallic, triangle index lists
+                                   world normal, albedo as 8-bit colour, roughness, metallic, optionally the baked occlusion,
+                                   triangle index lists
 
 Pure host code (numpy / torch serialization): no kernels, works on CPU tensors.  `plyfile` is not needed; the reader
 parses the PLY header itself (ascii and binary little-endian vertex elements with scalar properties).  Checkpoints are
@@ -144,14 +145,17 @@ def load_ply(path: str, max_sh_degree: int, device="cpu") -> Dict[str, torch.Ten
 
 _MESH_VERTEX = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"),
                 ("green", "u1"), ("blue", "u1"), ("roughness", "<f4"), ("metallic", "<f4")]
+_MESH_OCCLUSION = ("occlusion", "<f4")  # the optional last vertex property
 _MESH_FACE = [("n", "u1"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4")]
 
 
-def save_mesh_ply(path: str, vertices, faces, normals, albedo, roughness, metallic) -> None:
+def save_mesh_ply(path: str, vertices, faces, normals, albedo, roughness, metallic, occlusion=None) -> None:
     """A triangle mesh with its materials (mesh.Mesh's fields, tensors or arrays) as a binary little-endian PLY: vertex
     properties x y z nx ny nz (float), red green blue (uchar), roughness metallic (float); faces as `property list uchar
     int vertex_indices`.  The colour is the albedo quantised as gigs_pack_images does with bias 0.5:
-    trunc(clamp(x * 255 + 0.5, 0, 255)) in float32 with the product and the sum rounded separately, NaN -> 0."""
+    trunc(clamp(x * 255 + 0.5, 0, 255)) in float32 with the product and the sum rounded separately, NaN -> 0.
+    `occlusion` ([V], mesh.bake_occlusion's; 1 = open) adds one more `property float occlusion` after metallic; with None
+    the file is the one without the argument, byte for byte."""
     v = np.asarray(_np(vertices), dtype=np.float32).reshape(-1, 3)
     n = np.asarray(_np(normals), dtype=np.float32).reshape(-1, 3)
     a = np.asarray(_np(albedo), dtype=np.float32).reshape(-1, 3)
@@ -166,7 +170,15 @@ def save_mesh_ply(path: str, vertices, faces, normals, albedo, roughness, metall
     with np.errstate(invalid="ignore"):
         q = a * np.float32(255.0) + np.float32(0.5)
         q = np.where(np.isnan(q), np.float32(0.0), np.clip(q, np.float32(0.0), np.float32(255.0))).astype(np.uint8)
-    vt = np.empty(V, dtype=_MESH_VERTEX)
+    layout = list(_MESH_VERTEX)
+    if occlusion is not None:
+        occlusion = np.asarray(_np(occlusion), dtype=np.float32).reshape(-1)
+        if occlusion.shape[0] != V:
+            raise ValueError("save_mesh_ply: occlusion must have one value per vertex")
+        layout.append(_MESH_OCCLUSION)
+    vt = np.empty(V, dtype=layout)
+    if occlusion is not None:
+        vt["occlusion"] = occlusion
     for i, k in enumerate("xyz"):
         vt[k], vt["n" + k] = v[:, i], n[:, i]
     vt["red"], vt["green"], vt["blue"], vt["roughness"], vt["metallic"] = q[:, 0], q[:, 1], q[:, 2], r, m
@@ -174,7 +186,7 @@ def save_mesh_ply(path: str, vertices, faces, normals, albedo, roughness, metall
     ft["n"] = 3
     ft["a"], ft["b"], ft["c"] = f[:, 0], f[:, 1], f[:, 2]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {V}"]
-    header += ["property %s %s" % ("uchar" if t == "u1" else "float", k) for k, t in _MESH_VERTEX]
+    header += ["property %s %s" % ("uchar" if t == "u1" else "float", k) for k, t in layout]
     header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     d = os.path.dirname(path)
     if d:
@@ -187,7 +199,8 @@ def save_mesh_ply(path: str, vertices, faces, normals, albedo, roughness, metall
 
 def read_mesh_ply(path: str) -> Dict[str, np.ndarray]:
     """A file of save_mesh_ply -> {vertices [V,3], faces [F,3] int32, normals [V,3], albedo [V,3] (colour / 255), roughness
-    [V], metallic [V]}.  Reads that layout only: anything else raises ValueError."""
+    [V], metallic [V]}, and occlusion [V] if the file carries that property after metallic.  Reads these two layouts only:
+    anything else raises ValueError."""
     with open(path, "rb") as f:
         lines = []
         while True:
@@ -200,12 +213,15 @@ def read_mesh_ply(path: str) -> Dict[str, np.ndarray]:
         if len(lines) < 4 or lines[0] != "ply" or lines[1] != "format binary_little_endian 1.0":
             raise ValueError(f"{path}: not a binary little-endian PLY file")
         body = [ln for ln in lines[2:-1] if ln and not ln.startswith(("comment", "obj_info"))]
-        want = ["property %s %s" % ("uchar" if t == "u1" else "float", k) for k, t in _MESH_VERTEX]
+        layout = list(_MESH_VERTEX)
+        if len(body) == len(layout) + 4 and body[1 + len(layout)] == "property float " + _MESH_OCCLUSION[0]:
+            layout.append(_MESH_OCCLUSION)
+        want = ["property %s %s" % ("uchar" if t == "u1" else "float", k) for k, t in layout]
         if (len(body) != len(want) + 3 or not body[0].startswith("element vertex ") or body[1:1 + len(want)] != want
                 or not body[-2].startswith("element face ") or body[-1] != "property list uchar int vertex_indices"):
             raise ValueError(f"{path}: not the mesh layout of save_mesh_ply")
         V, F = int(body[0].split()[2]), int(body[-2].split()[2])
-        vdt, fdt = np.dtype(_MESH_VERTEX), np.dtype(_MESH_FACE)
+        vdt, fdt = np.dtype(layout), np.dtype(_MESH_FACE)
         raw_v, raw_f = f.read(vdt.itemsize * V), f.read(fdt.itemsize * F)
         if len(raw_v) != vdt.itemsize * V or len(raw_f) != fdt.itemsize * F:
             raise ValueError(f"{path}: truncated")
@@ -216,9 +232,12 @@ def read_mesh_ply(path: str) -> Dict[str, np.ndarray]:
     if F and (faces.min() < 0 or faces.max() >= V):
         raise ValueError(f"{path}: a face refers to a vertex that does not exist")
     col = lambda *ks: np.stack([vt[k] for k in ks], axis=1).astype(np.float32)  # noqa: E731
-    return dict(vertices=col("x", "y", "z"), faces=faces, normals=col("nx", "ny", "nz"),
-                albedo=col("red", "green", "blue") / np.float32(255.0), roughness=vt["roughness"].astype(np.float32),
-                metallic=vt["metallic"].astype(np.float32))
+    out = dict(vertices=col("x", "y", "z"), faces=faces, normals=col("nx", "ny", "nz"),
+               albedo=col("red", "green", "blue") / np.float32(255.0), roughness=vt["roughness"].astype(np.float32),
+               metallic=vt["metallic"].astype(np.float32))
+    if len(layout) > len(_MESH_VERTEX):
+        out["occlusion"] = vt["occlusion"].astype(np.float32)
+    return out
 
 
 def capture(active_sh_degree: int, params: Dict[str, torch.Tensor], stats, optimizer, spatial_lr_scale: float) -> Tuple:

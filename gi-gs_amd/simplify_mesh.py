@@ -29,7 +29,7 @@ if __package__ in (None, ""):  # run as a script: make the package's modules imp
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Mesh simplification parameters")
-    p.add_argument("input", type=str, help="a PLY written by extract_mesh.py")
+    p.add_argument("input", type=str, help="a PLY written by extract_mesh.py (an occlusion channel of bake_mesh.py is read and dropped)")
     p.add_argument("-o", "--output", type=str, required=True)
     size = p.add_mutually_exclusive_group(required=True)
     size.add_argument("--cell", type=float, default=None, help="cell size in world units")

@@ -858,6 +858,66 @@ int gigs_mesh_closest(int n_vertices, int n_faces, const float* vertices, const 
                       const int* dims, const long long* cell_start, const long long* pair_keys, long long n_pairs,
                       int n_points, const float* points, const long long* order, double max_distance, float* distance,
                       int* face, int* counts, int* overflow, void* stream);
+/* Baking occlusion (gigs-hip extension; the device half of mesh.raycast / mesh.bake_occlusion): the nearest usable face a
+ * ray hits, searched through the triangle grid of "Comparing meshes", and on top of it the ambient occlusion of every
+ * vertex.  All arrays are DEVICE memory except `lo` and `dims` (host, read during the call); the calls neither synchronise
+ * nor allocate; the sorts before them are the caller's.  One independent thread per ray, no float atomics, no thread waits
+ * on another.  All arithmetic is float64 on the float32 inputs, + - * / only, every product and sum rounded on its own
+ * (dot and cross as under "Comparing meshes"): there is no sqrt and no transcendental, so tests/mesh_raycast_ref.py
+ * reproduces every bit in numpy.
+ *   1 Usable faces and the grid: 1 and 4 of "Comparing meshes".  A face that is in no grid cell cannot be hit.
+ *   2 Edge functions.  For the ray (o, d) and the face (i0, i1, i2) with corners p0, p1, p2 let a_k = p_k - o.  The edge
+ *     between the vertices j and k has s = dot(d, cross(a_lo, a_hi)) with (lo, hi) = (j, k) if i_j < i_k, else (k, j): the
+ *     ends are always taken in ascending vertex INDEX.  w = s if i_j < i_k, else -s.  w0 is that of the edge 1 -> 2 (the
+ *     edge opposite vertex 0), w1 of 2 -> 0, w2 of 0 -> 1.  Two faces that share an edge and traverse it in opposite
+ *     directions compute the same bits with opposite signs: no ray passes between them.
+ *   3 Inside.  The ray is inside iff w0, w1, w2 are all >= 0 or all <= 0, and not all zero.  Faces are two-sided.
+ *   4 Plane.  n = cross(p1 - p0, p2 - p0), dn = dot(d, n).  The face is a candidate only if
+ *     dn dn > 2^-40 (dot(d, d) dot(n, n)): a ray within about 10^-6 rad of the face's plane misses it BY DEFINITION.
+ *     t = dot(a_0, n) / dn, and 0 <= t <= t_max is required.
+ *   5 Box.  With sigma = 2^-26 (M + max(|o_x|, |o_y|, |o_z|)), M = `scale` = the largest |coordinate| of a corner of a usable
+ *     face (the caller's; a larger value keeps the traversal complete but is another definition), the
+ *     hit point x_a = o_a + t d_a must satisfy  min_k p_k,a - sigma <= x_a <= max_k p_k,a + sigma  on every axis.  Under
+ *     the guard of 4 the rounding of t moves x by less than 2^-30 (M + |o|), so a ray through the face never fails this
+ *     test; it bounds how far outside its face an ACCEPTED hit can lie, which the inside test alone does not (an edge
+ *     function of a tiny edge far from o has no useful relative accuracy), and that bound is what makes the traversal
+ *     provably complete ("Baking occlusion").  A face that passes 3, 4 and 5 is ACCEPTED.
+ *   6 Result.  The minimum of (t, face index) over ALL accepted usable faces, float64 t compared, ties to the smaller
+ *     index: a function of ray, mesh, t_max and M alone.  t = float32(t), bary = (float32(w1 / W), float32(w2 / W)),
+ *     W = (w0 + w1) + w2.  A miss: +inf, -1, (0, 0).  A ray with a non-finite component or d = 0: the same, and
+ *     counts[1] += 1; counts[0] counts the hits.
+ *   7 Traversal.  A = the axis of the largest |d_a| (the lowest on a tie), U = A + 1 mod 3, W = A + 2 mod 3.  Slabs
+ *     k = c_A(o_A -+ 3 sigma) (-: d_A > 0, +: d_A < 0) onwards in the direction of travel, at most G_A of them:
+ *       ta = ((plane_A(k) - 2 sigma) - o_A) / d_A, tb = ((plane_A(k + 1) + 2 sigma) - o_A) / d_A, tn = min, tf = max;
+ *       tf < 0: next slab;  tn > t_max or best t < tn: stop;  tn = max(tn, 0), tf = min(tf, t_max);
+ *       on U (and W alike): y_n = o_U + tn d_U, y_f = o_U + tf d_U, cells c_U(min(y_n, y_f) - 2 sigma) ..
+ *       c_U(max(y_n, y_f) + 2 sigma); every face listed in a cell of that rectangle of slab k is tested.
+ *     |d_U| <= |d_A| keeps the rectangle at 3 x 3 cells while 8 sigma < cell; a ray whose origin is so far away that
+ *     sigma reaches the cell size widens it, up to the slab.  Every accepted face is listed in a visited cell.
+ *   8 Bake.  directions [K, R, 3] float32 in the local frame (z >= 0), R a multiple of 64 in [64, 1024], K in [1, 64].
+ *     Vertex v with position p and stored normal n (float32 -> float64, NOT renormalised): if p is not finite or
+ *     dot(n, n) is not in [1 - 2^-10, 1 + 2^-10], occlusion = 1, hits = 0 and counts[1] += 1.  Else, the basis of Duff et
+ *     al. 2017: s = copysign(1, n_z), a = -1 / (s + n_z), b = (n_x n_y) a, T = (1 + ((s n_x) n_x) a, s b, (-s) n_x),
+ *     B = (b, s + (n_y n_y) a, -n_y); rotation k = mix((seed 2^32 + v) mod 2^64) mod K; ray j of R: origin o_c = p_c +
+ *     bias n_c, direction d_c = (x T_c + y B_c) + z n_c with (x, y, z) = directions[k, j], as doubles; hits = the rays with
+ *     an accepted face at 0 <= t <= max_distance; occlusion = float32((R - hits) / R), 1 = open; counts[0] += hits.
+ * gigs_mesh_raycast, one thread per row of `order` [N] int64 (the rays sorted by the cell they enter the grid in, or NULL):
+ *   ray order[i] gets t [N], face [N], bary [N,2] as in 6; counts [2] int32 (cleared inside the call) = hits, invalid.
+ *   n_rays == 0 launches nothing.
+ * gigs_mesh_bake_occlusion, one one-wave block per row of `order` [V] int64 (the vertices sorted by cell, or NULL): the
+ *   wave walks the vertex's R / 64 chunks of 64 directions, one per lane, and stores occlusion [V] float32 and hits [V]
+ *   int32 itself; counts [2] uint64 (cleared inside the call) = hits in all, vertices without a normal.
+ * An order row, a cell_start entry, a pair key or a face index outside its range sets *overflow (cleared by the caller) and
+ *   the thread (the wave, in the bake) stores nothing. */
+int gigs_mesh_raycast(int n_vertices, int n_faces, const float* vertices, const int* faces, const float* lo, double cell,
+                      const int* dims, const long long* cell_start, const long long* pair_keys, long long n_pairs, double scale,
+                      int n_rays, const float* origins, const float* directions, const long long* order, double t_max, float* t,
+                      int* face, float* bary, int* counts, int* overflow, void* stream);
+int gigs_mesh_bake_occlusion(int n_vertices, int n_faces, const float* vertices, const float* normals, const int* faces,
+                             const float* lo, double cell, const int* dims, const long long* cell_start,
+                             const long long* pair_keys, long long n_pairs, double scale, const long long* order,
+                             const float* directions, int n_rays, int n_rotations, unsigned long long seed, double max_distance, double bias,
+                             float* occlusion, int* hits, unsigned long long* counts, int* overflow, void* stream);
 /* Rendering meshes (gigs-hip extension; the device half of mesh_render.py): a triangle mesh -- vertices [V,3], faces [F,3]
  * int32 and mesh.py's per-vertex attributes -- as the G-buffer planes the blend kernel writes in inference mode, by a
  * visibility buffer.  Coverage and visibility are integer decisions, so no result depends on the order of execution and a
