@@ -5,7 +5,7 @@ their depth and material planes fused into a truncated signed distance volume, a
     python gi-gs_amd/extract_mesh.py -m <out> --checkpoint <out>/chkpntN.pth [--grid 256] [--bounds x0 y0 z0 x1 y1 z1]
                                      [--trunc_voxels 4] [--min_weight 2] [--opacity_min 0.5] [--no_carve]
                                      [--split train] [--keep_largest K] [--min_faces M] [--simplify R]
-                                     [--bake_occlusion RAYS] [--ao_distance D]
+                                     [--bake_occlusion RAYS] [--ao_distance D] [--texture B]
                                      -o mesh.ply                                                           (CLI)
     extract_mesh(args) -> {...}                                                                            (API)
 
@@ -20,7 +20,11 @@ grid: the face count falls by about R^2 while the volume keeps its resolution.  
 faces_collapsed, faces_duplicate and simplify_s.  --bake_occlusion RAYS (0: off, as before, byte for byte) runs
 mesh.bake_occlusion with RAYS rays per vertex (a multiple of 64) on the mesh that is written -- after cleaning and
 simplifying -- and the PLY gains `property float occlusion` (1 = open); --ao_distance D is its max_distance (default: 0.1 of
-the longest axis of the mesh's grid).  The result gains occlusion (the bake's report) and bake_s.
+the longest axis of the mesh's grid).  The result gains occlusion (the bake's report) and bake_s.  --texture B (0: off, as
+before, byte for byte; needs --simplify R and an -o that ends in .obj) writes the simplified mesh as OBJ + MTL + PNG instead
+of a PLY: mesh.bake_atlas stores the materials of the level set BEFORE the simplification in an atlas of charts of B texels
+over the simplified mesh (texture_mesh.py's files), and --bake_occlusion then bakes that unsimplified mesh, whose occlusion
+becomes the first channel of the ORM image.  The result gains texture (the atlas's report), files and texture_s.
 """
 from __future__ import annotations
 
@@ -55,6 +59,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--simplify", type=float, default=0.0, help="cluster the vertices in cells of this many voxels (0: off)")
     p.add_argument("--bake_occlusion", type=int, default=0, help="rays per vertex of the occlusion bake, a multiple of 64 (0: off)")
     p.add_argument("--ao_distance", type=float, default=None, help="how far an occluder counts (default: 0.1 of the longest axis)")
+    p.add_argument("--texture", type=int, default=0, help="texels along a chart of the texture atlas; needs --simplify and a .obj output (0: off)")
     p.add_argument("-o", "--output", type=str, default="mesh.ply")
     return p
 
@@ -75,6 +80,8 @@ def extract_mesh(args) -> Dict:
     args = render_scene.combine_args(render_scene.as_namespace(args, parse_args))
     if not torch.cuda.is_available():
         raise RuntimeError("extract_mesh needs the GPU")
+    if args.texture != 0 and not (args.texture >= 3 and args.simplify > 0 and args.output.endswith(".obj")):
+        raise ValueError("extract_mesh: --texture B needs B >= 3, --simplify R and an output that ends in .obj")
     dev = torch.device("cuda", torch.cuda.current_device())
     args.source_path = os.path.abspath(args.source_path)
     sync = torch.cuda.synchronize
@@ -108,24 +115,35 @@ def extract_mesh(args) -> Dict:
             sync()
         t4c = time.perf_counter()
         simplified = None
+        level_set = m  # what --texture reads the materials from
         if args.simplify > 0:
             m, simplified = mesh.simplify(m, args.simplify * voxel, origin=vol.lo)
             sync()
         t4s = time.perf_counter()
         occlusion = baked = None
         if args.bake_occlusion > 0:
-            occlusion, baked = mesh.bake_occlusion(m, rays=args.bake_occlusion, max_distance=args.ao_distance)
+            occlusion, baked = mesh.bake_occlusion(level_set if args.texture else m, rays=args.bake_occlusion,
+                                                   max_distance=args.ao_distance)
             sync()
         t4b = time.perf_counter()
         path = args.output if os.path.isabs(args.output) else os.path.join(args.model_path, args.output)
-        scene_io.save_mesh_ply(path, *m, occlusion=occlusion)
+        textured = files = None
+        if args.texture:
+            import texture_mesh
+            atlas, textured = mesh.bake_atlas(m, level_set, block=args.texture, occlusion=occlusion)
+            sync()
+            t4t = time.perf_counter()
+            files = texture_mesh.save_textured_mesh(path, m, atlas)
+        else:
+            t4t = t4b
+            scene_io.save_mesh_ply(path, *m, occlusion=occlusion)
         t5 = time.perf_counter()
     finally:
         pipeline._collect_idle()
     res = dict(path=path, views=len(views), samples=vol.n_samples, dims=list(dims), voxel=voxel,
                lo=[float(v) for v in lo], hi=[float(v) for v in hi], vertices=int(m.vertices.shape[0]),
                faces=int(m.faces.shape[0]), load_s=round(t1 - t0, 4), cameras_s=round(t2 - t1, 4),
-               fuse_s=round(t3 - t2, 4), extract_s=round(t4 - t3, 4), write_s=round(t5 - t4b, 4))
+               fuse_s=round(t3 - t2, 4), extract_s=round(t4 - t3, 4), write_s=round(t5 - t4t, 4))
     if report is not None:
         res.update(components=report["components"], components_kept=report["components_kept"],
                    faces_removed=report["faces_removed"], clean_s=round(t4c - t4, 4))
@@ -134,6 +152,8 @@ def extract_mesh(args) -> Dict:
                    faces_duplicate=simplified["faces_duplicate"], simplify_s=round(t4s - t4c, 4))
     if baked is not None:
         res.update(occlusion=baked, bake_s=round(t4b - t4s, 4))
+    if textured is not None:
+        res.update(texture=textured, files=files, texture_s=round(t4t - t4b, 4))
     return res
 
 
@@ -152,6 +172,9 @@ def main(argv=None) -> int:
     if "occlusion" in res:
         print("bake %.3f s: %d rays per vertex, %d hits, %d vertices without a normal" % (
             res["bake_s"], res["occlusion"]["rays"], res["occlusion"]["hits_total"], res["occlusion"]["no_normal"]))
+    if "texture" in res:
+        print("texture %.3f s: %d x %d texels, %d baked" % (res["texture_s"], res["texture"]["width"], res["texture"]["height"],
+                                                          res["texture"]["baked"]))
     print(json.dumps(res))
     return 0
 

@@ -28,6 +28,12 @@
     occlusion_directions(rays, rotations)   the bake's default direction table: a cosine-weighted spiral lattice (host)
     bake_occlusion(mesh, rays, ...)      per-vertex ambient occlusion, 1 = open: a wave per vertex casts `rays`
                                          cosine-distributed rays and counts the hits (gigs_mesh_bake_occlusion)
+    atlas_layout(F, block, width)        the texture atlas of equal per-face charts, face_uvs(F, layout) its UVs (host)
+    transfer_attributes(points, src, values)   per-vertex channels of src interpolated at the closest point of src to
+                                         every query (gigs_mesh_closest, gigs_mesh_transfer)
+    bake_atlas(dst, src, block, ...)     src's materials as albedo / ORM / normal planes over dst's atlas: a surface point
+                                         per texel (gigs_mesh_atlas_points), the search, the transfer; sample_atlas looks
+                                         the planes up again (torch)
 
 The route is the one of 2DGS and GOF: depth and material planes of the training views go into a truncated signed
 distance volume, and the mesh is its zero level set.  The arithmetic of both halves is stated in include/gigs_hip.h and
@@ -998,3 +1004,271 @@ def bake_occlusion(mesh, rays=256, max_distance=None, bias=None, seed=0, rotatio
     rotations, seed, max_distance, bias, faces_skipped, cell, dims, pairs.  One read-back."""
     occlusion, _, report = _bake_occlusion(mesh, rays, max_distance, bias, seed, rotations, directions, cell, grid)
     return occlusion, report
+
+
+# ---- texturing: the atlas of per-face charts, texel -> surface point, transfer (include/gigs_hip.h, "Texturing meshes") ------
+TRANSFER_MAX_CHANNELS = 16
+ATLAS_MAX_BLOCK = 1024
+
+
+class AtlasLayout(NamedTuple):
+    block: int           # B: a block is (B + 1) x B texels and holds two faces
+    width: int           # W
+    height: int          # H = rows B
+    blocks_per_row: int  # W // (B + 1)
+    n_blocks: int        # ceil(F / 2)
+
+
+class Atlas(NamedTuple):
+    layout: AtlasLayout
+    uvs: torch.Tensor       # [F,3,2] float32, v = 0 at the bottom row of the image
+    albedo: torch.Tensor    # [3,H,W] float32
+    orm: torch.Tensor       # [3,H,W]: occlusion, roughness, metallic
+    normal: torch.Tensor    # [3,H,W]: the world normal as interpolated, not normalised
+    coverage: torch.Tensor  # [H,W] uint8: 1 where a texel was baked
+
+
+def atlas_layout(F: int, block: int = 8, width=None) -> AtlasLayout:
+    """The atlas of equal per-face charts for F faces: blocks of (block + 1) x block texels, two faces to a block (face f in
+    block f // 2, half f % 2), row-major, width // (block + 1) to a row; height = rows * block.  `width` defaults to the
+    smallest power of two whose square image holds the ceil(F / 2) blocks.  Host arithmetic."""
+    B, F = int(block), int(F)
+    if B < 3 or B > ATLAS_MAX_BLOCK:
+        raise ValueError("atlas_layout: block must lie in [3, %d], got %d" % (ATLAS_MAX_BLOCK, B))
+    if F < 0:
+        raise ValueError("atlas_layout: F must be >= 0, got %d" % F)
+    n_blocks = (F + 1) // 2
+    if width is None:
+        width = 1
+        while width < B + 1 or (width // (B + 1)) * (width // B) < n_blocks:
+            width *= 2
+    width = int(width)
+    if width < B + 1:
+        raise ValueError("atlas_layout: a width of %d holds no block of %d x %d texels" % (width, B + 1, B))
+    per_row = width // (B + 1)
+    lay = AtlasLayout(B, width, -(-n_blocks // per_row) * B, per_row, n_blocks)
+    if n_blocks * B * (B + 1) >= 2 ** 31:
+        raise ValueError("atlas_layout: %d blocks of %d x %d texels are more than 2^31 texels" % (n_blocks, B + 1, B))
+    return lay
+
+
+def face_uvs(F: int, layout: AtlasLayout, device=None) -> torch.Tensor:
+    """[F,3,2] float32: the UV of every face corner in `layout`, each the centre of a texel of the face's half of its block:
+    (X / W, 1 - Y / H) for the point (X, Y) in texel coordinates, Y down the image rows, so v = 0 is the bottom row (the
+    OBJ convention; include/gigs_hip.h, "Texturing meshes", 3).  Host arithmetic in float64, rounded once."""
+    B, W, H, per_row = layout.block, layout.width, layout.height, layout.blocks_per_row
+    F = int(F)
+    if (F + 1) // 2 > layout.n_blocks:
+        raise ValueError("face_uvs: %d faces do not fit the layout's %d blocks" % (F, layout.n_blocks))
+    if F == 0:
+        return torch.zeros((0, 3, 2), dtype=torch.float32, device=device)
+    f = np.arange(F, dtype=np.int64)
+    b, half = f // 2, f % 2
+    corner = np.array([[(0, 0), (B - 2, 0), (0, B - 2)], [(B, B - 1), (2, B - 1), (B, 1)]], np.int64)[half]
+    X = ((b % per_row) * (B + 1))[:, None] + corner[..., 0] + 0.5
+    Y = ((b // per_row) * B)[:, None] + corner[..., 1] + 0.5
+    uv = np.stack([X / float(W), 1.0 - Y / float(H)], -1).astype(np.float32)
+    return torch.from_numpy(uv).to(device) if device is not None else torch.from_numpy(uv)
+
+
+def _atlas_points(m: Mesh, lay: AtlasLayout):
+    """-> (points [Q,3], bary [Q,2], texel_face [Q] int32, dest [Q] int64, overflow [1] int32 on the device)."""
+    dev = m.vertices.device
+    Q = lay.n_blocks * lay.block * (lay.block + 1)
+    points, bary = torch.empty((Q, 3), dtype=torch.float32, device=dev), torch.empty((Q, 2), dtype=torch.float32, device=dev)
+    texel_face, dest = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int64, device=dev)
+    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+    if Q:
+        gigs_lib.check(gigs_lib.lib().gigs_mesh_atlas_points(
+            int(m.vertices.shape[0]), int(m.faces.shape[0]), _p(m.vertices), _p(m.faces), lay.block, lay.width, lay.height,
+            lay.n_blocks, _p(points), _p(bary), _p(texel_face), _p(dest), overflow.data_ptr(), _stream()), "mesh_atlas_points")
+    return points, bary, texel_face, dest, overflow
+
+
+def atlas_points(mesh, layout: AtlasLayout):
+    """(points [Q,3] float32, bary [Q,2] float32, texel_face [Q] int32, dest [Q] int64) for the Q = n_blocks B (B + 1) texels
+    of `layout`'s blocks, block-major: the point of `mesh`'s surface each texel stands for, its weights (w1, w2) on its
+    face, the face (-1 for a slot past F) and the texel's index y W + x in the image -- -1, with a NaN point, where nothing
+    is to be baked (gigs_mesh_atlas_points).  One read-back (the flag)."""
+    m = _mesh_tensors(mesh, "atlas_points")
+    if (int(m.faces.shape[0]) + 1) // 2 != layout.n_blocks:
+        raise ValueError("atlas_points: the layout is not the one of %d faces" % int(m.faces.shape[0]))
+    with torch.cuda.device(m.vertices.device):
+        points, bary, texel_face, dest, overflow = _atlas_points(m, layout)
+        if int(overflow.item()) != 0:
+            raise MeshOverflow("atlas_points: a texel left the %d x %d image" % (layout.width, layout.height))
+    return points, bary, texel_face, dest
+
+
+def _transfer(points: torch.Tensor, face: torch.Tensor, m: Mesh, values: torch.Tensor, dest=None, plane: int = 0):
+    """-> (out ([N,C], or [C,plane] with dest; zero where nothing is stored), coverage [plane] uint8 or None, bary [N,2],
+    counts [3] int64 on the device: transferred, skipped, overflow (an int32 in its low half))."""
+    dev = m.vertices.device
+    N, Cn = int(points.shape[0]), int(values.shape[1])
+    out = torch.zeros((Cn, plane) if dest is not None else (N, Cn), dtype=torch.float32, device=dev)
+    coverage = torch.zeros(plane, dtype=torch.uint8, device=dev) if dest is not None else None
+    bary = torch.zeros((N, 2), dtype=torch.float32, device=dev)
+    counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    if N:
+        gigs_lib.check(gigs_lib.lib().gigs_mesh_transfer(
+            int(m.vertices.shape[0]), int(m.faces.shape[0]), _p(m.vertices), _p(m.faces), Cn, _p(values), N, _p(points), _p(face),
+            _p(dest) if dest is not None else None, int(plane), out.data_ptr(),
+            coverage.data_ptr() if coverage is not None else None, _p(bary), counts.data_ptr(), counts[2:].data_ptr(), _stream()),
+            "mesh_transfer")
+    return out, coverage, bary, counts
+
+
+def _check_values(values, m: Mesh, what: str) -> torch.Tensor:
+    dev = m.vertices.device
+    if not isinstance(values, torch.Tensor) or values.device != dev:
+        raise RuntimeError("%s: values must be a tensor on the mesh's device: gigs-hip has no CPU path" % what)
+    if values.dim() == 1:
+        values = values[:, None]
+    if (values.dtype != torch.float32 or values.dim() != 2 or values.shape[0] != m.vertices.shape[0]
+            or not 1 <= values.shape[1] <= TRANSFER_MAX_CHANNELS):
+        raise ValueError("%s: values must be [V,C] float32 with 1 <= C <= %d, got %s %s" % (what, TRANSFER_MAX_CHANNELS,
+                                                                                        tuple(values.shape), values.dtype))
+    return values.contiguous()
+
+
+def _check_points(points, dev, what: str) -> torch.Tensor:
+    if not isinstance(points, torch.Tensor) or points.device != dev:
+        raise RuntimeError("%s: points must be a tensor on the mesh's device: gigs-hip has no CPU path" % what)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("%s: points must be [N,3] float32, got %s %s" % (what, tuple(points.shape), points.dtype))
+    return points.contiguous()
+
+
+def transfer_at(points, face, src, values):
+    """(out [N,C] float32, bary [N,2] float32, report): transfer_attributes without its search -- `face` [N] int32 names the
+    face of `src` each point is projected on (-1: none; the point keeps 0).  Report: n, transferred, skipped.  A face index
+    >= F raises MeshOverflow.  One read-back."""
+    m = _mesh_tensors(src, "transfer_at")
+    dev = m.vertices.device
+    values = _check_values(values, m, "transfer_at")
+    points = _check_points(points, dev, "transfer_at")
+    N = int(points.shape[0])
+    if not isinstance(face, torch.Tensor) or face.device != dev or face.dtype != torch.int32 or tuple(face.shape) != (N,):
+        raise ValueError("transfer_at: face must be a [%d] int32 tensor on the mesh's device" % N)
+    with torch.cuda.device(dev):
+        out, _, bary, counts = _transfer(points, face.contiguous(), m, values)
+        got = [int(x) for x in counts.cpu()]  # the one read-back
+        if got[2] != 0:
+            raise MeshOverflow("transfer_at: an index left its range (%d faces, %d queries)" % (int(m.faces.shape[0]), N))
+    return out, bary, dict(n=N, transferred=got[0], skipped=got[1])
+
+
+def transfer_attributes(points, src, values, cell=None, max_distance=None, grid=None):
+    """(out [N,C] float32, face [N] int32, bary [N,2] float32, distance [N] float32, report): the per-vertex channels
+    `values` ([V,C] float32, 1 <= C <= 16) of the mesh `src`, interpolated at the point of `src` closest to every point of
+    `points` ([N,3] float32 on the mesh's device).  closest_point's search finds the face and the distance;
+    gigs_mesh_transfer finds where on that face the closest point lies -- `bary` holds the weights of the face's second and
+    third vertex -- and interpolates there.  A point the search gives no face (far, non-finite, no usable face) keeps 0 in
+    `out` and `bary`.  With points = another mesh's vertices this is a per-vertex transfer.  `cell`, `grid`, `max_distance`
+    as in closest_point.  Report: n, transferred, skipped, far, queries_invalid, faces_skipped, cell, dims, pairs.  One
+    read-back."""
+    _check_max_distance(max_distance)
+    m = _mesh_tensors(src, "transfer_attributes")
+    dev = m.vertices.device
+    values = _check_values(values, m, "transfer_attributes")
+    points = _check_points(points, dev, "transfer_attributes")
+    N, F = int(points.shape[0]), int(m.faces.shape[0])
+    if N == 0:
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        report = dict(n=0, transferred=0, skipped=0, far=0, queries_invalid=0)
+        report.update(_grid_report(None, F))
+        return (torch.empty((0, values.shape[1]), **f32), torch.empty(0, **i32), torch.empty((0, 2), **f32), torch.empty(0, **f32),
+                report)
+    with torch.cuda.device(dev):
+        if grid is None:
+            grid = triangle_grid(m, cell)
+        distance, face, flags = _closest(points, m, grid, max_distance)
+        out, _, bary, counts = _transfer(points, face, m, values)
+        got = [int(x) for x in torch.cat((flags.long(), counts)).cpu()]  # the one read-back
+        if got[2] != 0 or got[5] != 0:
+            raise MeshOverflow("transfer_attributes: an index left its range (%d faces, %d queries)" % (F, N))
+    report = dict(n=N, transferred=got[3], skipped=got[4], far=got[0], queries_invalid=got[1])
+    report.update(_grid_report(grid, F))
+    return out, face, bary, distance, report
+
+
+def bake_atlas(dst, src, block: int = 8, width=None, occlusion=None, max_distance=None, cell=None, grid=None):
+    """(Atlas, report): the materials of the mesh `src` baked into a texture atlas over the mesh `dst` (a simplification of
+    src, usually).  Every face of dst gets a chart of its own in atlas_layout(F, block, width); every texel of a chart
+    stands for a point of its face (gigs_mesh_atlas_points; the one row of texels past the chart's long edge for the
+    extrapolated point of the face's plane: the gutter), the closest face of src to that point is searched
+    (triangle_grid(src) unless `grid` is passed, gigs_mesh_closest), and src's albedo, occlusion, roughness, metallic and
+    normal are interpolated at the closest point (gigs_mesh_transfer, nine channels in one launch).  `occlusion`: [V_src]
+    float32 such as bake_occlusion's, 1 where None.  The normal plane holds the interpolated world normal as it is, not
+    normalised.  Texels of no face, of an unusable face of dst, or with no face of src within `max_distance` stay 0 with
+    coverage 0.  max_distance=None searches without a limit: a texel far from src then walks O(G^3) cell headers alone
+    (closest_point), which a dst that is a simplification of src never does.  The result is a pure function of (dst, src,
+    block, width, occlusion, max_distance): `cell` and `grid` only change the time.  Report: texels (= W H), baked,
+    unbaked, far, queries_invalid, faces_skipped, block, width, height, blocks_per_row, n_blocks, cell, dims, pairs,
+    distance_mean, distance_max (texel to src, over the baked texels).  F == 0 launches nothing.  One read-back."""
+    _check_max_distance(max_distance)
+    d, m = _mesh_tensors(dst, "bake_atlas"), _mesh_tensors(src, "bake_atlas")
+    dev = m.vertices.device
+    if d.vertices.device != dev:
+        raise RuntimeError("bake_atlas: the two meshes must live on one device")
+    V, F_src, F = int(m.vertices.shape[0]), int(m.faces.shape[0]), int(d.faces.shape[0])
+    if occlusion is None:
+        occlusion = torch.ones(V, dtype=torch.float32, device=dev)
+    elif (not isinstance(occlusion, torch.Tensor) or occlusion.device != dev or occlusion.dtype != torch.float32
+          or tuple(occlusion.shape) != (V,)):
+        raise ValueError("bake_atlas: occlusion must be a [%d] float32 tensor on the mesh's device" % V)
+    lay = atlas_layout(F, block, width)
+    W, H = lay.width, lay.height
+    report = dict(texels=W * H, baked=0, unbaked=W * H, far=0, queries_invalid=0, **lay._asdict())
+    with torch.cuda.device(dev):
+        uvs = face_uvs(F, lay, device=dev)
+        if F == 0:
+            z3 = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
+            report.update(_grid_report(None, F_src), distance_mean=0.0, distance_max=0.0)
+            return Atlas(lay, uvs, z3, z3.clone(), z3.clone(), torch.zeros((H, W), dtype=torch.uint8, device=dev)), report
+        values = torch.cat((m.albedo, occlusion[:, None], m.roughness[:, None], m.metallic[:, None], m.normals), 1).contiguous()
+        points, _, _, dest, flag = _atlas_points(d, lay)
+        if grid is None:
+            grid = triangle_grid(m, cell)
+        distance, face, flags = _closest(points, m, grid, max_distance)
+        out, coverage, _, counts = _transfer(points, face, m, values, dest, W * H)
+        near = face >= 0
+        dn = torch.where(near, distance, torch.zeros_like(distance)).double()
+        stats = torch.stack((dn.sum(), dn.max(), near.sum().double()))
+        got = torch.cat((flags.double(), counts.double(), flag.double(), stats)).cpu().tolist()  # the one read-back
+        if got[2] != 0 or got[5] != 0 or got[6] != 0:
+            raise MeshOverflow("bake_atlas: an index left its range (%d faces, %d texels)" % (F_src, int(points.shape[0])))
+    baked = int(got[3])
+    report.update(baked=baked, unbaked=W * H - baked, far=int(got[0]), queries_invalid=int(got[1]),
+                  distance_mean=got[7] / got[9] if got[9] else 0.0, distance_max=got[8])
+    report.update(_grid_report(grid, F_src))
+    planes = out.view(9, H, W)
+    return Atlas(lay, uvs, planes[0:3], planes[3:6], planes[6:9], coverage.view(H, W)), report
+
+
+def sample_atlas(atlas_planes: torch.Tensor, layout: AtlasLayout, face: torch.Tensor, bary: torch.Tensor) -> torch.Tensor:
+    """[N,C] float64: the planes [C,H,W] of an atlas looked up bilinearly at the UV of the points (face [N], bary [N,2] =
+    the weights of the face's second and third vertex): uv = w0 uv0 + w1 uv1 + w2 uv2 on face_uvs' float32 corners, texel
+    coordinates x = u W - 1/2, y = (1 - v) H - 1/2, the four taps clamped to the image.  Torch gathers in float64 on the
+    planes' device: host glue for tests and reports, not a kernel."""
+    dev = atlas_planes.device
+    Cn, H, W = (int(s) for s in atlas_planes.shape)
+    face = face.to(dev).long()
+    N = int(face.shape[0])
+    if N == 0 or H == 0:
+        return torch.zeros((N, Cn), dtype=torch.float64, device=dev)
+    uv = face_uvs(2 * layout.n_blocks, layout, device=dev).double()[face]  # [N,3,2]
+    b = bary.to(dev).double()
+    w1, w2 = b[:, 0], b[:, 1]
+    w0 = (1.0 - w1) - w2
+    u = (w0 * uv[:, 0, 0] + w1 * uv[:, 1, 0]) + w2 * uv[:, 2, 0]
+    v = (w0 * uv[:, 0, 1] + w1 * uv[:, 1, 1]) + w2 * uv[:, 2, 1]
+    x, y = u * W - 0.5, (1.0 - v) * H - 0.5
+    x0, y0 = x.floor(), y.floor()
+    fx, fy = x - x0, y - y0
+    xa, xb = x0.clamp(0, W - 1).long(), (x0 + 1).clamp(0, W - 1).long()
+    ya, yb = y0.clamp(0, H - 1).long(), (y0 + 1).clamp(0, H - 1).long()
+    flat = atlas_planes.reshape(Cn, H * W).double()
+    top = (1.0 - fx) * flat[:, ya * W + xa] + fx * flat[:, ya * W + xb]
+    bot = (1.0 - fx) * flat[:, yb * W + xa] + fx * flat[:, yb * W + xb]
+    return ((1.0 - fy) * top + fy * bot).T.contiguous()

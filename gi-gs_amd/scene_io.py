@@ -11,6 +11,8 @@
     save_mesh_ply / read_mesh_ply  a triangle mesh with per-vertex materials (mesh.Mesh; not a reference format): position,
                                    world normal, albedo as 8-bit colour, roughness, metallic, optionally the baked occlusion,
                                    triangle index lists
+    save_mesh_obj / read_mesh_obj  a textured triangle mesh as Wavefront OBJ + MTL: positions, normals, one UV per face
+                                   corner, and a material that names the albedo / roughness / metallic / normal / ORM images
 
 Pure host code (numpy / torch serialization): no kernels, works on CPU tensors.  `plyfile` is not needed; the reader
 parses the PLY header itself (ascii and binary little-endian vertex elements with scalar properties).  Checkpoints are
@@ -238,6 +240,126 @@ def read_mesh_ply(path: str) -> Dict[str, np.ndarray]:
     if len(layout) > len(_MESH_VERTEX):
         out["occlusion"] = vt["occlusion"].astype(np.float32)
     return out
+
+
+_OBJ_MAPS = (("albedo", "map_Kd"), ("roughness", "map_Pr"), ("metallic", "map_Pm"), ("normal", "norm"), ("orm", "map_ORM"))
+_OBJ_MATERIAL = "baked"
+
+
+def obj_texture_names(path: str) -> Dict[str, str]:
+    """The image files save_mesh_obj names by default, relative to the .obj: STEM_albedo.png, STEM_roughness.png,
+    STEM_metallic.png, STEM_normal.png and STEM_orm.png (occlusion, roughness, metallic packed into one image)."""
+    stem = os.path.splitext(os.path.basename(path))[0]
+    return {k: "%s_%s.png" % (stem, k) for k, _ in _OBJ_MAPS}
+
+
+def save_mesh_obj(path: str, vertices, faces, uvs, normals=None, textures=None) -> None:
+    """A textured triangle mesh as Wavefront OBJ with its material library beside it (PATH with the extension .mtl).  The
+    .obj holds `mtllib`, one `v` per vertex, one `vn` per vertex if `normals` is given, one `vt` per FACE CORNER (uvs
+    [F,3,2], mesh.face_uvs'; v = 0 is the bottom row of the image), `usemtl` and `f a/ta/na` (`a/ta` without normals):
+    OBJ indexes positions and UVs separately, so no vertex is split.  Floats are written with nine significant digits:
+    float32 values read back exactly.  The .mtl holds one material with map_Kd (albedo), map_Pr (roughness), map_Pm
+    (metallic), norm (the normal map) and map_ORM (the packed occlusion / roughness / metallic image, not a standard
+    statement: readers that do not know it skip it).  `textures`: {albedo, roughness, metallic, normal, orm} -> file name
+    relative to the .obj, default obj_texture_names(path).  The images themselves are the caller's to write."""
+    v = np.asarray(_np(vertices), dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(_np(faces)).reshape(-1, 3).astype(np.int64)
+    uv = np.asarray(_np(uvs), dtype=np.float32)
+    if uv.shape != (f.shape[0], 3, 2):
+        raise ValueError("save_mesh_obj: uvs must be [F,3,2], got %s for %d faces" % (uv.shape, f.shape[0]))
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("save_mesh_obj: a face refers to a vertex that does not exist")
+    n = None
+    if normals is not None:
+        n = np.asarray(_np(normals), dtype=np.float32).reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise ValueError("save_mesh_obj: normals must have one row per vertex")
+    names = dict(obj_texture_names(path))
+    if textures is not None:
+        if set(textures) - set(names):
+            raise ValueError("save_mesh_obj: unknown texture %s" % sorted(set(textures) - set(names)))
+        names.update(textures)
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    mtl = os.path.splitext(path)[0] + ".mtl"
+    rows = lambda tag, a: "".join("%s %s\n" % (tag, " ".join("%.9g" % x for x in r)) for r in a.tolist())  # noqa: E731
+    t = 3 * np.arange(f.shape[0], dtype=np.int64)[:, None] + np.arange(3)[None] + 1
+    a = f + 1
+    if n is not None:
+        corner = ["%d/%d/%d" % (x, y, x) for x, y in zip(a.reshape(-1).tolist(), t.reshape(-1).tolist())]
+    else:
+        corner = ["%d/%d" % (x, y) for x, y in zip(a.reshape(-1).tolist(), t.reshape(-1).tolist())]
+    with open(path, "w", encoding="ascii") as fh:
+        fh.write("mtllib %s\n" % os.path.basename(mtl))
+        fh.write(rows("v", v))
+        if n is not None:
+            fh.write(rows("vn", n))
+        fh.write(rows("vt", uv.reshape(-1, 2)))
+        fh.write("usemtl %s\n" % _OBJ_MATERIAL)
+        fh.write("".join("f %s %s %s\n" % tuple(corner[3 * i:3 * i + 3]) for i in range(f.shape[0])))
+    with open(mtl, "w", encoding="ascii") as fh:
+        fh.write("newmtl %s\nKd 1 1 1\nPr 1\nPm 1\n" % _OBJ_MATERIAL)
+        fh.write("".join("%s %s\n" % (key, names[k]) for k, key in _OBJ_MAPS))
+
+
+def read_mesh_obj(path: str) -> Dict:
+    """A file of save_mesh_obj -> {vertices [V,3], faces [F,3] int32, vt [3F,2], uv_faces [F,3] int32 (rows of vt), uvs
+    [F,3,2] = vt[uv_faces], normals [V,3] or None, mtllib, material, textures {albedo, roughness, metallic, normal, orm} ->
+    the file names the .mtl gives}.  Reads what the writer writes and nothing grander: anything else raises ValueError."""
+    v, vn, vt, fa, ft = [], [], [], [], []
+    mtllib = material = None
+    with_normals = None
+    with open(path, "r", encoding="ascii") as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok or tok[0].startswith("#"):
+                continue
+            if tok[0] == "v" and len(tok) == 4:
+                v.append([float(x) for x in tok[1:]])
+            elif tok[0] == "vn" and len(tok) == 4:
+                vn.append([float(x) for x in tok[1:]])
+            elif tok[0] == "vt" and len(tok) == 3:
+                vt.append([float(x) for x in tok[1:]])
+            elif tok[0] == "f" and len(tok) == 4:
+                parts = [c.split("/") for c in tok[1:]]
+                if with_normals is None:
+                    with_normals = len(parts[0]) == 3
+                if any(len(c) != (3 if with_normals else 2) for c in parts) or (with_normals and any(c[0] != c[2] for c in parts)):
+                    raise ValueError(f"{path}: not the face statement of save_mesh_obj: {line.strip()}")
+                fa.append([int(c[0]) - 1 for c in parts])
+                ft.append([int(c[1]) - 1 for c in parts])
+            elif tok[0] == "mtllib" and len(tok) == 2:
+                mtllib = tok[1]
+            elif tok[0] == "usemtl" and len(tok) == 2:
+                material = tok[1]
+            else:
+                raise ValueError(f"{path}: not a statement of save_mesh_obj: {line.strip()}")
+    V, F = len(v), len(fa)
+    faces = np.asarray(fa, np.int32).reshape(F, 3)
+    uv_faces = np.asarray(ft, np.int32).reshape(F, 3)
+    vt = np.asarray(vt, np.float32).reshape(-1, 2)
+    if mtllib is None or material is None or (vn and len(vn) != V) or (F and bool(vn) != bool(with_normals)):
+        raise ValueError(f"{path}: not the layout of save_mesh_obj")
+    if F and (faces.min() < 0 or faces.max() >= V or uv_faces.min() < 0 or uv_faces.max() >= len(vt)):
+        raise ValueError(f"{path}: a face refers to a vertex or a vt that does not exist")
+    keys = {key: k for k, key in _OBJ_MAPS}
+    textures, found = {}, None
+    with open(os.path.join(os.path.dirname(path), mtllib), "r", encoding="ascii") as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "newmtl":
+                found = tok[1]
+            elif tok[0] in keys and len(tok) == 2 and found == material:
+                textures[keys[tok[0]]] = tok[1]
+    if found != material or sorted(textures) != sorted(keys.values()):
+        raise ValueError(f"{path}: {mtllib} is not the material library of save_mesh_obj")
+    return dict(vertices=np.asarray(v, np.float32).reshape(V, 3), faces=faces, vt=vt, uv_faces=uv_faces,
+                uvs=vt[uv_faces] if F else np.zeros((0, 3, 2), np.float32),
+                normals=np.asarray(vn, np.float32).reshape(V, 3) if vn else None, mtllib=mtllib, material=material,
+                textures=textures)
 
 
 def capture(active_sh_degree: int, params: Dict[str, torch.Tensor], stats, optimizer, spatial_lr_scale: float) -> Tuple:

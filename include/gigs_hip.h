@@ -918,6 +918,60 @@ int gigs_mesh_bake_occlusion(int n_vertices, int n_faces, const float* vertices,
                              const long long* pair_keys, long long n_pairs, double scale, const long long* order,
                              const float* directions, int n_rays, int n_rotations, unsigned long long seed, double max_distance, double bias,
                              float* occlusion, int* hits, unsigned long long* counts, int* overflow, void* stream);
+/* Texturing meshes (gigs-hip extension; the device half of mesh.bake_atlas / mesh.transfer_attributes): the per-vertex
+ * channels of a heavy SOURCE mesh stored in the texels of an atlas over a light TARGET mesh.  Every texel of the atlas gets
+ * the point of the target's surface it stands for (gigs_mesh_atlas_points), the search of "Comparing meshes" finds the
+ * source face closest to that point (gigs_mesh_closest), and gigs_mesh_transfer finds WHERE on that face the closest point
+ * lies and interpolates the channels there.  All arrays are DEVICE memory; the calls neither synchronise nor allocate.  One
+ * independent thread per texel or query, no float atomics, no thread waits on another.  All arithmetic is float64 on the
+ * float32 inputs, + - * / only, every product and sum rounded on its own (dot and cross as under "Comparing meshes"): no
+ * sqrt, no transcendental, so tests/mesh_atlas_ref.py reproduces every bit in numpy.
+ *   1 Blocks.  B = block >= 3.  A block is (B + 1) x B texels (wide x high) and holds two faces: face f lies in block
+ *     f / 2, half f % 2.  Texel (i, j) of a block, 0 <= i <= B, 0 <= j <= B - 1, belongs to the LOWER half (0) if
+ *     i + j <= B - 1, else to the UPPER half (1); each half owns B (B + 1) / 2 texels.  The upper half is the point
+ *     reflection (i, j) -> (B - i, B - 1 - j) of the lower: an upper texel takes the lower half's formulas at its reflected
+ *     coordinates (li, lj); a lower texel has (li, lj) = (i, j).
+ *   2 Image.  per_row = W / (B + 1) blocks to a row (integer division, per_row >= 1), block b at column b % per_row and
+ *     row b / per_row: its texel (i, j) is the image texel x = (b % per_row)(B + 1) + i, y = (b / per_row) B + j, row y
+ *     counted from the TOP of the image, and dest = y W + x.  H = ceil(n_blocks / per_row) B, n_blocks = ceil(F / 2).
+ *     mesh.atlas_layout's default W is the smallest power of two >= B + 1 with (W / (B + 1)) (W / B) >= n_blocks.  The
+ *     columns right of the last whole block, the slots past F and the texels of an unusable face are UNBAKED: value 0,
+ *     coverage 0.
+ *   3 UV.  The centre of texel (x, y) is the point (x + 1/2, y + 1/2) in texel coordinates.  Corner k of a face sits at the
+ *     centre of a texel of its half: lower (0, 0), (B - 2, 0), (0, B - 2); upper (B, B - 1), (2, B - 1), (B, 1).  uv =
+ *     (float32(X / W), float32(1 - Y / H)) for the point (X, Y) in texel coordinates: v = 0 is the BOTTOM row of the image
+ *     (the OBJ convention), kept by scene_io.save_mesh_obj and mesh.sample_atlas.  For every point of a face's UV
+ *     triangle, edges and corners included, every bilinear tap of non-zero weight is a texel of that face's half.
+ *   4 Texel to point.  w1 = li / (B - 2), w2 = lj / (B - 2), w0 = (1 - w1) - w2; point = float32((w0 p0 + w1 p1) + w2 p2)
+ *     per component, bary = (float32(w1), float32(w2)).  The texels with li + lj = B - 1 lie outside the UV triangle: w0 =
+ *     -1 / (B - 2), and the point is the EXTRAPOLATED one of the face's plane.  That is the gutter; there is no dilation.
+ *     texel_face = f, or -1 for a slot past F.  For a slot past F, a face with an index outside [0, V) or a non-finite
+ *     corner: dest = -1 and point = NaN in every component (gigs_mesh_closest then answers face -1).  A face without area
+ *     is baked like any other.
+ *   5 Closest point on a given face (i0, i1, i2), corners p0, p1, p2.  The candidates, expressions and order of 5 of
+ *     "Comparing meshes": edge 01, edge 12, edge 20, each walked from the vertex with the lower INDEX with s = 0 for
+ *     t <= 0, s = 1 for t >= den, else s = t / den, and the same d^2; the weights are (1 - s, s) on the edge's ends in the
+ *     walking direction and 0 on the third vertex.  Then, if the three edge functions f0 over (p0, p1), f1 over (p1, p2),
+ *     f2 over (p2, p0) are >= 0, the interior with d^2 = dot(p - p0, n)^2 / dot(n, n) and the weights (w0, w1, w2) =
+ *     (f1 / S, f2 / S, f0 / S), S = (f0 + f1) + f2 (the raycast's W); it is taken only with S > 0.  A later candidate wins
+ *     only with a strictly smaller d^2.
+ *   6 Transfer.  values [V, C] float32, 1 <= C <= 16: out[c] = float32((w0 a0[c] + w1 a1[c]) + w2 a2[c]) with a_k the row
+ *     of vertex i_k; bary = (float32(w1), float32(w2)).  With `dest` [N] int64, out is C planes of `plane` floats, the
+ *     query stores at out[c plane + dest[q]] and sets coverage[dest[q]] = 1; without it, out is [N, C] and coverage is
+ *     not used.  A query with face -1 or dest -1, a non-finite query point or a non-finite corner stores nothing (the
+ *     caller zero-fills) and counts[1] += 1; every other query counts[0] += 1.
+ * gigs_mesh_atlas_points, one thread per texel of the n_blocks blocks, block-major: q = b B (B + 1) + j (B + 1) + i gets
+ *   points [Q,3], bary [Q,2], texel_face [Q], dest [Q] int64 as in 4.  3 <= block <= 1024, Q < 2^31.  A texel outside the
+ *   W x H image sets *overflow.  n_blocks == 0 launches nothing.
+ * gigs_mesh_transfer, one thread per query: out, coverage, bary [N,2] as in 5 and 6; counts [2] uint64 (cleared inside the
+ *   call; integer atomics) = transferred, skipped.  A face >= F or < -1, a dest outside [-1, plane) or a vertex index
+ *   outside [0, V) sets *overflow (device int, cleared by the caller) and the thread stores nothing. */
+int gigs_mesh_atlas_points(int n_vertices, int n_faces, const float* vertices, const int* faces, int block, int width, int height,
+                           int n_blocks, float* points, float* bary, int* texel_face, long long* dest, int* overflow,
+                           void* stream);
+int gigs_mesh_transfer(int n_vertices, int n_faces, const float* vertices, const int* faces, int n_channels, const float* values,
+                       int n_points, const float* points, const int* face, const long long* dest, long long plane, float* out,
+                       unsigned char* coverage, float* bary, unsigned long long* counts, int* overflow, void* stream);
 /* Rendering meshes (gigs-hip extension; the device half of mesh_render.py): a triangle mesh -- vertices [V,3], faces [F,3]
  * int32 and mesh.py's per-vertex attributes -- as the G-buffer planes the blend kernel writes in inference mode, by a
  * visibility buffer.  Coverage and visibility are integer decisions, so no result depends on the order of execution and a
