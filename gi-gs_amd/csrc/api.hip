@@ -116,8 +116,8 @@ gigs::Options options_from_env() {
   o.shade_bwd_blocks = std::max(0, env_int("GIGS_SHADE_BWD_BLOCKS", 0));
   o.shade_bwd_rows = env_int("GIGS_SHADE_BWD_ROWS", 0) != 0;
   o.spec_sparse = env_int("GIGS_SPEC_SPARSE", 1) != 0;
-  o.spec_sparse_permille = env_int("GIGS_SPEC_SPARSE_PERMILLE", 37);
-  if (o.spec_sparse_permille < 0 || o.spec_sparse_permille > 1000) o.spec_sparse_permille = 37;
+  o.spec_sparse_permille = env_int("GIGS_SPEC_SPARSE_PERMILLE", 100);
+  if (o.spec_sparse_permille < 0 || o.spec_sparse_permille > 1000) o.spec_sparse_permille = 100;
   return o;
 }
 const gigs::Ctx& ctx_of(const gigs_ctx* c) { return c ? *reinterpret_cast<const gigs::Ctx*>(c) : gigs::default_ctx(); }

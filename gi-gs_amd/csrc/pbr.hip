@@ -630,16 +630,17 @@ static void launch_specular_apply(const Options& o, int res, int avg_window, con
 // The shade backward zero-fills the level gradients and adds into the sampled texels only, so a fine level receives a
 // few thousand nonzero texels (or none: every pixel rougher than the level's range).  The gather above still streams
 // the level's whole table.  Instead: a census lists the nonzero texels of every level, and a level whose list fits its
-// capacity is SCATTERED from them with their runs of the forward table -- W_fwd[o][i] is the same float as
-// W_swapped[i][o] (specular_weights_kernel evaluates one expression for both), so (w / wsum[o]) * g[o] is the very
-// product the gather forms from its pre-divided table; only the order of the additions differs.
-// state: [0..7] working counters, [8..15] path taken (1 scatter, 0 gather), [16..23] nonzero texels counted.
+// capacity is summed from them with their runs of the forward table (the tile gather below) -- W_fwd[o][i] is the same
+// float as W_swapped[i][o] (specular_weights_kernel evaluates one expression for both), so (w / wsum[o]) * g[o] is the
+// very product the gather forms from its pre-divided table; only the order of the additions differs.
+// state: [0..7] working counters, [8..15] path taken (1 sparse, 0 gather), [16..23] nonzero texels counted.
 // ------------------------------------------------------------------------------------------
 struct SparseLevel {
-  int total, cap, block_begin, group_begin, N;
-  int vec;  // src and dst are 16-byte aligned: the census may use 16-byte accesses
-  int chunks;  // waves that share one listed texel's window in the scatter
-  int lds;     // a level with wide windows: scattered through LDS images of face tiles
+  int total, cap, block_begin, unit_begin, N;
+  int vec;    // src and dst are 16-byte aligned: the census may use 16-byte accesses
+  int narrow; // scattered, one wave per slot, instead of the tile gather
+  int nt;     // tiles along a face edge
+  int parts;  // slices of the list, i.e. workgroups per tile
   const float* src;
   float* dst;
   const float* bounds;
@@ -713,91 +714,153 @@ __global__ void __launch_bounds__(256) specular_census_kernel(SparseLevels L, in
   }
 }
 
-// `chunks` waves per slot of every level's list.  The waves of a listed texel o share its window 64 candidates at a
-// time.  A lane forms the quotient w / wsum[o] and the texel of ONE candidate; the adds are then issued by DWORD of dst
-// -- three instructions per 64 candidates, lane L of instruction j adding channel (64 j + L) % 3 of candidate
-// (64 j + L) / 3, fetched from that candidate's lane -- so that one atomic instruction covers 64 consecutive floats of
-// dst wherever the window's row goes on (256 contiguous bytes, the shape the memory-side adders take at full rate).
-// A wave is latency-bound (weight load, then its atomics), so a texel's window is shared by as many waves as leave each
-// about two trips, and a trip requests kScatterU weights before it consumes one.  The run of the table and the face
-// rectangles are read exactly as specular_apply_body reads them: rectangles in face order, row-major inside one.
-constexpr int kScatterU = 2;
-constexpr int kLdsTile = 32;  // a level with wide windows is accumulated in LDS images of 32 x 32 texels (12 KB)
-constexpr int kLdsParts = 8;  // workgroups that share one such tile
-constexpr int kLdsWide = 16;  // wide: the mean window holds at least 1 / 16 of the level's texels
+// Sparse levels are summed ON CHIP by the owners of the destination texels.  A workgroup owns one kSpTile x kSpTile tile
+// of one face and one slice of kSpSlice slots of the level's list: a tile next to a highlight sees thousands of listed
+// texels, so a tile's sources are split over `parts` workgroups, one slice each.
+//   * test: a thread takes a slot o of the slice and o's OWN rectangle on the tile's face (the pinned meaning of a sparse
+//     level is the forward table's runs; the bounds are not symmetric everywhere); the slots whose rectangle meets the
+//     tile are packed into LDS records in slot order (ballots and a prefix over the waves: no LDS atomics);
+//   * sum: a wave owns an 8 x 8 quadrant, a lane one texel.  The wave lists the records that meet its quadrant (in record
+//     order) and walks that list: a record is wave-uniform, so the lanes inside its rectangle read 8 contiguous pieces
+//     of o's run; kSpU records are in flight per lane, each with an accumulator of its own, and the accumulators are
+//     folded in a fixed tree.  The product is the gather's: (w / wsum[o]) * g[o], markers (w < 0, and a NaN weight)
+//     skipped, a NaN quotient kept;
+//   * the tile is written once: stored where the level has one slice, else added to dst (zeroed by the census) with one
+//     atomic per texel, channel and slice -- never one per pair.
+// No workgroup waits for another.  A workgroup whose slice lies past the count returns at entry.
+constexpr int kSpTile = 16;
+constexpr int kSpSlice = 256;  // one slot per thread
+constexpr int kSpU = 8;
 
-__global__ void __launch_bounds__(256) specular_scatter_kernel(SparseLevels L, int* __restrict__ state) {
-  const int lane = threadIdx.x & 63;
-  const int group = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
-  if (blockIdx.x == 0 && threadIdx.x < 8 && (int)threadIdx.x < L.n) {
-    // the report the caller may read, and the flags the gather's workgroups test (nobody reads them in this kernel)
-    const int c = state[threadIdx.x];
-    state[8 + threadIdx.x] = c <= L.lv[threadIdx.x].cap ? 1 : 0;
-    state[16 + threadIdx.x] = c;
-  }
-  int k = 0;
-#pragma unroll
-  for (int i = 1; i < 8; i++)
-    if (i < L.n && group >= L.lv[i].group_begin) k = i;
-  const SparseLevel& v = L.lv[k];
-  const int count = state[k];
-  if (count > v.cap) return;  // a gathered level
-  if (v.lds) {
-    // A level with wide windows: a texel of dst receives a term from a large share of the listed texels.  Added one by
-    // one with global atomics, each term would be rounded at the size of the running sum; here a workgroup sums its share
-    // of the list into an LDS image of ONE kLdsTile^2 tile of a face first and adds that image to dst once -- 8 partial
-    // sums per texel, like the partial sums of the gather's lanes, and 1 / 8 of the list per image.
-    __shared__ float img[kLdsTile * kLdsTile * 3];
-    const int N = v.N, nt = (N + kLdsTile - 1) / kLdsTile, bl = (group - v.group_begin) >> 2;
-    const int face = bl % 6, tile = (bl / 6) % (nt * nt), part = bl / (6 * nt * nt);
-    const int tx0 = (tile % nt) * kLdsTile, ty0 = (tile / nt) * kLdsTile;
-    const int tx1 = min(tx0 + kLdsTile, N) - 1, ty1 = min(ty0 + kLdsTile, N) - 1;
-    const int wave = (int)threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < kLdsTile * kLdsTile * 3; i += 256) img[i] = 0.0f;
-    __syncthreads();
-    const int listed = min(count, v.cap);
-    for (int slot = part + kLdsParts * wave; slot < listed; slot += kLdsParts * 4) {
-      const int o = __builtin_amdgcn_readfirstlane(v.list[slot]);
-      const float4* b4 = reinterpret_cast<const float4*>(v.bounds + 24 * (size_t)o);
-      int before = 0, xmin = 0, xmax = -1, ymin = 0, ymax = -1;
-#pragma unroll
-      for (int s = 0; s < 6; ++s) {
-        const float4 b = b4[s];
-        const int x0 = (int)b.x, x1 = (int)b.y, y0 = (int)b.z, y1 = (int)b.w;
-        const int cnt = (x0 > x1 || y0 > y1) ? 0 : (x1 - x0 + 1) * (y1 - y0 + 1);
-        if (s < face) before += cnt;
-        if (s == face && cnt) { xmin = x0; xmax = x1; ymin = y0; ymax = y1; }
-      }
-      // the part of o's rectangle on this face that lies in the tile
-      const int ix0 = max(xmin, tx0), ix1 = min(xmax, tx1), iy0 = max(ymin, ty0), iy1 = min(ymax, ty1);
-      if (ix0 > ix1 || iy0 > iy1) continue;  // wave-uniform
-      const int wd = xmax - xmin + 1, iw = ix1 - ix0 + 1, ni = iw * (iy1 - iy0 + 1);
-      const float* W = v.Wfwd + v.offsets[6 * (size_t)o] + before;
-      const float ws = v.wsum[o], inv = 1.0f / (float)iw;
+__device__ __forceinline__ void specular_tile_gather_body(const SparseLevel& v, int unit, int count) {
+  const int N = v.N, nt = v.nt, tiles = 6 * nt * nt;
+  const int part = unit / tiles, tile = unit - part * tiles;
+  const int slot = part * kSpSlice + (int)threadIdx.x, end = min(count, v.cap);
+  if (part * kSpSlice >= end) return;  // uniform over the workgroup
+  const int face = tile / (nt * nt), tt = tile - face * nt * nt;
+  const int tx0 = (tt % nt) * kSpTile, ty0 = (tt / nt) * kSpTile;
+  const int tx1 = min(tx0 + kSpTile, N) - 1, ty1 = min(ty0 + kSpTile, N) - 1;
+  const int lane = threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+
+  __shared__ uint32_t r_base[kSpSlice];  // index into Wfwd of the rectangle's (virtual) texel (0, 0), modulo 2^32
+  __shared__ int r_wd[kSpSlice], r_x[kSpSlice], r_y[kSpSlice];  // row length; xmin | xmax << 16; ymin | ymax << 16
+  __shared__ float r_ws[kSpSlice], r_g0[kSpSlice], r_g1[kSpSlice], r_g2[kSpSlice];
+  __shared__ unsigned short q_rec[4][kSpSlice];  // per wave: the records that meet its quadrant
+  __shared__ int wave_cnt[4];
+
+  bool hit = false;
+  int wd = 0, px = 0, py = 0;
+  uint32_t t_base = 0;
+  float t_ws = 0.0f, t_g0 = 0.0f, t_g1 = 0.0f, t_g2 = 0.0f;
+  if (slot < end) {
+    const int o = v.list[slot];
+    const float4 b = reinterpret_cast<const float4*>(v.bounds + 24 * (size_t)o)[face];
+    const int xmin = (int)b.x, xmax = (int)b.y, ymin = (int)b.z, ymax = (int)b.w;
+    hit = xmin <= xmax && ymin <= ymax && xmin <= tx1 && xmax >= tx0 && ymin <= ty1 && ymax >= ty0;
+    if (hit) {
+      wd = xmax - xmin + 1; px = xmin | (xmax << 16); py = ymin | (ymax << 16);
+      t_base = v.offsets[6 * (size_t)o + face] - (uint32_t)(ymin * wd + xmin);
+      t_ws = v.wsum[o];
       const float* g = v.src + 3 * (size_t)o;
-      const float g0 = g[0], g1 = g[1], g2 = g[2];
-      for (int i = lane; i < ni; i += 64) {
-        const int ry = (int)(((float)i + 0.5f) * inv), y = iy0 + ry, x = ix0 + (i - ry * iw);
-        const float w = W[(y - ymin) * wd + (x - xmin)];  // row-major over the face's rectangle
-        if (!(w >= 0.0f)) continue;  // -1 marks a candidate outside the cone
-        float* t = img + 3 * ((y - ty0) * kLdsTile + (x - tx0));
-        const float q = w / ws;
-        const float v0 = q * g0, v1 = q * g1, v2 = q * g2;
-        if (v0 != 0.0f) atomicAdd(t, v0);
-        if (v1 != 0.0f) atomicAdd(t + 1, v1);
-        if (v2 != 0.0f) atomicAdd(t + 2, v2);
+      t_g0 = g[0]; t_g1 = g[1]; t_g2 = g[2];
+    }
+  }
+  const unsigned long long hits = __ballot(hit);
+  if (lane == 0) wave_cnt[wave] = __popcll(hits);
+  __syncthreads();
+  int n_rec = 0, first = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    if (j == wave) first = n_rec;
+    n_rec += wave_cnt[j];
+  }
+  if (n_rec == 0) return;  // uniform over the workgroup
+  if (hit) {
+    const int j = first + __popcll(hits & ((1ull << lane) - 1ull));
+    r_base[j] = t_base; r_wd[j] = wd; r_x[j] = px; r_y[j] = py;
+    r_ws[j] = t_ws; r_g0[j] = t_g0; r_g1[j] = t_g1; r_g2[j] = t_g2;
+  }
+  __syncthreads();
+
+  const int qx0 = tx0 + (wave & 1) * 8, qy0 = ty0 + (wave >> 1) * 8;
+  if (qx0 >= N || qy0 >= N) return;  // uniform over the wave; no barrier follows
+  // the records that meet this wave's quadrant, in record order
+  unsigned short* mine = q_rec[wave];
+  int n_q = 0;
+  for (int j0 = 0; j0 < n_rec; j0 += 64) {
+    const int j = j0 + lane;
+    bool t = false;
+    if (j < n_rec) {
+      const int xr = r_x[j], yr = r_y[j];
+      t = (xr & 0xffff) <= qx0 + 7 && (xr >> 16) >= qx0 && (yr & 0xffff) <= qy0 + 7 && (yr >> 16) >= qy0;
+    }
+    const unsigned long long m = __ballot(t);
+    if (t) mine[n_q + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)j;
+    n_q += __popcll(m);
+  }
+  if (n_q == 0) return;
+  // written and read by lanes of the same wave only: LDS operations of a wave complete in order
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  const int x = qx0 + (lane & 7), y = qy0 + (lane >> 3);
+  const bool inside = x < N && y < N;
+  float a0[kSpU], a1[kSpU], a2[kSpU];
+#pragma unroll
+  for (int u = 0; u < kSpU; u++) { a0[u] = 0.0f; a1[u] = 0.0f; a2[u] = 0.0f; }
+  for (int i0 = 0; i0 < n_q; i0 += kSpU) {
+    float w[kSpU];
+    int rec[kSpU];
+#pragma unroll
+    for (int u = 0; u < kSpU; u++) {
+      const int j = mine[min(i0 + u, n_q - 1)];
+      rec[u] = j;
+      const int xr = r_x[j], yr = r_y[j];
+      const bool in = inside && i0 + u < n_q && x >= (xr & 0xffff) && x <= (xr >> 16) && y >= (yr & 0xffff) && y <= (yr >> 16);
+      // every lane loads (a lane outside the rectangle reads its first weight, one line for all of them): kSpU
+      // independent loads in flight, no branch between them
+      const int rw = r_wd[j];
+      const uint32_t at = in ? (uint32_t)(y * rw + x) : (uint32_t)((yr & 0xffff) * rw + (xr & 0xffff));
+      const float wl = v.Wfwd[(size_t)(uint32_t)(r_base[j] + at)];
+      w[u] = in ? wl : -1.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < kSpU; u++) {
+      const int j = rec[u];
+      if (w[u] >= 0.0f) {  // -1 marks a candidate outside the cone; a NaN quotient (0 / 0) reaches dst like the gather's
+        const float q = w[u] / r_ws[j];
+        a0[u] += q * r_g0[j]; a1[u] += q * r_g1[j]; a2[u] += q * r_g2[j];
       }
     }
-    __syncthreads();
-    const int row3 = 3 * (tx1 - tx0 + 1), cells = row3 * (ty1 - ty0 + 1);
-    for (int i = threadIdx.x; i < cells; i += 256) {
-      const int yy = i / row3, xc = i - yy * row3;
-      const float val = img[3 * yy * kLdsTile + xc];
-      if (val != 0.0f) atomicAdd(v.dst + 3 * ((size_t)(face * N + ty0 + yy) * N + tx0) + xc, val);
-    }
-    return;
   }
-  const int slot = (group - v.group_begin) / v.chunks, chunk = (group - v.group_begin) % v.chunks;
+#pragma unroll
+  for (int h = kSpU / 2; h > 0; h >>= 1)
+#pragma unroll
+    for (int u = 0; u < h; u++) { a0[u] += a0[u + h]; a1[u] += a1[u + h]; a2[u] += a2[u + h]; }
+  if (!inside) return;
+  float* d = v.dst + 3 * ((size_t)(face * N + y) * N + x);
+  const float val[3] = {a0[0], a1[0], a2[0]};
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (!(val[c] != 0.0f)) continue;  // dst holds the census' zeros
+    if (v.parts == 1) d[c] = val[c];
+    else atomicAdd(d + c, val[c]);
+  }
+}
+
+// A level whose windows are no wider than a tile (the 256^2 level: 81 candidates a window) is SCATTERED instead, one
+// wave per slot of its list: there the tile gather's test -- tiles x listed texels -- outweighs the sums, and the
+// scatter's adds are few (measured, tools/spec_sparse_sweep.py).  A lane forms the quotient w / wsum[o] and the texel of
+// ONE candidate; the adds are then issued by DWORD of dst -- three instructions per 64 candidates, lane L of instruction
+// j adding channel (64 j + L) % 3 of candidate (64 j + L) / 3, fetched from that candidate's lane -- so that one atomic
+// instruction covers 64 consecutive floats of dst wherever the window's row goes on (256 contiguous bytes, the shape the
+// memory-side adders take at full rate).  The run of the table and the face rectangles are read exactly as
+// specular_apply_body reads them: rectangles in face order, row-major inside one.
+constexpr int kScatterU = 2;  // weights requested before one is consumed
+
+__device__ __forceinline__ void specular_scatter_body(const SparseLevel& v, int slot, int count) {
+  const int lane = threadIdx.x & 63;
   if (slot >= count || slot >= v.cap) return;  // past the end of the list
   const int o = __builtin_amdgcn_readfirstlane(v.list[slot]);
   const int N = v.N;
@@ -820,7 +883,6 @@ __global__ void __launch_bounds__(256) specular_scatter_kernel(SparseLevels L, i
   const float ws = v.wsum[o];
   const float* g = v.src + 3 * (size_t)o;
   const float g0 = g[0], g1 = g[1], g2 = g[2];
-  const int step = 64 * v.chunks;
   // lane L of add instruction j: candidate lane (64 j + L) / 3 and channel (64 j + L) % 3
   int from[3];
   float gch[3];
@@ -831,17 +893,17 @@ __global__ void __launch_bounds__(256) specular_scatter_kernel(SparseLevels L, i
     gch[j] = ch == 0 ? g0 : ch == 1 ? g1 : g2;
   }
   const int ch0 = lane % 3;  // channels of the three instructions: ch0, (ch0 + 1) % 3, (ch0 + 2) % 3 (64 % 3 = 1)
-  for (int c0 = 64 * chunk; c0 < n; c0 += step * kScatterU) {
+  for (int c0 = 0; c0 < n; c0 += 64 * kScatterU) {
     float w[kScatterU];
 #pragma unroll
     for (int u = 0; u < kScatterU; u++) {
-      const int c = c0 + u * step + lane;
+      const int c = c0 + u * 64 + lane;
       w[u] = c < n ? W[c] : -1.0f;  // -1 marks a candidate outside the cone
     }
 #pragma unroll
     for (int u = 0; u < kScatterU; u++) {
-      if (c0 + u * step >= n) break;  // wave-uniform
-      const int c = c0 + u * step + lane;
+      if (c0 + u * 64 >= n) break;  // wave-uniform
+      const int c = c0 + u * 64 + lane;
       float q = -1.0f;
       int texel = 0;
       if (w[u] >= 0.0f) {
@@ -871,20 +933,49 @@ __global__ void __launch_bounds__(256) specular_scatter_kernel(SparseLevels L, i
   }
 }
 
-// specular_apply_multi_kernel<true> whose workgroups of a scattered level return at entry; it runs last of the three
-// and clears the working counters for the next call (no kernel reads them after the scatter).
-__global__ void __launch_bounds__(256) specular_apply_multi_bwd_sparse_kernel(SpecLevels L, int* __restrict__ state) {
+// One launch behind the census for every level of the chain: the tile workgroups of the sparse levels first (tile gather or scatter; they wait
+// for memory round trips, the gather for bandwidth: started together they overlap), then specular_apply_multi_kernel<true>'s
+// workgroups.  Each workgroup reads its level's count and returns at entry where the level took the other path.
+__global__ void __launch_bounds__(256)
+specular_apply_multi_bwd_sparse_kernel(SpecLevels L, SparseLevels S, int tile_units, const int* __restrict__ state) {
+  if ((int)blockIdx.x < tile_units) {
+    int k = 0;
+#pragma unroll
+    for (int i = 1; i < 8; i++)
+      if (i < S.n && (int)blockIdx.x >= S.lv[i].unit_begin) k = i;
+    const SparseLevel& v = S.lv[k];
+    const int count = state[k];
+    if (count > v.cap) return;  // a gathered level
+    const int unit = (int)blockIdx.x - v.unit_begin;
+    if (v.narrow) specular_scatter_body(v, unit * 4 + ((int)threadIdx.x >> 6), count);
+    else specular_tile_gather_body(v, unit, count);
+    return;
+  }
+  const int gblock = (int)blockIdx.x - tile_units;
   int k = 0;
 #pragma unroll
   for (int i = 1; i < 8; i++)
-    if (i < L.n && (int)blockIdx.x >= L.lv[i].block_begin) k = i;
-  if (blockIdx.x == 0 && threadIdx.x < 8) state[threadIdx.x] = 0;
-  if (state[8 + k] != 0) return;
+    if (i < L.n && gblock >= L.lv[i].block_begin) k = i;
+  if (state[k] <= S.lv[k].cap) return;  // a sparse level
   const SpecLevel& v = L.lv[k];
-  const int block = (int)blockIdx.x - v.block_begin;
+  const int block = gblock - v.block_begin;
   if (v.lanes == 8) specular_apply_body<true, true, 8>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out);
   else if (v.lanes == 16) specular_apply_body<true, true, 16>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out);
   else specular_apply_body<true, true, 64>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out);
+}
+
+// Runs last: the report the caller may read, and the working counters cleared for the next call (every workgroup of the
+// launch before it has read its level's count by then).
+struct SparseCaps { int n; int cap[8]; };
+__global__ void __launch_bounds__(64) specular_sparse_finish_kernel(SparseCaps c, int* __restrict__ state) {
+  const int t = threadIdx.x;
+  if (t >= 8) return;
+  const int count = state[t];
+  if (t < c.n) {
+    state[8 + t] = count <= c.cap[t] ? 1 : 0;
+    state[16 + t] = count;
+  }
+  state[t] = 0;
 }
 
 static int spec_sparse_capacity(const Options& o, int res) {
@@ -1997,7 +2088,9 @@ int gigs_specular_cubemap_multi_bwd_sparse(gigs_ctx* ctx, int n_levels, const gi
   gigs::SpecLevels L;
   gigs::SparseLevels S;
   L.n = S.n = n_levels;
-  int blocks = 0, census_blocks = 0, groups = 0;
+  int blocks = 0, census_blocks = 0, units = 0;
+  gigs::SparseCaps caps = {};
+  caps.n = n_levels;
   size_t list_begin = 0;
   for (int i = 0; i < n_levels; i++) {
     const gigs_spec_level& a = levels[i];
@@ -2005,24 +2098,25 @@ int gigs_specular_cubemap_multi_bwd_sparse(gigs_ctx* ctx, int n_levels, const gi
       return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_multi_bwd_sparse: bad level");
     const int total = fill_spec_level(o, a, L.lv[i], blocks);
     gigs::SparseLevel& q = S.lv[i];
-    q.total = total; q.cap = gigs::spec_sparse_capacity(o, a.res); q.block_begin = census_blocks; q.group_begin = groups; q.N = a.res;
+    q.total = total; q.cap = gigs::spec_sparse_capacity(o, a.res); q.block_begin = census_blocks; q.unit_begin = units; q.N = a.res;
     q.vec = ((((uintptr_t)a.src) | ((uintptr_t)a.dst)) & 15) == 0;
     q.src = a.src; q.dst = a.dst; q.bounds = a.bounds; q.offsets = a.offsets; q.Wfwd = weights_fwd[i]; q.wsum = wsum[i];
     q.list = lists + list_begin;
     const int per_block = 256 * gigs::kCensusPerThread;
     census_blocks += (total + per_block - 1) / per_block;
-    // 64 candidates per wave and step: about two trips of kScatterU steps per wave at the level's mean window
-    q.chunks = std::min(32, std::max(1, (std::max(1, a.avg_window) + 64 * 2 * gigs::kScatterU - 1) / (64 * 2 * gigs::kScatterU)));
-    q.lds = (long long)a.avg_window * gigs::kLdsWide >= total;
-    const int nt = (a.res + gigs::kLdsTile - 1) / gigs::kLdsTile;
-    groups += q.lds ? 4 * 6 * nt * nt * gigs::kLdsParts : (q.cap * q.chunks + 3) / 4 * 4;  // whole workgroups per level
+    // windows no wider than a tile are scattered (see specular_scatter_body)
+    q.narrow = a.avg_window <= gigs::kSpTile * gigs::kSpTile;
+    q.nt = (a.res + gigs::kSpTile - 1) / gigs::kSpTile;
+    q.parts = (q.cap + gigs::kSpSlice - 1) / gigs::kSpSlice;
+    units += q.narrow ? (q.cap + 3) / 4 : 6 * q.nt * q.nt * q.parts;
+    caps.cap[i] = q.cap;
     list_begin += (size_t)q.cap;
   }
   hipStream_t s = (hipStream_t)stream;
   gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
   hipLaunchKernelGGL(gigs::specular_census_kernel, dim3(census_blocks), dim3(256), 0, s, S, state);
-  hipLaunchKernelGGL(gigs::specular_scatter_kernel, dim3(std::max(1, (groups + 3) / 4)), dim3(256), 0, s, S, state);
-  hipLaunchKernelGGL(gigs::specular_apply_multi_bwd_sparse_kernel, dim3(blocks), dim3(256), 0, s, L, state);
+  hipLaunchKernelGGL(gigs::specular_apply_multi_bwd_sparse_kernel, dim3(units + blocks), dim3(256), 0, s, L, S, units, state);
+  hipLaunchKernelGGL(gigs::specular_sparse_finish_kernel, dim3(1), dim3(64), 0, s, caps, state);
   return gigs_internal_check_launch("specular_cubemap_multi_bwd_sparse");
 }
 

@@ -217,7 +217,8 @@ class _specular_levels(torch.autograd.Function):
         with torch.cuda.device(dev):
             if bwd_head_start_ns > 0:  # see gigs_stream_delay: set by pipeline.WholeStepGraph while it captures the backward
                 gigs_lib.check(_lib.gigs_stream_delay(int(bwd_head_start_ns), _stream()), "stream_delay")
-            # nonzero-texel census, scatter of the sparse levels, gather of the others (gigs_options.spec_sparse = 0: the gather)
+            # nonzero-texel census, then one launch: tile gather or scatter of the sparse levels, gather of the others
+            # (gigs_options.spec_sparse = 0: the gather alone)
             state, lists = _sparse_buffers(tuple(ctx.shapes), dev)
             gigs_lib.check(_lib.gigs_specular_cubemap_multi_bwd_sparse(gigs_lib.ctx_ptr(), n, C.cast(arr, C.c_void_p), w_fwd, w_sum,
                                                                        None if state is None else state.data_ptr(),

@@ -85,7 +85,7 @@ typedef struct gigs_options {
                            (every per-pixel output the same bits).                         env GIGS_SHADE_BWD_ROWS */
   int spec_sparse;      /* 1 (default): gigs_specular_cubemap_multi_bwd_sparse scatters the levels whose incoming gradient
                            has few nonzero texels; 0 = it launches what gigs_specular_cubemap_multi_w launches. env GIGS_SPEC_SPARSE */
-  int spec_sparse_permille; /* capacity of a level's list of nonzero texels in thousandths of its texels, 0..1000 (37): a
+  int spec_sparse_permille; /* capacity of a level's list of nonzero texels in thousandths of its texels, 0..1000 (100): a
                            level with more nonzero texels is gathered.                     env GIGS_SPEC_SPARSE_PERMILLE */
 } gigs_options;
 /* A new context holds a copy of the default options.  Destroying a context frees host memory only; work queued
@@ -309,13 +309,15 @@ int gigs_specular_cubemap_multi_w(gigs_ctx* ctx, int n_levels, const gigs_spec_l
  * taken on the device (fixed grids, no read-back: capturable in a graph and replayable with other gradients):
  *   census   one pass over every level's src: zero-fills dst, counts the texels with a channel != 0 (NaN counts, -0 does
  *            not) and lists their indices, up to the level's capacity = gigs_spec_sparse_capacity(ctx, res);
- *   scatter  a level whose count is within its capacity is SPARSE: every listed texel o adds (w / wsum[o]) * src[o] into the
- *            dst texels of its window with float atomics, w >= 0 from o's run of the FORWARD table weights_fwd[level]
- *            (the products of the gather's pre-divided table, in arrival order);
- *   gather   the kernel of gigs_specular_cubemap_multi_w, whose workgroups of a sparse level return at entry; the other
- *            levels get the same bits as from gigs_specular_cubemap_multi_w.
+ *   apply    one launch for every level.  A level whose count is within its capacity is SPARSE: the products
+ *            (w / wsum[o]) * src[o], w >= 0 from the listed texel o's run of the FORWARD table weights_fwd[level] (the
+ *            products of the gather's pre-divided table), are summed on chip by the workgroups that own 16 x 16 tiles
+ *            of dst, or, for a level whose mean window holds at most 256 candidates, added into dst with float atomics
+ *            by one wave per listed texel.  The other levels are gathered by the workgroups of
+ *            gigs_specular_cubemap_multi_w and get the same bits as from that call;
+ *   finish   one wave: writes the report below and clears the working counters.
  * wsum[level] = the forward's weight sums [6,res,res].  state: GIGS_SPEC_SPARSE_STATE_INTS device ints, zero before the
- * first call and owned by one stream at a time; after a call state[8 + l] = 1 if level l was scattered, 0 if gathered, and
+ * first call and owned by one stream at a time; after a call state[8 + l] = 1 if level l took a sparse path, 0 if gathered, and
  * state[16 + l] = its count of nonzero texels (state[0..7] are the working counters: the last kernel clears them for the
  * next call).  lists: device ints, the levels' capacities in level order.  With gigs_options.spec_sparse = 0 the call is
  * gigs_specular_cubemap_multi_w(backward = 1) and touches neither state nor lists. */
