@@ -9,6 +9,8 @@
 //   raster_large_kernel  a fixed grid of waves strides over that list (the count is read on the device): one wave per
 //                        triangle, lanes over the box
 //   resolve_kernel       one thread per pixel: the winner's attributes, perspective-correct, or the blend kernel's background
+//   resolve_textured_kernel  the same pixel, the same key: materials (and the normal) looked up bilinearly in the planes of a
+//                        texture atlas at the perspective-correct UV of the face's corners, 36 independent gathers
 // Both raster kernels and the resolve go through tri_setup / tri_sample, so the depth in a key and the depth plane have the
 // same bits, and both paths and any small_max give the same visibility buffer.  No clipping: a triangle with a vertex
 // behind the near cull (or outside the guard band) is dropped whole.
@@ -60,6 +62,7 @@ struct Tri {
   int X[3], Y[3];
   float iz[3];
   float fA;
+  bool flip;  // vertices 1 and 2 swapped roles: what is stored per face CORNER (the UVs) swaps with them
 };
 
 // False for a triangle that is dropped: an index outside [0, V), a flagged vertex, zero area.  Nothing is read through a
@@ -73,7 +76,8 @@ __device__ __forceinline__ bool tri_setup(const MeshK& m, unsigned t, Tri& T) {
   int X2 = m.screen[2 * (size_t)i2], Y2 = m.screen[2 * (size_t)i2 + 1];
   long long A = (long long)(X1 - X0) * (long long)(Y2 - Y0) - (long long)(Y1 - Y0) * (long long)(X2 - X0);
   if (A == 0) return false;
-  if (A < 0) {  // vertices 1 and 2 swap roles
+  const bool flip = A < 0;
+  if (flip) {  // vertices 1 and 2 swap roles
     int tmp = i1; i1 = i2; i2 = tmp;
     tmp = X1; X1 = X2; X2 = tmp;
     tmp = Y1; Y1 = Y2; Y2 = tmp;
@@ -86,6 +90,7 @@ __device__ __forceinline__ bool tri_setup(const MeshK& m, unsigned t, Tri& T) {
   T.iz[1] = 1.0f / m.view_pos[3 * (size_t)i1 + 2];
   T.iz[2] = 1.0f / m.view_pos[3 * (size_t)i2 + 2];
   T.fA = (float)A;
+  T.flip = flip;
   return true;
 }
 
@@ -235,6 +240,112 @@ __global__ __launch_bounds__(256) void resolve_kernel(MeshK m, AttrK a, const un
   o.tri_id[pix] = id;
 }
 
+struct TexK {
+  const float* uvs;                     // [F,3,2]: one UV per face corner
+  const float *albedo, *orm, *normal;   // [3,Ht,Wt] planes; normal may be NULL (the vertex normals are interpolated)
+  int Wt, Ht;
+};
+
+// One texel coordinate: the two taps (clamped to [0, n - 1]) and the weight of the second.  c is brought into [-1, n]
+// first (fmaxf returns its non-NaN argument: a NaN becomes -1), so the conversion to int is always in range.
+__device__ __forceinline__ void tex_axis(float c, int n, int& a, int& b, float& f) {
+  c = fminf(fmaxf(c, -1.0f), (float)n);
+  const float c0 = floorf(c);
+  f = c - c0;
+  const int i = (int)c0;
+  a = min(max(i, 0), n - 1);
+  b = min(max(i + 1, 0), n - 1);
+}
+
+__device__ __forceinline__ float bilerp(float t00, float t01, float t10, float t11, float fx, float gx, float fy, float gy) {
+  return gy * (gx * t00 + fx * t01) + fy * (gx * t10 + fx * t11);
+}
+
+__global__ __launch_bounds__(256) void resolve_textured_kernel(MeshK m, AttrK a, TexK x,
+                                                               const unsigned long long* __restrict__ vis, PlanesK o,
+                                                               float* __restrict__ occlusion) {
+  const size_t HW = (size_t)m.H * m.W;
+  const size_t pix = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= HW) return;
+  const int j = (int)(pix / (unsigned)m.W), i = (int)(pix - (size_t)j * m.W);
+  const unsigned long long key = vis[pix];
+  const unsigned t = (unsigned)(key & 0xffffffffull);
+  Tri T;
+  Sample S;
+  const bool hit = key != kEmpty && t < (unsigned)m.F && tri_setup(m, t, T) && tri_sample(T, i, j, S);
+  // the background of resolve_kernel, and occlusion 1: open
+  v3 N = {0.0f, 0.0f, 0.0f}, Al = {0.0f, 0.0f, 0.0f}, P = {0.0f, 0.0f, 0.0f};
+  float O = 0.0f, D = 0.0f, Rr = 1.0f, Mm = 0.0f, Oc = 1.0f;
+  int id = -1;
+  if (hit) {
+    const size_t v0 = T.v[0], v1 = T.v[1], v2 = T.v[2];
+    const float* uv = x.uvs + 6 * (size_t)t;
+    const int k1 = T.flip ? 2 : 1, k2 = T.flip ? 1 : 2;  // the corner that became T.v[1], T.v[2]
+    const float u = interp(S, uv[0], uv[2 * k1], uv[2 * k2]);
+    const float v = interp(S, uv[1], uv[2 * k1 + 1], uv[2 * k2 + 1]);
+    int xa, xb, ya, yb;
+    float fx, fy;
+    tex_axis(u * (float)x.Wt - 0.5f, x.Wt, xa, xb, fx);
+    tex_axis((1.0f - v) * (float)x.Ht - 0.5f, x.Ht, ya, yb, fy);  // v = 0 is the bottom row
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    const size_t plane = (size_t)x.Wt * x.Ht;
+    const size_t q00 = (size_t)ya * x.Wt + xa, q01 = (size_t)ya * x.Wt + xb;
+    const size_t q10 = (size_t)yb * x.Wt + xa, q11 = (size_t)yb * x.Wt + xb;
+    // every gather is issued before the first is used: the taps are independent
+    float ta[3][4], tm[3][4], tn[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const float* pa = x.albedo + c * plane;
+      const float* pm = x.orm + c * plane;
+      ta[c][0] = pa[q00]; ta[c][1] = pa[q01]; ta[c][2] = pa[q10]; ta[c][3] = pa[q11];
+      tm[c][0] = pm[q00]; tm[c][1] = pm[q01]; tm[c][2] = pm[q10]; tm[c][3] = pm[q11];
+    }
+    if (x.normal != nullptr) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const float* pn = x.normal + c * plane;
+        tn[c][0] = pn[q00]; tn[c][1] = pn[q01]; tn[c][2] = pn[q10]; tn[c][3] = pn[q11];
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        tn[c][0] = a.normals[3 * v0 + c]; tn[c][1] = a.normals[3 * v1 + c]; tn[c][2] = a.normals[3 * v2 + c];
+        tn[c][3] = 0.0f;
+      }
+    }
+    O = 1.0f;
+    D = S.z;
+    id = (int)t;
+    P = {interp(S, m.view_pos[3 * v0], m.view_pos[3 * v1], m.view_pos[3 * v2]),
+         interp(S, m.view_pos[3 * v0 + 1], m.view_pos[3 * v1 + 1], m.view_pos[3 * v2 + 1]),
+         interp(S, m.view_pos[3 * v0 + 2], m.view_pos[3 * v1 + 2], m.view_pos[3 * v2 + 2])};
+    Al = {bilerp(ta[0][0], ta[0][1], ta[0][2], ta[0][3], fx, gx, fy, gy),
+          bilerp(ta[1][0], ta[1][1], ta[1][2], ta[1][3], fx, gx, fy, gy),
+          bilerp(ta[2][0], ta[2][1], ta[2][2], ta[2][3], fx, gx, fy, gy)};
+    Oc = bilerp(tm[0][0], tm[0][1], tm[0][2], tm[0][3], fx, gx, fy, gy);
+    Rr = bilerp(tm[1][0], tm[1][1], tm[1][2], tm[1][3], fx, gx, fy, gy);
+    Mm = bilerp(tm[2][0], tm[2][1], tm[2][2], tm[2][3], fx, gx, fy, gy);
+    if (x.normal != nullptr)
+      N = {bilerp(tn[0][0], tn[0][1], tn[0][2], tn[0][3], fx, gx, fy, gy),
+           bilerp(tn[1][0], tn[1][1], tn[1][2], tn[1][3], fx, gx, fy, gy),
+           bilerp(tn[2][0], tn[2][1], tn[2][2], tn[2][3], fx, gx, fy, gy)};
+    else
+      N = {interp(S, tn[0][0], tn[0][1], tn[0][2]), interp(S, tn[1][0], tn[1][1], tn[1][2]),
+           interp(S, tn[2][0], tn[2][1], tn[2][2])};
+  }
+  const v3 nv = normalize3(xform_vec_4x3(N, a.viewmatrix));  // NaN when N == 0, as in resolve_kernel
+  o.opacity[pix] = O;
+  o.depth[pix] = D;
+  o.pos[pix] = P.x; o.pos[HW + pix] = P.y; o.pos[2 * HW + pix] = P.z;
+  o.normal[pix] = N.x; o.normal[HW + pix] = N.y; o.normal[2 * HW + pix] = N.z;
+  o.normal_view[pix] = nv.x; o.normal_view[HW + pix] = nv.y; o.normal_view[2 * HW + pix] = nv.z;
+  o.albedo[pix] = Al.x; o.albedo[HW + pix] = Al.y; o.albedo[2 * HW + pix] = Al.z;
+  o.roughness[pix] = Rr;
+  o.metallic[pix] = Mm;
+  occlusion[pix] = Oc;
+  o.tri_id[pix] = id;
+}
+
 inline bool image_ok(int W, int H) { return W >= 1 && H >= 1 && W <= (int)kGuard && H <= (int)kGuard; }
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -297,5 +408,28 @@ int gigs_mesh_resolve(int n_vertices, int n_faces, const int* faces, const float
   const PlanesK o = {opacity, depth, pos, normal, normal_view, albedo_out, roughness_out, metallic_out, tri_id};
   hipLaunchKernelGGL(resolve_kernel, dim3(blocks_for((size_t)width * height)), dim3(256), 0, (hipStream_t)stream, m, a, vis, o);
   return gigs_internal_check_launch("mesh_resolve");
+}
+
+int gigs_mesh_resolve_textured(int n_vertices, int n_faces, const int* faces, const float* view_pos, const int* screen,
+                               const uint8_t* flags, const float* uvs, const float* normals, int tex_width, int tex_height,
+                               const float* tex_albedo, const float* tex_orm, const float* tex_normal, const float* viewmatrix,
+                               int width, int height, const unsigned long long* vis, float* opacity, float* depth, float* pos,
+                               float* normal, float* normal_view, float* albedo_out, float* roughness_out, float* metallic_out,
+                               float* occlusion_out, int* tri_id, void* stream) {
+  using namespace gigs::mesh_raster;
+  if (n_vertices < 0 || n_faces < 0 || !image_ok(width, height) || !image_ok(tex_width, tex_height) || !vis || !viewmatrix ||
+      !opacity || !depth || !pos || !normal || !normal_view || !albedo_out || !roughness_out || !metallic_out ||
+      !occlusion_out || !tri_id)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "mesh_resolve_textured: bad argument");
+  if (n_faces > 0 && (!faces || !uvs || !tex_albedo || !tex_orm ||
+                      (n_vertices > 0 && (!view_pos || !screen || !flags || (!tex_normal && !normals)))))
+    return gigs_internal_fail(GIGS_ERR_INVALID, "mesh_resolve_textured: NULL mesh or texture array");
+  const MeshK m = {n_vertices, n_faces, width, height, faces, view_pos, screen, flags};
+  const AttrK a = {normals, nullptr, nullptr, nullptr, viewmatrix};
+  const TexK x = {uvs, tex_albedo, tex_orm, tex_normal, tex_width, tex_height};
+  const PlanesK o = {opacity, depth, pos, normal, normal_view, albedo_out, roughness_out, metallic_out, tri_id};
+  hipLaunchKernelGGL(resolve_textured_kernel, dim3(blocks_for((size_t)width * height)), dim3(256), 0, (hipStream_t)stream, m, a,
+                     x, vis, o, occlusion_out);
+  return gigs_internal_check_launch("mesh_resolve_textured");
 }
 }  // extern "C"

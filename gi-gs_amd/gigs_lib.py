@@ -164,6 +164,8 @@ SIGNATURES = {
     "gigs_mesh_raster": (_i, [_i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, C.c_void_p]),
     "gigs_mesh_resolve": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f,
                                _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_resolve_textured": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _f, _f, _i, _i, _f,
+                                        _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_fwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_tv_loss_bwd": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_masked_l1_fwd": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),

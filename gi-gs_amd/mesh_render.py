@@ -1,25 +1,33 @@
-"""Rendering and relighting a triangle mesh with per-vertex materials (mesh.Mesh, the PLY of extract_mesh.py): a
-visibility-buffer rasterizer fills the G-buffer planes the blend kernel writes in inference mode, and the deferred chain
+"""Rendering and relighting a triangle mesh with per-vertex materials (mesh.Mesh, the PLY of extract_mesh.py) or with a
+texture atlas (mesh.Atlas, the OBJ + PNGs of texture_mesh.py): a visibility-buffer rasterizer fills the G-buffer planes the blend kernel writes in inference mode, and the deferred chain
 behind them is the existing one, unchanged.
 
     mesh_arrays(mesh)                 a mesh.Mesh, a dict of scene_io.read_mesh_ply or a path -> checked numpy arrays
     MeshRasterizer(mesh)(cam)         gigs_mesh_project, gigs_mesh_raster, gigs_mesh_resolve -> opacity, depth, pos, normal,
                                       normal_view, albedo, roughness, metallic ([C,H,W]) and tri_id [H,W] (-1 = background)
-    mesh_planes(rast, cam, gi)        those planes plus the derived normals (gigs_derive_normal) and SSAO with the GI
-                                      settings: the rasterizer's twelve outputs, by name
+    TexturedMeshRasterizer(mesh, uvs, albedo, orm, normal)(cam)   the same rasterizer over a mesh whose materials live in a
+                                      texture atlas (mesh.bake_atlas's planes, texture_mesh.py's OBJ + PNGs): project and raster
+                                      are inherited, the resolve is gigs_mesh_resolve_textured -> the same planes and
+                                      `occlusion` [1,H,W], the atlas's baked O channel.  from_atlas(mesh, atlas) takes a
+                                      mesh.Atlas as it is; load_textured_mesh(path.obj) reads the files back
+    mesh_planes(rast, cam, gi, occlusion="ssao")   those planes plus the derived normals (gigs_derive_normal) and the
+                                      occlusion: SSAO with the GI settings ("ssao"), the atlas's baked channel ("baked", no
+                                      SSAO launch) or their product ("both"): the rasterizer's twelve outputs, by name
     MeshGBuffer(gi, metallic)(cam, rast)   the G-buffer source of relight.py's relighters: mesh_planes, then
                                       relight.gbuffer_from_planes (G-buffer post, the reference's F0 quirk)
     MeshRelighter / MeshMultiRelighter / MeshTurntableRelighter   relight.py's three relighters constructed over that source:
                                       rl(cam, rast, view_dirs).  Only the G-buffer differs; shade, SSR march and the sRGB /
                                       median finish are theirs, and the result gains the source's extra planes
 
-The arithmetic is stated in include/gigs_hip.h and restated in numpy by tests/mesh_raster_ref.py.  There is no clipping:
+The arithmetic is stated in include/gigs_hip.h and restated in numpy by tests/mesh_raster_ref.py (the textured resolve by
+tests/mesh_texture_ref.py).  There is no clipping:
 a triangle with a vertex behind the near cull (view z <= 0.2) or outside the guard band of 16384 pixels is dropped whole.
 There is no CPU path, and no hipGraph replay (the source says so: relight.py's replay is keyed on the Gaussian tensors and
 asynchronous binning): graphs=True raises.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import numpy as np
@@ -33,6 +41,9 @@ _lib = gigs_lib.lib()
 
 MESH_KEYS = ("vertices", "faces", "normals", "albedo", "roughness", "metallic")
 PLANES = {"opacity": 1, "depth": 1, "pos": 3, "normal": 3, "normal_view": 3, "albedo": 3, "roughness": 1, "metallic": 1}
+TEXTURED_PLANES = dict(PLANES, occlusion=1)  # gigs_mesh_resolve_textured's float planes, in its argument order
+OCCLUSION_MODES = ("ssao", "baked", "both")
+TEXTURE_MAX = 16384  # texels a side: gigs_mesh_resolve_textured's limit
 
 
 def mesh_arrays(mesh) -> Dict[str, np.ndarray]:
@@ -74,15 +85,22 @@ class MeshRasterizer:
     gigs_lib.MESH_SMALL_MAX); the result does not depend on it."""
 
     def __init__(self, mesh, device="cuda", small_max: Optional[int] = None):
+        self._set_device(device)
+        arrays = mesh_arrays(mesh)
+        self._upload({k: torch.from_numpy(v) for k, v in arrays.items()}, small_max)
+
+    def _set_device(self, device) -> None:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("MeshRasterizer: the mesh must live on a CUDA/HIP device: gigs-hip has no CPU path")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        arrays = mesh_arrays(mesh)
-        self.V, self.F = int(arrays["vertices"].shape[0]), int(arrays["faces"].shape[0])
+
+    def _upload(self, tensors: Dict[str, torch.Tensor], small_max: Optional[int]) -> None:
+        """The checked arrays on the device, and the scratch of a view."""
+        self.V, self.F = int(tensors["vertices"].shape[0]), int(tensors["faces"].shape[0])
         self.small_max = small_max
-        self._mesh = {k: torch.from_numpy(v).to(self.device) for k, v in arrays.items()}
+        self._mesh = {k: v.to(self.device) for k, v in tensors.items()}
         dev = self.device
         self._view_pos = torch.empty((self.V, 3), dtype=torch.float32, device=dev)
         self._screen = torch.empty((self.V, 2), dtype=torch.int32, device=dev)
@@ -173,11 +191,125 @@ class MeshRasterizer:
         return self.resolve(cam)
 
 
+def _texture(t, name: str) -> torch.Tensor:
+    """A [3,Ht,Wt] float32 plane set as a contiguous tensor (wherever it lives), 1 <= Wt, Ht <= TEXTURE_MAX."""
+    if not isinstance(t, torch.Tensor):
+        t = torch.from_numpy(np.ascontiguousarray(t))
+    if t.dtype != torch.float32 or t.dim() != 3 or t.shape[0] != 3:
+        raise ValueError("TexturedMeshRasterizer: %s must be [3,Ht,Wt] float32, got %s %s" % (name, tuple(t.shape), t.dtype))
+    if not (1 <= t.shape[1] <= TEXTURE_MAX and 1 <= t.shape[2] <= TEXTURE_MAX):
+        raise ValueError("TexturedMeshRasterizer: %s is %d x %d texels; 1 to %d a side" % (name, t.shape[2], t.shape[1],
+                                                                                        TEXTURE_MAX))
+    return t.detach().contiguous()
+
+
+
+class TexturedMeshRasterizer(MeshRasterizer):
+    """MeshRasterizer over a mesh whose materials are textures.  mesh: a dict with vertices [V,3] and faces [F,3] (and
+    normals [V,3], needed only without a normal texture), a mesh.Mesh or any sequence in its field order; per-vertex
+    albedo / roughness / metallic are not looked at.  uvs [F,3,2] float32: one UV per face corner (mesh.face_uvs',
+    scene_io.read_mesh_obj()["uvs"]; v = 0 is the bottom row).  albedo, orm (occlusion, roughness, metallic) and normal (the
+    world normal, not normalised; None = interpolate the vertex normals) are [3,Ht,Wt] float32 tensors or arrays of one
+    size.  project and raster are MeshRasterizer's; resolve calls gigs_mesh_resolve_textured."""
+
+    def __init__(self, mesh, uvs, albedo, orm, normal=None, device="cuda", small_max: Optional[int] = None):
+        self._set_device(device)
+        if not isinstance(mesh, dict):
+            mesh = dict(zip(MESH_KEYS, mesh))
+        if "vertices" not in mesh or "faces" not in mesh:
+            raise ValueError("TexturedMeshRasterizer: the mesh lacks vertices or faces")
+
+        def tensor(a, dtype, cols):
+            t = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+            return t.to(dtype).reshape(-1, *cols).contiguous()
+
+        tensors = dict(vertices=tensor(mesh["vertices"], torch.float32, (3,)), faces=tensor(mesh["faces"], torch.int32, (3,)))
+        V, F = int(tensors["vertices"].shape[0]), int(tensors["faces"].shape[0])
+        if mesh.get("normals") is not None:
+            tensors["normals"] = tensor(mesh["normals"], torch.float32, (3,))
+            if int(tensors["normals"].shape[0]) != V:
+                raise ValueError("TexturedMeshRasterizer: normals has %d rows for %d vertices" % (tensors["normals"].shape[0], V))
+        elif normal is None:
+            raise ValueError("TexturedMeshRasterizer: without a normal texture the mesh needs per-vertex normals")
+        uv = uvs.detach() if isinstance(uvs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uvs))
+        if uv.dtype != torch.float32 or tuple(uv.shape) != (F, 3, 2):
+            raise ValueError("TexturedMeshRasterizer: uvs must be [%d,3,2] float32, got %s %s" % (F, tuple(uv.shape), uv.dtype))
+        tensors["uvs"] = uv.contiguous()
+        tensors["tex_albedo"], tensors["tex_orm"] = _texture(albedo, "albedo"), _texture(orm, "orm")
+        if normal is not None:
+            tensors["tex_normal"] = _texture(normal, "normal")
+        size = tuple(tensors["tex_albedo"].shape)
+        for k in ("tex_orm", "tex_normal"):
+            if k in tensors and tuple(tensors[k].shape) != size:
+                raise ValueError("TexturedMeshRasterizer: %s is %s, albedo is %s" % (k[4:], tuple(tensors[k].shape), size))
+        self.texture_size = (int(size[2]), int(size[1]))  # (Wt, Ht)
+        self._upload(tensors, small_max)
+
+    @classmethod
+    def from_atlas(cls, mesh, atlas, device=None, small_max: Optional[int] = None):
+        """The rasterizer over a mesh.Atlas of `mesh` (mesh.bake_atlas's): its float planes as they are, no quantisation."""
+        return cls(mesh, atlas.uvs, atlas.albedo, atlas.orm, atlas.normal, device=atlas.albedo.device if device is None else device,
+                   small_max=small_max)
+
+    def resolve(self, cam: Dict, vis: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """gigs_mesh_resolve_textured of a key plane (by default the last raster()'s) with the last project()'s arrays ->
+        fresh planes: MeshRasterizer.resolve's, and occlusion [1,H,W]."""
+        self._check()
+        W, H = int(cam["image_width"]), int(cam["image_height"])
+        dev = self.device
+        vis = self._vis if vis is None else vis
+        if vis is None or tuple(vis.shape) != (H, W):
+            raise ValueError("TexturedMeshRasterizer.resolve: no key plane of %d x %d" % (H, W))
+        vm = self._viewmatrix(cam, dev)
+        out = {k: torch.empty((c, H, W), dtype=torch.float32, device=dev) for k, c in TEXTURED_PLANES.items()}
+        out["tri_id"] = torch.empty((H, W), dtype=torch.int32, device=dev)
+        m = self._mesh
+        Wt, Ht = self.texture_size
+        with torch.cuda.device(dev):
+            gigs_lib.check(_lib.gigs_mesh_resolve_textured(
+                self.V, self.F, _p(m["faces"]), _p(self._view_pos), _p(self._screen), _p(self._flags), _p(m["uvs"]),
+                _p(m.get("normals")), Wt, Ht, m["tex_albedo"].data_ptr(), m["tex_orm"].data_ptr(), _p(m.get("tex_normal")),
+                vm.data_ptr(), W, H, vis.data_ptr(), *(out[k].data_ptr() for k in TEXTURED_PLANES), out["tri_id"].data_ptr(),
+                _stream()), "mesh_resolve_textured")
+        return out
+
+
+def load_textured_mesh(path_obj: str) -> Dict:
+    """An OBJ of scene_io.save_mesh_obj with the PNGs its .mtl names (texture_mesh.py's output) -> the arguments of
+    TexturedMeshRasterizer: {mesh: {vertices, faces, normals (or None)}, uvs [F,3,2], albedo, orm, normal [3,Ht,Wt] float32}.
+    The PNGs are decoded on the host (PIL): albedo and ORM as c / 255, the normal as 2 c / 255 - 1, the inverse of
+    texture_mesh.normal_image up to the 8 bits; it is not renormalised (the resolve does not ask for unit length)."""
+    from PIL import Image
+
+    import scene_io
+    obj = scene_io.read_mesh_obj(path_obj)
+    folder = os.path.dirname(path_obj)
+
+    def png(name):
+        with Image.open(os.path.join(folder, obj["textures"][name])) as im:
+            c = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        return np.ascontiguousarray(c.transpose(2, 0, 1)).astype(np.float32)
+
+    albedo, orm, normal = png("albedo") / np.float32(255.0), png("orm") / np.float32(255.0), png("normal")
+    normal = np.float32(2.0) * normal / np.float32(255.0) - np.float32(1.0)
+    if albedo.shape != orm.shape or albedo.shape != normal.shape:
+        raise ValueError("%s: the albedo, ORM and normal images differ in size" % path_obj)
+    return dict(mesh=dict(vertices=obj["vertices"], faces=obj["faces"], normals=obj["normals"]), uvs=obj["uvs"], albedo=albedo,
+                orm=orm, normal=normal)
+
+
 @torch.no_grad()
-def mesh_planes(rast: MeshRasterizer, cam: Dict, gi: Dict) -> Dict[str, torch.Tensor]:
+def mesh_planes(rast: MeshRasterizer, cam: Dict, gi: Dict, occlusion: str = "ssao") -> Dict[str, torch.Tensor]:
     """What GaussianRasterizer.forward returns for the Gaussians (inference, derive_normal), for the mesh and by name:
     the resolve's planes, normal_from_depth and depth_pos (gigs_derive_normal of the depth plane: 3x3 median, depth to
-    normal, bilateral filter, median of the positions) and occlusion (SSAO of normal_view over depth_pos)."""
+    normal, bilateral filter, median of the positions) and occlusion_map: "ssao", SSAO of normal_view over depth_pos;
+    "baked", the occlusion plane of a TexturedMeshRasterizer's resolve, with no SSAO launch; "both", their product.  A
+    textured rasterizer's result also holds that plane as baked_occlusion."""
+    if occlusion not in OCCLUSION_MODES:
+        raise ValueError("mesh_planes: occlusion is one of %s, got %r" % (", ".join(OCCLUSION_MODES), occlusion))
+    textured = isinstance(rast, TexturedMeshRasterizer)
+    if occlusion != "ssao" and not textured:
+        raise ValueError("mesh_planes: occlusion=%r needs a TexturedMeshRasterizer: a plain mesh has no baked channel" % occlusion)
     W, H = int(cam["image_width"]), int(cam["image_height"])
     if W < 2 or H < 2:
         raise ValueError("mesh_planes: the derived normals need an image of at least 2 x 2")
@@ -186,58 +318,72 @@ def mesh_planes(rast: MeshRasterizer, cam: Dict, gi: Dict) -> Dict[str, torch.Te
     vm = rast._viewmatrix(cam, rast.device)
     with torch.cuda.device(rast.device):
         normal_from_depth, depth_pos = _derive_normal(W, H, fx, fy, vm, o["depth"])
-        occlusion = _ops.SSAO(W, H, fx, fy, gi["radius"], gi["bias"], gi["thick"], gi["delta"], gi["step"], gi["start"],
-                              o["normal_view"], depth_pos)
-    return dict(opacity_map=o["opacity"], depth_map=o["depth"], normal_map_from_depth=normal_from_depth,
-                normal_map=o["normal"], occlusion_map=occlusion, albedo_map=o["albedo"], roughness_map=o["roughness"],
-                metallic_map=o["metallic"], out_normal_view=o["normal_view"], depth_pos=depth_pos, pos=o["pos"],
-                tri_id=o["tri_id"], viewmatrix=vm)
+        if occlusion == "baked":
+            occlusion_map = o["occlusion"]
+        else:
+            occlusion_map = _ops.SSAO(W, H, fx, fy, gi["radius"], gi["bias"], gi["thick"], gi["delta"], gi["step"], gi["start"],
+                                      o["normal_view"], depth_pos)
+            if occlusion == "both":
+                occlusion_map = occlusion_map * o["occlusion"]
+    r = dict(opacity_map=o["opacity"], depth_map=o["depth"], normal_map_from_depth=normal_from_depth,
+             normal_map=o["normal"], occlusion_map=occlusion_map, albedo_map=o["albedo"], roughness_map=o["roughness"],
+             metallic_map=o["metallic"], out_normal_view=o["normal_view"], depth_pos=depth_pos, pos=o["pos"],
+             tri_id=o["tri_id"], viewmatrix=vm)
+    if textured:
+        r["baked_occlusion"] = o["occlusion"]
+    return r
 
 
 class MeshGBuffer:
     """The G-buffer of a mesh (relight.py documents its keys): source(cam, rast) runs mesh_planes over a MeshRasterizer and
-    relight.gbuffer_from_planes.  `radii` is None and `extra` holds tri_id, opacity_map and the material planes.  The source
+    relight.gbuffer_from_planes.  `radii` is None and `extra` holds tri_id, opacity_map and the material planes, and
+    baked_occlusion for a TexturedMeshRasterizer; `occlusion` is mesh_planes' ("baked" and "both" need one).  The source
     owns the scratch planes of its result, which is valid until its next call."""
     replayable = False  # relight.ViewReplay is keyed on Gaussian tensors and asynchronous binning
 
-    def __init__(self, gi: Dict, metallic: bool = False):
-        self.gi, self.metallic = gi, bool(metallic)
+    def __init__(self, gi: Dict, metallic: bool = False, occlusion: str = "ssao"):
+        if occlusion not in OCCLUSION_MODES:
+            raise ValueError("MeshGBuffer: occlusion is one of %s, got %r" % (", ".join(OCCLUSION_MODES), occlusion))
+        self.gi, self.metallic, self.occlusion = gi, bool(metallic), occlusion
         self._scratch = relight.Scratch()
 
     @torch.no_grad()
     def __call__(self, cam: Dict, rast: MeshRasterizer) -> Dict:
         if not isinstance(rast, MeshRasterizer):
             raise TypeError("MeshGBuffer: the second argument is a MeshRasterizer")
-        r = mesh_planes(rast, cam, self.gi)
+        r = mesh_planes(rast, cam, self.gi, self.occlusion)
         b = relight.gbuffer_from_planes(r, r["viewmatrix"], self.metallic, self._scratch)
         b["extra"] = {k: r[k] for k in ("tri_id", "opacity_map", "albedo_map", "roughness_map", "metallic_map")}
+        if "baked_occlusion" in r:
+            b["extra"]["baked_occlusion"] = r["baked_occlusion"]
         return b
 
 
 class MeshRelighter(relight.Relighter):
-    """relight.Relighter(fused=True) on a mesh: rl(cam, rast, view_dirs, alpha_mask=None, albedo_ratio=None)."""
+    """relight.Relighter(fused=True) on a mesh: rl(cam, rast, view_dirs, alpha_mask=None, albedo_ratio=None).  occlusion:
+    mesh_planes' ("ssao", or "baked" / "both" over a TexturedMeshRasterizer); the same keyword on the other two."""
 
     def __init__(self, light, gi: Dict, metallic: bool = False, tone: bool = False, gamma: bool = False,
-                 brdf_lut: Optional[torch.Tensor] = None, graphs: bool = False):
+                 brdf_lut: Optional[torch.Tensor] = None, graphs: bool = False, occlusion: str = "ssao"):
         super().__init__(light, gi, 0, metallic=metallic, tone=tone, gamma=gamma, fused=True, brdf_lut=brdf_lut, graphs=graphs,
-                         source=MeshGBuffer(gi, metallic))
+                         source=MeshGBuffer(gi, metallic, occlusion))
 
 
 class MeshMultiRelighter(relight.MultiRelighter):
     """relight.MultiRelighter on a mesh: up to relight.MAX_LIGHTS lights over one G-buffer."""
 
     def __init__(self, lights, gi: Dict, metallic: bool = False, tone: bool = False, gamma: bool = False,
-                 graphs: bool = False, brdf_lut: Optional[torch.Tensor] = None):
+                 graphs: bool = False, brdf_lut: Optional[torch.Tensor] = None, occlusion: str = "ssao"):
         super().__init__(lights, gi, 0, metallic=metallic, tone=tone, gamma=gamma, graphs=graphs, brdf_lut=brdf_lut,
-                         source=MeshGBuffer(gi, metallic))
+                         source=MeshGBuffer(gi, metallic, occlusion))
 
 
 class MeshTurntableRelighter(relight.TurntableRelighter):
     """relight.TurntableRelighter on a mesh: any number of lights, the SSR march recorded once."""
 
     def __init__(self, lights, gi: Dict, metallic: bool = False, tone: bool = False, gamma: bool = False,
-                 brdf_lut: Optional[torch.Tensor] = None, graphs: bool = False):
+                 brdf_lut: Optional[torch.Tensor] = None, graphs: bool = False, occlusion: str = "ssao"):
         if graphs:
             raise ValueError("MeshTurntableRelighter replays no hipGraph: graphs=False only")
         super().__init__(lights, gi, 0, metallic=metallic, tone=tone, gamma=gamma, brdf_lut=brdf_lut,
-                         source=MeshGBuffer(gi, metallic))
+                         source=MeshGBuffer(gi, metallic, occlusion))

@@ -1,8 +1,9 @@
-"""An exported mesh (extract_mesh.py's PLY) rendered and relit from the cameras of its scene (mesh_render.py), and compared
-with the splat render it came from.
+"""An exported mesh (extract_mesh.py's PLY, or texture_mesh.py's OBJ with its PNGs) rendered and relit from the cameras of
+its scene (mesh_render.py), and compared with the splat render it came from or with another mesh.
 
-    python gi-gs_amd/render_mesh.py -m <out> --mesh mesh.ply [--checkpoint <out>/chkpntN.pth] [--hdri a.hdr b.hdr ...]
-                                    [--rotations N] [--compare] [--split test] [--metallic --tone --gamma]        (CLI)
+    python gi-gs_amd/render_mesh.py -m <out> --mesh mesh.ply|mesh.obj [--checkpoint <out>/chkpntN.pth] [--hdri a.hdr b.hdr ...]
+                                    [--rotations N] [--compare] [--reference_mesh other.ply|other.obj]
+                                    [--occlusion ssao|baked|both] [--split test] [--metallic --tone --gamma]      (CLI)
     render_mesh(args) -> {...}                                                                                   (API)
 
 The scene path and the resolution come from <out>/cfg_args as in render_scene.py, command-line values first; a relative
@@ -17,6 +18,16 @@ and with --compare (needs --checkpoint) renders the same views from the Gaussian
 mesh_vs_splat.json: per view and on average the PSNR / SSIM (gigs_image_metrics) of the mesh's relit image and albedo
 against the splats', and the mean absolute depth difference over the pixels both cover.  There is no clipping: triangles
 that reach behind the camera's near cull are dropped (mesh_render.py).
+
+A --mesh ending in .obj is read with its material library and PNGs (mesh_render.load_textured_mesh) and rendered through the
+textured resolve; its views gain <image_name>_baked_occlusion.png, the atlas's occlusion channel, and --occlusion chooses
+what the shading is given: `ssao` (the default: screen-space, as for a PLY), `baked` (that channel, no SSAO launch) or
+`both` (their product).  Anything but `ssao` needs an OBJ.
+
+--reference_mesh renders every view from a second mesh too (a PLY, or an OBJ under the same --occlusion) and writes
+<out>/mesh_<split>/mesh_vs_mesh.json: per view and on average the intersection over union of the two coverages
+(tri_id >= 0), over the pixels both cover the PSNR of albedo, roughness, metallic and every relit image, and the mean
+angle between the two normal planes: texture_mesh.material_error's comparison, made in the image.
 """
 from __future__ import annotations
 
@@ -32,13 +43,17 @@ if __package__ in (None, ""):  # run as a script: make the package's modules imp
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 G_PLANES = ("depth", "normal", "albedo", "roughness", "metallic", "occlusion")
+OCCLUSION_MODES = ("ssao", "baked", "both")  # mesh_render.OCCLUSION_MODES, without its imports
 
 
 def build_parser() -> argparse.ArgumentParser:
     import render_scene
     p = argparse.ArgumentParser(description="Mesh rendering parameters")
     render_scene.add_model_arguments(p)
-    p.add_argument("--mesh", type=str, required=True, help="The PLY written by extract_mesh.py.")
+    p.add_argument("--mesh", type=str, required=True, help="The PLY of extract_mesh.py, or the OBJ of texture_mesh.py.")
+    p.add_argument("--occlusion", choices=OCCLUSION_MODES, default="ssao",
+                   help="what shades: screen-space occlusion, the OBJ's baked channel, or their product")
+    p.add_argument("--reference_mesh", type=str, default=None, help="a second mesh (PLY or OBJ): writes mesh_vs_mesh.json")
     p.add_argument("--checkpoint", type=str, default=None, help="The checkpoint: its light, and the Gaussians of --compare.")
     p.add_argument("--hdri", type=str, nargs="+", default=None, help="Environment maps to light the mesh with (.hdr or .npy).")
     p.add_argument("--rotations", type=int, default=0, help="light under N equal turns of every map about its up axis")
@@ -53,7 +68,15 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def parse_args(argv: Optional[List[str]] = None) -> Namespace:
-    return build_parser().parse_args(argv)
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.occlusion != "ssao" and not is_textured(args.mesh):
+        p.error("--occlusion %s needs a textured mesh (.obj): a PLY has no baked channel" % args.occlusion)
+    return args
+
+
+def is_textured(path: str) -> bool:
+    return str(path).lower().endswith(".obj")
 
 
 def light_names(hdris: Optional[Sequence[str]], n_rot: int) -> List[str]:
@@ -65,9 +88,9 @@ def light_names(hdris: Optional[Sequence[str]], n_rot: int) -> List[str]:
     return names
 
 
-def view_paths(out: str, split: str, image_name: str, lights: Sequence[str]) -> Dict:
+def view_paths(out: str, split: str, image_name: str, lights: Sequence[str], textured: bool = False) -> Dict:
     base = os.path.join(out, "mesh_" + split)
-    paths: Dict = {k: os.path.join(base, "%s_%s.png" % (image_name, k)) for k in G_PLANES}
+    paths: Dict = {k: os.path.join(base, "%s_%s.png" % (image_name, k)) for k in G_PLANES + (("baked_occlusion",) if textured else ())}
     paths["relit"] = [os.path.join(base, "%s_%s.png" % (image_name, n)) for n in lights]
     return paths
 
@@ -82,7 +105,64 @@ def _check(args: Namespace) -> int:
         raise ValueError("a light is needed: --checkpoint or --hdri")
     if not args.checkpoint and not args.model_path:
         raise ValueError("-m is required without --checkpoint")
+    occlusion = getattr(args, "occlusion", "ssao")
+    if occlusion not in OCCLUSION_MODES:
+        raise ValueError("--occlusion: one of %s, got %r" % (", ".join(OCCLUSION_MODES), occlusion))
+    if occlusion != "ssao" and not is_textured(args.mesh):
+        raise ValueError("--occlusion %s needs a textured mesh (.obj): a PLY has no baked channel" % occlusion)
     return n_rot
+
+
+def open_mesh(path: str, device):
+    """The rasterizer of a mesh file: textured for an .obj, per-vertex for a PLY."""
+    import mesh_render
+    if is_textured(path):
+        return mesh_render.TexturedMeshRasterizer(**mesh_render.load_textured_mesh(path), device=device)
+    return mesh_render.MeshRasterizer(path, device=device)
+
+
+MESH_VS_MESH_KEYS = ("coverage_iou", "albedo_psnr", "roughness_psnr", "metallic_psnr", "normal_angle_deg")
+
+
+def mesh_vs_mesh(o: Dict, r: Dict) -> Dict:
+    """Two relit results of one view (a mesh relighter's, `o` the mesh and `r` the reference) -> device scalars: the
+    intersection over union of the coverages tri_id >= 0, the number of pixels both cover and, over those, the PSNR (peak
+    1) of albedo, roughness and metallic and of every relit image (`relit_psnr` [L], the images clamped to [0, 1] with NaN as
+    0), and the mean angle in degrees between the normal planes.  A report's arithmetic, in torch."""
+    import torch
+    a, b = o["tri_id"] >= 0, r["tri_id"] >= 0
+    both = a & b
+    n = both.sum().clamp(min=1).double()
+
+    def psnr(x, y):  # [..., C, H, W] -> [...]
+        d2 = ((x.double() - y.double()).pow(2) * both).sum(dim=(-3, -2, -1)) / (n * x.shape[-3])
+        return -10.0 * torch.log10(d2)
+
+    unit = lambda v: v.double() / v.double().pow(2).sum(0, keepdim=True).sqrt().clamp(min=1e-30)  # noqa: E731
+    cos = (unit(o["normal_map"]) * unit(r["normal_map"])).sum(0).nan_to_num().clamp(-1.0, 1.0)
+    lit = lambda v: v.nan_to_num().clamp(0, 1)  # noqa: E731
+    x, y = lit(o["render_rgb"]), lit(r["render_rgb"])
+    if x.dim() == 3:
+        x, y = x[None], y[None]
+    return dict(coverage_iou=both.sum().double() / (a | b).sum().clamp(min=1).double(), pixels_both_cover=both.sum(),
+                albedo_psnr=psnr(o["albedo_map"], r["albedo_map"]), roughness_psnr=psnr(o["roughness_map"], r["roughness_map"]),
+                metallic_psnr=psnr(o["metallic_map"], r["metallic_map"]), relit_psnr=psnr(x, y),
+                normal_angle_deg=torch.rad2deg((torch.acos(cos) * both).sum() / n))
+
+
+def mesh_vs_mesh_report(per_view: List[Dict], names: Sequence[str]) -> Dict:
+    """mesh_vs_mesh's scalars of every view (with `image_name`) -> {views, average}, as plain numbers.  The PSNR of two
+    equal planes is infinite and is written as such."""
+    views = []
+    for v in per_view:
+        relit = [float(x) for x in v["relit_psnr"].cpu()]
+        row = dict(image_name=v["image_name"], pixels_both_cover=int(v["pixels_both_cover"]),
+                   relit_psnr={n: x for n, x in zip(names, relit)})
+        row.update({k: float(v[k]) for k in MESH_VS_MESH_KEYS})
+        views.append(row)
+    average = {k: sum(v[k] for v in views) / len(views) for k in MESH_VS_MESH_KEYS}
+    average["relit_psnr"] = {n: sum(v["relit_psnr"][n] for v in views) / len(views) for n in names}
+    return dict(views=views, average=average)
 
 
 def render_mesh(args) -> Dict:
@@ -110,7 +190,10 @@ def render_mesh(args) -> Dict:
     dev = torch.device("cuda", torch.cuda.current_device())
     args.source_path = os.path.abspath(args.source_path)
     out = args.model_path
-    mesh_path = args.mesh if os.path.isabs(args.mesh) or os.path.exists(args.mesh) else os.path.join(out, args.mesh)
+    locate = lambda p: p if os.path.isabs(p) or os.path.exists(p) else os.path.join(out, p)  # noqa: E731
+    mesh_path = locate(args.mesh)
+    ref_path = locate(args.reference_mesh) if getattr(args, "reference_mesh", None) else None
+    occlusion = getattr(args, "occlusion", "ssao")
     t0 = time.perf_counter()
     g = sh_degree = ck = None
     if checkpoint:
@@ -142,12 +225,19 @@ def render_mesh(args) -> Dict:
     os.makedirs(os.path.join(out, "mesh_" + args.split), exist_ok=True)
     res: Dict = {"mesh": mesh_path, "n_views": len(infos), "lights": names}
     per_view: List[Dict] = []
+    vs_mesh: List[Dict] = []
+    ref_rast = ref_tr = None
     try:
-        with mesh_render.MeshRasterizer(mesh_path, device=dev) as rast, image_writer.ImageWriter(workers=args.workers) as wr, \
-                torch.no_grad():
+        with open_mesh(mesh_path, dev) as rast, image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
             res.update(vertices=rast.V, faces=rast.F)
+            textured = isinstance(rast, mesh_render.TexturedMeshRasterizer)
             tr = mesh_render.MeshTurntableRelighter(lights, gi, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
-                                                    brdf_lut=lut)
+                                                    brdf_lut=lut, occlusion=occlusion)
+            if ref_path:
+                ref_rast = open_mesh(ref_path, dev)
+                ref_tr = mesh_render.MeshTurntableRelighter(
+                    lights, gi, metallic=args.metallic, tone=args.tone, gamma=args.gamma, brdf_lut=lut,
+                    occlusion=occlusion if isinstance(ref_rast, mesh_render.TexturedMeshRasterizer) else "ssao")
             splat = relight.Relighter(lights[0], gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
                                       brdf_lut=lut) if args.compare else None
             try:
@@ -158,15 +248,19 @@ def render_mesh(args) -> Dict:
                         rays = pipeline.canonical_rays(c, dev)
                     vd = pipeline.view_dirs_for(c, rays, dev)
                     o = tr(c, rast, vd)
-                    paths = view_paths(out, args.split, ci.image_name, names)
+                    paths = view_paths(out, args.split, ci.image_name, names, textured)
                     images = [image_writer.Image(paths["depth"], o["depth_map"], normalize=True),
                               image_writer.Image(paths["normal"], o["normal_map"] * 0.5 + 0.5),
                               image_writer.Image(paths["occlusion"], o["occlusion"], bias=0.0)]
                     images += [image_writer.Image(paths[k], o[k + "_map"]) for k in ("albedo", "roughness", "metallic")]
+                    if textured:
+                        images.append(image_writer.Image(paths["baked_occlusion"], o["baked_occlusion"], bias=0.0))
                     wr.submit(images)
                     relit = [(p, o["render_rgb"][k]) for k, p in enumerate(paths["relit"])]
                     for first in range(0, len(relit), relight.MAX_LIGHTS):
                         wr.submit(relit[first:first + relight.MAX_LIGHTS])
+                    if ref_tr is not None:
+                        vs_mesh.append(dict(mesh_vs_mesh(o, ref_tr(c, ref_rast, vd)), image_name=ci.image_name))
                     if splat is not None:
                         b = splat.source(c, g)  # the relighter's result holds no albedo plane: the G-buffer does
                         s = splat.from_gbuffer(c, b, vd)
@@ -182,7 +276,17 @@ def render_mesh(args) -> Dict:
                 tr.close()
                 if splat is not None:
                     splat.close()
+                if ref_tr is not None:
+                    ref_tr.close()
+                if ref_rast is not None:
+                    ref_rast.close()
         res.update(files=wr.files, png_bytes=wr.bytes_written)
+        if ref_path:
+            cmp = dict(mesh=mesh_path, reference=ref_path, occlusion=occlusion, lights=names, **mesh_vs_mesh_report(vs_mesh, names))
+            path = os.path.join(out, "mesh_" + args.split, "mesh_vs_mesh.json")
+            with open(path, "w") as f:
+                json.dump(cmp, f, indent=4)
+            res.update(mesh_vs_mesh_json=path, mesh_vs_mesh=cmp["average"])
         if args.compare:
             views = []
             for v in per_view:

@@ -1009,6 +1009,27 @@ int gigs_mesh_transfer(int n_vertices, int n_faces, const float* vertices, const
  *   normalize3(xform_vec_4x3(normal, viewmatrix)), tri_id [H,W] int32 = the triangle.  A pixel with an empty key gets what
  *   the blend kernel writes where no Gaussian contributes under a black background with inference = 1: zeros,
  *   roughness = 1, normal_view = normalize3 of the zero vector (NaN), and tri_id = -1.
+ * gigs_mesh_resolve_textured, one thread per pixel: gigs_mesh_resolve for a mesh whose materials live in a texture atlas
+ *   (mesh.bake_atlas's planes, texture_mesh.py's images) instead of per-vertex tables.  The same device functions set the
+ *   triangle up and sample it, so tri_id, opacity, depth and pos have the bits gigs_mesh_resolve gives on the same key
+ *   plane.  uvs [F,3,2] float32 holds one UV per face CORNER and is indexed by the triangle alone (no second index table);
+ *   tex_albedo, tex_orm (occlusion, roughness, metallic) and tex_normal are planes [3,Ht,Wt] float32, 1 <= Wt, Ht <= 16384;
+ *   tex_normal holds the world normal as interpolated, not normalised, and may be NULL: then `normals` [V,3] is
+ *   interpolated exactly as in gigs_mesh_resolve (it is not read otherwise and may be NULL).  Every operation is rounded on
+ *   its own, in float32:
+ *     Corners.  Where the set-up swapped vertices 1 and 2 (A < 0) the corner UVs swap with them: uv_k is the UV of the
+ *       corner that became vertex k.
+ *     u = ((w0 u_0 + w1 u_1) + w2 u_2) / s, v likewise (perspective-correct, as every attribute).
+ *     x = u Wt - 0.5, y = (1 - v) Ht - 0.5: v = 0 is the BOTTOM row of the image (the OBJ convention, mesh.sample_atlas's
+ *       formulas).  x = fminf(fmaxf(x, -1), Wt), y = fminf(fmaxf(y, -1), Ht); fmaxf returns its non-NaN argument, so a NaN
+ *       coordinate becomes -1 and no conversion to int is out of range.
+ *     x0 = floorf(x), fx = x - x0, xa = clamp(int(x0), 0, Wt - 1), xb = clamp(int(x0) + 1, 0, Wt - 1); y0, fy, ya, yb
+ *       likewise.
+ *     Per channel of a plane t: (1 - fy) ((1 - fx) t[ya,xa] + fx t[ya,xb]) + fy ((1 - fx) t[yb,xa] + fx t[yb,xb]).
+ *   There are no mips and no coverage test: an unbaked texel reads as the 0 it holds.  Planes: the eight of
+ *   gigs_mesh_resolve -- albedo, roughness, metallic from the textures, normal from tex_normal (or the vertex normals),
+ *   normal_view = normalize3(xform_vec_4x3(normal, viewmatrix)) -- plus occlusion [1,H,W], the O channel, and tri_id.  An
+ *   empty key gives gigs_mesh_resolve's background and occlusion = 1 (open).
  * Images up to 16384 x 16384. */
 #define GIGS_MESH_SMALL_MAX 64
 int gigs_mesh_project(int n_vertices, const float* vertices, const float* viewmatrix, float tanfovx, float tanfovy, int width,
@@ -1022,6 +1043,12 @@ int gigs_mesh_resolve(int n_vertices, int n_faces, const int* faces, const float
                       const float* metallic, const float* viewmatrix, int width, int height, const unsigned long long* vis,
                       float* opacity, float* depth, float* pos, float* normal, float* normal_view, float* albedo_out,
                       float* roughness_out, float* metallic_out, int* tri_id, void* stream);
+int gigs_mesh_resolve_textured(int n_vertices, int n_faces, const int* faces, const float* view_pos, const int* screen,
+                               const uint8_t* flags, const float* uvs, const float* normals, int tex_width, int tex_height,
+                               const float* tex_albedo, const float* tex_orm, const float* tex_normal, const float* viewmatrix,
+                               int width, int height, const unsigned long long* vis, float* opacity, float* depth, float* pos,
+                               float* normal, float* normal_view, float* albedo_out, float* roughness_out, float* metallic_out,
+                               float* occlusion_out, int* tri_id, void* stream);
 int gigs_tv_loss_fwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
                      const float* mask_f, float* scratch, float* loss, void* stream);
 int gigs_tv_loss_bwd(int channels, int height, int width, int step, const float* gt, const float* prediction,
