@@ -52,8 +52,7 @@ def bake_mesh(args) -> Dict:
     if not torch.cuda.is_available():
         raise RuntimeError("bake_mesh needs the GPU")
     dev = torch.device("cuda", torch.cuda.current_device())
-    arrays = mesh_render.mesh_arrays(scene_io.read_mesh_ply(args.input))
-    m = mesh.Mesh(*(torch.from_numpy(arrays[k]).to(dev) for k in mesh.Mesh._fields))
+    m = mesh_render.device_mesh(args.input, dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     occlusion, report = mesh.bake_occlusion(m, rays=args.rays, max_distance=args.distance, bias=args.bias, seed=args.seed,

@@ -46,19 +46,13 @@ def compare_mesh(args) -> Dict:
 
     import mesh
     import mesh_render
-    import scene_io
     if not isinstance(args, Namespace):
         args = parse_args(list(args))
     if not torch.cuda.is_available():
         raise RuntimeError("compare_mesh needs the GPU")
     dev = torch.device("cuda", torch.cuda.current_device())
-
-    def load(path):
-        arrays = mesh_render.mesh_arrays(scene_io.read_mesh_ply(path))
-        return mesh.Mesh(*(torch.from_numpy(arrays[k]).to(dev) for k in mesh.Mesh._fields))
-
-    report = mesh.distance(load(args.a), load(args.b), samples=args.samples, seed=args.seed, taus=args.tau,
-                           max_distance=args.max_distance)
+    report = mesh.distance(mesh_render.device_mesh(args.a, dev), mesh_render.device_mesh(args.b, dev), samples=args.samples,
+                           seed=args.seed, taus=args.tau, max_distance=args.max_distance)
     report = dict(report, a=args.a, b=args.b)
     if args.output:
         with open(args.output, "w") as f:

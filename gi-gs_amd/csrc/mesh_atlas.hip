@@ -10,17 +10,17 @@
 //   addresses     A face or vertex index, a destination texel and a texel's place in the image are compared with their
 //                 ranges before they are used; a violation that mesh.py cannot produce sets *overflow and the thread
 //                 stores nothing (gigs_mesh_compact's convention).
-//   closest       segment_w / triangle_w are mesh_distance.hip's segment_d2 / triangle_d2 with the weights kept: the same
-//                 candidates, expressions and order, so the d^2 that decides between the candidates has the bits the
-//                 search compared.  Nothing is shared with that unit but mesh_grid.h: its kernels keep their code.
+//   closest       triangle_closest<true> (mesh_triangle.h) is the routine the search calls as triangle_closest<false>, with
+//                 the weights kept: one definition of the candidates, expressions and order, so the d^2 that decides
+//                 between the candidates has the bits the search compared.
 //   registers     The weights and corners live in named scalars and fixed-size arrays with compile-time indices; the
 //                 channel loop reads and writes memory only.  No scratch.
-#include "mesh_grid.h"  // the vector helpers
+#include "mesh_triangle.h"  // triangle_closest; through it mesh_grid.h: the per-thread and vector helpers
 
 namespace gigs {
 namespace mesh_atlas {
 
-using namespace gigs::mesh_distance;  // item, in_range, finite3, dot3, cross3, load3, blocks_for
+using namespace gigs::mesh_common;  // item, in_range, finite3, load3, blocks_for, triangle_closest
 
 // ---- texel -> surface point --------------------------------------------------------------------------------------------------
 struct PointsArgs {
@@ -76,81 +76,7 @@ __global__ __launch_bounds__(256) void points_kernel(PointsArgs a) {
   a.dest[q] = d;
 }
 
-// ---- closest point on a triangle, as weights -----------------------------------------------------------------------------------
-// segment_d2 of mesh_distance.hip with the parameter kept: d^2 from p to the segment a -> b, *s in [0, 1] the place on it
-__device__ __forceinline__ double segment_w(const double* p, const double* a, const double* b, double* s) {
-  double ab[3], ap[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) ab[c] = b[c] - a[c], ap[c] = p[c] - a[c];
-  const double t = dot3(ap, ab), den = dot3(ab, ab);
-  if (t <= 0.0) {
-    *s = 0.0;
-    return dot3(ap, ap);
-  }
-  if (t >= den) {
-    double bp[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) bp[c] = p[c] - b[c];
-    *s = 1.0;
-    return dot3(bp, bp);
-  }
-  *s = t / den;
-  double q[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) q[c] = ap[c] - *s * ab[c];
-  return dot3(q, q);
-}
-
-// the edge from vertex (ia, a) to vertex (ib, b), walked from the lower index: d^2, and the weights of a and of b
-__device__ __forceinline__ double edge_w(const double* p, int ia, const double* a, int ib, const double* b, double* wa,
-                                         double* wb) {
-  double s;
-  if (ia > ib) {
-    const double d2 = segment_w(p, b, a, &s);
-    *wb = 1.0 - s, *wa = s;
-    return d2;
-  }
-  const double d2 = segment_w(p, a, b, &s);
-  *wa = 1.0 - s, *wb = s;
-  return d2;
-}
-
-__device__ __forceinline__ double edge_fn(const double* p, const double* a, const double* b, const double* n) {
-  double ab[3], ap[3], c[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) ab[k] = b[k] - a[k], ap[k] = p[k] - a[k];
-  cross3(ab, ap, c);
-  return dot3(c, n);
-}
-
-// triangle_d2 of mesh_distance.hip with the weights of the winning candidate; finite inputs, so edge 01 always enters
-__device__ __forceinline__ void triangle_w(const double* p, int i0, int i1, int i2, const double* p0, const double* p1,
-                                           const double* p2, double* w0, double* w1, double* w2) {
-  double d2 = INFINITY, wa, wb;
-  *w0 = 1.0, *w1 = 0.0, *w2 = 0.0;
-  double s = edge_w(p, i0, p0, i1, p1, &wa, &wb);
-  if (s < d2) d2 = s, *w0 = wa, *w1 = wb, *w2 = 0.0;
-  s = edge_w(p, i1, p1, i2, p2, &wa, &wb);
-  if (s < d2) d2 = s, *w0 = 0.0, *w1 = wa, *w2 = wb;
-  s = edge_w(p, i2, p2, i0, p0, &wa, &wb);
-  if (s < d2) d2 = s, *w0 = wb, *w1 = 0.0, *w2 = wa;
-  double e1[3], e2[3], n[3], w[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) e1[c] = p1[c] - p0[c], e2[c] = p2[c] - p0[c], w[c] = p[c] - p0[c];
-  cross3(e1, e2, n);
-  const double f0 = edge_fn(p, p0, p1, n), f1 = edge_fn(p, p1, p2, n), f2 = edge_fn(p, p2, p0, n);
-  if (f0 >= 0.0 && f1 >= 0.0 && f2 >= 0.0) {
-    const double h = dot3(w, n);
-    const double plane = h * h / dot3(n, n);
-    const double W = (f0 + f1) + f2;
-    if (plane < d2 && W > 0.0) {  // a NaN (n = 0) loses
-      *w0 = f1 / W;  // the edge function of an edge weighs the vertex opposite
-      *w1 = f2 / W;
-      *w2 = f0 / W;
-    }
-  }
-}
-
+// ---- channels at the closest point of a given triangle ----------------------------------------------------------------------
 struct TransferArgs {
   int V, F, C, N;
   const float* vertices;
@@ -194,7 +120,7 @@ __global__ __launch_bounds__(256) void transfer_kernel(TransferArgs a) {
     return;
   }
   double w0, w1, w2;
-  triangle_w(p, i0, i1, i2, p0, p1, p2, &w0, &w1, &w2);
+  triangle_closest<true>(p, i0, i1, i2, p0, p1, p2, &w0, &w1, &w2);
   a.bary[2 * (size_t)q] = (float)w1;
   a.bary[2 * (size_t)q + 1] = (float)w2;
   const float *v0 = a.values + (size_t)i0 * a.C, *v1 = a.values + (size_t)i1 * a.C, *v2 = a.values + (size_t)i2 * a.C;

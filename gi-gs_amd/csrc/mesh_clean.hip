@@ -27,10 +27,12 @@
 //   progress    A pass that sets *changed lowers the parent of at least one vertex that was a root, so the number of
 //               roots falls: at most V passes in any schedule.  The host's cap is far lower (mesh.py, DESIGN.md
 //               "Cleaning meshes") and reaching it is an error, never a result.
-#include "gigs_internal.h"
+#include "mesh_grid.h"  // item, in_range, blocks_for
 
 namespace gigs {
 namespace mesh_clean {
+
+using namespace gigs::mesh_common;
 
 // the root of x's chain.  Ends by itself: x strictly decreases; p outside [0, x) (a root, or corrupt input) stops it.
 __device__ __forceinline__ int root_of(const int* parent, int x) {
@@ -41,21 +43,11 @@ __device__ __forceinline__ int root_of(const int* parent, int x) {
   }
 }
 
-// this thread's item of n, or -1: the index is formed and compared unsigned, so n close to 2^31 cannot wrap it
-__device__ __forceinline__ int item(int n) {
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  return i < (unsigned)n ? (int)i : -1;
-}
-
-__device__ __forceinline__ bool face_valid(int a, int b, int c, int V) {
-  return a >= 0 && a < V && b >= 0 && b < V && c >= 0 && c < V;
-}
-
 __global__ __launch_bounds__(256) void hook_kernel(int V, int F, const int* __restrict__ faces, int* parent, int* changed) {
-  const int f = item(F);
+  const int f = item<256>(F);
   if (f < 0) return;
   const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  if (!face_valid(a, b, c, V)) return;  // never dereferenced
+  if (!in_range(a, b, c, V)) return;  // never dereferenced
   const int ra = root_of(parent, a), rb = root_of(parent, b), rc = root_of(parent, c);
   const int m = min(ra, min(rb, rc));
   if (ra == m && rb == m && rc == m) return;
@@ -66,7 +58,7 @@ __global__ __launch_bounds__(256) void hook_kernel(int V, int F, const int* __re
 }
 
 __global__ __launch_bounds__(256) void flatten_kernel(int V, int* parent) {
-  const int v = item(V);
+  const int v = item<256>(V);
   if (v < 0) return;
   // no root changes during this kernel and every concurrent store replaces an entry by a vertex further down the same
   // chain, so the walk reaches v's root whichever of the two values it reads
@@ -79,12 +71,12 @@ __global__ __launch_bounds__(256) void flatten_kernel(int V, int* parent) {
 // their number, the others one atomic each.
 __global__ __launch_bounds__(256) void count_kernel(int V, int F, const int* __restrict__ faces, const int* __restrict__ parent,
                                                     int* __restrict__ face_label, int* count, int* invalid) {
-  const int f = item(F);
+  const int f = item<256>(F);
   int label = -2;  // -2: no face, -1: an invalid face
   if (f >= 0) {
     const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
     label = -1;
-    if (face_valid(a, b, c, V)) {
+    if (in_range(a, b, c, V)) {
       const int r = parent[a];
       label = (r >= 0 && r < V) ? r : -1;  // a flat parent array never takes the second branch
     }
@@ -109,11 +101,11 @@ __global__ __launch_bounds__(256) void count_kernel(int V, int F, const int* __r
 __global__ __launch_bounds__(256) void mark_kernel(int V, int F, const int* __restrict__ faces, const int* __restrict__ face_label,
                                                    const uint8_t* __restrict__ root_keep, int* __restrict__ face_keep,
                                                    int* vertex_keep) {
-  const int f = item(F);
+  const int f = item<256>(F);
   if (f < 0) return;
   const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
   const int r = face_label[f];
-  const bool keep = face_valid(a, b, c, V) && r >= 0 && r < V && root_keep[r] != 0;
+  const bool keep = in_range(a, b, c, V) && r >= 0 && r < V && root_keep[r] != 0;
   face_keep[f] = keep ? 1 : 0;
   if (keep) {
     vertex_keep[a] = 1;  // plain stores of the same value
@@ -132,7 +124,7 @@ struct MeshOut {
 __global__ __launch_bounds__(256) void compact_vertices_kernel(int V, MeshIn in, const int* __restrict__ vertex_keep,
                                                                const int* __restrict__ vertex_offsets, int capacity, MeshOut out,
                                                                int* overflow) {
-  const int v = item(V);
+  const int v = item<256>(V);
   if (v < 0 || vertex_keep[v] == 0) return;
   const int o = vertex_offsets[v];
   if (o < 0 || o >= capacity) {
@@ -155,16 +147,16 @@ __global__ __launch_bounds__(256) void compact_faces_kernel(int V, int F, const 
                                                             const int* __restrict__ face_keep,
                                                             const int* __restrict__ face_offsets, int vertex_capacity,
                                                             int face_capacity, int* __restrict__ out_faces, int* overflow) {
-  const int f = item(F);
+  const int f = item<256>(F);
   if (f < 0 || face_keep[f] == 0) return;
   const int o = face_offsets[f];
   const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  if (o < 0 || o >= face_capacity || !face_valid(a, b, c, V)) {
+  if (o < 0 || o >= face_capacity || !in_range(a, b, c, V)) {
     *overflow = 1;
     return;
   }
   const int na = vertex_offsets[a], nb = vertex_offsets[b], nc = vertex_offsets[c];
-  if (vertex_keep[a] == 0 || vertex_keep[b] == 0 || vertex_keep[c] == 0 || !face_valid(na, nb, nc, vertex_capacity)) {
+  if (vertex_keep[a] == 0 || vertex_keep[b] == 0 || vertex_keep[c] == 0 || !in_range(na, nb, nc, vertex_capacity)) {
     *overflow = 1;  // a kept face on a vertex that was not kept, or a new index outside the vertex outputs
     return;
   }
@@ -172,8 +164,6 @@ __global__ __launch_bounds__(256) void compact_faces_kernel(int V, int F, const 
   out_faces[3 * (size_t)o + 1] = nb;
   out_faces[3 * (size_t)o + 2] = nc;
 }
-
-inline unsigned blocks_for(int n) { return ((unsigned)n + 255u) / 256u; }
 
 }  // namespace mesh_clean
 }  // namespace gigs

@@ -16,7 +16,8 @@
 //                 A lane group per query would share one query's faces among its lanes, but the lists hold a dozen faces
 //                 where a group wants 16 or 64, and the (d^2, index) minimum would need a cross-lane reduction per shell.
 //                 One-wave blocks: a block retires with its slowest wave, and an outlier query keeps only its own wave.
-#include "mesh_grid.h"  // the vector helpers, the hash and the grid arithmetic, shared with mesh_raycast.hip
+#include "mesh_triangle.h"  // triangle_closest, shared with mesh_atlas.hip; through it mesh_grid.h: the per-thread and vector
+                            // helpers, the hash, and the grid arithmetic shared with mesh_raycast.hip
 
 namespace gigs {
 namespace mesh_distance {
@@ -146,61 +147,6 @@ __global__ __launch_bounds__(256) void grid_pairs_kernel(Grid g, int V, int F, c
 }
 
 // ---- closest ---------------------------------------------------------------------------------------------------------------
-// d^2 from p to the segment a -> b
-__device__ __forceinline__ double segment_d2(const double* p, const double* a, const double* b) {
-  double ab[3], ap[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) ab[c] = b[c] - a[c], ap[c] = p[c] - a[c];
-  const double t = dot3(ap, ab), den = dot3(ab, ab);
-  if (t <= 0.0) return dot3(ap, ap);
-  if (t >= den) {
-    double bp[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) bp[c] = p[c] - b[c];
-    return dot3(bp, bp);
-  }
-  const double s = t / den;
-  double q[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) q[c] = ap[c] - s * ab[c];
-  return dot3(q, q);
-}
-
-// every segment is walked from its lower vertex index, so two faces that share an edge get the same bits from it
-__device__ __forceinline__ double edge_d2(const double* p, int ia, const double* a, int ib, const double* b) {
-  return ia > ib ? segment_d2(p, b, a) : segment_d2(p, a, b);
-}
-
-__device__ __forceinline__ double edge_fn(const double* p, const double* a, const double* b, const double* n) {
-  double ab[3], ap[3], c[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) ab[k] = b[k] - a[k], ap[k] = p[k] - a[k];
-  cross3(ab, ap, c);
-  return dot3(c, n);
-}
-
-__device__ __forceinline__ double triangle_d2(const double* p, const int* idx, const double* p0, const double* p1,
-                                              const double* p2) {
-  double d2 = INFINITY;
-  double s = edge_d2(p, idx[0], p0, idx[1], p1);
-  if (s < d2) d2 = s;
-  s = edge_d2(p, idx[1], p1, idx[2], p2);
-  if (s < d2) d2 = s;
-  s = edge_d2(p, idx[2], p2, idx[0], p0);
-  if (s < d2) d2 = s;
-  double e1[3], e2[3], n[3], w[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) e1[c] = p1[c] - p0[c], e2[c] = p2[c] - p0[c], w[c] = p[c] - p0[c];
-  cross3(e1, e2, n);
-  const bool inside = edge_fn(p, p0, p1, n) >= 0.0 && edge_fn(p, p1, p2, n) >= 0.0 && edge_fn(p, p2, p0, n) >= 0.0;
-  if (inside) {
-    const double h = dot3(w, n);
-    const double plane = h * h / dot3(n, n);
-    if (plane < d2) d2 = plane;  // a NaN (n = 0) loses
-  }
-  return d2;
-}
-
 struct ClosestArgs {
   Grid g;
   int V, F, N;
@@ -263,7 +209,7 @@ __global__ __launch_bounds__(kClosestBlock) void closest_kernel(ClosestArgs a) {
       load3(a.vertices, idx[0], p0);
       load3(a.vertices, idx[1], p1);
       load3(a.vertices, idx[2], p2);
-      const double d2 = triangle_d2(p, idx, p0, p1, p2);
+      const double d2 = triangle_closest<false>(p, idx[0], idx[1], idx[2], p0, p1, p2);
       if (d2 < best2 || (d2 == best2 && (int)f < bestf)) best2 = d2, bestf = (int)f;
     }
   };

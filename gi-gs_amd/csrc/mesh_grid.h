@@ -1,6 +1,8 @@
-// mesh_grid.h -- what mesh_distance.hip and mesh_raycast.hip share on the device: the float64 vector helpers, the counter
-// hash, the triangle grid's cell arithmetic (include/gigs_hip.h, "Comparing meshes", 4) and the host-side argument check of
-// a grid.  Header-only; every function is the one mesh_distance.hip had, so its kernels keep their bits.
+// mesh_grid.h -- what the mesh units share.  gigs::mesh_common, for mesh_clean, mesh_simplify, mesh_distance, mesh_raycast
+// and mesh_atlas: this thread's item, the index range check, the float64 vector helpers, the counter hash and the block
+// count of a launch.  gigs::mesh_distance, for mesh_distance and mesh_raycast: the triangle grid's cell arithmetic
+// (include/gigs_hip.h, "Comparing meshes", 4) and the host-side argument check of a grid; Grid is named by their kernels'
+// signatures, so it keeps its namespace.  Header-only; nothing here is a symbol of the library.
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -8,10 +10,9 @@
 #include "gigs_internal.h"
 
 namespace gigs {
-namespace mesh_distance {
+namespace mesh_common {
 
-constexpr int kGridAxis = 256;
-
+// this thread's item of n, or -1: the index is formed and compared unsigned, so n close to 2^31 cannot wrap it
 template <unsigned kBlock>
 __device__ __forceinline__ int item(int n) {
   const unsigned i = blockIdx.x * kBlock + threadIdx.x;
@@ -40,6 +41,22 @@ __device__ __forceinline__ void load3(const float* v, int i, double* p) {
   p[2] = (double)v[3 * (size_t)i + 2];
 }
 
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+  return z ^ (z >> 31);
+}
+
+inline unsigned blocks_for(int n, unsigned block = 256u) { return ((unsigned)n + block - 1u) / block; }
+
+}  // namespace mesh_common
+
+namespace mesh_distance {
+
+using namespace gigs::mesh_common;
+
+constexpr int kGridAxis = 256;
+
 struct Grid {
   double lo[3], cell;
   int G[3];
@@ -62,14 +79,6 @@ __device__ __forceinline__ int cell_at(double lo, double cell, int G, double x) 
 }
 
 __device__ __forceinline__ double plane_at(double lo, double cell, int k) { return lo + (double)k * cell; }
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
-}
-
-inline unsigned blocks_for(int n, unsigned block = 256u) { return ((unsigned)n + block - 1u) / block; }
 
 // the grid of a call, or false
 inline bool make_grid(const float* lo, double cell, const int* dims, Grid* g) {

@@ -24,7 +24,8 @@
 namespace gigs {
 namespace mesh_raycast {
 
-using namespace gigs::mesh_distance;
+using namespace gigs::mesh_common;    // item, in_range, finite3, dot3, cross3, load3, mix64, blocks_for
+using namespace gigs::mesh_distance;  // Grid, cell_at, plane_at, make_grid
 
 constexpr double kGuard = 0x1p-40;  // a face is a candidate only if dn^2 > kGuard (d.d)(n.n)
 constexpr double kSlack = 0x1p-26;  // sigma = kSlack (M + max |o_a|)

@@ -10,9 +10,7 @@
 //   addresses     Every index read from `faces`, from a sort order, from an offset table or out of a pair key is compared
 //                 with its range before it is used.  A violation cannot come from mesh.simplify; it sets *overflow and the
 //                 thread stores nothing (gigs_mesh_compact's convention).
-#include <cfloat>
-
-#include "gigs_internal.h"
+#include "mesh_grid.h"  // item, in_range, blocks_for
 
 namespace gigs {
 namespace mesh_simplify {
@@ -22,16 +20,7 @@ constexpr float kCellLimit = 2097152.0f;  // 2^21: cell coordinates lie in [0, 2
 constexpr long long kCellMask = (1LL << kCellBits) - 1;
 constexpr long long kNoPair = 0x7fffffffffffffffLL;  // sorts behind every (cluster, face) pair
 
-// this thread's item of n, or -1: the index is formed and compared unsigned, so n close to 2^31 cannot wrap it
-template <unsigned kBlock>
-__device__ __forceinline__ int item(int n) {
-  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-  return i < (unsigned)n ? (int)i : -1;
-}
-
-__device__ __forceinline__ bool in_range(int a, int b, int c, int n) {
-  return a >= 0 && a < n && b >= 0 && b < n && c >= 0 && c < n;
-}
+using namespace gigs::mesh_common;
 
 __global__ __launch_bounds__(256) void keys_kernel(int V, const float* __restrict__ vertices, float ox, float oy, float oz,
                                                    float inv, long long* __restrict__ keys) {
@@ -240,8 +229,6 @@ __global__ __launch_bounds__(kSolveBlock) void solve_kernel(SolveArgs p) {
   p.out_roughness[k] = (float)(sr / n);
   p.out_metallic[k] = (float)(st / n);
 }
-
-inline unsigned blocks_for(int n, unsigned block = 256u) { return ((unsigned)n + block - 1u) / block; }
 
 }  // namespace mesh_simplify
 }  // namespace gigs

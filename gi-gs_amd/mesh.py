@@ -83,6 +83,16 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _p(t):
+    return t.data_ptr() if t.numel() else None
+
+
+def _sized(dev, v: int, f: int) -> Mesh:
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    return Mesh(torch.empty((v, 3), **f32), torch.empty((f, 3), **i32), torch.empty((v, 3), **f32),
+                torch.empty((v, 3), **f32), torch.empty((v,), **f32), torch.empty((v,), **f32))
+
+
 class TSDFVolume:
     """Samples s(i,j,k) = lo + (i,j,k) voxel, dims = (Gx, Gy, Gz), x fastest.  `tsdf` (initially 1), `weight` (0) and
     `attr_weight` (0) are [Gz,Gy,Gx] tensors; the eight attributes are kept planar ([8,Gz,Gy,Gx]: the hot pair tsdf /
@@ -185,13 +195,11 @@ class TSDFVolume:
         """The zero level set by naive surface nets: one vertex per active cell (ascending cell index), two triangles per
         crossed grid edge whose four cells are valid (ordered by sample index, then axis)."""
         dev = self.device
-        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-        empty = Mesh(torch.empty((0, 3), **f32), torch.empty((0, 3), **i32), torch.empty((0, 3), **f32),
-                     torch.empty((0, 3), **f32), torch.empty((0,), **f32), torch.empty((0,), **f32))
+        i32 = dict(dtype=torch.int32, device=dev)
         Gx, Gy, Gz = self.dims
         cells = (Gx - 1) * (Gy - 1) * (Gz - 1)
         if cells == 0:
-            return empty
+            return _sized(dev, 0, 0)
         lib = gigs_lib.lib()
         grid = self._grid()
         with torch.cuda.device(dev):
@@ -203,11 +211,10 @@ class TSDFVolume:
             quad_incl = torch.cumsum(quads, 0, dtype=torch.int32)
             V, Q = (int(x) for x in torch.stack((cell_incl[-1], quad_incl[-1])).cpu())  # the one read-back
             if V == 0:
-                return empty
+                return _sized(dev, 0, 0)
             cell_off, quad_off = cell_incl - flags, quad_incl - quads
             F = 2 * Q
-            m = Mesh(torch.empty((V, 3), **f32), torch.empty((F, 3), **i32), torch.empty((V, 3), **f32),
-                     torch.empty((V, 3), **f32), torch.empty((V,), **f32), torch.empty((V,), **f32))
+            m = _sized(dev, V, F)
             overflow = torch.zeros(1, **i32)
             gigs_lib.check(lib.gigs_mesh_write(C.byref(grid), float(min_weight), cell_off.data_ptr(), quad_off.data_ptr(), V, F,
                                                m.vertices.data_ptr(), m.normals.data_ptr(), m.albedo.data_ptr(),
@@ -298,16 +305,6 @@ def _mesh_tensors(mesh, what: str) -> Mesh:
     return Mesh(*(t.contiguous() for t in m))
 
 
-def _p(t):
-    return t.data_ptr() if t.numel() else None
-
-
-def _sized(dev, v: int, f: int) -> Mesh:
-    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-    return Mesh(torch.empty((v, 3), **f32), torch.empty((f, 3), **i32), torch.empty((v, 3), **f32),
-                torch.empty((v, 3), **f32), torch.empty((v,), **f32), torch.empty((v,), **f32))
-
-
 def _label(m: Mesh):
     """-> (labels [V], face_labels [F], count [V] per root, invalid (device int [1]), rounds)."""
     dev = m.vertices.device
@@ -362,6 +359,36 @@ def keep_threshold(counts, keep_largest: int = 0, min_faces: int = 0) -> int:
     return max(int(min_faces), c_k, 1)
 
 
+def _compact(what: str, src: Mesh, faces, face_labels, root_keep, extra=(), check=None):
+    """The tail of clean() and simplify(): keeps the valid faces of `faces` ([F,3], indices into the vertex rows of `src`;
+    src.faces is not read) whose label ([F]) has root_keep ([rows] uint8) set, and the vertices they reference:
+    gigs_mesh_mark, two scans, the one read-back, gigs_mesh_compact.  `extra`: 1-D int32 device tensors fetched in that
+    read-back; `check(values)` sees their values before anything is sized.  -> (Mesh, values).  Errors name `what`."""
+    dev = src.vertices.device
+    V, F = int(src.vertices.shape[0]), int(faces.shape[0])
+    i32 = dict(dtype=torch.int32, device=dev)
+    lib = gigs_lib.lib()
+    face_keep, vertex_keep = torch.empty(F, **i32), torch.empty(V, **i32)
+    gigs_lib.check(lib.gigs_mesh_mark(V, F, _p(faces), _p(face_labels), _p(root_keep), _p(face_keep), _p(vertex_keep), _stream()),
+                   "mesh_mark")
+    v_incl = torch.cumsum(vertex_keep, 0, dtype=torch.int32)
+    f_incl = torch.cumsum(face_keep, 0, dtype=torch.int32)
+    V2, F2, *got = (int(x) for x in torch.cat((v_incl[-1:], f_incl[-1:], *extra)).cpu())
+    if check is not None:
+        check(got)
+    out = _sized(dev, V2, F2)
+    if V2 and F2:
+        v_off, f_off = v_incl - vertex_keep, f_incl - face_keep
+        overflow = torch.zeros(1, **i32)
+        gigs_lib.check(lib.gigs_mesh_compact(
+            V, F, _p(src.vertices), _p(src.normals), _p(src.albedo), _p(src.roughness), _p(src.metallic), _p(faces),
+            _p(vertex_keep), _p(v_off), _p(face_keep), _p(f_off), V2, F2, _p(out.vertices), _p(out.normals), _p(out.albedo),
+            _p(out.roughness), _p(out.metallic), _p(out.faces), overflow.data_ptr(), _stream()), "mesh_compact")
+        if int(overflow.item()) != 0:
+            raise MeshOverflow("%s: an index left the outputs (%d vertices, %d faces)" % (what, V2, F2))
+    return out, got
+
+
 def clean(mesh, keep_largest: int = 0, min_faces: int = 0) -> Tuple[Mesh, Dict]:
     """(the mesh without the components of fewer than keep_threshold faces, a report).  Invalid faces and the vertices no
     kept face references go too; with keep_largest = min_faces = 0 nothing else does.  Kept vertices and faces stay in
@@ -370,36 +397,17 @@ def clean(mesh, keep_largest: int = 0, min_faces: int = 0) -> Tuple[Mesh, Dict]:
     m = _mesh_tensors(mesh, "clean")
     dev = m.vertices.device
     V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
-    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-
-    sized = lambda v, f: _sized(dev, v, f)  # noqa: E731
     if V == 0 or F == 0:
-        return sized(0, 0), dict(components=0, components_kept=0, faces_removed=F, vertices_removed=V, invalid_faces=F,
-                                 rounds=0, threshold=keep_threshold([], keep_largest, min_faces))
-    lib = gigs_lib.lib()
+        return _sized(dev, 0, 0), dict(components=0, components_kept=0, faces_removed=F, vertices_removed=V, invalid_faces=F,
+                                       rounds=0, threshold=keep_threshold([], keep_largest, min_faces))
     with torch.cuda.device(dev):
         labels, face_labels, count, invalid, rounds = _label(m)
         comp = count > 0
         thr = keep_threshold(count[comp], keep_largest, min_faces)
         root_keep = (count >= thr).to(torch.uint8)
-        face_keep, vertex_keep = torch.empty(F, **i32), torch.empty(V, **i32)
-        gigs_lib.check(lib.gigs_mesh_mark(V, F, _p(m.faces), _p(face_labels), _p(root_keep), _p(face_keep), _p(vertex_keep),
-                                          _stream()), "mesh_mark")
-        v_incl = torch.cumsum(vertex_keep, 0, dtype=torch.int32)
-        f_incl = torch.cumsum(face_keep, 0, dtype=torch.int32)
-        V2, F2, n_comp, n_kept, n_invalid = (int(x) for x in torch.stack(
-            (v_incl[-1], f_incl[-1], comp.sum().to(torch.int32), root_keep.sum().to(torch.int32), invalid[0])).cpu())
-        out = sized(V2, F2)
-        v_off, f_off = v_incl - vertex_keep, f_incl - face_keep
-        if V2 and F2:
-            overflow = torch.zeros(1, **i32)
-            gigs_lib.check(lib.gigs_mesh_compact(
-                V, F, _p(m.vertices), _p(m.normals), _p(m.albedo), _p(m.roughness), _p(m.metallic), _p(m.faces), _p(vertex_keep),
-                _p(v_off), _p(face_keep), _p(f_off), V2, F2, _p(out.vertices), _p(out.normals),
-                _p(out.albedo), _p(out.roughness), _p(out.metallic), _p(out.faces), overflow.data_ptr(), _stream()),
-                "mesh_compact")
-            if int(overflow.item()) != 0:
-                raise MeshOverflow("clean: an index left the outputs (%d vertices, %d faces)" % (V2, F2))
+        n = lambda t: t.sum().to(torch.int32).reshape(1)  # noqa: E731
+        out, (n_comp, n_kept, n_invalid) = _compact("clean", m, m.faces, face_labels, root_keep, (n(comp), n(root_keep), invalid))
+    V2, F2 = int(out.vertices.shape[0]), int(out.faces.shape[0])
     return out, dict(components=n_comp, components_kept=n_kept, faces_removed=F - F2, vertices_removed=V - V2,
                      invalid_faces=n_invalid, rounds=rounds, threshold=thr)
 
@@ -557,26 +565,14 @@ def simplify(mesh, cell, origin=None, reg: float = 1e-3) -> Tuple[Mesh, Dict]:
         gigs_lib.check(lib.gigs_mesh_face_dedupe(F, _p(triples), _p(order), _p(faces), flags[1:].data_ptr(), flags.data_ptr(),
                                                  _stream()), "mesh_face_dedupe")
         # clean(.., 0, 0)'s compaction without its labelling: every face that is still a triple is kept
-        face_keep, vertex_keep = torch.empty(F, **i32), torch.empty(Cn, **i32)
-        label, root_keep = torch.zeros(F, **i32), torch.ones(Cn, dtype=torch.uint8, device=dev)
-        gigs_lib.check(lib.gigs_mesh_mark(Cn, F, _p(faces), _p(label), _p(root_keep), _p(face_keep), _p(vertex_keep), _stream()),
-                       "mesh_mark")
-        v_incl = torch.cumsum(vertex_keep, 0, dtype=torch.int32)
-        f_incl = torch.cumsum(face_keep, 0, dtype=torch.int32)
-        V2, F2, n_invalid, n_collapsed, overflow, n_dup, n_unclustered = (int(x) for x in torch.cat(
-            (torch.stack((v_incl[-1], f_incl[-1])), counts, flags, cl.unclustered.to(torch.int32).reshape(1))).cpu())
-        if overflow != 0:
-            raise MeshOverflow("simplify: an index left its range (%d clusters, %d faces)" % (Cn, F))
-        out = _sized(dev, V2, F2)
-        if V2 and F2:
-            v_off, f_off = v_incl - vertex_keep, f_incl - face_keep
-            flag = torch.zeros(1, **i32)
-            gigs_lib.check(lib.gigs_mesh_compact(
-                Cn, F, _p(cv.vertices), _p(cv.normals), _p(cv.albedo), _p(cv.roughness), _p(cv.metallic), _p(faces),
-                _p(vertex_keep), _p(v_off), _p(face_keep), _p(f_off), V2, F2, _p(out.vertices), _p(out.normals), _p(out.albedo),
-                _p(out.roughness), _p(out.metallic), _p(out.faces), flag.data_ptr(), _stream()), "mesh_compact")
-            if int(flag.item()) != 0:
-                raise MeshOverflow("simplify: an index left the outputs (%d vertices, %d faces)" % (V2, F2))
+        def solved(got):  # its own flag, from the same read-back and before anything is compacted
+            if got[2] != 0:
+                raise MeshOverflow("simplify: an index left its range (%d clusters, %d faces)" % (Cn, F))
+
+        out, (n_invalid, n_collapsed, _, n_dup, n_unclustered) = _compact(
+            "simplify", cv, faces, torch.zeros(F, **i32), torch.ones(Cn, dtype=torch.uint8, device=dev),
+            (counts, flags, cl.unclustered.to(torch.int32).reshape(1)), solved)
+    V2, F2 = int(out.vertices.shape[0]), int(out.faces.shape[0])
     return out, report(cl.origin, clusters=Cn, vertices=V2, faces=F2, faces_collapsed=n_collapsed, faces_duplicate=n_dup,
                        faces_invalid=n_invalid, vertices_unclustered=n_unclustered)
 
@@ -714,10 +710,7 @@ def _closest(points: torch.Tensor, m: Mesh, grid, max_distance):
     if grid is None:  # no usable face: nothing is launched
         flags[1] = (~torch.isfinite(points).all(1)).sum()
         return distance, face, flags
-    lo = torch.from_numpy(grid.lo.astype(np.float64)).to(dev)
-    G = torch.tensor(grid.dims, dtype=torch.float64, device=dev)
-    c = torch.nan_to_num(((points.double() - lo) / grid.cell).floor(), nan=0.0).clamp_(min=0).minimum(G - 1).long()
-    order = torch.sort((c[:, 2] * grid.dims[1] + c[:, 1]) * grid.dims[0] + c[:, 0]).indices  # lanes of a wave share lists
+    order = _cell_order(points.double(), grid)  # lanes of a wave share lists
     c_lo, c_dims = _c_grid(grid.lo, grid.dims)
     gigs_lib.check(gigs_lib.lib().gigs_mesh_closest(
         int(m.vertices.shape[0]), int(m.faces.shape[0]), _p(m.vertices), _p(m.faces), c_lo, grid.cell, c_dims,
@@ -742,11 +735,7 @@ def closest_point(points, mesh_b, cell=None, max_distance=None, grid=None) -> Tu
     _check_max_distance(max_distance)
     m = _mesh_tensors(mesh_b, "closest_point")
     dev = m.vertices.device
-    if not isinstance(points, torch.Tensor) or points.device != dev:
-        raise RuntimeError("closest_point: points must be a tensor on the mesh's device: gigs-hip has no CPU path")
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("closest_point: points must be [N,3] float32, got %s %s" % (tuple(points.shape), points.dtype))
-    points = points.contiguous()
+    points = _check_points(points, dev, "closest_point")
     N = int(points.shape[0])
     if N == 0:  # nothing is launched, so nothing is known about the faces either
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
@@ -759,10 +748,8 @@ def closest_point(points, mesh_b, cell=None, max_distance=None, grid=None) -> Tu
         flags = [int(x) for x in flags.cpu()]  # the one read-back
         if flags[2] != 0:
             raise MeshOverflow("closest_point: an index left its range (%d faces, %d queries)" % (int(m.faces.shape[0]), N))
-    report = dict(n=N, far=flags[0], queries_invalid=flags[1],
-                  faces_skipped=grid.faces_skipped if grid is not None else int(m.faces.shape[0]),
-                  cell=grid.cell if grid is not None else 0.0, dims=list(grid.dims) if grid is not None else [0, 0, 0],
-                  pairs=int(grid.pairs.shape[0]) if grid is not None else 0)
+    report = dict(n=N, far=flags[0], queries_invalid=flags[1])
+    report.update(_grid_report(grid, int(m.faces.shape[0])))
     return distance, face, report
 
 
@@ -891,14 +878,10 @@ def raycast(origins, directions, mesh, t_max=None, cell=None, grid=None):
         raise ValueError("raycast: t_max must be >= 0 or None, got %r" % (t_max,))
     m = _mesh_tensors(mesh, "raycast")
     dev = m.vertices.device
-    for name, r in (("origins", origins), ("directions", directions)):
-        if not isinstance(r, torch.Tensor) or r.device != dev:
-            raise RuntimeError("raycast: %s must be a tensor on the mesh's device: gigs-hip has no CPU path" % name)
-        if r.dtype != torch.float32 or r.dim() != 2 or r.shape[1] != 3:
-            raise ValueError("raycast: %s must be [N,3] float32, got %s %s" % (name, tuple(r.shape), r.dtype))
+    origins = _check_points(origins, dev, "raycast", "origins")
+    directions = _check_points(directions, dev, "raycast", "directions")
     if origins.shape[0] != directions.shape[0]:
         raise ValueError("raycast: %d origins, %d directions" % (origins.shape[0], directions.shape[0]))
-    origins, directions = origins.contiguous(), directions.contiguous()
     N = int(origins.shape[0])
     if N == 0:  # nothing is launched, so nothing is known about the faces either
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
@@ -1131,11 +1114,11 @@ def _check_values(values, m: Mesh, what: str) -> torch.Tensor:
     return values.contiguous()
 
 
-def _check_points(points, dev, what: str) -> torch.Tensor:
+def _check_points(points, dev, what: str, name: str = "points") -> torch.Tensor:
     if not isinstance(points, torch.Tensor) or points.device != dev:
-        raise RuntimeError("%s: points must be a tensor on the mesh's device: gigs-hip has no CPU path" % what)
+        raise RuntimeError("%s: %s must be a tensor on the mesh's device: gigs-hip has no CPU path" % (what, name))
     if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("%s: points must be [N,3] float32, got %s %s" % (what, tuple(points.shape), points.dtype))
+        raise ValueError("%s: %s must be [N,3] float32, got %s %s" % (what, name, tuple(points.shape), points.dtype))
     return points.contiguous()
 
 

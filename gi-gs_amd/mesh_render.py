@@ -3,6 +3,7 @@ texture atlas (mesh.Atlas, the OBJ + PNGs of texture_mesh.py): a visibility-buff
 behind them is the existing one, unchanged.
 
     mesh_arrays(mesh)                 a mesh.Mesh, a dict of scene_io.read_mesh_ply or a path -> checked numpy arrays
+    device_mesh(source, device)       those arrays as a mesh.Mesh on the device: what the mesh tools load a PLY with
     MeshRasterizer(mesh)(cam)         gigs_mesh_project, gigs_mesh_raster, gigs_mesh_resolve -> opacity, depth, pos, normal,
                                       normal_view, albedo, roughness, metallic ([C,H,W]) and tri_id [H,W] (-1 = background)
     TexturedMeshRasterizer(mesh, uvs, albedo, orm, normal)(cam)   the same rasterizer over a mesh whose materials live in a
@@ -34,6 +35,7 @@ import numpy as np
 import torch
 
 import gigs_lib
+import mesh as mesh_ops
 import relight
 from diff_gaussian_rasterization import _C as _ops, _derive_normal
 
@@ -69,6 +71,12 @@ def mesh_arrays(mesh) -> Dict[str, np.ndarray]:
         if out[k].shape[0] != V:
             raise ValueError("mesh_arrays: %s has %d rows for %d vertices" % (k, out[k].shape[0], V))
     return out
+
+
+def device_mesh(source, device) -> mesh_ops.Mesh:
+    """mesh_arrays(source) as a mesh.Mesh of tensors on `device`."""
+    arrays = mesh_arrays(source)
+    return mesh_ops.Mesh(*(torch.from_numpy(arrays[k]).to(device) for k in mesh_ops.Mesh._fields))
 
 
 def _stream():

@@ -56,8 +56,7 @@ def simplify_mesh(args) -> Dict:
     if not torch.cuda.is_available():
         raise RuntimeError("simplify_mesh needs the GPU")
     dev = torch.device("cuda", torch.cuda.current_device())
-    arrays = mesh_render.mesh_arrays(scene_io.read_mesh_ply(args.input))
-    m = mesh.Mesh(*(torch.from_numpy(arrays[k]).to(dev) for k in mesh.Mesh._fields))
+    m = mesh_render.device_mesh(args.input, dev)
     extra = {}
     cell = args.cell
     if cell is None:

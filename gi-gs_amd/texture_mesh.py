@@ -134,9 +134,8 @@ def texture_mesh(args) -> Dict:
 
     def load(path):
         read = scene_io.read_mesh_ply(path)
-        arrays = mesh_render.mesh_arrays(read)
         occ = torch.from_numpy(read["occlusion"]).to(dev) if "occlusion" in read else None
-        return mesh.Mesh(*(torch.from_numpy(arrays[k]).to(dev) for k in mesh.Mesh._fields)), occ
+        return mesh_render.device_mesh(read, dev), occ
 
     src, src_occ = load(args.input)
     res: Dict = dict(input=args.input)

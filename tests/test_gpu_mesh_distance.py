@@ -363,8 +363,7 @@ def test_tools(tmp_path):
     assert json.load(open(out)) == rep == json.loads(json.dumps(rep))
 
     def load(path):
-        arrays = mesh_render.mesh_arrays(scene_io.read_mesh_ply(path))
-        return mesh.Mesh(*(torch.from_numpy(arrays[k]).to(DEV) for k in mesh.Mesh._fields))
+        return mesh_render.device_mesh(path, DEV)
 
     direct = mesh.distance(load(raw), load(plain["path"]), samples=3000, seed=4, taus=(0.01, 0.05), max_distance=0.5)
     assert {k: rep[k] for k in direct} == direct and rep["a"] == raw and rep["b"] == plain["path"]

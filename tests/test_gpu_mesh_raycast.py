@@ -308,7 +308,7 @@ def test_extract_mesh_bake_and_bake_mesh_tool(tmp_path):
         assert np.array_equal(baked[k], arrays[k], equal_nan=True), k
     # the same bake on the device mesh the tool had: extract again through the API pieces is the PLY's arrays but for the
     # albedo's 8 bits, which the bake does not read
-    m = mesh.Mesh(*(torch.from_numpy(arrays[k]).to(DEV) for k in mesh.Mesh._fields))
+    m = mesh_render.device_mesh(arrays, DEV)
     occ, rep = mesh.bake_occlusion(m, rays=64)
     assert np.array_equal(_bits(baked["occlusion"]), _bits(occ)) and rep == r2["occlusion"]
     assert 0.0 < float(occ.mean()) < 1.0

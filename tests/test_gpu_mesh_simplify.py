@@ -106,6 +106,23 @@ def test_simplify_equals_the_restatement(name):
         assert report["clusters"] == report["vertices_in"] == 98 and report["faces"] == 192
 
 
+def test_clean_of_a_simplified_mesh_changes_nothing():
+    """simplify() and clean() end in one compaction (mesh._compact): what it left has no invalid face and no vertex without
+    a face, so clean(.., 0, 0) of it -- the labelling, then the same tail -- returns it bit for bit, for every shared case."""
+    import mesh
+    cases = sr.shared_cases()
+    assert sorted(cases) == sorted(["cube", "plane", "identity", "debris", "sheets", "fan", "strip"])
+    for name, (d, cell, origin) in cases.items():
+        simple = mesh.simplify(_to_mesh(d), cell, origin)[0]
+        again, report = mesh.clean(simple, 0, 0)
+        assert (report["faces_removed"], report["vertices_removed"], report["invalid_faces"]) == (0, 0, 0), name
+        want, got = _to_dict(simple), _to_dict(again)
+        assert got["faces"].dtype == np.int32 and np.array_equal(got["faces"], want["faces"]), name
+        for k in FLOAT_KEYS:
+            assert got[k].dtype == np.float32 and got[k].shape == want[k].shape, (name, k)
+            assert np.array_equal(_bits(got[k]), _bits(want[k])), (name, k)
+
+
 @pytest.mark.parametrize("ratio,clusters,faces,vertices", [(2, 195, 376, 193), (3, 89, 166, 86)])
 def test_blob_mesh(ratio, clusters, faces, vertices):
     m, d, h = _blob()
