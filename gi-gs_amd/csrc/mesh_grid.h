@@ -1,6 +1,6 @@
-// mesh_grid.h -- what the mesh units share.  gigs::mesh_common, for mesh_clean, mesh_simplify, mesh_distance, mesh_raycast
-// and mesh_atlas: this thread's item, the index range check, the float64 vector helpers, the counter hash and the block
-// count of a launch.  gigs::mesh_distance, for mesh_distance and mesh_raycast: the triangle grid's cell arithmetic
+// mesh_grid.h -- what the mesh units share.  gigs::mesh_common, for mesh_clean, mesh_simplify, mesh_distance, mesh_raycast,
+// mesh_light and mesh_atlas: this thread's item, the index range check, the float64 vector helpers, the counter hash and the block
+// count of a launch.  gigs::mesh_distance, for mesh_distance and mesh_ray.h: the triangle grid's cell arithmetic
 // (include/gigs_hip.h, "Comparing meshes", 4) and the host-side argument check of a grid; Grid is named by their kernels'
 // signatures, so it keeps its namespace.  Header-only; nothing here is a symbol of the library.
 #pragma once

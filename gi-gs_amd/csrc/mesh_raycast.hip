@@ -19,140 +19,10 @@
 //                 directions, one direction per lane, and OWNS the vertex: the 64 lanes share origin and first cells (their
 //                 first loads hit the same lines), a chunk's hits are __popcll(__ballot(hit)), and lane 0 stores the count
 //                 and the float32 value itself -- no per-vertex atomic, no second kernel, no LDS.
-#include "mesh_grid.h"
+#include "mesh_ray.h"  // ray_triangle, traverse, the hemisphere of a vertex: shared with mesh_light.hip
 
 namespace gigs {
 namespace mesh_raycast {
-
-using namespace gigs::mesh_common;    // item, in_range, finite3, dot3, cross3, load3, mix64, blocks_for
-using namespace gigs::mesh_distance;  // Grid, cell_at, plane_at, make_grid
-
-constexpr double kGuard = 0x1p-40;  // a face is a candidate only if dn^2 > kGuard (d.d)(n.n)
-constexpr double kSlack = 0x1p-26;  // sigma = kSlack (M + max |o_a|)
-constexpr unsigned kWave = 64;
-
-struct MeshView {
-  Grid g;
-  int V, F;
-  const float* vertices;
-  const int* faces;
-  const long long *cell_start, *pairs;
-  long long n_pairs;
-  double M;  // the largest |coordinate| of a corner of a usable face: the scale of sigma
-};
-
-struct Hit {
-  double t, w1, w2, sum;
-  int face;
-};
-
-// w of the edge a -> b (a, b: the two ends minus the ray's origin): the ends are taken in ascending vertex index, so two
-// faces that share an edge compute the same bits with opposite signs
-__device__ __forceinline__ double edge_w(const double* d, int ia, const double* a, int ib, const double* b) {
-  double c[3];
-  if (ia < ib) {
-    cross3(a, b, c);
-    return dot3(d, c);
-  }
-  cross3(b, a, c);
-  return -dot3(d, c);
-}
-
-__device__ __forceinline__ double min3(double a, double b, double c) { return fmin(a, fmin(b, c)); }
-__device__ __forceinline__ double max3(double a, double b, double c) { return fmax(a, fmax(b, c)); }
-
-// the ray (o, d) against one face; true if the face is accepted, then h->t, w1, w2, sum are its
-__device__ __forceinline__ bool ray_triangle(const double* o, const double* d, double dd, double sigma, double tmax,
-                                             const int* idx, const double* p0, const double* p1, const double* p2, Hit* h) {
-  double a0[3], a1[3], a2[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) a0[c] = p0[c] - o[c], a1[c] = p1[c] - o[c], a2[c] = p2[c] - o[c];
-  const double w0 = edge_w(d, idx[1], a1, idx[2], a2);
-  const double w1 = edge_w(d, idx[2], a2, idx[0], a0);
-  const double w2 = edge_w(d, idx[0], a0, idx[1], a1);
-  const bool pos = w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0, neg = w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0;
-  if (!(pos || neg) || (pos && neg)) return false;  // pos && neg: all three are zero
-  double e1[3], e2[3], n[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) e1[c] = p1[c] - p0[c], e2[c] = p2[c] - p0[c];
-  cross3(e1, e2, n);
-  const double dn = dot3(d, n);
-  if (!(dn * dn > kGuard * (dd * dot3(n, n)))) return false;
-  const double t = dot3(a0, n) / dn;
-  if (!(t >= 0.0 && t <= tmax)) return false;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {  // the hit point lies in the face's box, widened by sigma
-    const double x = o[c] + t * d[c];
-    if (!(x >= min3(p0[c], p1[c], p2[c]) - sigma && x <= max3(p0[c], p1[c], p2[c]) + sigma)) return false;
-  }
-  h->t = t, h->w1 = w1, h->w2 = w2, h->sum = (w0 + w1) + w2;
-  return true;
-}
-
-__device__ __forceinline__ double pick(const double* p, int a) { return a == 0 ? p[0] : (a == 1 ? p[1] : p[2]); }
-__device__ __forceinline__ int pick(const int* p, int a) { return a == 0 ? p[0] : (a == 1 ? p[1] : p[2]); }
-
-// The nearest accepted face of the ray, by slabs along its dominant axis.  *best: t = +inf, face = -1 on entry.  Returns
-// false if an index left its range.
-__device__ __forceinline__ bool traverse(const MeshView& m, const double* o, const double* d, double tmax, Hit* best) {
-  const Grid& g = m.g;
-  const double ax = fabs(d[0]), ay = fabs(d[1]), az = fabs(d[2]);
-  const int A = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2), U = A == 2 ? 0 : A + 1, W = A == 0 ? 2 : A - 1;
-  const double oA = pick(o, A), dA = pick(d, A), oU = pick(o, U), dU = pick(d, U), oW = pick(o, W), dW = pick(d, W);
-  const double loA = pick(g.lo, A), loU = pick(g.lo, U), loW = pick(g.lo, W), cell = g.cell;
-  const int GA = pick(g.G, A), GU = pick(g.G, U), GW = pick(g.G, W);
-  const int stride[3] = {1, g.G[0], g.G[0] * g.G[1]};
-  const int sA = pick(stride, A), sU = pick(stride, U), sW = pick(stride, W);
-  const double sigma = kSlack * (m.M + max3(fabs(o[0]), fabs(o[1]), fabs(o[2])));
-  const double s2 = 2.0 * sigma, s3 = 3.0 * sigma;
-  const double dd = dot3(d, d);
-  const bool up = dA > 0.0;
-  const int step = up ? 1 : -1;
-  bool ok = true;
-  for (int k = cell_at(loA, cell, GA, up ? oA - s3 : oA + s3); k >= 0 && k < GA; k += step) {
-    const double ta = ((plane_at(loA, cell, k) - s2) - oA) / dA, tb = ((plane_at(loA, cell, k + 1) + s2) - oA) / dA;
-    double tn = fmin(ta, tb), tf = fmax(ta, tb);
-    if (tf < 0.0) continue;                 // the slab lies behind the origin
-    if (tn > tmax || best->t < tn) break;  // every later slab starts later still
-    tn = fmax(tn, 0.0), tf = fmin(tf, tmax);
-    const double u_n = oU + tn * dU, u_f = oU + tf * dU, w_n = oW + tn * dW, w_f = oW + tf * dW;
-    const int u0 = cell_at(loU, cell, GU, fmin(u_n, u_f) - s2), u1 = cell_at(loU, cell, GU, fmax(u_n, u_f) + s2);
-    const int w0 = cell_at(loW, cell, GW, fmin(w_n, w_f) - s2), w1 = cell_at(loW, cell, GW, fmax(w_n, w_f) + s2);
-    for (int w = w0; w <= w1; w++)
-      for (int u = u0; u <= u1; u++) {
-        const long long c = (long long)k * sA + (long long)u * sU + (long long)w * sW;
-        const long long s = m.cell_start[c], e = m.cell_start[c + 1];
-        if (s < 0 || e < s || e > m.n_pairs) {
-          ok = false;
-          continue;
-        }
-        for (long long r = s; r < e; r++) {
-          const long long key = m.pairs[r];
-          const long long f = key & 0xffffffffLL;
-          if ((key >> 32) != c || f >= m.F) {
-            ok = false;
-            continue;
-          }
-          const int idx[3] = {m.faces[3 * (size_t)f], m.faces[3 * (size_t)f + 1], m.faces[3 * (size_t)f + 2]};
-          if (!in_range(idx[0], idx[1], idx[2], m.V)) {
-            ok = false;
-            continue;
-          }
-          double p0[3], p1[3], p2[3];
-          load3(m.vertices, idx[0], p0);
-          load3(m.vertices, idx[1], p1);
-          load3(m.vertices, idx[2], p2);
-          Hit h;
-          if (ray_triangle(o, d, dd, sigma, tmax, idx, p0, p1, p2, &h) &&
-              (h.t < best->t || (h.t == best->t && (int)f < best->face))) {
-            *best = h;
-            best->face = (int)f;
-          }
-        }
-      }
-  }
-  return ok;
-}
 
 // ---- raycast ---------------------------------------------------------------------------------------------------------------
 struct RaycastArgs {
@@ -215,11 +85,8 @@ __global__ __launch_bounds__(kWave) void bake_kernel(BakeArgs a) {
     *a.overflow = 1;
     return;
   }
-  double p[3], n[3];
-  load3(a.m.vertices, (int)v, p);
-  load3(a.normals, (int)v, n);
-  const double n2 = dot3(n, n);
-  if (!finite3(p) || !(n2 >= 1.0 - 0x1p-10 && n2 <= 1.0 + 0x1p-10)) {
+  Hemisphere h;
+  if (!hemisphere(a.m.vertices, a.normals, a.table, a.R, a.K, a.seed, a.bias, v, lane, &h)) {
     if (lane == 0) {
       a.occlusion[v] = 1.0f;
       a.hits[v] = 0;
@@ -227,27 +94,15 @@ __global__ __launch_bounds__(kWave) void bake_kernel(BakeArgs a) {
     }
     return;
   }
-  // the branch-free orthonormal basis of Duff et al. (2017)
-  const double sign = copysign(1.0, n[2]);
-  const double fa = -1.0 / (sign + n[2]);
-  const double fb = (n[0] * n[1]) * fa;
-  const double T[3] = {1.0 + ((sign * n[0]) * n[0]) * fa, sign * fb, (-sign) * n[0]};
-  const double B[3] = {fb, sign + (n[1] * n[1]) * fa, -n[1]};
-  double o[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) o[c] = p[c] + a.bias * n[c];
-  const unsigned k = (unsigned)(mix64((a.seed << 32) + (unsigned long long)v) % (unsigned long long)a.K);
-  const float* row = a.table + 3 * ((size_t)k * a.R + lane);
+  const float* row = h.row;
   int hits = 0;
   bool ok = true;
   for (int j = 0; j < a.R; j += kWave, row += 3 * kWave) {
-    const double x = (double)row[0], y = (double)row[1], z = (double)row[2];
     double d[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) d[c] = (x * T[c] + y * B[c]) + z * n[c];
+    hemisphere_direction(h, row, d);
     Hit best;
     best.t = INFINITY, best.face = -1;
-    ok = traverse(a.m, o, d, a.tmax, &best) && ok;
+    ok = traverse(a.m, h.o, d, a.tmax, &best) && ok;
     hits += __popcll(__ballot(best.face >= 0));
   }
   if (__ballot(!ok) != 0ULL) {
@@ -259,18 +114,6 @@ __global__ __launch_bounds__(kWave) void bake_kernel(BakeArgs a) {
     a.occlusion[v] = (float)((double)(a.R - hits) / (double)a.R);
     atomicAdd(a.counts, (unsigned long long)hits);
   }
-}
-
-inline bool make_view(int n_vertices, int n_faces, const float* vertices, const int* faces, const float* lo, double cell,
-                      const int* dims, const long long* cell_start, const long long* pair_keys, long long n_pairs, double scale,
-                      MeshView* m) {
-  if (!(scale >= 0.0 && scale <= DBL_MAX) || n_vertices < 0 || n_faces < 0 || n_pairs < 0 || !make_grid(lo, cell, dims, &m->g) || !cell_start ||
-      (n_pairs > 0 && (!pair_keys || !faces || !vertices)))
-    return false;
-  m->V = n_vertices, m->F = n_faces, m->vertices = vertices, m->faces = faces;
-  m->cell_start = cell_start, m->pairs = pair_keys, m->n_pairs = n_pairs;
-  m->M = scale;
-  return true;
 }
 
 }  // namespace mesh_raycast
@@ -305,8 +148,7 @@ int gigs_mesh_bake_occlusion(int n_vertices, int n_faces, const float* vertices,
                              float* occlusion, int* hits, unsigned long long* counts, int* overflow, void* stream) {
   using namespace gigs::mesh_raycast;
   BakeArgs a;
-  if (!counts || !overflow || !(max_distance >= 0.0) || !(std::fabs(bias) <= DBL_MAX) || n_rays < 64 || n_rays > 1024 ||
-      n_rays % 64 != 0 || n_rotations < 1 || n_rotations > 64 ||
+  if (!counts || !overflow || !hemisphere_args(n_rays, n_rotations, max_distance, bias) ||
       !make_view(n_vertices, n_faces, vertices, faces, lo, cell, dims, cell_start, pair_keys, n_pairs, scale, &a.m))
     return gigs_internal_fail(GIGS_ERR_INVALID, "mesh_bake_occlusion: bad argument");
   hipStream_t s = (hipStream_t)stream;

@@ -6,6 +6,7 @@ their depth and material planes fused into a truncated signed distance volume, a
                                      [--trunc_voxels 4] [--min_weight 2] [--opacity_min 0.5] [--no_carve]
                                      [--split train] [--keep_largest K] [--min_faces M] [--simplify R]
                                      [--bake_occlusion RAYS] [--ao_distance D] [--texture B]
+                                     [--bake_light a.hdr [--bounces 1] [--sky_res 32] [--light_rays 256]]
                                      -o mesh.ply                                                           (CLI)
     extract_mesh(args) -> {...}                                                                            (API)
 
@@ -25,6 +26,10 @@ before, byte for byte; needs --simplify R and an -o that ends in .obj) writes th
 of a PLY: mesh.bake_atlas stores the materials of the level set BEFORE the simplification in an atlas of charts of B texels
 over the simplified mesh (texture_mesh.py's files), and --bake_occlusion then bakes that unsimplified mesh, whose occlusion
 becomes the first channel of the ORM image.  The result gains texture (the atlas's report), files and texture_s.
+--bake_light a.hdr (or .npy; off by default, and then every byte is what it was) runs mesh.bake_light under that map with
+--bounces, --sky_res and --light_rays as bake_mesh.py --light does (bias, seed and rotations are the bake's defaults here:
+this tool has no flags for them), on the mesh the occlusion is baked on: the PLY gains irradiance_r / _g / _b, or, with --texture, the
+atlas gains a light-map written as <name>_lightmap.hdr.  The result gains light (the bake's report) and light_s.
 """
 from __future__ import annotations
 
@@ -60,6 +65,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--bake_occlusion", type=int, default=0, help="rays per vertex of the occlusion bake, a multiple of 64 (0: off)")
     p.add_argument("--ao_distance", type=float, default=None, help="how far an occluder counts (default: 0.1 of the longest axis)")
     p.add_argument("--texture", type=int, default=0, help="texels along a chart of the texture atlas; needs --simplify and a .obj output (0: off)")
+    p.add_argument("--bake_light", type=str, default=None, help="an environment map (.hdr or .npy) to bake light under (default: off)")
+    p.add_argument("--bounces", type=int, default=1, help="diffuse inter-reflections of the light bake")
+    p.add_argument("--sky_res", type=int, default=32, help="texels an edge of the sky cube the light bake looks up")
+    p.add_argument("--light_rays", type=int, default=256, help="rays per vertex of the light bake, a multiple of 64 in [64, 1024]")
     p.add_argument("-o", "--output", type=str, default="mesh.ply")
     return p
 
@@ -126,17 +135,25 @@ def extract_mesh(args) -> Dict:
                                                    max_distance=args.ao_distance)
             sync()
         t4b = time.perf_counter()
+        irradiance = lit = None
+        if getattr(args, "bake_light", None):
+            import bake_mesh
+            irradiance, lit = mesh.bake_light(level_set if args.texture else m, bake_mesh.load_sky(args.bake_light, args.sky_res, dev),
+                                              rays=args.light_rays, bounces=args.bounces)
+            lit["map"] = args.bake_light
+            sync()
+        t4l = time.perf_counter()
         path = args.output if os.path.isabs(args.output) else os.path.join(args.model_path, args.output)
         textured = files = None
         if args.texture:
             import texture_mesh
-            atlas, textured = mesh.bake_atlas(m, level_set, block=args.texture, occlusion=occlusion)
+            atlas, textured = mesh.bake_atlas(m, level_set, block=args.texture, occlusion=occlusion, extra=irradiance)
             sync()
             t4t = time.perf_counter()
-            files = texture_mesh.save_textured_mesh(path, m, atlas)
+            files = texture_mesh.save_textured_mesh(path, m, atlas, lightmap=irradiance is not None)
         else:
-            t4t = t4b
-            scene_io.save_mesh_ply(path, *m, occlusion=occlusion)
+            t4t = t4l
+            scene_io.save_mesh_ply(path, *m, occlusion=occlusion, irradiance=irradiance)
         t5 = time.perf_counter()
     finally:
         pipeline._collect_idle()
@@ -153,7 +170,9 @@ def extract_mesh(args) -> Dict:
     if baked is not None:
         res.update(occlusion=baked, bake_s=round(t4b - t4s, 4))
     if textured is not None:
-        res.update(texture=textured, files=files, texture_s=round(t4t - t4b, 4))
+        res.update(texture=textured, files=files, texture_s=round(t4t - t4l, 4))
+    if lit is not None:
+        res.update(light=lit, light_s=round(t4l - t4b, 4))
     return res
 
 

@@ -28,6 +28,11 @@
     occlusion_directions(rays, rotations)   the bake's default direction table: a cosine-weighted spiral lattice (host)
     bake_occlusion(mesh, rays, ...)      per-vertex ambient occlusion, 1 = open: a wave per vertex casts `rays`
                                          cosine-distributed rays and counts the hits (gigs_mesh_bake_occlusion)
+    trace_hemispheres(mesh, rays, ...)   the same rays with every hit recorded: face, side and weights
+                                         (gigs_mesh_trace_hemisphere)
+    gather_light(mesh, hits, cube, bounces)   per-vertex irradiance under an environment cube over those records: the
+                                         shadowed sky plus `bounces` diffuse inter-reflections, a launch per pass
+                                         (gigs_mesh_gather_light); bake_light runs both, sky_cube pools a light's cube (torch)
     atlas_layout(F, block, width)        the texture atlas of equal per-face charts, face_uvs(F, layout) its UVs (host)
     transfer_attributes(points, src, values)   per-vertex channels of src interpolated at the closest point of src to
                                          every query (gigs_mesh_closest, gigs_mesh_transfer)
@@ -912,29 +917,41 @@ def occlusion_directions(rays: int = 256, rotations: int = 16) -> np.ndarray:
     return np.stack([r[None] * np.cos(phi), r[None] * np.sin(phi), np.broadcast_to(z, phi.shape)], -1).astype(np.float32)
 
 
-def _bake_occlusion(mesh, rays=256, max_distance=None, bias=None, seed=0, rotations=16, directions=None, cell=None, grid=None,
-                    sort: bool = True):
-    """bake_occlusion with the per-vertex hit counts: -> (occlusion [V] float32, hits [V] int32, report)."""
-    m = _mesh_tensors(mesh, "bake_occlusion")
-    dev = m.vertices.device
+def _hemisphere_args(what: str, rays, rotations, directions, max_distance, bias):
+    """The checks bake_occlusion and trace_hemispheres share.  -> (R, K, the table [K,R,3] float32 numpy)."""
     if directions is None:
         R, K = int(rays), int(rotations)
     else:
         directions = np.ascontiguousarray(directions, dtype=np.float32)
         if directions.ndim != 3 or directions.shape[2] != 3:
-            raise ValueError("bake_occlusion: directions must be [K,R,3], got %s" % (directions.shape,))
+            raise ValueError("%s: directions must be [K,R,3], got %s" % (what, directions.shape,))
         K, R = int(directions.shape[0]), int(directions.shape[1])
     if R < 64 or R > BAKE_MAX_RAYS or R % 64 != 0:
-        raise ValueError("bake_occlusion: rays must be a multiple of 64 in [64, %d], got %d" % (BAKE_MAX_RAYS, R))
+        raise ValueError("%s: rays must be a multiple of 64 in [64, %d], got %d" % (what, BAKE_MAX_RAYS, R))
     if K < 1 or K > BAKE_MAX_ROTATIONS:
-        raise ValueError("bake_occlusion: rotations must lie in [1, %d], got %d" % (BAKE_MAX_ROTATIONS, K))
+        raise ValueError("%s: rotations must lie in [1, %d], got %d" % (what, BAKE_MAX_ROTATIONS, K))
     if directions is None:
         directions = occlusion_directions(R, K)
     elif not (np.isfinite(directions).all() and (directions[..., 2] >= 0).all()):
-        raise ValueError("bake_occlusion: directions must be finite with z >= 0")
+        raise ValueError("%s: directions must be finite with z >= 0" % what)
     for name, x in (("max_distance", max_distance), ("bias", bias)):
         if x is not None and not (float(x) >= 0 and np.isfinite(float(x))):
-            raise ValueError("bake_occlusion: %s must be finite and >= 0 or None, got %r" % (name, x))
+            raise ValueError("%s: %s must be finite and >= 0 or None, got %r" % (what, name, x))
+    return R, K, directions
+
+
+def _no_normal(m: Mesh) -> torch.Tensor:
+    """[V] bool: the vertices the hemisphere kernels give no rays (a position that is not finite, a normal not of unit length)."""
+    n2 = (m.normals.double() ** 2).sum(1)
+    return ~(torch.isfinite(m.vertices).all(1) & (n2 >= 1.0 - 2.0 ** -10) & (n2 <= 1.0 + 2.0 ** -10))
+
+
+def _bake_occlusion(mesh, rays=256, max_distance=None, bias=None, seed=0, rotations=16, directions=None, cell=None, grid=None,
+                    sort: bool = True):
+    """bake_occlusion with the per-vertex hit counts: -> (occlusion [V] float32, hits [V] int32, report)."""
+    m = _mesh_tensors(mesh, "bake_occlusion")
+    dev = m.vertices.device
+    R, K, directions = _hemisphere_args("bake_occlusion", rays, rotations, directions, max_distance, bias)
     V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     occlusion = torch.ones(V, dtype=torch.float32, device=dev)
@@ -949,9 +966,7 @@ def _bake_occlusion(mesh, rays=256, max_distance=None, bias=None, seed=0, rotati
             grid = triangle_grid(m, cell)
         report.update(_grid_report(grid, F))
         if grid is None:  # no usable face: every vertex is open and nothing is launched
-            n2 = (m.normals.double() ** 2).sum(1)
-            ok = torch.isfinite(m.vertices).all(1) & (n2 >= 1.0 - 2.0 ** -10) & (n2 <= 1.0 + 2.0 ** -10)
-            report["no_normal"] = int((~ok).sum().item())
+            report["no_normal"] = int(_no_normal(m).sum().item())
             return occlusion, hits, report
         if max_distance is None:
             max_distance = 0.1 * (max(grid.dims) * grid.cell)
@@ -989,6 +1004,182 @@ def bake_occlusion(mesh, rays=256, max_distance=None, bias=None, seed=0, rotatio
     return occlusion, report
 
 
+# ---- baking light: the hemispheres traced once, then gathers over the records (include/gigs_hip.h, "Baking light") ---------
+TRACE_MEMORY_LIMIT = 8 << 30  # bytes of records (12 V R) trace_hemispheres allocates without being told otherwise
+SKY_MAX_RES = 4096
+
+
+class HemisphereHits(NamedTuple):
+    face: torch.Tensor       # [V,R] int32: -1 a miss, f a front hit of face f, -2 - f a back hit
+    bary: torch.Tensor       # [V,R,2] float32: the weights of the face's second and third vertex at the hit
+    directions: np.ndarray   # [K,R,3] float32: the table the rays came from
+    seed: int
+    rays: int
+    rotations: int
+
+
+def trace_hemispheres(mesh, rays=256, max_distance=None, bias=None, seed=0, rotations=16, directions=None, cell=None, grid=None,
+                      memory_limit=TRACE_MEMORY_LIMIT):
+    """(HemisphereHits, report): bake_occlusion's rays -- the same table, rotation, frame, origin and no_normal rule -- with
+    what every ray hit RECORDED in place of a count, for gather_light to light the mesh any number of times without
+    tracing again.  face [V,R] int32: -1 a miss, f a hit on the FRONT of face f (direction . geometric normal < 0; the
+    extraction orients faces outward), -2 - f a hit on its back, which carries no light; bary [V,R,2] float32 as
+    mesh.raycast's.  max_distance=None traces without a limit, because light rays see the whole scene; a finite value works
+    as in bake_occlusion, and a hit beyond it is a miss that sees the sky.  bias defaults to 1e-4 of the longest axis of the
+    grid's box, the value bake_occlusion ends up with (a convention).  The records take 12 V R bytes; above `memory_limit`
+    (8 GiB) the call raises ValueError instead of tracing in chunks.  A no_normal vertex has -1 in all its records.  Report:
+    n, misses, front_hits, back_hits, no_normal, rays, rotations, seed, max_distance (None: unlimited), bias, record_bytes,
+    faces_skipped, cell, dims, pairs.  V == 0 or a mesh with no usable face launches nothing.  One read-back."""
+    R, K, directions = _hemisphere_args("trace_hemispheres", rays, rotations, directions, max_distance, bias)
+    first = (mesh if isinstance(mesh, Mesh) else Mesh(*mesh)).vertices  # a malformed mesh is _mesh_tensors' to report, below
+    V = int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() == 2 else 0
+    if 12 * V * R > int(memory_limit):  # before the device check: the limit is about the arguments alone
+        raise ValueError("trace_hemispheres: the records of %d vertices x %d rays take %d bytes, more than memory_limit = %d; "
+                         "trace fewer rays or a simplified mesh (a trace in chunks would re-trace for every bounce)"
+                         % (V, R, 12 * V * R, int(memory_limit)))
+    m = _mesh_tensors(mesh, "trace_hemispheres")
+    dev = m.vertices.device
+    V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    face = torch.full((V, R), -1, dtype=torch.int32, device=dev)
+    bary = torch.zeros((V, R, 2), dtype=torch.float32, device=dev)
+    hits = HemisphereHits(face, bary, directions, seed, R, K)
+    report = dict(n=V, misses=0, front_hits=0, back_hits=0, no_normal=0, rays=R, rotations=K, seed=seed,
+                  max_distance=None if max_distance is None else float(max_distance), bias=0.0 if bias is None else float(bias),
+                  record_bytes=12 * V * R)
+    if V == 0:
+        report.update(_grid_report(None, F))
+        return hits, report
+    with torch.cuda.device(dev):
+        if grid is None:
+            grid = triangle_grid(m, cell)
+        report.update(_grid_report(grid, F))
+        if grid is None:  # no usable face: every ray of a vertex with a normal sees the sky and nothing is launched
+            report["no_normal"] = int(_no_normal(m).sum().item())
+            report["misses"] = R * (V - report["no_normal"])
+            return hits, report
+        if bias is None:  # bake_occlusion's: 1e-3 of its default max_distance, 0.1 of the grid's longest axis
+            bias = 1e-3 * (0.1 * (max(grid.dims) * grid.cell))
+        report["bias"] = float(bias)
+        order = _cell_order(m.vertices.double(), grid)
+        table = torch.from_numpy(directions).to(dev)
+        counts = torch.zeros(5, dtype=torch.int64, device=dev)  # misses, front, back, no normal; overflow (an int32 in its low half)
+        c_lo, c_dims = _c_grid(grid.lo, grid.dims)
+        gigs_lib.check(gigs_lib.lib().gigs_mesh_trace_hemisphere(
+            V, F, _p(m.vertices), _p(m.normals), _p(m.faces), c_lo, grid.cell, c_dims, _p(grid.cell_start), _p(grid.pairs),
+            int(grid.pairs.shape[0]), _scale(grid), _p(order), _p(table), R, K, seed,
+            float("inf") if max_distance is None else float(max_distance), float(bias), _p(face), _p(bary), counts.data_ptr(),
+            counts[4:].data_ptr(), _stream()), "mesh_trace_hemisphere")
+        got = [int(x) for x in counts.cpu()]  # the one read-back
+        if got[4] != 0:
+            raise MeshOverflow("trace_hemispheres: an index left its range (%d vertices, %d faces)" % (V, F))
+        report["misses"], report["front_hits"], report["back_hits"], report["no_normal"] = got[:4]
+    return hits, report
+
+
+def _check_cube(cube, what: str) -> torch.Tensor:
+    if not isinstance(cube, torch.Tensor):
+        raise ValueError("%s: the cube must be a [6,n,n,3] float32 tensor, got %s" % (what, type(cube).__name__))
+    if (cube.dtype != torch.float32 or cube.dim() != 4 or cube.shape[0] != 6 or cube.shape[1] != cube.shape[2] or cube.shape[3] != 3
+            or not 1 <= cube.shape[1] <= SKY_MAX_RES):
+        raise ValueError("%s: the cube must be [6,n,n,3] float32 with 1 <= n <= %d, got %s %s" % (what, SKY_MAX_RES,
+                                                                                                   tuple(cube.shape), cube.dtype))
+    cube = cube.detach()
+    if not bool((torch.isfinite(cube) & (cube >= 0)).all()):
+        raise ValueError("%s: the cube must be finite and >= 0" % what)
+    return cube.contiguous()
+
+
+def _gather_light(mesh, hits: HemisphereHits, cube, bounces: int = 1, reflectance=None):
+    """gather_light with every pass: -> (irradiance [bounces + 1, V, 3], radiosity likewise, report)."""
+    bounces = int(bounces)
+    if bounces < 0:
+        raise ValueError("gather_light: bounces must be >= 0, got %d" % bounces)
+    cube = _check_cube(cube, "gather_light")
+    m = _mesh_tensors(mesh, "gather_light")
+    dev = m.vertices.device
+    V, F = int(m.vertices.shape[0]), int(m.faces.shape[0])
+    if cube.device != dev:
+        raise RuntimeError("gather_light: the cube must be a tensor on the mesh's device: gigs-hip has no CPU path")
+    R, K = int(hits.rays), int(hits.rotations)
+    table = np.ascontiguousarray(hits.directions, dtype=np.float32)
+    if (not isinstance(hits.face, torch.Tensor) or hits.face.device != dev or hits.face.dtype != torch.int32
+            or tuple(hits.face.shape) != (V, R) or not isinstance(hits.bary, torch.Tensor) or hits.bary.device != dev
+            or hits.bary.dtype != torch.float32 or tuple(hits.bary.shape) != (V, R, 2) or table.shape != (K, R, 3)):
+        raise ValueError("gather_light: the records are not those of this mesh (%d vertices, %d rays, %d rotations)" % (V, R, K))
+    _hemisphere_args("gather_light", R, K, table, None, None)
+    if reflectance is None:
+        reflectance = m.albedo * (1.0 - m.metallic)[:, None]
+    elif (not isinstance(reflectance, torch.Tensor) or reflectance.device != dev or reflectance.dtype != torch.float32
+          or tuple(reflectance.shape) != (V, 3)):
+        raise ValueError("gather_light: reflectance must be a [%d,3] float32 tensor on the mesh's device" % V)
+    reflectance = reflectance.detach().contiguous()
+    n = int(cube.shape[1])
+    passes = torch.zeros((bounces + 1, V, 3), dtype=torch.float32, device=dev)
+    radiosity = torch.zeros_like(passes)
+    report = dict(n=V, rays=R, bounces=bounces, passes=bounces + 1, sky_res=n, mean_irradiance=[0.0] * (bounces + 1))
+    if V == 0:
+        return passes, radiosity, report
+    with torch.cuda.device(dev):
+        face, bary, d_table = hits.face.contiguous(), hits.bary.contiguous(), torch.from_numpy(table).to(dev)
+        overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        for b in range(bounces + 1):
+            gigs_lib.check(gigs_lib.lib().gigs_mesh_gather_light(
+                V, F, _p(m.vertices), _p(m.normals), _p(m.faces), _p(d_table), R, K, int(hits.seed) & 0xFFFFFFFFFFFFFFFF, _p(face),
+                _p(bary), n, _p(cube), _p(reflectance), radiosity[b - 1].data_ptr() if b else None, passes[b].data_ptr(),
+                radiosity[b].data_ptr(), overflow.data_ptr(), _stream()), "mesh_gather_light")
+        got = torch.cat((overflow.double(), passes.double().mean(dim=(1, 2)))).cpu().tolist()  # the one read-back
+        if got[0] != 0:
+            raise MeshOverflow("gather_light: a record or a face index left its range (%d vertices, %d faces)" % (V, F))
+        report["mean_irradiance"] = got[1:]
+    return passes, radiosity, report
+
+
+def gather_light(mesh, hits: HemisphereHits, cube, bounces: int = 1, reflectance=None, return_passes: bool = False):
+    """(irradiance [V,3] float32, report): the light every vertex receives from the environment `cube` ([6,n,n,3] float32,
+    finite and >= 0, the cube of the lights with the world's axes, looked up at the NEAREST texel: sky_cube makes one) over
+    the records of trace_hemispheres, after `bounces` diffuse inter-reflections.  The irradiance is the cosine-weighted MEAN
+    of the incoming radiance, the normalisation of the shade's diffuse cube.  Pass 0 is the shadowed sky: a ray that
+    escaped brings its sky texel, a ray that hit brings nothing.  Pass b adds, at every front hit, the radiosity
+    reflectance x I(b-1) of the face's vertices interpolated at the hit: a Jacobi iteration over the same rays, one launch
+    per pass, bounces + 1 in all (gigs_mesh_gather_light).  `reflectance` [V,3] float32 defaults to
+    albedo * (1 - metallic)[:, None].  return_passes=True returns [bounces + 1, V, 3], every pass.  A no_normal vertex gets
+    0.  The result is a pure function of the arguments: no float atomics, a fixed summation order.  Report: n, rays,
+    bounces, passes, sky_res, mean_irradiance (per pass, over vertices and channels).  V == 0 launches nothing.  One
+    read-back (after the cube's check)."""
+    passes, _, report = _gather_light(mesh, hits, cube, bounces, reflectance)
+    return (passes if return_passes else passes[-1]), report
+
+
+def bake_light(mesh, cube, rays=256, bounces=1, reflectance=None, max_distance=None, bias=None, seed=0, rotations=16,
+               directions=None, cell=None, grid=None, memory_limit=TRACE_MEMORY_LIMIT, return_passes: bool = False):
+    """(irradiance [V,3] float32, report): trace_hemispheres, then gather_light over its records; the report is the two
+    reports in one.  To light one mesh under several cubes, trace once and gather per cube: the bits are the same."""
+    hits, report = trace_hemispheres(mesh, rays, max_distance, bias, seed, rotations, directions, cell, grid, memory_limit)
+    irradiance, gathered = gather_light(mesh, hits, cube, bounces, reflectance, return_passes)
+    report.update(gathered)
+    return irradiance, report
+
+
+def sky_cube(light_or_base, res: int = 32) -> torch.Tensor:
+    """[6,res,res,3] float32: a light's base cube ([6,N,N,3], a CubemapLight or its `base`) average-pooled to `res` texels an
+    edge (N a multiple of res; res >= N returns the cube as it is) and clamped at 0, in torch: the sky gather_light looks up
+    at the nearest texel.  A coarser sky trades angular detail for less noise at a few hundred rays; the default of 32, and
+    the trade, are conventions, not measurements."""
+    base = getattr(light_or_base, "base", light_or_base)
+    if not isinstance(base, torch.Tensor) or base.dim() != 4 or base.shape[0] != 6 or base.shape[1] != base.shape[2] or base.shape[3] != 3:
+        raise ValueError("sky_cube: expected a [6,N,N,3] cube, got %s" % (tuple(base.shape) if isinstance(base, torch.Tensor) else type(base).__name__,))
+    base, N, res = base.detach().float(), int(base.shape[1]), int(res)
+    if res < 1:
+        raise ValueError("sky_cube: res must be >= 1, got %d" % res)
+    if res < N:
+        if N % res != 0:
+            raise ValueError("sky_cube: the cube's edge %d is no multiple of res = %d" % (N, res))
+        k = N // res
+        base = base.view(6, res, k, res, k, 3).mean(dim=(2, 4))
+    return base.clamp_min(0.0).contiguous()
+
+
 # ---- texturing: the atlas of per-face charts, texel -> surface point, transfer (include/gigs_hip.h, "Texturing meshes") ------
 TRANSFER_MAX_CHANNELS = 16
 ATLAS_MAX_BLOCK = 1024
@@ -1009,6 +1200,7 @@ class Atlas(NamedTuple):
     orm: torch.Tensor       # [3,H,W]: occlusion, roughness, metallic
     normal: torch.Tensor    # [3,H,W]: the world normal as interpolated, not normalised
     coverage: torch.Tensor  # [H,W] uint8: 1 where a texel was baked
+    extra: torch.Tensor = None  # [C,H,W]: bake_atlas' `extra` channels (a light-map, say), None without them
 
 
 def atlas_layout(F: int, block: int = 8, width=None) -> AtlasLayout:
@@ -1175,14 +1367,16 @@ def transfer_attributes(points, src, values, cell=None, max_distance=None, grid=
     return out, face, bary, distance, report
 
 
-def bake_atlas(dst, src, block: int = 8, width=None, occlusion=None, max_distance=None, cell=None, grid=None):
+def bake_atlas(dst, src, block: int = 8, width=None, occlusion=None, max_distance=None, cell=None, grid=None, extra=None):
     """(Atlas, report): the materials of the mesh `src` baked into a texture atlas over the mesh `dst` (a simplification of
     src, usually).  Every face of dst gets a chart of its own in atlas_layout(F, block, width); every texel of a chart
     stands for a point of its face (gigs_mesh_atlas_points; the one row of texels past the chart's long edge for the
     extrapolated point of the face's plane: the gutter), the closest face of src to that point is searched
     (triangle_grid(src) unless `grid` is passed, gigs_mesh_closest), and src's albedo, occlusion, roughness, metallic and
     normal are interpolated at the closest point (gigs_mesh_transfer, nine channels in one launch).  `occlusion`: [V_src]
-    float32 such as bake_occlusion's, 1 where None.  The normal plane holds the interpolated world normal as it is, not
+    float32 such as bake_occlusion's, 1 where None.  `extra`: [V_src, C] float32, C <= 7, more per-vertex channels of src (the
+    irradiance of bake_light, for a light-map) interpolated in the same launch and returned as Atlas.extra [C,H,W]; None
+    changes nothing.  The normal plane holds the interpolated world normal as it is, not
     normalised.  Texels of no face, of an unusable face of dst, or with no face of src within `max_distance` stay 0 with
     coverage 0.  max_distance=None searches without a limit: a texel far from src then walks O(G^3) cell headers alone
     (closest_point), which a dst that is a simplification of src never does.  The result is a pure function of (dst, src,
@@ -1200,6 +1394,13 @@ def bake_atlas(dst, src, block: int = 8, width=None, occlusion=None, max_distanc
     elif (not isinstance(occlusion, torch.Tensor) or occlusion.device != dev or occlusion.dtype != torch.float32
           or tuple(occlusion.shape) != (V,)):
         raise ValueError("bake_atlas: occlusion must be a [%d] float32 tensor on the mesh's device" % V)
+    Ce = 0
+    if extra is not None:
+        if (not isinstance(extra, torch.Tensor) or extra.device != dev or extra.dtype != torch.float32 or extra.dim() != 2
+                or extra.shape[0] != V or not 1 <= extra.shape[1] <= TRANSFER_MAX_CHANNELS - 9):
+            raise ValueError("bake_atlas: extra must be a [%d,C] float32 tensor on the mesh's device with 1 <= C <= %d"
+                             % (V, TRANSFER_MAX_CHANNELS - 9))
+        Ce = int(extra.shape[1])
     lay = atlas_layout(F, block, width)
     W, H = lay.width, lay.height
     report = dict(texels=W * H, baked=0, unbaked=W * H, far=0, queries_invalid=0, **lay._asdict())
@@ -1208,8 +1409,10 @@ def bake_atlas(dst, src, block: int = 8, width=None, occlusion=None, max_distanc
         if F == 0:
             z3 = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
             report.update(_grid_report(None, F_src), distance_mean=0.0, distance_max=0.0)
-            return Atlas(lay, uvs, z3, z3.clone(), z3.clone(), torch.zeros((H, W), dtype=torch.uint8, device=dev)), report
-        values = torch.cat((m.albedo, occlusion[:, None], m.roughness[:, None], m.metallic[:, None], m.normals), 1).contiguous()
+            return Atlas(lay, uvs, z3, z3.clone(), z3.clone(), torch.zeros((H, W), dtype=torch.uint8, device=dev),
+                         torch.zeros((Ce, H, W), dtype=torch.float32, device=dev) if Ce else None), report
+        values = torch.cat((m.albedo, occlusion[:, None], m.roughness[:, None], m.metallic[:, None], m.normals)
+                           + ((extra,) if Ce else ()), 1).contiguous()
         points, _, _, dest, flag = _atlas_points(d, lay)
         if grid is None:
             grid = triangle_grid(m, cell)
@@ -1225,8 +1428,8 @@ def bake_atlas(dst, src, block: int = 8, width=None, occlusion=None, max_distanc
     report.update(baked=baked, unbaked=W * H - baked, far=int(got[0]), queries_invalid=int(got[1]),
                   distance_mean=got[7] / got[9] if got[9] else 0.0, distance_max=got[8])
     report.update(_grid_report(grid, F_src))
-    planes = out.view(9, H, W)
-    return Atlas(lay, uvs, planes[0:3], planes[3:6], planes[6:9], coverage.view(H, W)), report
+    planes = out.view(9 + Ce, H, W)
+    return Atlas(lay, uvs, planes[0:3], planes[3:6], planes[6:9], coverage.view(H, W), planes[9:] if Ce else None), report
 
 
 def sample_atlas(atlas_planes: torch.Tensor, layout: AtlasLayout, face: torch.Tensor, bary: torch.Tensor) -> torch.Tensor:

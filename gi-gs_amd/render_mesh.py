@@ -3,7 +3,8 @@ its scene (mesh_render.py), and compared with the splat render it came from or w
 
     python gi-gs_amd/render_mesh.py -m <out> --mesh mesh.ply|mesh.obj [--checkpoint <out>/chkpntN.pth] [--hdri a.hdr b.hdr ...]
                                     [--rotations N] [--compare] [--reference_mesh other.ply|other.obj]
-                                    [--occlusion ssao|baked|both] [--split test] [--metallic --tone --gamma]      (CLI)
+                                    [--occlusion ssao|baked|both] [--split test] [--metallic --tone --gamma]
+                                    [--lighting baked [--bounces 1] [--sky_res 32] [--light_rays 256]]            (CLI)
     render_mesh(args) -> {...}                                                                                   (API)
 
 The scene path and the resolution come from <out>/cfg_args as in render_scene.py, command-line values first; a relative
@@ -28,6 +29,15 @@ what the shading is given: `ssao` (the default: screen-space, as for a PLY), `ba
 <out>/mesh_<split>/mesh_vs_mesh.json: per view and on average the intersection over union of the two coverages
 (tri_id >= 0), over the pixels both cover the PSNR of albedo, roughness, metallic and every relit image, and the mean
 angle between the two normal planes: texture_mesh.material_error's comparison, made in the image.
+
+--lighting baked (needs --hdri and a PLY; the first light) also renders the BAKED diffuse light of the mesh through the same
+cameras: mesh.bake_light traces the mesh once and gathers --bounces passes, a MeshRasterizer over the mesh whose albedo
+attribute is reflectance x irradiance puts that product through the existing resolve, and its albedo plane is written as
+<image_name>_baked_diffuse.png after linear_to_srgb.  mesh_<split>/baked_vs_screen.json holds, per view and on average, the
+PSNR (peak 1, over the pixels the mesh covers) of that plane against the screen-space diffuse of the same light -- shade_ssr's
+diffuse_rgb with the gamma epilogue, i.e. albedo x diffuse cube x SSAO -- for 0 bounces and for --bounces.  The shade looks
+its cubes up at (-n.y, n.z, -n.x); the bake's sky is the light's cube in that frame (shade_frame_sky), so both see one
+environment.
 """
 from __future__ import annotations
 
@@ -44,6 +54,7 @@ if __package__ in (None, ""):  # run as a script: make the package's modules imp
 
 G_PLANES = ("depth", "normal", "albedo", "roughness", "metallic", "occlusion")
 OCCLUSION_MODES = ("ssao", "baked", "both")  # mesh_render.OCCLUSION_MODES, without its imports
+LIGHTING_MODES = ("screen", "baked")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -64,6 +75,11 @@ def build_parser() -> argparse.ArgumentParser:
     for k, v in render_scene.GI_FLAGS.items():
         p.add_argument("--" + k, type=type(v), default=v)
     p.add_argument("--workers", type=int, default=12, help="PNG encoder threads (at most 16)")
+    p.add_argument("--lighting", choices=LIGHTING_MODES, default="screen",
+                   help="baked: also render the ray-cast diffuse light of mesh.bake_light and compare it with the screen-space one")
+    p.add_argument("--bounces", type=int, default=1, help="diffuse inter-reflections of the light bake")
+    p.add_argument("--sky_res", type=int, default=32, help="texels an edge of the sky cube the light bake looks up")
+    p.add_argument("--light_rays", type=int, default=256, help="rays per vertex of the light bake, a multiple of 64 in [64, 1024]")
     return p
 
 
@@ -110,7 +126,87 @@ def _check(args: Namespace) -> int:
         raise ValueError("--occlusion: one of %s, got %r" % (", ".join(OCCLUSION_MODES), occlusion))
     if occlusion != "ssao" and not is_textured(args.mesh):
         raise ValueError("--occlusion %s needs a textured mesh (.obj): a PLY has no baked channel" % occlusion)
+    lighting = getattr(args, "lighting", "screen")
+    if lighting not in LIGHTING_MODES:
+        raise ValueError("--lighting: one of %s, got %r" % (", ".join(LIGHTING_MODES), lighting))
+    if lighting == "baked":
+        if not args.hdri or is_textured(args.mesh):
+            raise ValueError("--lighting baked needs --hdri and a per-vertex mesh (.ply)")
+        if int(getattr(args, "bounces", 1)) < 0:
+            raise ValueError("--bounces: a count of inter-reflections, got %d" % int(args.bounces))
     return n_rot
+
+
+def shade_frame_sky(light, res: int):
+    """mesh.sky_cube(light, res) in the frame the shade looks its cubes up in: texel d of the result is the pooled cube's texel
+    at (-d.y, d.z, -d.x), the shade's swizzle of a world direction d.  The swizzle is a signed permutation of the axes, so it
+    maps texel centres onto texel centres and cube_texture_precise returns single texels."""
+    import torch
+
+    import mesh
+    from pbr.texture import cube_texture_precise
+    sky = mesh.sky_cube(light, res)
+    n, dev = int(sky.shape[1]), sky.device
+    t = (torch.arange(n, dtype=torch.float32, device=dev) + 0.5) / n * 2.0 - 1.0
+    q, p = torch.meshgrid(t, t, indexing="ij")  # [iy, ix]
+    one = torch.ones_like(p)
+    d = torch.stack([torch.stack(c, -1) for c in ((one, -q, -p), (-one, -q, p), (p, one, q), (p, -one, -q), (p, -q, one),
+                                                  (-p, -q, -one))])  # the centre of texel [face, iy, ix] (cube_face_uv's layout)
+    return cube_texture_precise(sky, torch.stack((-d[..., 1], d[..., 2], -d[..., 0]), -1).contiguous()).contiguous()
+
+
+def render_baked(args: Namespace, mesh_path: str, light, gi: Dict, lut, infos, dev, out: str) -> Dict:
+    """--lighting baked: the files and the report described in the module docstring -> what render_mesh adds to its result."""
+    import torch
+
+    import dataset_readers as dr
+    import image_writer
+    import mesh
+    import mesh_render
+    import pipeline
+    import relight
+    m = mesh_render.device_mesh(mesh_path, dev)
+    B = int(args.bounces)
+    rho = (m.albedo * (1.0 - m.metallic)[:, None]).contiguous()
+    passes, report = mesh.bake_light(m, shade_frame_sky(light, args.sky_res), rays=args.light_rays, bounces=B, reflectance=rho,
+                                     return_passes=True)
+    which = sorted({0, B})
+    source, scratch = mesh_render.MeshGBuffer(gi, args.metallic), relight.Scratch()
+    base = os.path.join(out, "mesh_" + args.split)
+    rows, files = [], []
+    with mesh_render.MeshRasterizer(m, device=dev) as plain, image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
+        baked = {b: mesh_render.MeshRasterizer(m._replace(albedo=(rho * passes[b]).contiguous()), device=dev) for b in which}
+        try:
+            rays = None
+            for ci in infos:
+                c = dr.camera_from_info(ci, args.resolution, device=dev)
+                if rays is None:
+                    rays = pipeline.canonical_rays(c, dev)
+                g = source(c, plain)
+                screen = relight.shade_ssr(light, lut, gi, args.metallic, False, True, c, pipeline.view_dirs_for(c, rays, dev), g,
+                                           g["albedo_map"], scratch, parts=True)[3].nan_to_num().clamp(0, 1).double()
+                cover = g["extra"]["tri_id"] >= 0
+                n = cover.sum().clamp(min=1).double() * 3.0
+                row = dict(image_name=ci.image_name, pixels=cover.sum())
+                for b in which:
+                    plane = pipeline.linear_to_srgb(baked[b](c)["albedo"])
+                    row[b] = -10.0 * torch.log10(((plane.clamp(0, 1).double() - screen).pow(2) * cover).sum() / n)
+                    if b == B:
+                        files.append(os.path.join(base, "%s_baked_diffuse.png" % ci.image_name))
+                        wr.submit([image_writer.Image(files[-1], plane)])
+                rows.append(row)
+        finally:
+            for r in baked.values():
+                r.close()
+    keys = ["psnr_bounces_%d" % b for b in which]
+    views = [dict(image_name=r["image_name"], pixels_covered=int(r["pixels"]), **{k: float(r[b]) for k, b in zip(keys, which)})
+             for r in rows]
+    cmp = dict(mesh=mesh_path, bounces=B, sky_res=int(args.sky_res), rays=int(args.light_rays), light=report, views=views,
+               average={k: sum(v[k] for v in views) / len(views) for k in keys})
+    path = os.path.join(base, "baked_vs_screen.json")
+    with open(path, "w") as f:
+        json.dump(cmp, f, indent=4)
+    return dict(baked_vs_screen_json=path, baked_vs_screen=cmp["average"], baked_diffuse=files)
 
 
 def open_mesh(path: str, device):
@@ -300,6 +396,8 @@ def render_mesh(args) -> Dict:
             with open(path, "w") as f:
                 json.dump(cmp, f, indent=4)
             res.update(compare_json=path, compare=cmp["average"])
+        if getattr(args, "lighting", "screen") == "baked":
+            res.update(render_baked(args, mesh_path, lights[0], gi, lut, infos, dev, out))
     finally:
         pipeline._collect_idle()
     res["total_s"] = round(time.perf_counter() - t0, 4)

@@ -147,17 +147,19 @@ def load_ply(path: str, max_sh_degree: int, device="cpu") -> Dict[str, torch.Ten
 
 _MESH_VERTEX = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"),
                 ("green", "u1"), ("blue", "u1"), ("roughness", "<f4"), ("metallic", "<f4")]
-_MESH_OCCLUSION = ("occlusion", "<f4")  # the optional last vertex property
+_MESH_OCCLUSION = ("occlusion", "<f4")  # the optional vertex property after metallic
+_MESH_IRRADIANCE = [("irradiance_r", "<f4"), ("irradiance_g", "<f4"), ("irradiance_b", "<f4")]  # the optional last three
 _MESH_FACE = [("n", "u1"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4")]
 
 
-def save_mesh_ply(path: str, vertices, faces, normals, albedo, roughness, metallic, occlusion=None) -> None:
+def save_mesh_ply(path: str, vertices, faces, normals, albedo, roughness, metallic, occlusion=None, irradiance=None) -> None:
     """A triangle mesh with its materials (mesh.Mesh's fields, tensors or arrays) as a binary little-endian PLY: vertex
     properties x y z nx ny nz (float), red green blue (uchar), roughness metallic (float); faces as `property list uchar
     int vertex_indices`.  The colour is the albedo quantised as gigs_pack_images does with bias 0.5:
     trunc(clamp(x * 255 + 0.5, 0, 255)) in float32 with the product and the sum rounded separately, NaN -> 0.
     `occlusion` ([V], mesh.bake_occlusion's; 1 = open) adds one more `property float occlusion` after metallic; with None
-    the file is the one without the argument, byte for byte."""
+    the file is the one without the argument, byte for byte.  `irradiance` ([V,3], mesh.bake_light's, linear and unclamped)
+    adds `property float irradiance_r / _g / _b` after that, stored as the float32 values they are; None changes nothing."""
     v = np.asarray(_np(vertices), dtype=np.float32).reshape(-1, 3)
     n = np.asarray(_np(normals), dtype=np.float32).reshape(-1, 3)
     a = np.asarray(_np(albedo), dtype=np.float32).reshape(-1, 3)
@@ -178,9 +180,17 @@ def save_mesh_ply(path: str, vertices, faces, normals, albedo, roughness, metall
         if occlusion.shape[0] != V:
             raise ValueError("save_mesh_ply: occlusion must have one value per vertex")
         layout.append(_MESH_OCCLUSION)
+    if irradiance is not None:
+        irradiance = np.asarray(_np(irradiance), dtype=np.float32)
+        if irradiance.shape != (V, 3):
+            raise ValueError("save_mesh_ply: irradiance must have three values per vertex")
+        layout += _MESH_IRRADIANCE
     vt = np.empty(V, dtype=layout)
     if occlusion is not None:
         vt["occlusion"] = occlusion
+    if irradiance is not None:
+        for i, (k, _) in enumerate(_MESH_IRRADIANCE):
+            vt[k] = irradiance[:, i]
     for i, k in enumerate("xyz"):
         vt[k], vt["n" + k] = v[:, i], n[:, i]
     vt["red"], vt["green"], vt["blue"], vt["roughness"], vt["metallic"] = q[:, 0], q[:, 1], q[:, 2], r, m
@@ -216,8 +226,10 @@ def read_mesh_ply(path: str) -> Dict[str, np.ndarray]:
             raise ValueError(f"{path}: not a binary little-endian PLY file")
         body = [ln for ln in lines[2:-1] if ln and not ln.startswith(("comment", "obj_info"))]
         layout = list(_MESH_VERTEX)
-        if len(body) == len(layout) + 4 and body[1 + len(layout)] == "property float " + _MESH_OCCLUSION[0]:
+        if len(body) > 1 + len(layout) and body[1 + len(layout)] == "property float " + _MESH_OCCLUSION[0]:
             layout.append(_MESH_OCCLUSION)
+        if len(body) > 1 + len(layout) and body[1 + len(layout)] == "property float " + _MESH_IRRADIANCE[0][0]:
+            layout += _MESH_IRRADIANCE
         want = ["property %s %s" % ("uchar" if t == "u1" else "float", k) for k, t in layout]
         if (len(body) != len(want) + 3 or not body[0].startswith("element vertex ") or body[1:1 + len(want)] != want
                 or not body[-2].startswith("element face ") or body[-1] != "property list uchar int vertex_indices"):
@@ -237,8 +249,10 @@ def read_mesh_ply(path: str) -> Dict[str, np.ndarray]:
     out = dict(vertices=col("x", "y", "z"), faces=faces, normals=col("nx", "ny", "nz"),
                albedo=col("red", "green", "blue") / np.float32(255.0), roughness=vt["roughness"].astype(np.float32),
                metallic=vt["metallic"].astype(np.float32))
-    if len(layout) > len(_MESH_VERTEX):
+    if _MESH_OCCLUSION in layout:
         out["occlusion"] = vt["occlusion"].astype(np.float32)
+    if _MESH_IRRADIANCE[0] in layout:
+        out["irradiance"] = col(*(k for k, _ in _MESH_IRRADIANCE))
     return out
 
 

@@ -3,7 +3,8 @@ baked into an atlas over a simplification of it (mesh.bake_atlas) and written as
 engines read.
 
     python gi-gs_amd/texture_mesh.py SRC.ply -o OUT.obj (--target LOW.ply | --cell_edges R | --cell X) [--block 8]
-                                     [--width W] [--bake_occlusion RAYS] [--max_distance D] [--samples N]        (CLI)
+                                     [--width W] [--bake_occlusion RAYS] [--max_distance D] [--samples N]
+                                     [--light a.hdr [--bounces 1] [--sky_res 32] [--light_rays 256]]             (CLI)
     texture_mesh(args) -> {...}                                                                                   (API)
 
 The light mesh is --target, or SRC simplified by mesh.simplify with cells of --cell world units or --cell_edges median
@@ -14,6 +15,10 @@ SRC's surface.  SRC's occlusion is the PLY's channel if it has one, else mesh.ba
 OUT_albedo.png, OUT_orm.png (occlusion, roughness, metallic), OUT_roughness.png, OUT_metallic.png and OUT_normal.png (the
 world normal n / |n| / 2 + 1/2, a zero normal as 1/2), through image_writer.  Prints the report as JSON: mesh.bake_atlas's
 (`atlas`), the simplification's if it ran (`simplify`), the files and the times.
+
+--light a.hdr (or .npy) adds a light-map: mesh.bake_light on SRC under that map (bake_mesh.py's options), carried through the
+same atlas launch (bake_atlas's `extra`) and written as OUT_lightmap.hdr, linear irradiance, with the host Radiance writer; the
+report names it under `files` and gains `light`, the bake's report.  Without --light every file is what it was.
 
 --samples N adds `samples`, the number the textures exist for: at N surface samples of the light mesh
 (mesh.sample_surface), per channel group, the RMS difference to SRC's attributes at the closest point of SRC
@@ -51,6 +56,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--bake_occlusion", type=int, default=0, help="rays per vertex if the input has no occlusion channel (0: occlusion 1)")
     p.add_argument("--max_distance", type=float, default=None, help="texels farther than this from the input stay unbaked")
     p.add_argument("--samples", type=int, default=0, help="report the material error of the atlas and of the light mesh's vertices at N samples")
+    p.add_argument("--light", type=str, default=None, help="an environment map (.hdr or .npy): bake a light-map under it")
+    p.add_argument("--bounces", type=int, default=1, help="diffuse inter-reflections of the light bake")
+    p.add_argument("--sky_res", type=int, default=32, help="texels an edge of the sky cube the light bake looks up")
+    p.add_argument("--light_rays", type=int, default=256, help="rays per vertex of the light bake, a multiple of 64 in [64, 1024]")
     return p
 
 
@@ -66,9 +75,10 @@ def normal_image(normal):
     return (unit * 0.5 + 0.5).float()
 
 
-def save_textured_mesh(path: str, m, atlas) -> Dict[str, str]:
+def save_textured_mesh(path: str, m, atlas, lightmap: bool = False) -> Dict[str, str]:
     """Writes the light mesh `m` (a mesh.Mesh) with `atlas` (a mesh.Atlas over it) as PATH (.obj), its .mtl and the five PNGs
-    beside it.  -> {obj, mtl, albedo, orm, roughness, metallic, normal}: the paths written."""
+    beside it.  -> {obj, mtl, albedo, orm, roughness, metallic, normal}: the paths written.  `lightmap`: atlas.extra [3,H,W]
+    (linear irradiance) goes to STEM_lightmap.hdr as well, and the result names it."""
     import image_writer
     import scene_io
     if atlas.layout.height < 1:
@@ -81,7 +91,13 @@ def save_textured_mesh(path: str, m, atlas) -> Dict[str, str]:
         writer.submit([image_writer.Image(files["albedo"], atlas.albedo), image_writer.Image(files["orm"], atlas.orm),
                        image_writer.Image(files["roughness"], atlas.orm[1:2]), image_writer.Image(files["metallic"], atlas.orm[2:3]),
                        image_writer.Image(files["normal"], normal_image(atlas.normal))])
-    return dict(files, obj=path, mtl=os.path.splitext(path)[0] + ".mtl")
+    out = dict(files, obj=path, mtl=os.path.splitext(path)[0] + ".mtl")
+    if lightmap:
+        if atlas.extra is None or atlas.extra.shape[0] != 3:
+            raise ValueError("save_textured_mesh: a light-map needs an atlas with three extra channels")
+        out["lightmap"] = os.path.splitext(path)[0] + "_lightmap.hdr"
+        image_writer.write_hdr(out["lightmap"], atlas.extra.permute(1, 2, 0).contiguous().cpu().numpy())
+    return out
 
 
 def _unit(n):
@@ -168,13 +184,23 @@ def texture_mesh(args) -> Dict:
         dst, res["simplify"] = mesh.simplify(src, cell)
         sync()
         times["simplify_s"] = round(time.perf_counter() - t0, 4)
+    irradiance = None
+    if getattr(args, "light", None):
+        import bake_mesh
+        sync()
+        t0 = time.perf_counter()
+        irradiance, res["light"] = mesh.bake_light(src, bake_mesh.load_sky(args.light, args.sky_res, dev), rays=args.light_rays,
+                                                   bounces=args.bounces, grid=grid)
+        sync()
+        times["bake_light_s"] = round(time.perf_counter() - t0, 4)
+        res["light"]["map"] = args.light
     sync()
     t0 = time.perf_counter()
     atlas, res["atlas"] = mesh.bake_atlas(dst, src, block=args.block, width=args.width, occlusion=src_occ,
-                                          max_distance=args.max_distance, grid=grid)
+                                          max_distance=args.max_distance, grid=grid, extra=irradiance)
     sync()
     t1 = time.perf_counter()
-    res["files"] = save_textured_mesh(args.output, dst, atlas)
+    res["files"] = save_textured_mesh(args.output, dst, atlas, lightmap=irradiance is not None)
     times.update(bake_atlas_s=round(t1 - t0, 4), write_s=round(time.perf_counter() - t1, 4))
     if args.samples > 0:
         ones = torch.ones(int(src.vertices.shape[0]), dtype=torch.float32, device=dev)

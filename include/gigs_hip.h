@@ -920,6 +920,53 @@ int gigs_mesh_bake_occlusion(int n_vertices, int n_faces, const float* vertices,
                              const long long* pair_keys, long long n_pairs, double scale, const long long* order,
                              const float* directions, int n_rays, int n_rotations, unsigned long long seed, double max_distance, double bias,
                              float* occlusion, int* hits, unsigned long long* counts, int* overflow, void* stream);
+/* Baking light (gigs-hip extension; the device half of mesh.trace_hemispheres / mesh.gather_light / mesh.bake_light): the
+ * light every vertex receives from an environment cube, shadowed by the mesh and with any number of diffuse bounces.  The
+ * hemisphere of every vertex is traced ONCE and every ray's hit is RECORDED (gigs_mesh_trace_hemisphere); every pass, and
+ * every other environment, is one gather over the records (gigs_mesh_gather_light).  All arrays are DEVICE memory except
+ * `lo` and `dims`; the calls neither synchronise nor allocate.  The conventions are those of "Baking occlusion": float64 on
+ * the float32 inputs, + - * / only, every product and sum rounded on its own, no sqrt and no transcendental, no float
+ * atomics: tests/mesh_light_ref.py reproduces every bit in numpy.
+ *   1 Rays.  Those of "Baking occlusion", 8, by the same code: the table [K, R, 3], the rotation k, the basis (T, B, n), the
+ *     origin o = p + bias n, the direction d_i = (x T + y B) + z n of row (k, i), and the no_normal rule.  Vertex v casts
+ *     the rays i = 0 .. R - 1 of ITS rotation in every call: a gather rebuilds d_i from the table.
+ *   2 Records.  Ray i of vertex v is traversed as in 2 to 7 there with t_max = max_distance (+inf: no limit; a face beyond
+ *     it is not accepted, the ray then misses).  hit_face [V, R] int32: a miss is -1.  For the winning face f let
+ *     n_g = cross(p1 - p0, p2 - p0) of its corners and s = dot(d, n_g) (not 0 under the guard of 4): s < 0 is a FRONT hit,
+ *     recorded as f; otherwise a BACK hit, recorded as -2 - f: the ray reached the inside of a shell, which carries no
+ *     light.  hit_bary [V, R, 2] float32 = (float32(w1 / W), float32(w2 / W)) as gigs_mesh_raycast writes them; (0, 0) on
+ *     a miss.  A no_normal vertex gets -1 and (0, 0) in all its records and counts[3] += 1; its rays are in no other
+ *     counter.  counts [4] uint64 (cleared inside the call) = misses, front hits, back hits, no_normal vertices.
+ *   3 Sky.  sky [6, n, n, 3] float32, the cube of the lights (pbr.hip, cube_face_uv; the cube's axes are the world's).  For a
+ *     direction (x, y, z): if |z| > max(|x|, |y|): face 4, c = z, (a, b) = (x, y); else if |y| > |x|: face 2, c = y,
+ *     (a, b) = (x, z); else face 0, c = x, (a, b) = (z, y); face += 1 if c < 0.  m = 0.5 / |c|; m0 = -m on the faces 0 and
+ *     5, else m; m1 = m on face 2, else -m; u = min(max(a m0 + 0.5, 0), 1), v = min(max(b m1 + 0.5, 0), 1); texel
+ *     ix = min(n - 1, floor(u n)), iy = min(n - 1, floor(v n)) (a NaN goes to texel 0): sky[face, iy, ix], the nearest
+ *     texel, unfiltered.
+ *   4 Contribution c_i of ray i, three float64 values.  Miss: the sky texel of d_i.  Front hit of face f = (i0, i1, i2) with
+ *     `previous` [V, 3] float32 given: b1, b2 = the record's float32 weights as doubles, b0 = max(0, (1 - b1) - b2),
+ *     c = (b0 Q[i0] + b1 Q[i1]) + b2 Q[i2], Q = previous as doubles.  A back hit, or any hit with previous == NULL: 0.
+ *   5 Sum.  Lane l of the wave adds c_i for i = l, l + 64, l + 128, .. in that order, starting from 0.0; then
+ *     S_l <- S_l + S_(l xor s) for s = 32, 16, 8, 4, 2, 1, all lanes at once: IEEE addition is commutative, so all lanes hold
+ *     the same bits.  irradiance[v] = float32(S / R); radiosity[v] = float32(double(reflectance[v]) double(irradiance[v])),
+ *     per channel.  A no_normal vertex (rule 1, from `vertices` and `normals`) gets 0 in both.
+ *   6 Passes.  I(0) = gather with previous = NULL: the shadowed sky.  I(b) = gather with previous = the radiosity of pass
+ *     b - 1: a Jacobi iteration over the same rays.  The irradiance is the cosine-weighted MEAN of the incoming radiance,
+ *     the normalisation of the shade's diffuse cube: a constant sky c on an open vertex gives c.
+ * gigs_mesh_trace_hemisphere, one one-wave block per row of `order` [V] int64 (the vertices sorted by cell, or NULL): the
+ *   wave walks the R / 64 chunks, one direction per lane, and stores 64 records side by side per chunk.
+ * gigs_mesh_gather_light, one one-wave block per vertex; sky_res = n in [1, 4096].  n_vertices == 0 launches nothing.
+ * An order row, a cell_start entry, a pair key, a face index or a record (f or -2 - f not in [0, F)) outside its range sets
+ *   *overflow (cleared by the caller) and the wave stores nothing from then on. */
+int gigs_mesh_trace_hemisphere(int n_vertices, int n_faces, const float* vertices, const float* normals, const int* faces,
+                               const float* lo, double cell, const int* dims, const long long* cell_start,
+                               const long long* pair_keys, long long n_pairs, double scale, const long long* order,
+                               const float* directions, int n_rays, int n_rotations, unsigned long long seed, double max_distance,
+                               double bias, int* hit_face, float* hit_bary, unsigned long long* counts, int* overflow, void* stream);
+int gigs_mesh_gather_light(int n_vertices, int n_faces, const float* vertices, const float* normals, const int* faces,
+                           const float* directions, int n_rays, int n_rotations, unsigned long long seed, const int* hit_face,
+                           const float* hit_bary, int sky_res, const float* sky, const float* reflectance, const float* previous,
+                           float* irradiance, float* radiosity, int* overflow, void* stream);
 /* Texturing meshes (gigs-hip extension; the device half of mesh.bake_atlas / mesh.transfer_attributes): the per-vertex
  * channels of a heavy SOURCE mesh stored in the texels of an atlas over a light TARGET mesh.  Every texel of the atlas gets
  * the point of the target's surface it stands for (gigs_mesh_atlas_points), the search of "Comparing meshes" finds the
