@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.environ.get("GIGS_OBJ", os.path.join(HERE, "build"))
 LIB = os.environ.get("GIGS_LIB", os.path.join(HERE, "libgigs_hip.so"))
-SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "blend.hip", "gi.hip", "pbr.hip", "stage2.hip", "train_glue.hip", "knn.hip", "lpips.hip",
+SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "blend.hip", "gi.hip", "light_filter.hip", "cube_texture.hip", "shade.hip", "stage2.hip", "train_glue.hip", "knn.hip", "lpips.hip",
            "image_out.hip", "mesh.hip", "mesh_raster.hip", "mesh_clean.hip", "mesh_simplify.hip", "mesh_distance.hip",
            "mesh_raycast.hip", "mesh_light.hip", "mesh_atlas.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -43,9 +43,11 @@ def _stale(target: str, deps) -> bool:
 
 def build(force: bool = False, save_temps: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    sources = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    missing = [s for s in SOURCES if not os.path.exists(os.path.join(CSRC, s))]
+    if missing:
+        raise FileNotFoundError("build.SOURCES lists units that are not in csrc/: " + ", ".join(missing))
     objs, jobs = [], []
-    for src in sources:
+    for src in SOURCES:
         obj = os.path.join(OBJ, src.replace(".hip", ".o"))
         objs.append(obj)
         if force or _stale(obj, _deps(src)):

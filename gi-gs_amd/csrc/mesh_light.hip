@@ -118,7 +118,7 @@ __device__ __forceinline__ int texel_of(double u, int n) {
   return !(t >= 0.0) ? 0 : (t > (double)(n - 1) ? n - 1 : (int)t);
 }
 
-// the index of the sky texel of d: cube_face_uv's face, swaps and signs (pbr.hip) in float64, the nearest texel
+// the index of the sky texel of d: cube_face_uv's face, swaps and signs (cube.h) in float64, the nearest texel
 __device__ __forceinline__ size_t sky_texel(const double* d, int n) {
   double x = d[0], y = d[1];
   const double z = d[2], ax = fabs(x), ay = fabs(y), az = fabs(z);

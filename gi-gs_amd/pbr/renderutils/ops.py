@@ -3,6 +3,7 @@ backed by the HIP kernels of libgigs_hip.so instead of the JIT-compiled CUDA plu
 from __future__ import annotations
 
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -55,7 +56,7 @@ def diffuse_cubemap(cubemap, use_python=False):
 
 class _specular_cubemap(torch.autograd.Function):
     """`tables` = None (recompute the pair weights every call, like the reference) or the cached
-    (offsets, weights_fwd, weights_bwd) of `_weight_tables`."""
+    `WeightTables` of `_weight_tables`."""
 
     @staticmethod
     def forward(ctx, cubemap, roughness, costheta_cutoff, bounds, tables=None):
@@ -68,8 +69,8 @@ class _specular_cubemap(torch.autograd.Function):
                                                               float(costheta_cutoff), out.data_ptr(), _stream()),
                                "specular_cubemap_fwd")
             else:
-                gigs_lib.check(_lib.gigs_specular_cubemap_fwd_w(gigs_lib.ctx_ptr(), res, c.data_ptr(), bounds.data_ptr(), tables[0].data_ptr(),
-                                                                tables[1].data_ptr(), _avg_window(tables, res),
+                gigs_lib.check(_lib.gigs_specular_cubemap_fwd_w(gigs_lib.ctx_ptr(), res, c.data_ptr(), bounds.data_ptr(), tables.offsets.data_ptr(),
+                                                                tables.fwd.data_ptr(), _avg_window(tables, res),
                                                                 out.data_ptr(), None, _stream()),
                                "specular_cubemap_fwd_w")
         ctx.save_for_backward(bounds)
@@ -90,8 +91,8 @@ class _specular_cubemap(torch.autograd.Function):
                                                               float(ctx.theta_cutoff), g.data_ptr(), _stream()),
                                "specular_cubemap_bwd")
             else:
-                gigs_lib.check(_lib.gigs_specular_cubemap_bwd_w(gigs_lib.ctx_ptr(), ctx.res, bounds.data_ptr(), ctx.tables[0].data_ptr(),
-                                                                ctx.tables[2].data_ptr(), _avg_window(ctx.tables, ctx.res),
+                gigs_lib.check(_lib.gigs_specular_cubemap_bwd_w(gigs_lib.ctx_ptr(), ctx.res, bounds.data_ptr(), ctx.tables.offsets.data_ptr(),
+                                                                ctx.tables.bwd.data_ptr(), _avg_window(ctx.tables, ctx.res),
                                                                 d.data_ptr(), 0, g.data_ptr(), _stream()),
                                "specular_cubemap_bwd_w")
         return g, None, None, None, None
@@ -99,7 +100,7 @@ class _specular_cubemap(torch.autograd.Function):
 
 def _avg_window(tables, res: int) -> int:
     """Mean number of window candidates per texel (scheduling hint of the *_w entry points)."""
-    return max(1, tables[1].numel() // (6 * res * res))
+    return max(1, tables.fwd.numel() // (6 * res * res))
 
 
 def _ndf_cutoff(roughness: float, cutoff: float) -> float:
@@ -141,8 +142,8 @@ class _specular_cubemap_normalized(torch.autograd.Function):
         out = torch.empty((6, res, res, 3), dtype=torch.float32, device=c.device)
         wsum = torch.empty((6, res, res, 1), dtype=torch.float32, device=c.device)
         with torch.cuda.device(c.device):
-            gigs_lib.check(_lib.gigs_specular_cubemap_fwd_w(gigs_lib.ctx_ptr(), res, c.data_ptr(), bounds.data_ptr(), tables[0].data_ptr(),
-                                                            tables[1].data_ptr(), _avg_window(tables, res), out.data_ptr(),
+            gigs_lib.check(_lib.gigs_specular_cubemap_fwd_w(gigs_lib.ctx_ptr(), res, c.data_ptr(), bounds.data_ptr(), tables.offsets.data_ptr(),
+                                                            tables.fwd.data_ptr(), _avg_window(tables, res), out.data_ptr(),
                                                             wsum.data_ptr(), _stream()),
                            "specular_cubemap_fwd_w")
         ctx.save_for_backward(bounds, wsum)
@@ -154,14 +155,14 @@ class _specular_cubemap_normalized(torch.autograd.Function):
     @gigs_lib.with_forward_context
     def backward(ctx, dout):
         bounds, wsum = ctx.saved_tensors
-        if len(ctx.tables) > 3 and ctx.tables[3] is not None:
+        if ctx.tables.bwd_scaled is not None:
             # the 1 / wsum of d(rgb / w) / d(rgb) is folded into the cached table (gigs_specular_weights_divide)
-            d, table = _gpu(dout, "dout"), ctx.tables[3]
+            d, table = _gpu(dout, "dout"), ctx.tables.bwd_scaled
         else:
-            d, table = (_gpu(dout, "dout") / wsum).contiguous(), ctx.tables[2]  # w does not depend on the cubemap
+            d, table = (_gpu(dout, "dout") / wsum).contiguous(), ctx.tables.bwd  # w does not depend on the cubemap
         g = torch.empty((6, ctx.res, ctx.res, 3), dtype=torch.float32, device=d.device)
         with torch.cuda.device(d.device):
-            gigs_lib.check(_lib.gigs_specular_cubemap_bwd_w(gigs_lib.ctx_ptr(), ctx.res, bounds.data_ptr(), ctx.tables[0].data_ptr(),
+            gigs_lib.check(_lib.gigs_specular_cubemap_bwd_w(gigs_lib.ctx_ptr(), ctx.res, bounds.data_ptr(), ctx.tables.offsets.data_ptr(),
                                                             table.data_ptr(), _avg_window(ctx.tables, ctx.res),
                                                             d.data_ptr(), 1, g.data_ptr(), _stream()),
                            "specular_cubemap_bwd_w")
@@ -188,8 +189,8 @@ class _specular_levels(torch.autograd.Function):
             wsum = torch.empty((6, res, res, 1), dtype=torch.float32, device=dev)
             outs.append(out)
             wsums.append(wsum)
-            arr[i] = gigs_lib.SpecLevel(res, _avg_window(tables, res), c.data_ptr(), bounds.data_ptr(), tables[0].data_ptr(),
-                                        tables[1].data_ptr(), out.data_ptr(), wsum.data_ptr())
+            arr[i] = gigs_lib.SpecLevel(res, _avg_window(tables, res), c.data_ptr(), bounds.data_ptr(), tables.offsets.data_ptr(),
+                                        tables.fwd.data_ptr(), out.data_ptr(), wsum.data_ptr())
         with torch.cuda.device(dev):
             gigs_lib.check(_lib.gigs_specular_cubemap_multi_w(gigs_lib.ctx_ptr(), len(cs), C.cast(arr, C.c_void_p), 0, _stream()),
                            "specular_cubemap_multi_w")
@@ -211,9 +212,9 @@ class _specular_levels(torch.autograd.Function):
             keep.append(d)
             g = torch.empty((6, res, res, 3), dtype=torch.float32, device=dev)
             gs.append(g)
-            arr[i] = gigs_lib.SpecLevel(res, _avg_window(tables, res), d.data_ptr(), bounds.data_ptr(), tables[0].data_ptr(),
-                                        tables[3].data_ptr(), g.data_ptr(), None)
-            w_fwd[i], w_sum[i] = tables[1].data_ptr(), tables[4].data_ptr()
+            arr[i] = gigs_lib.SpecLevel(res, _avg_window(tables, res), d.data_ptr(), bounds.data_ptr(), tables.offsets.data_ptr(),
+                                        tables.bwd_scaled.data_ptr(), g.data_ptr(), None)
+            w_fwd[i], w_sum[i] = tables.fwd.data_ptr(), tables.wsum.data_ptr()
         with torch.cuda.device(dev):
             if bwd_head_start_ns > 0:  # see gigs_stream_delay: set by pipeline.WholeStepGraph while it captures the backward
                 gigs_lib.check(_lib.gigs_stream_delay(int(bwd_head_start_ns), _stream()), "stream_delay")
@@ -288,16 +289,27 @@ def specular_cubemap_levels(mips, roughnesses, cutoff=0.99):
     for m, r in zip(mips, roughnesses):
         _, bounds = _ndf_bounds(m.shape[1], r, cutoff, m.device)
         tables = _weight_tables(m.shape[1], r, cutoff, m.device)
-        if tables is None or len(tables) < 4 or tables[3] is None:
+        if tables is None or tables.bwd_scaled is None:
             return None
         meta.append((bounds, tables))
     return list(_specular_levels.apply(meta, *mips))
 
 
-# Cached pair-weight tables (see csrc/pbr.hip): 0.74 GB for the 256..16 chain, x2 for the backward.
+# Cached pair-weight tables (see csrc/light_filter.hip): 0.74 GB for the 256..16 chain, x2 for the backward.
 # HBM is 288 GB on MI355X; set GIGS_SPEC_TABLE_MAX_GB=0 to recompute the weights every call instead.
 _TABLE_MAX_BYTES = float(os.environ.get("GIGS_SPEC_TABLE_MAX_GB", "8")) * 1e9
 _weightTables = {}
+
+
+class WeightTables(NamedTuple):
+    """The cached tables of one (resolution, roughness, cutoff): `fwd` / `bwd` hold the pair weights in the forward's
+    and the gather-form backward's roles, `bwd_scaled` is `bwd` pre-divided by the forward's weight sums `wsum` (both
+    None without the switch spec_prescaled or past the byte budget)."""
+    offsets: torch.Tensor
+    fwd: torch.Tensor
+    bwd: torch.Tensor
+    bwd_scaled: Optional[torch.Tensor]
+    wsum: Optional[torch.Tensor]
 
 
 def _weight_tables(res, roughness, cutoff, device):
@@ -309,7 +321,7 @@ def _weight_tables(res, roughness, cutoff, device):
         h = torch.where(b[..., 2] <= b[..., 3], b[..., 3] - b[..., 2] + 1, torch.zeros_like(b[..., 0]))
         cnt = (w * h).to(torch.int64).reshape(-1)
         total = int(cnt.sum().item())
-        used = sum(t[1].numel() * (12 if t[3] is not None else 8) for t in _weightTables.values() if t is not None)
+        used = sum(t.fwd.numel() * (12 if t.bwd_scaled is not None else 8) for t in _weightTables.values() if t is not None)
         if total == 0 or total >= 2 ** 31 or used + total * 8 > _TABLE_MAX_BYTES:
             _weightTables[key] = None
         else:
@@ -337,7 +349,7 @@ def _weight_tables(res, roughness, cutoff, device):
                     gigs_lib.check(_lib.gigs_specular_weights_divide(res, bounds.data_ptr(), offsets.data_ptr(),
                                                                      tabs[1].data_ptr(), wsum.data_ptr(), scaled.data_ptr(),
                                                                      _stream()), "specular_weights_divide")
-            _weightTables[key] = (offsets, tabs[0], tabs[1], scaled, wsum if scaled is not None else None)
+            _weightTables[key] = WeightTables(offsets, tabs[0], tabs[1], scaled, wsum if scaled is not None else None)
     return _weightTables[key]
 
 

@@ -937,7 +937,7 @@ int gigs_mesh_bake_occlusion(int n_vertices, int n_faces, const float* vertices,
  *     light.  hit_bary [V, R, 2] float32 = (float32(w1 / W), float32(w2 / W)) as gigs_mesh_raycast writes them; (0, 0) on
  *     a miss.  A no_normal vertex gets -1 and (0, 0) in all its records and counts[3] += 1; its rays are in no other
  *     counter.  counts [4] uint64 (cleared inside the call) = misses, front hits, back hits, no_normal vertices.
- *   3 Sky.  sky [6, n, n, 3] float32, the cube of the lights (pbr.hip, cube_face_uv; the cube's axes are the world's).  For a
+ *   3 Sky.  sky [6, n, n, 3] float32, the cube of the lights (cube.h, cube_face_uv; the cube's axes are the world's).  For a
  *     direction (x, y, z): if |z| > max(|x|, |y|): face 4, c = z, (a, b) = (x, y); else if |y| > |x|: face 2, c = y,
  *     (a, b) = (x, z); else face 0, c = x, (a, b) = (z, y); face += 1 if c < 0.  m = 0.5 / |c|; m0 = -m on the faces 0 and
  *     5, else m; m1 = m on face 2, else -m; u = min(max(a m0 + 0.5, 0), 1), v = min(max(b m1 + 0.5, 0), 1); texel

@@ -1,5 +1,5 @@
 """Shared cases for the per-pixel / per-texel float64 checks of the deferred shade (tests/test_shade_f64_cpu.py,
-tests/test_gpu_shade_f64.py, tests/golden/make_shade_f64_bounds.py): csrc/pbr.hip shade_pixel_n, shade_fwd_kernel,
+tests/test_gpu_shade_f64.py, tests/golden/make_shade_f64_bounds.py): csrc/shade.hip shade_pixel_n, shade_fwd_kernel,
 shade_bwd_kernel, cube_taps, wave_dedup_add, run_add3.
 
 A case is a small G-buffer, a light, upstream gradients and the entry points' options, built deterministically so that it

@@ -1,4 +1,4 @@
-"""The light-gradient scatter of the shade backward (csrc/pbr.hip shade_bwd_kernel).  The default formulation walks
+"""The light-gradient scatter of the shade backward (csrc/shade.hip shade_bwd_kernel).  The default formulation walks
 32 x 32 pixel tiles with 8 x 8 pixel waves and adds once per distinct texel of a wave into the global (fine) light
 levels; the previous one (row-major 1024-pixel chunks, 16-lane runs) stays selectable as gigs_options.shade_bwd_rows.
 Cases: bench.py's C2 view, a hot spot (every pixel reflects into the same texels), random per-pixel normals (more

@@ -1,4 +1,4 @@
-"""GPU tests: the deferred shade's kernels (csrc/pbr.hip shade_fwd_kernel, shade_bwd_kernel<kTiles>, cube_taps and the
+"""GPU tests: the deferred shade's kernels (csrc/shade.hip shade_fwd_kernel, shade_bwd_kernel<kTiles>, cube_taps and the
 scatter helpers wave_dedup_add / run_add3, through gigs_shade_fwd_ex, gigs_shade_bwd_ex, pbr.pbr_shading and gigs_cube_taps)
 against the float64 restatement (oracle/torch_pbr_ref.py), per pixel and per light texel, on the cases of
 tests/shade_cases.py that enter every branch on purpose: cube seams and corners at every level in either role of the blend,

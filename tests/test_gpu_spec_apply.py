@@ -1,4 +1,4 @@
-"""The table-driven GGX pre-filter (specular_apply_* in csrc/pbr.hip) on ragged shapes, against the table-free kernels.
+"""The table-driven GGX pre-filter (specular_apply_* in csrc/light_filter.hip) on ragged shapes, against the table-free kernels.
 
 The table-free kernels compute every pair weight with the IEEE sequence the tables cache ("bit-identical per term"),
 so the two paths differ in summation order only: the tolerance is the one test_gpu_pbr.py uses against the oracle
@@ -44,7 +44,7 @@ def rel_peak(a, b):
 
 
 def spec_lanes_for(avg_window, max8, max16):
-    """spec_lanes_for of csrc/pbr.hip."""
+    """spec_lanes_for of csrc/light_filter.hip."""
     return 8 if 0 < avg_window <= max8 else 16 if 0 < avg_window <= max16 else 64
 
 

@@ -1,4 +1,4 @@
-"""The sparse GGX backward (gigs_specular_cubemap_multi_bwd_sparse in csrc/pbr.hip): census of the nonzero gradient
+"""The sparse GGX backward (gigs_specular_cubemap_multi_bwd_sparse in csrc/light_filter.hip): census of the nonzero gradient
 texels, scatter of the levels whose list fits its capacity, gather of the others.
 
 The level API is driven directly, one level per call at res 16 and 32 with roughness 0.08, 0.22 and 1.0 (8-, 16- and
@@ -28,12 +28,12 @@ _cache = {}
 
 
 def spec_lanes_for(avg_window, max8=128, max16=1500):
-    """spec_lanes_for of csrc/pbr.hip at the default thresholds."""
+    """spec_lanes_for of csrc/light_filter.hip at the default thresholds."""
     return 8 if 0 < avg_window <= max8 else 16 if 0 < avg_window <= max16 else 64
 
 
 def scatter_plan(res, avg_window):
-    """(wide, chunks, tiles per face) as gigs_specular_cubemap_multi_bwd_sparse of csrc/pbr.hip chooses them."""
+    """(wide, chunks, tiles per face) as gigs_specular_cubemap_multi_bwd_sparse of csrc/light_filter.hip chooses them."""
     wide = avg_window * 16 >= 6 * res * res
     return wide, min(32, max(1, (max(1, avg_window) + 255) // 256)), ((res + 31) // 32) ** 2
 

@@ -1,4 +1,4 @@
-"""The sparse paths of the GGX backward (csrc/pbr.hip) under clustered gradients.
+"""The sparse paths of the GGX backward (csrc/light_filter.hip) under clustered gradients.
 
 specular_tile_gather_body: a workgroup owns a 16 x 16 tile of destination texels of one face and a slice of 256 slots of
 the level's list, and sums the listed texels whose own rectangle on that face meets the tile.  A level whose mean window
@@ -27,7 +27,7 @@ LEVELS = [(16, 0.08), (16, 1.0), (32, 0.22), (64, 0.08), (64, 0.28), (64, 0.36)]
 
 
 def tile_plan(res, avg_window, cap):
-    """(scattered, tiles per face, slices) as gigs_specular_cubemap_multi_bwd_sparse of csrc/pbr.hip chooses them."""
+    """(scattered, tiles per face, slices) as gigs_specular_cubemap_multi_bwd_sparse of csrc/light_filter.hip chooses them."""
     return avg_window <= 256, ((res + 15) // 16) ** 2, (cap + 255) // 256
 
 

@@ -2,7 +2,7 @@
 
   * gigs_stage2_loss_gather (csrc/stage2.hip: the loss, its unit gradient planes and the four sums without global atomics
     and without cleared buffers) against gigs_stage2_loss_fwd_grad on the same inputs;
-  * gigs_shade_fwd_post (csrc/pbr.hip: the G-buffer post-processing inside the shade forward) against gigs_gbuffer_post
+  * gigs_shade_fwd_post (csrc/shade.hip: the G-buffer post-processing inside the shade forward) against gigs_gbuffer_post
     followed by gigs_shade_fwd_ex;
   * stage2_fused._Stage2Fused with the switches stage2_gather / shade_post_fused on and off.
 

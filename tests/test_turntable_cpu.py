@@ -136,14 +136,33 @@ def test_turntable_entries_declared_and_exported():
     assert not hasattr(a, "specular")  # refused before any mips were built
 
 
-def test_new_kernels_compile_for_gfx950_without_scratch(tmp_path):
-    """gi-gs_amd/build.py's compiler and flags on the two sources that gained kernels: every instance of the hit-list
-    gather (the single-light one included) and the rotated conversion use no scratch memory."""
+def _load_build():
     import importlib.util
     spec = importlib.util.spec_from_file_location("gigs_build", os.path.join(ROOT, "gi-gs_amd", "build.py"))
     bld = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bld)
-    assert "--offload-arch=gfx950" in bld.FLAGS and "gi.hip" in bld.SOURCES and "pbr.hip" in bld.SOURCES
+    return bld
+
+
+def test_build_sources_are_the_units_of_csrc(tmp_path, monkeypatch):
+    """build.SOURCES lists every csrc/*.hip exactly once and nothing else, and build() refuses a listed unit that is not
+    there instead of linking what is left (it raises before it compiles anything)."""
+    bld = _load_build()
+    on_disk = sorted(f for f in os.listdir(bld.CSRC) if f.endswith(".hip"))
+    assert sorted(bld.SOURCES) == on_disk
+    monkeypatch.setattr(bld, "OBJ", str(tmp_path / "obj"))
+    monkeypatch.setattr(bld, "LIB", str(tmp_path / "libgigs_hip.so"))
+    monkeypatch.setattr(bld, "SOURCES", bld.SOURCES + ["no_such_unit.hip"])
+    with pytest.raises(FileNotFoundError, match="no_such_unit.hip"):
+        bld.build(verbose=False)
+    assert not os.path.exists(bld.LIB) and not any(f.endswith(".o") for f in os.listdir(bld.OBJ))
+
+
+def test_new_kernels_compile_for_gfx950_without_scratch(tmp_path):
+    """gi-gs_amd/build.py's compiler and flags on the two sources that gained kernels: every instance of the hit-list
+    gather (the single-light one included) and the rotated conversion use no scratch memory."""
+    bld = _load_build()
+    assert "--offload-arch=gfx950" in bld.FLAGS and "gi.hip" in bld.SOURCES and "cube_texture.hip" in bld.SOURCES
 
     def compile_one(src):
         cmd = [bld.HIPCC, *bld.FLAGS, "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
@@ -153,7 +172,7 @@ def test_new_kernels_compile_for_gfx950_without_scratch(tmp_path):
         return r.stderr
 
     with ThreadPoolExecutor(max_workers=2) as ex:
-        log = "\n".join(ex.map(compile_one, ["gi.hip", "pbr.hip"]))
+        log = "\n".join(ex.map(compile_one, ["gi.hip", "cube_texture.hip"]))
     found = {}
     for block in re.split(r"(?=remark: [^\n]*Function Name:)", log):
         m = re.search(r"Function Name: (\S+)", block)

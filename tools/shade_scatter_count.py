@@ -3,7 +3,7 @@
 
 Works on the CPU from the oracle G-buffer of bench.py's C2 view (oracle/stage2_ref.py: rasterizer, filters, SSAO,
 gbuffer_post -- the path `bench.py --full` checks parity against) and restates the kernel's cube taps in float32
-numpy (csrc/pbr.hip cube_taps).  Every masked pixel contributes 4 taps of its level l0 and, between two levels, 4 of
+numpy (csrc/cube.h cube_taps).  Every masked pixel contributes 4 taps of its level l0 and, between two levels, 4 of
 l1; an entry of weight 0 adds nothing.  The fine levels are those the kernel keeps in global memory (256^2, 128^2,
 64^2 at base 256: they do not fit the 30 720-float LDS plan).  One "add" is one (texel, RGB) triple.
 
