@@ -1,6 +1,7 @@
 // gigs_internal.h -- what the library's translation units share on the HOST side and nobody outside sees: the
-// profile stage ids, the stack-scoped stage timer, the error helper, the options accessor and the launch check.
-// Not installed; everything declared here has hidden visibility and is defined in api.hip.
+// profile stage ids, the stack-scoped stage timer, the error helper, the options accessor, the launch check and the
+// ray table of the screen-space marches.  Not installed; everything declared here has hidden visibility and is
+// defined in api.hip, but for the ray table (gi.hip).
 #pragma once
 #include "../../include/gigs_hip.h"
 #include "gigs_common.h"
@@ -42,6 +43,20 @@ class GIGS_HIDDEN StageTimer {
   bool on_;
   hipEvent_t a_, b_;
 };
+
+// ---- the ray set of SSAO / SSR -----------------------------------------------------------------------------------
+// One table per (device, delta) and process, built on first use and never modified; gi.hip owns the cache and
+// describes the layout.  `out` is a copy of the entry; 0, or -1 for an unusable delta, -2 for a HIP failure.
+struct RayTable {
+  int device = -1;
+  float delta = -1.0f;
+  int nrays = 0;   // all rays of the reference's loops (SSR's nrSamples)
+  int n_live = 0;  // rays with a non-zero weight: table entries [0, n_live)
+  int n_dead = 0;  // identical zero-weight rays: entries [n_live, n_live + n_dead)
+  float sum_w = 0.0f;  // SSAO's nrSamples, accumulated in fp32 in ray order
+  float4* dev = nullptr;
+};
+GIGS_HIDDEN int get_ray_table(float delta, hipStream_t s, RayTable& out);
 
 }  // namespace gigs
 

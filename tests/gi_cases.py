@@ -1,6 +1,7 @@
 """Shared cases for the per-ray / per-pixel float64 checks of the screen-space GI passes (tests/test_gi_f64_cpu.py,
 tests/test_gpu_gi_f64.py, tests/golden/make_gi_f64_bounds.py): csrc/gi.hip ssao_kernel, ssr_kernel (march, hit list),
-ssr_apply_kernel, depth_to_normal_kernel, median3x3(_bwd)_kernel, bilateral3x3_kernel, derive_normal_fused_kernel.
+csrc/ssr_apply.hip ssr_apply_kernel, csrc/normal_filters.hip depth_to_normal_kernel, median3x3(_bwd)_kernel,
+bilateral3x3_kernel, derive_normal_fused_kernel.
 
 A march case is an ANALYTIC G-buffer -- planes meeting in concave corners, a free-standing slab in front of them (depth edges
 that rays pass behind), a floor at a grazing angle, holes (pos = 0, normal = 0), patches of NaN normals, of normals exactly

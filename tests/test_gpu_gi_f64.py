@@ -1,5 +1,6 @@
-"""GPU tests: the screen-space GI kernels (csrc/gi.hip ssao_kernel, ssr_kernel and its hit list, ssr_apply_kernel,
-depth_to_normal_kernel, median3x3(_bwd)_kernel, bilateral3x3_kernel, derive_normal_fused_kernel) against the float64
+"""GPU tests: the screen-space GI kernels (csrc/gi.hip ssao_kernel, ssr_kernel and its hit list; csrc/ssr_apply.hip
+ssr_apply_kernel; csrc/normal_filters.hip depth_to_normal_kernel, median3x3(_bwd)_kernel, bilateral3x3_kernel,
+derive_normal_fused_kernel) against the float64
 restatement oracle/gi_ref.py on the analytic cases of tests/gi_cases.py, which enter every branch of the march on purpose.
 
   * decisions: the default march's recorded hit list (gigs_ssr_hits) gives, per pixel, {ray -> hit pixel}; every DECIDED ray

@@ -528,7 +528,7 @@ def test_median_backward_routes_gradient(orc):
 
 def test_fast_div2_and_rounding_are_bit_exact():
     """The SSAO/SSR march replaces two IEEE divisions by a shared-reciprocal FMA chain and roundf by
-    add-and-truncate; both must be bit-identical to the plain forms (gi.hip: div2_exact, round_to_int)."""
+    add-and-truncate; both must be bit-identical to the plain forms (gi_march.h: div2_exact, round_to_int)."""
     import gigs_lib
     lib = gigs_lib.lib()
     rng = np.random.default_rng(0)
@@ -558,7 +558,7 @@ def test_fast_div2_and_rounding_are_bit_exact():
 
 
 def test_pixel_rounding_is_exact_for_every_float():
-    """gi.hip rounds projected coordinates with floor(t + (0.5 - 2^-25)) instead of (int)roundf(t); the device sweeps
+    """gi_march.h (round_pix) rounds projected coordinates with floor(t + (0.5 - 2^-25)) instead of (int)roundf(t); the device sweeps
     all 2^32 floats and counts those where the two would pick a different pixel or a different inside/outside
     decision for an image side below 2^15."""
     import gigs_lib

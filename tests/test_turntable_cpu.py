@@ -162,7 +162,7 @@ def test_new_kernels_compile_for_gfx950_without_scratch(tmp_path):
     """gi-gs_amd/build.py's compiler and flags on the two sources that gained kernels: every instance of the hit-list
     gather (the single-light one included) and the rotated conversion use no scratch memory."""
     bld = _load_build()
-    assert "--offload-arch=gfx950" in bld.FLAGS and "gi.hip" in bld.SOURCES and "cube_texture.hip" in bld.SOURCES
+    assert "--offload-arch=gfx950" in bld.FLAGS and "ssr_apply.hip" in bld.SOURCES and "cube_texture.hip" in bld.SOURCES
 
     def compile_one(src):
         cmd = [bld.HIPCC, *bld.FLAGS, "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
@@ -172,7 +172,7 @@ def test_new_kernels_compile_for_gfx950_without_scratch(tmp_path):
         return r.stderr
 
     with ThreadPoolExecutor(max_workers=2) as ex:
-        log = "\n".join(ex.map(compile_one, ["gi.hip", "cube_texture.hip"]))
+        log = "\n".join(ex.map(compile_one, ["ssr_apply.hip", "cube_texture.hip"]))
     found = {}
     for block in re.split(r"(?=remark: [^\n]*Function Name:)", log):
         m = re.search(r"Function Name: (\S+)", block)

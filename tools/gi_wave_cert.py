@@ -103,7 +103,7 @@ def main():
         p = pos[:, ys, xs].T.astype(np.float64)[live]
         a = 1 + p[:, 2] / 100
         s = a * a * radius
-        # per-pixel constants of the projective march (gi.hip::make_fast / make_fast_tbn, mode 4)
+        # per-pixel constants of the projective march (gi_march.h::make_fast / make_fast_tbn, mode 4)
         Ax, Ay, Dz = p[:, 0] * fx, p[:, 1] * fy, p[:, 2] + 1e-7
         M = np.stack([np.stack([t[:, 0] * s * fx, b[:, 0] * s * fx, n[:, 0] * s * fx], 1),
                       np.stack([t[:, 1] * s * fy, b[:, 1] * s * fy, n[:, 1] * s * fy], 1),
