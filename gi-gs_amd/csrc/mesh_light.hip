@@ -112,32 +112,6 @@ struct GatherArgs {
   int* overflow;
 };
 
-// the texel of u in [0, 1] on an edge of n texels: min(n - 1, floor(u n)); a NaN goes to 0
-__device__ __forceinline__ int texel_of(double u, int n) {
-  const double t = floor(u * (double)n);
-  return !(t >= 0.0) ? 0 : (t > (double)(n - 1) ? n - 1 : (int)t);
-}
-
-// the index of the sky texel of d: cube_face_uv's face, swaps and signs (cube.h) in float64, the nearest texel
-__device__ __forceinline__ size_t sky_texel(const double* d, int n) {
-  double x = d[0], y = d[1];
-  const double z = d[2], ax = fabs(x), ay = fabs(y), az = fabs(z);
-  int idx;
-  double c;
-  if (az > fmax(ax, ay)) {
-    idx = 4, c = z;
-  } else if (ay > ax) {
-    idx = 2, c = y, y = z;
-  } else {
-    idx = 0, c = x, x = z;
-  }
-  if (c < 0.0) idx += 1;
-  const double m = 0.5 / fabs(c);
-  const double m0 = (idx == 0 || idx == 5) ? -m : m, m1 = (idx != 2) ? -m : m;
-  const double u = fmin(fmax(x * m0 + 0.5, 0.0), 1.0), w = fmin(fmax(y * m1 + 0.5, 0.0), 1.0);
-  return ((size_t)idx * n + texel_of(w, n)) * n + texel_of(u, n);
-}
-
 __global__ __launch_bounds__(kWave) void gather_kernel(GatherArgs a) {
   const unsigned lane = threadIdx.x;
   const long long v = blockIdx.x;

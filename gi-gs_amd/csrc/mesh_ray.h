@@ -1,6 +1,7 @@
-// mesh_ray.h -- what mesh_raycast.hip and mesh_light.hip share: the ray against one face, the slab traversal of the triangle
-// grid (include/gigs_hip.h, "Baking occlusion", 2 to 7) and the hemisphere of a vertex (8: the no_normal rule, the basis of
-// Duff et al., the origin, the rotation and the direction of a table row).  Header-only; nothing here is a symbol of the
+// mesh_ray.h -- what mesh_raycast.hip, mesh_light.hip and mesh_gather.hip share: the ray against one face, the slab traversal
+// of the triangle grid (include/gigs_hip.h, "Baking occlusion", 2 to 7), the hemisphere of a vertex (8: the no_normal rule, the
+// basis of Duff et al., the origin, the rotation and the direction of a table row) and the sky texel of a direction ("Baking
+// light", 3).  Header-only; nothing here is a symbol of the
 // library.  float64 on the float32 inputs, + - * / only, and the library is built with -ffp-contract=off.
 #pragma once
 #include "mesh_grid.h"
@@ -171,6 +172,33 @@ __device__ __forceinline__ void hemisphere_direction(const Hemisphere& h, const 
   const double x = (double)row[0], y = (double)row[1], z = (double)row[2];
 #pragma unroll
   for (int c = 0; c < 3; c++) d[c] = (x * h.T[c] + y * h.B[c]) + z * h.n[c];
+}
+
+// ---- the sky of a direction ("Baking light", 3): shared by mesh_light.hip and mesh_gather.hip ----------------------------------
+// the texel of u in [0, 1] on an edge of n texels: min(n - 1, floor(u n)); a NaN goes to 0
+__device__ __forceinline__ int texel_of(double u, int n) {
+  const double t = floor(u * (double)n);
+  return !(t >= 0.0) ? 0 : (t > (double)(n - 1) ? n - 1 : (int)t);
+}
+
+// the index of the sky texel of d: cube_face_uv's face, swaps and signs (cube.h) in float64, the nearest texel
+__device__ __forceinline__ size_t sky_texel(const double* d, int n) {
+  double x = d[0], y = d[1];
+  const double z = d[2], ax = fabs(x), ay = fabs(y), az = fabs(z);
+  int idx;
+  double c;
+  if (az > fmax(ax, ay)) {
+    idx = 4, c = z;
+  } else if (ay > ax) {
+    idx = 2, c = y, y = z;
+  } else {
+    idx = 0, c = x, x = z;
+  }
+  if (c < 0.0) idx += 1;
+  const double m = 0.5 / fabs(c);
+  const double m0 = (idx == 0 || idx == 5) ? -m : m, m1 = (idx != 2) ? -m : m;
+  const double u = fmin(fmax(x * m0 + 0.5, 0.0), 1.0), w = fmin(fmax(y * m1 + 0.5, 0.0), 1.0);
+  return ((size_t)idx * n + texel_of(w, n)) * n + texel_of(u, n);
 }
 
 // the arguments the hemisphere kernels share, checked on the host

@@ -33,6 +33,9 @@
     gather_light(mesh, hits, cube, bounces)   per-vertex irradiance under an environment cube over those records: the
                                          shadowed sky plus `bounces` diffuse inter-reflections, a launch per pass
                                          (gigs_mesh_gather_light); bake_light runs both, sky_cube pools a light's cube (torch)
+    gather_points(points, normals, mesh, cube, radiosity)   the same rays from ANY surface points (a G-buffer's pixels):
+                                         occlusion, shadowed sky and bounced light in one launch (gigs_mesh_gather_points);
+                                         final_gather bakes the vertex radiosity first
     atlas_layout(F, block, width)        the texture atlas of equal per-face charts, face_uvs(F, layout) its UVs (host)
     transfer_attributes(points, src, values)   per-vertex channels of src interpolated at the closest point of src to
                                          every query (gigs_mesh_closest, gigs_mesh_transfer)
@@ -1159,6 +1162,159 @@ def bake_light(mesh, cube, rays=256, bounces=1, reflectance=None, max_distance=N
     irradiance, gathered = gather_light(mesh, hits, cube, bounces, reflectance, return_passes)
     report.update(gathered)
     return irradiance, report
+
+
+# ---- ray-traced light per point: a final gather (include/gigs_hip.h, "Ray-traced light per point") -------------------------
+class PointLight(NamedTuple):
+    occlusion: torch.Tensor   # [N] float32: the open share of the hemisphere within ao_distance, 1 = open
+    hits: torch.Tensor        # [N] int32: the rays with a face within ao_distance
+    irradiance: torch.Tensor  # [N,3] float32 or None (no cube): the shadowed sky plus the bounced light
+    indirect: torch.Tensor    # [N,3] float32 or None: the bounced light alone
+
+
+def _check_radiosity(radiosity, m: Mesh, what: str) -> torch.Tensor:
+    V = int(m.vertices.shape[0])
+    if (not isinstance(radiosity, torch.Tensor) or radiosity.device != m.vertices.device or radiosity.dtype != torch.float32
+            or tuple(radiosity.shape) != (V, 3)):
+        raise ValueError("%s: radiosity must be a [%d,3] float32 tensor on the mesh's device" % (what, V))
+    radiosity = radiosity.detach().contiguous()
+    if not bool(torch.isfinite(radiosity).all()):
+        raise ValueError("%s: radiosity must be finite" % what)
+    return radiosity
+
+
+def _gather_points(points, normals, m: Mesh, grid, cube, radiosity, R, K, directions, ao_distance, max_distance, bias, seed,
+                   mask, report):
+    """The launch of gather_points on checked arguments (grid is not None, N > 0) -> PointLight; fills the counters of report."""
+    dev = m.vertices.device
+    N, V, F = int(points.shape[0]), int(m.vertices.shape[0]), int(m.faces.shape[0])
+    hits = torch.zeros(N, dtype=torch.int32, device=dev)
+    occlusion = torch.ones(N, dtype=torch.float32, device=dev)
+    irradiance = torch.zeros((N, 3), dtype=torch.float32, device=dev) if cube is not None else None
+    indirect = torch.zeros((N, 3), dtype=torch.float32, device=dev) if cube is not None else None
+    order = _cell_order(points.double(), grid)
+    table = torch.from_numpy(directions).to(dev)
+    counts = torch.zeros(6, dtype=torch.int64, device=dev)  # misses, front, back, no normal, masked; overflow (an int32 in its low half)
+    c_lo, c_dims = _c_grid(grid.lo, grid.dims)
+    gigs_lib.check(gigs_lib.lib().gigs_mesh_gather_points(
+        V, F, _p(m.vertices), _p(m.faces), c_lo, grid.cell, c_dims, _p(grid.cell_start), _p(grid.pairs), int(grid.pairs.shape[0]),
+        _scale(grid), N, _p(points), _p(normals), _p(mask) if mask is not None else None, _p(order), _p(table), R, K, seed,
+        float(ao_distance), float("inf") if max_distance is None else float(max_distance), float(bias),
+        int(cube.shape[1]) if cube is not None else 0, _p(cube) if cube is not None else None,
+        _p(radiosity) if radiosity is not None else None, _p(hits), _p(occlusion),
+        _p(irradiance) if cube is not None else None, _p(indirect) if cube is not None else None, counts.data_ptr(),
+        counts[5:].data_ptr(), _stream()), "mesh_gather_points")
+    got = [int(x) for x in counts.cpu()]  # the one read-back
+    if got[5] != 0:
+        raise MeshOverflow("gather_points: an index left its range (%d points, %d vertices, %d faces)" % (N, V, F))
+    report["misses"], report["front_hits"], report["back_hits"], report["no_normal"], report["masked"] = got[:5]
+    return PointLight(occlusion, hits, irradiance, indirect)
+
+
+def gather_points(points, normals, mesh, cube=None, radiosity=None, rays=256, ao_distance=None, max_distance=None, bias=None,
+                  seed=0, rotations=16, directions=None, mask=None, cell=None, grid=None):
+    """(PointLight(occlusion, hits, irradiance, indirect), report): bake_occlusion and one pass of gather_light for ANY surface
+    points -- `points` and `normals` [N,3] float32 on the mesh's device, in practice the covered pixels of a G-buffer -- in one
+    launch (gigs_mesh_gather_points): a wave per point casts bake_occlusion's rays (the same table, frame, origin
+    point + bias normal, and rotation mix64(seed 2^32 + q) mod rotations of point q) against `mesh`.  hits [N] int32 counts
+    the rays whose nearest face lies within `ao_distance`, occlusion [N] = (rays - hits) / rays, 1 = open.  With a `cube`
+    ([6,n,n,3] float32, as gather_light's) the rays run to `max_distance` (None: no limit, as trace_hemispheres) and
+    irradiance [N,3] is the cosine-weighted mean of what they bring: the sky texel where a ray escapes, `radiosity` [V,3]
+    float32 (finite; the mesh's baked reflectance x irradiance; None: nothing) interpolated where it meets the front of a
+    face, nothing at a back; indirect [N,3] is the share of the front hits.  Without a cube both are None and the rays stop
+    at ao_distance, which changes no count.  A point with mask [N] (uint8 or bool) == 0 is `masked`, a point whose position
+    is not finite or whose normal is not of unit length within 2^-10 is `no_normal`: occlusion 1, hits 0, no light.
+    ao_distance and bias default as bake_occlusion's max_distance and bias.  The result is a pure function of the arguments
+    and does not depend on the grid (`cell`, `grid`).  N == 0 or a mesh with no usable face launches nothing and leaves every
+    point open, and then no light is gathered either: irradiance and indirect are 0.  Report: n, misses, front_hits,
+    back_hits, no_normal, masked, rays, rotations, seed, ao_distance, max_distance (None: unlimited), bias, sky_res (None: no
+    cube), radiosity (bool), faces_skipped, cell, dims, pairs.  One read-back (after the checks of cube and radiosity)."""
+    what = "gather_points"
+    R, K, directions = _hemisphere_args(what, rays, rotations, directions, max_distance, bias)
+    if ao_distance is not None and not (float(ao_distance) >= 0 and np.isfinite(float(ao_distance))):
+        raise ValueError("%s: ao_distance must be finite and >= 0 or None, got %r" % (what, ao_distance))
+    m = _mesh_tensors(mesh, what)
+    dev = m.vertices.device
+    points = _check_points(points, dev, what)
+    normals = _check_points(normals, dev, what, "normals")
+    N, F = int(points.shape[0]), int(m.faces.shape[0])
+    if int(normals.shape[0]) != N:
+        raise ValueError("%s: %d points, %d normals" % (what, N, int(normals.shape[0])))
+    if mask is not None:
+        if (not isinstance(mask, torch.Tensor) or mask.device != dev or mask.dtype not in (torch.uint8, torch.bool)
+                or tuple(mask.shape) != (N,)):
+            raise ValueError("%s: mask must be a [%d] uint8 or bool tensor on the mesh's device" % (what, N))
+        mask = mask.detach().to(torch.uint8).contiguous()
+    if cube is not None:
+        cube = _check_cube(cube, what)
+        if cube.device != dev:
+            raise RuntimeError("%s: the cube must be a tensor on the mesh's device: gigs-hip has no CPU path" % what)
+    if radiosity is not None:
+        radiosity = _check_radiosity(radiosity, m, what)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    report = dict(n=N, misses=0, front_hits=0, back_hits=0, no_normal=0, masked=0, rays=R, rotations=K, seed=seed,
+                  ao_distance=0.0 if ao_distance is None else float(ao_distance),
+                  max_distance=None if max_distance is None else float(max_distance), bias=0.0 if bias is None else float(bias),
+                  sky_res=int(cube.shape[1]) if cube is not None else None, radiosity=radiosity is not None)
+    f32 = dict(dtype=torch.float32, device=dev)
+    light = (torch.zeros((N, 3), **f32), torch.zeros((N, 3), **f32)) if cube is not None else (None, None)
+    empty = PointLight(torch.ones(N, **f32), torch.zeros(N, dtype=torch.int32, device=dev), *light)
+    if N == 0:
+        report.update(_grid_report(None, F))
+        return empty, report
+    with torch.cuda.device(dev):
+        if grid is None:
+            grid = triangle_grid(m, cell)
+        report.update(_grid_report(grid, F))
+        if grid is None:  # no usable face: every point is open and nothing is launched
+            live = mask != 0 if mask is not None else torch.ones(N, dtype=torch.bool, device=dev)
+            n2 = (normals.double() ** 2).sum(1)
+            bad = live & ~(torch.isfinite(points).all(1) & (n2 >= 1.0 - 2.0 ** -10) & (n2 <= 1.0 + 2.0 ** -10))
+            got = torch.stack(((~live).sum(), bad.sum())).cpu().tolist()
+            report["masked"], report["no_normal"] = int(got[0]), int(got[1])
+            report["misses"] = R * (N - report["masked"] - report["no_normal"])
+            return empty, report
+        if ao_distance is None:
+            ao_distance = 0.1 * (max(grid.dims) * grid.cell)
+        if bias is None:
+            bias = 1e-3 * float(ao_distance)
+        report["ao_distance"], report["bias"] = float(ao_distance), float(bias)
+        return _gather_points(points, normals, m, grid, cube, radiosity, R, K, directions, ao_distance, max_distance, bias, seed,
+                              mask, report), report
+
+
+def final_gather(points, normals, mesh, cube, bounces=1, reflectance=None, light_rays=None, rays=256, ao_distance=None,
+                 max_distance=None, bias=None, seed=0, rotations=16, directions=None, mask=None, cell=None, grid=None,
+                 memory_limit=TRACE_MEMORY_LIMIT):
+    """(PointLight, report): the irradiance of every point after `bounces` diffuse inter-reflections, a lightmap final gather:
+    bake_light's passes 0 .. bounces - 1 on the VERTICES (trace_hemispheres with `light_rays` rays, default `rays`, then
+    gather_light), then gather_points with the radiosity of pass bounces - 1 (bounces = 0: none, the shadowed sky alone).
+    Both traces share table parameters, seed, bias, max_distance and the grid, so with points = the vertices, normals = the
+    mesh's and light_rays = rays the irradiance is bake_light(bounces)'s bit for bit.  `directions` overrides the table of
+    both.  The report is gather_points' with `bounces` and, under "bake", the vertex passes' report (None for bounces = 0)."""
+    bounces = int(bounces)
+    if bounces < 0:
+        raise ValueError("final_gather: bounces must be >= 0, got %d" % bounces)
+    if cube is None:
+        raise ValueError("final_gather: a cube is needed; gather_points(cube=None) gives the occlusion alone")
+    m = _mesh_tensors(mesh, "final_gather")
+    radiosity, baked = None, None
+    with torch.cuda.device(m.vertices.device):
+        if grid is None:
+            grid = triangle_grid(m, cell)
+        if bounces > 0 and grid is not None:
+            if bias is None:  # one bias for both traces: gather_points' default
+                ao = ao_distance if ao_distance is not None else 0.1 * (max(grid.dims) * grid.cell)
+                bias = 1e-3 * float(ao)
+            hits, baked = trace_hemispheres(m, rays if light_rays is None else light_rays, max_distance, bias, seed, rotations,
+                                            directions, cell, grid, memory_limit)
+            _, radiosities, gathered = _gather_light(m, hits, cube, bounces - 1, reflectance)
+            baked.update(gathered)
+            radiosity = radiosities[bounces - 1]
+        light, report = gather_points(points, normals, m, cube, radiosity, rays, ao_distance, max_distance, bias, seed, rotations,
+                                      directions, mask, cell, grid)
+    report["bounces"], report["bake"] = bounces, baked
+    return light, report
 
 
 def sky_cube(light_or_base, res: int = 32) -> torch.Tensor:

@@ -19,6 +19,11 @@ behind them is the existing one, unchanged.
     MeshRelighter / MeshMultiRelighter / MeshTurntableRelighter   relight.py's three relighters constructed over that source:
                                       rl(cam, rast, view_dirs).  Only the G-buffer differs; shade, SSR march and the sRGB /
                                       median finish are theirs, and the result gains the source's extra planes
+    RaytracedLight(mesh, rays, cube)  a mesh as occluder and bounce surface of any view's pixels: .planes(pos_view, normal,
+                                      viewmatrix, mask) -> occlusion, hits, irradiance, indirect by mesh.gather_points
+                                      (gigs_mesh_gather_points): a final gather per pixel over the mesh's baked radiosity
+    RaytracedGBuffer(inner, tracer)   a G-buffer source around MeshGBuffer or relight.SplatGBuffer whose occlusion plane is the
+                                      traced one, or its product with the inner plane: the relighters take it through source=
 
 The arithmetic is stated in include/gigs_hip.h and restated in numpy by tests/mesh_raster_ref.py (the textured resolve by
 tests/mesh_texture_ref.py).  There is no clipping:
@@ -395,3 +400,161 @@ class MeshTurntableRelighter(relight.TurntableRelighter):
             raise ValueError("MeshTurntableRelighter replays no hipGraph: graphs=False only")
         super().__init__(lights, gi, 0, metallic=metallic, tone=tone, gamma=gamma, brdf_lut=brdf_lut,
                          source=MeshGBuffer(gi, metallic, occlusion))
+
+
+# ---- ray-traced light per pixel: a G-buffer's covered pixels traced against a mesh (mesh.gather_points) ---------------------
+RAYTRACED_MODES = ("replace", "multiply")
+NORMAL_SPACES = ("world", "view")
+
+
+def occluder_mesh(rast: MeshRasterizer) -> mesh_ops.Mesh:
+    """The geometry a rasterizer holds as a mesh.Mesh on its device, for an occlusion-only RaytracedLight: vertices and faces
+    as they are; the normals and materials a textured rasterizer lacks are zero (rays start from pixels, not vertices)."""
+    rast._check()
+    m = rast._mesh
+    V = int(m["vertices"].shape[0])
+    zero3, zero1 = torch.zeros((V, 3), device=rast.device), torch.zeros(V, device=rast.device)
+    return mesh_ops.Mesh(m["vertices"], m["faces"], m.get("normals", zero3), m.get("albedo", zero3), m.get("roughness", zero1),
+                         m.get("metallic", zero1))
+
+
+class RaytracedLight:
+    """A mesh as the occluder and bounce surface of any view's pixels: the triangle grid is built once, and with a `cube`
+    ([6,n,n,3] float32, mesh.sky_cube's) so is the vertex radiosity of the passes 0 .. bounces - 1 (mesh.trace_hemispheres with
+    `light_rays` rays, mesh.gather_light); planes() then runs mesh.gather_points with `rays` rays per pixel.  mesh: what
+    mesh_arrays takes.  ao_distance and bias default as mesh.bake_occlusion's max_distance and bias; the light rays have no
+    distance limit.  Without a cube only the occlusion is traced.  close() / `with` as the rasterizers."""
+
+    def __init__(self, mesh, rays: int = 64, ao_distance=None, bias=None, seed: int = 0, rotations: int = 16, cube=None,
+                 bounces: int = 1, reflectance=None, light_rays: int = 256, device="cuda"):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("RaytracedLight: the mesh must live on a CUDA/HIP device: gigs-hip has no CPU path")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.bounces = int(bounces)
+        if self.bounces < 0:
+            raise ValueError("RaytracedLight: bounces must be >= 0, got %d" % self.bounces)
+        self.rays, self.seed, self.rotations = int(rays), int(seed), int(rotations)
+        mesh_ops._hemisphere_args("RaytracedLight", self.rays, self.rotations, None, ao_distance, bias)
+        self.mesh = mesh if isinstance(mesh, mesh_ops.Mesh) and mesh.vertices.device == dev else device_mesh(mesh, dev)
+        self.cube = None if cube is None else mesh_ops._check_cube(cube, "RaytracedLight").to(dev)
+        with torch.cuda.device(dev):
+            self.grid = mesh_ops.triangle_grid(self.mesh)
+        if self.grid is not None:
+            if ao_distance is None:
+                ao_distance = 0.1 * (max(self.grid.dims) * self.grid.cell)
+            if bias is None:
+                bias = 1e-3 * float(ao_distance)
+        self.ao_distance, self.bias = ao_distance, bias
+        self.radiosity, self.bake_report = None, None  # [bounces, V, 3]: the radiosity of the vertex passes
+        if self.cube is not None and self.bounces > 0 and self.grid is not None:
+            hits, self.bake_report = mesh_ops.trace_hemispheres(self.mesh, int(light_rays), None, self.bias, self.seed, self.rotations,
+                                                                grid=self.grid)
+            _, self.radiosity, gathered = mesh_ops._gather_light(self.mesh, hits, self.cube, self.bounces - 1, reflectance)
+            self.bake_report.update(gathered)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        self.mesh = self.grid = self.cube = self.radiosity = None
+
+    def _check(self):
+        if self.mesh is None:
+            raise RuntimeError("RaytracedLight: closed")
+
+    @torch.no_grad()
+    def prepare(self, pos_view, normal, viewmatrix, mask, normal_space: str = "world"):
+        """(points [H W,3], normals [H W,3] float32, mask [H W] uint8) on the device, row-major over the pixels, from the
+        view-space positions pos_view [3,H,W], the normal plane [3,H,W] and the pixel mask [H,W] or [1,H,W] (non-zero:
+        trace).  viewmatrix M [4,4] is the rasterizers' (p_view = p_world M[:3,:3] + M[3,:3]).  In float64 on the float32
+        inputs, elementwise and in this order, R = M[:3,:3], t = M[3,:3], the rotation taken as orthonormal:
+            d_j = p_view_j - t_j;   p_world_i = (d_0 R_i0 + d_1 R_i1) + d_2 R_i2
+            normal_space "world": w = normal;  "view": the G-buffer's normals_view = -(n_world R), so
+                                  w_i = -((v_0 R_i0 + v_1 R_i1) + v_2 R_i2)
+            n_i = w_i / sqrt((w_0 w_0 + w_1 w_1) + w_2 w_2)
+        and both are rounded to float32.  A zero normal gives NaN: a no_normal point if its mask is set."""
+        self._check()
+        if normal_space not in NORMAL_SPACES:
+            raise ValueError("RaytracedLight: normal_space is one of %s, got %r" % (", ".join(NORMAL_SPACES), normal_space))
+        dev = self.device
+        if not (isinstance(pos_view, torch.Tensor) and isinstance(normal, torch.Tensor) and pos_view.dim() == 3
+                and pos_view.shape[0] == 3 and normal.shape == pos_view.shape):
+            raise ValueError("RaytracedLight: pos_view and normal are [3,H,W] tensors")
+        _, H, W = pos_view.shape
+        if not isinstance(mask, torch.Tensor) or mask.numel() != H * W:
+            raise ValueError("RaytracedLight: mask is a tensor of %d x %d pixels" % (H, W))
+        M = MeshRasterizer._viewmatrix(dict(viewmatrix=viewmatrix), dev).double()
+        R = [[float(x) for x in row] for row in M[:3, :3].cpu().tolist()]
+        t = [float(x) for x in M[3, :3].cpu().tolist()]
+        p = pos_view.detach().to(dev).double().reshape(3, H * W)
+        v = normal.detach().to(dev).double().reshape(3, H * W)
+        d = [p[j] - t[j] for j in range(3)]
+        points = torch.stack([(d[0] * R[i][0] + d[1] * R[i][1]) + d[2] * R[i][2] for i in range(3)], 1)
+        if normal_space == "view":
+            w = [-((v[0] * R[i][0] + v[1] * R[i][1]) + v[2] * R[i][2]) for i in range(3)]
+        else:
+            w = [v[0], v[1], v[2]]
+        length = torch.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
+        normals = torch.stack([w[i] / length for i in range(3)], 1)
+        return points.float().contiguous(), normals.float().contiguous(), (mask.detach().to(dev).reshape(H * W) != 0).to(torch.uint8)
+
+    @torch.no_grad()
+    def planes(self, pos_view, normal, viewmatrix, mask, normal_space: str = "world", bounces=None) -> Dict:
+        """prepare(), then mesh.gather_points -> {occlusion [1,H,W] float32, hits [H,W] int32, irradiance, indirect [3,H,W]
+        float32 or None (no cube), points, normals, mask (the prepared arrays), report}.  bounces (None: the constructor's)
+        picks the vertex pass whose radiosity the front hits bring: irradiance is the light after that many bounces."""
+        points, normals, m = self.prepare(pos_view, normal, viewmatrix, mask, normal_space)
+        _, H, W = pos_view.shape
+        b = self.bounces if bounces is None else int(bounces)
+        if b < 0 or b > self.bounces:
+            raise ValueError("RaytracedLight: bounces must lie in [0, %d], got %d" % (self.bounces, b))
+        radiosity = self.radiosity[b - 1] if (b > 0 and self.radiosity is not None) else None
+        light, report = mesh_ops.gather_points(points, normals, self.mesh, self.cube, radiosity, self.rays, self.ao_distance, None,
+                                               self.bias, self.seed, self.rotations, mask=m, grid=self.grid)
+        report["bounces"] = b if self.cube is not None else None
+        plane3 = lambda x: None if x is None else x.t().reshape(3, H, W).contiguous()  # noqa: E731
+        return dict(occlusion=light.occlusion.reshape(1, H, W), hits=light.hits.reshape(H, W), irradiance=plane3(light.irradiance),
+                    indirect=plane3(light.indirect), points=points, normals=normals, mask=m, report=report)
+
+
+class RaytracedGBuffer:
+    """A G-buffer source around another (MeshGBuffer, relight.SplatGBuffer) whose `occlusion` plane is ray-traced against a
+    RaytracedLight's mesh: source(cam, scene) calls inner(cam, scene), traces from its depth_pos, normals_view (normal_space
+    "view") and mask_u8 with cam's viewmatrix, and puts the traced plane ("replace") or its product with the inner plane
+    ("multiply") in its place, shape and dtype kept.  `extra` gains raytraced_occlusion, and raytraced_irradiance and
+    raytraced_indirect when the tracer has a cube; `report` is the tracer's of the last view.  The relighters take it through
+    source=; graphs=True raises there, because a traced view replays no hipGraph.  depth_pos comes from the FILTERED depth and
+    lies off the mesh by up to the depth range of a pixel's 3x3 neighbourhood: give the tracer a `bias` above that, or the points
+    under the surface see its back (the report's back_hits show it)."""
+    replayable = False
+
+    def __init__(self, inner, tracer: RaytracedLight, occlusion: str = "replace"):
+        if occlusion not in RAYTRACED_MODES:
+            raise ValueError("RaytracedGBuffer: occlusion is one of %s, got %r" % (", ".join(RAYTRACED_MODES), occlusion))
+        if not isinstance(tracer, RaytracedLight):
+            raise TypeError("RaytracedGBuffer: the tracer is a RaytracedLight")
+        self.inner, self.tracer, self.occlusion = inner, tracer, occlusion
+        self.metallic = inner.metallic
+        self.report = None
+
+    @torch.no_grad()
+    def __call__(self, cam: Dict, scene) -> Dict:
+        b = dict(self.inner(cam, scene))
+        t = self.tracer.planes(b["depth_pos"], b["normals_view"], cam["viewmatrix"], b["mask_u8"], normal_space="view")
+        self.report = t["report"]
+        inner = b["occlusion"]
+        plane = t["occlusion"].to(inner.device)
+        if self.occlusion == "multiply":
+            plane = inner.reshape(plane.shape) * plane
+        b["occlusion"] = plane.to(inner.dtype).reshape(inner.shape).contiguous()
+        extra = dict(b.get("extra", {}), raytraced_occlusion=t["occlusion"])
+        if t["irradiance"] is not None:
+            extra["raytraced_irradiance"], extra["raytraced_indirect"] = t["irradiance"], t["indirect"]
+        b["extra"] = extra
+        return b

@@ -4,6 +4,8 @@ over relight.TurntableRelighter, relight.RelightEvaluator and image_writer.Image
     python gi-gs_amd/relight_scene.py -m <out> --checkpoint <out>/chkpntN.pth --hdri a.hdr [b.hdr ...]
                                       [--metallic --tone --gamma --skip_train --skip_test --gt_dir DIR --lpips_weights DIR]
                                       [--rotations N [--rotation_axis x y z]]
+                                      [--occluder mesh.ply [--ao_rays 64 --ao_distance D --ray_bias B
+                                       --occluder_mode replace|multiply]]
     relight_scene(args) -> {split: {...}}
 
 Flags and defaults are relight.py's (:340-356), with --hdri taking one or more maps (Radiance .hdr or .npy [H,W,3]): all
@@ -24,6 +26,12 @@ is <gt_dir>/<light>/<image_name>.png; each view feeds RelightEvaluator, and <lig
 lpips_avg with --lpips_weights) over the split's views -- relight_eval.py's metrics without its fixed view list r_0010 ..
 and its 400 x 400 resize target (the ground truth is resized to the prediction's size).
 
+--occluder mesh.ply (the scene's extracted mesh; a relative path is looked up in <out>) ray-traces the occlusion of every
+view's pixels against that mesh in place of SSAO (mesh_render.RaytracedGBuffer over relight.SplatGBuffer: --ao_rays rays a
+pixel, a multiple of 64, within --ao_distance, started --ray_bias off the surface; both default as mesh.bake_occlusion's), so
+geometry the view does not see occludes too; --occluder_mode multiply shades with the product of both.  The occlusion PNG is
+then that plane, and the split's result holds the last view's tracer report as `occluder`.
+
 Deviation: the reference writes <split>/envmap_relight.png, which every light of relight_all.bash overwrites; here the
 file carries the light's name.
 """
@@ -41,6 +49,8 @@ if __package__ in (None, ""):  # run as a script: make the package's modules imp
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import render_scene as rs  # noqa: E402
+
+OCCLUDER_MODES = ("replace", "multiply")  # mesh_render.RAYTRACED_MODES, without its imports
 
 
 def rotated_names(names: Sequence[str], rotations: int) -> List[str]:
@@ -90,11 +100,35 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rotation_axis", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                    help="axis of --rotations in the map's frame (default 0 1 0)")
     p.add_argument("--workers", type=int, default=12, help="PNG encoder threads (at most 16)")
+    p.add_argument("--occluder", type=str, default=None, help="a mesh PLY: ray-trace the occlusion against it in place of SSAO")
+    p.add_argument("--ao_rays", type=int, default=64, help="occlusion rays per pixel, a multiple of 64 in [64, 1024]")
+    p.add_argument("--ao_distance", type=float, default=None, help="how far an occluder counts (default: mesh.bake_occlusion's)")
+    p.add_argument("--ray_bias", type=float, default=None, help="the rays' start off the surface (default: 1e-3 ao_distance)")
+    p.add_argument("--occluder_mode", choices=OCCLUDER_MODES, default="replace",
+                   help="shade with the traced occlusion, or with its product with SSAO")
     return p
 
 
 def parse_args(argv: Optional[List[str]] = None) -> Namespace:
     return build_parser().parse_args(argv)
+
+
+def check_occluder(args: Namespace) -> bool:
+    """Whether --occluder is given; refuses the tracer's flags without it and values outside their ranges."""
+    rays, mode = int(getattr(args, "ao_rays", 64)), getattr(args, "occluder_mode", "replace")
+    distance, bias = getattr(args, "ao_distance", None), getattr(args, "ray_bias", None)
+    if not getattr(args, "occluder", None):
+        if rays != 64 or distance is not None or bias is not None or mode != "replace":
+            raise ValueError("--ao_rays, --ao_distance, --ray_bias and --occluder_mode need --occluder")
+        return False
+    if mode not in OCCLUDER_MODES:
+        raise ValueError("--occluder_mode: one of %s, got %r" % (", ".join(OCCLUDER_MODES), mode))
+    if rays < 64 or rays > 1024 or rays % 64 != 0:
+        raise ValueError("--ao_rays: a multiple of 64 in [64, 1024], got %d" % rays)
+    for name, x in (("--ao_distance", distance), ("--ray_bias", bias)):
+        if x is not None and not (0.0 <= float(x) < float("inf")):
+            raise ValueError("%s: finite and >= 0, got %r" % (name, x))
+    return True
 
 
 def check_rotations(args: Namespace) -> int:
@@ -134,8 +168,14 @@ def relight_split(args: Namespace, split: str, infos, g, sh_degree: int, lights,
     MAX_LIGHTS = relight.MAX_LIGHTS
     t0 = time.perf_counter()
     with image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
+        tracer = source = None
+        if getattr(args, "occluder", None):  # without it the relighter builds its own SplatGBuffer, as before
+            import mesh_render
+            path = args.occluder if os.path.isabs(args.occluder) or os.path.exists(args.occluder) else os.path.join(out, args.occluder)
+            tracer = mesh_render.RaytracedLight(path, rays=args.ao_rays, ao_distance=args.ao_distance, bias=args.ray_bias, device=dev)
+            source = mesh_render.RaytracedGBuffer(relight.SplatGBuffer(gi, sh_degree, args.metallic), tracer, args.occluder_mode)
         tr = relight.TurntableRelighter(lights, gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
-                                        brdf_lut=lut)  # build_mips per light (:141)
+                                        brdf_lut=lut, source=source)  # build_mips per light (:141)
         ev = relight.RelightEvaluator(names, device=dev, lpips=lp) if args.gt_dir else None
         try:
             for first in range(0, len(lights), MAX_LIGHTS):  # one batch of files per MAX_LIGHTS lights
@@ -167,6 +207,9 @@ def relight_split(args: Namespace, split: str, infos, g, sh_degree: int, lights,
                     res.setdefault("metrics", {})[n] = m
         finally:
             tr.close()
+            if tracer is not None:
+                res["occluder"] = source.report
+                tracer.close()
     res.update(files=wr.files, png_bytes=wr.bytes_written, submit_blocked_s=round(wr.blocked_s, 4),
                total_s=round(time.perf_counter() - t0, 4))
     return res
@@ -182,6 +225,7 @@ def relight_scene(args) -> Dict[str, Dict]:
     import relight
     args = rs.as_namespace(args, parse_args)
     n_rot = check_rotations(args)  # before anything is read
+    check_occluder(args)
     args = rs.combine_args(args)
     if not args.hdri:
         raise ValueError("--hdri: at least one environment map is required")

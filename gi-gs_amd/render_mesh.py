@@ -4,7 +4,8 @@ its scene (mesh_render.py), and compared with the splat render it came from or w
     python gi-gs_amd/render_mesh.py -m <out> --mesh mesh.ply|mesh.obj [--checkpoint <out>/chkpntN.pth] [--hdri a.hdr b.hdr ...]
                                     [--rotations N] [--compare] [--reference_mesh other.ply|other.obj]
                                     [--occlusion ssao|baked|both] [--split test] [--metallic --tone --gamma]
-                                    [--lighting baked [--bounces 1] [--sky_res 32] [--light_rays 256]]            (CLI)
+                                    [--lighting baked|raytraced [--bounces 1] [--sky_res 32] [--light_rays 256]]
+                                    [--occlusion raytraced] [--ao_rays 64] [--ao_distance D] [--ray_bias B]      (CLI)
     render_mesh(args) -> {...}                                                                                   (API)
 
 The scene path and the resolution come from <out>/cfg_args as in render_scene.py, command-line values first; a relative
@@ -38,6 +39,19 @@ PSNR (peak 1, over the pixels the mesh covers) of that plane against the screen-
 diffuse_rgb with the gamma epilogue, i.e. albedo x diffuse cube x SSAO -- for 0 bounces and for --bounces.  The shade looks
 its cubes up at (-n.y, n.z, -n.x); the bake's sky is the light's cube in that frame (shade_frame_sky), so both see one
 environment.
+
+--occlusion raytraced (a PLY or an OBJ) shades with occlusion ray-traced per pixel against the mesh itself in place of SSAO:
+every relighter's source is mesh_render.RaytracedGBuffer(MeshGBuffer, RaytracedLight(mesh)), --ao_rays rays a pixel (a
+multiple of 64) within --ao_distance, started --ray_bias off the surface (both default as mesh.bake_occlusion's).  Geometry
+that is off screen or hidden behind a nearer surface occludes too; <image_name>_occlusion.png is that plane.
+
+--lighting raytraced (needs --hdri and a PLY; the first light) renders the final gather of the baked light per PIXEL:
+mesh_render.RaytracedLight bakes the vertex radiosity once (--light_rays, --bounces, --sky_res, the sky in the shade's frame as
+above) and casts --ao_rays rays from every covered pixel of the mesh's own position and normal planes.
+<image_name>_raytraced_diffuse.png is linear_to_srgb(albedo_map (1 - metallic_map) irradiance), and
+mesh_<split>/raytraced_vs_screen.json holds, per view and on average, the PSNR (peak 1, over the covered pixels) of that plane
+against the screen-space diffuse (psnr_screen_bounces_<b>) and against the per-vertex baked plane of --lighting baked
+(psnr_baked_bounces_<b>), for b = 0 and --bounces, with the bake's report and the tracer's report of the last view.
 """
 from __future__ import annotations
 
@@ -54,7 +68,8 @@ if __package__ in (None, ""):  # run as a script: make the package's modules imp
 
 G_PLANES = ("depth", "normal", "albedo", "roughness", "metallic", "occlusion")
 OCCLUSION_MODES = ("ssao", "baked", "both")  # mesh_render.OCCLUSION_MODES, without its imports
-LIGHTING_MODES = ("screen", "baked")
+OCCLUSION_CHOICES = OCCLUSION_MODES + ("raytraced",)  # raytraced: mesh_render.RaytracedGBuffer around the "ssao" source
+LIGHTING_MODES = ("screen", "baked", "raytraced")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -62,8 +77,9 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Mesh rendering parameters")
     render_scene.add_model_arguments(p)
     p.add_argument("--mesh", type=str, required=True, help="The PLY of extract_mesh.py, or the OBJ of texture_mesh.py.")
-    p.add_argument("--occlusion", choices=OCCLUSION_MODES, default="ssao",
-                   help="what shades: screen-space occlusion, the OBJ's baked channel, or their product")
+    p.add_argument("--occlusion", choices=OCCLUSION_CHOICES, default="ssao",
+                   help="what shades: screen-space occlusion, the OBJ's baked channel, their product, or occlusion ray-traced "
+                        "per pixel against the mesh")
     p.add_argument("--reference_mesh", type=str, default=None, help="a second mesh (PLY or OBJ): writes mesh_vs_mesh.json")
     p.add_argument("--checkpoint", type=str, default=None, help="The checkpoint: its light, and the Gaussians of --compare.")
     p.add_argument("--hdri", type=str, nargs="+", default=None, help="Environment maps to light the mesh with (.hdr or .npy).")
@@ -76,17 +92,21 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--" + k, type=type(v), default=v)
     p.add_argument("--workers", type=int, default=12, help="PNG encoder threads (at most 16)")
     p.add_argument("--lighting", choices=LIGHTING_MODES, default="screen",
-                   help="baked: also render the ray-cast diffuse light of mesh.bake_light and compare it with the screen-space one")
+                   help="baked: also render the ray-cast diffuse light of mesh.bake_light and compare it with the screen-space one; "
+                        "raytraced: its final gather per pixel, compared with both")
     p.add_argument("--bounces", type=int, default=1, help="diffuse inter-reflections of the light bake")
     p.add_argument("--sky_res", type=int, default=32, help="texels an edge of the sky cube the light bake looks up")
     p.add_argument("--light_rays", type=int, default=256, help="rays per vertex of the light bake, a multiple of 64 in [64, 1024]")
+    p.add_argument("--ao_rays", type=int, default=64, help="rays per pixel of the ray-traced modes, a multiple of 64 in [64, 1024]")
+    p.add_argument("--ao_distance", type=float, default=None, help="how far an occluder counts (default: mesh.bake_occlusion's)")
+    p.add_argument("--ray_bias", type=float, default=None, help="the rays' start off the surface (default: 1e-3 ao_distance)")
     return p
 
 
 def parse_args(argv: Optional[List[str]] = None) -> Namespace:
     p = build_parser()
     args = p.parse_args(argv)
-    if args.occlusion != "ssao" and not is_textured(args.mesh):
+    if args.occlusion in ("baked", "both") and not is_textured(args.mesh):
         p.error("--occlusion %s needs a textured mesh (.obj): a PLY has no baked channel" % args.occlusion)
     return args
 
@@ -122,9 +142,9 @@ def _check(args: Namespace) -> int:
     if not args.checkpoint and not args.model_path:
         raise ValueError("-m is required without --checkpoint")
     occlusion = getattr(args, "occlusion", "ssao")
-    if occlusion not in OCCLUSION_MODES:
-        raise ValueError("--occlusion: one of %s, got %r" % (", ".join(OCCLUSION_MODES), occlusion))
-    if occlusion != "ssao" and not is_textured(args.mesh):
+    if occlusion not in OCCLUSION_CHOICES:
+        raise ValueError("--occlusion: one of %s, got %r" % (", ".join(OCCLUSION_CHOICES), occlusion))
+    if occlusion in ("baked", "both") and not is_textured(args.mesh):
         raise ValueError("--occlusion %s needs a textured mesh (.obj): a PLY has no baked channel" % occlusion)
     lighting = getattr(args, "lighting", "screen")
     if lighting not in LIGHTING_MODES:
@@ -134,6 +154,19 @@ def _check(args: Namespace) -> int:
             raise ValueError("--lighting baked needs --hdri and a per-vertex mesh (.ply)")
         if int(getattr(args, "bounces", 1)) < 0:
             raise ValueError("--bounces: a count of inter-reflections, got %d" % int(args.bounces))
+    if lighting == "raytraced":
+        if not args.hdri or is_textured(args.mesh):
+            raise ValueError("--lighting raytraced needs --hdri and a per-vertex mesh (.ply)")
+        if int(getattr(args, "bounces", 1)) < 0:
+            raise ValueError("--bounces: a count of inter-reflections, got %d" % int(args.bounces))
+    if lighting == "raytraced" or occlusion == "raytraced":
+        rays = int(getattr(args, "ao_rays", 64))
+        if rays < 64 or rays > 1024 or rays % 64 != 0:
+            raise ValueError("--ao_rays: a multiple of 64 in [64, 1024], got %d" % rays)
+        for name in ("ao_distance", "ray_bias"):
+            x = getattr(args, name, None)
+            if x is not None and not (0.0 <= float(x) < float("inf")):
+                raise ValueError("--%s: finite and >= 0, got %r" % (name, x))
     return n_rot
 
 
@@ -209,6 +242,68 @@ def render_baked(args: Namespace, mesh_path: str, light, gi: Dict, lut, infos, d
     return dict(baked_vs_screen_json=path, baked_vs_screen=cmp["average"], baked_diffuse=files)
 
 
+def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, infos, dev, out: str) -> Dict:
+    """--lighting raytraced: the files and the report described in the module docstring -> what render_mesh adds to its result."""
+    import torch
+
+    import dataset_readers as dr
+    import image_writer
+    import mesh
+    import mesh_render
+    import pipeline
+    import relight
+    m = mesh_render.device_mesh(mesh_path, dev)
+    B = int(args.bounces)
+    rho = (m.albedo * (1.0 - m.metallic)[:, None]).contiguous()
+    sky = shade_frame_sky(light, args.sky_res)
+    passes, bake = mesh.bake_light(m, sky, rays=args.light_rays, bounces=B, reflectance=rho, return_passes=True)
+    which = sorted({0, B})
+    source, scratch = mesh_render.MeshGBuffer(gi, args.metallic), relight.Scratch()
+    base = os.path.join(out, "mesh_" + args.split)
+    rows, files, report = [], [], None
+    with mesh_render.MeshRasterizer(m, device=dev) as plain, image_writer.ImageWriter(workers=args.workers) as wr, \
+            mesh_render.RaytracedLight(m, rays=args.ao_rays, ao_distance=args.ao_distance, bias=args.ray_bias, cube=sky, bounces=B,
+                                       reflectance=rho, light_rays=args.light_rays, device=dev) as tracer, torch.no_grad():
+        baked = {b: mesh_render.MeshRasterizer(m._replace(albedo=(rho * passes[b]).contiguous()), device=dev) for b in which}
+        try:
+            rays = None
+            for ci in infos:
+                c = dr.camera_from_info(ci, args.resolution, device=dev)
+                if rays is None:
+                    rays = pipeline.canonical_rays(c, dev)
+                g = source(c, plain)
+                screen = relight.shade_ssr(light, lut, gi, args.metallic, False, True, c, pipeline.view_dirs_for(c, rays, dev), g,
+                                           g["albedo_map"], scratch, parts=True)[3].nan_to_num().clamp(0, 1).double()
+                o = plain(c)  # the mesh's own position and normal planes: sharper than the G-buffer's filtered ones
+                cover = o["tri_id"] >= 0
+                n = cover.sum().clamp(min=1).double() * 3.0
+                psnr = lambda x, y: -10.0 * torch.log10(((x - y).pow(2) * cover).sum() / n)  # noqa: E731
+                row = dict(image_name=ci.image_name, pixels=cover.sum())
+                for b in which:
+                    t = tracer.planes(o["pos"], o["normal"], c["viewmatrix"], cover, "world", bounces=b)
+                    report = t["report"]
+                    plane = pipeline.linear_to_srgb(o["albedo"] * (1.0 - o["metallic"]) * t["irradiance"])
+                    mine = plane.nan_to_num().clamp(0, 1).double()
+                    row["screen", b] = psnr(mine, screen)
+                    row["baked", b] = psnr(mine, pipeline.linear_to_srgb(baked[b](c)["albedo"]).clamp(0, 1).double())
+                    if b == B:
+                        files.append(os.path.join(base, "%s_raytraced_diffuse.png" % ci.image_name))
+                        wr.submit([image_writer.Image(files[-1], plane)])
+                rows.append(row)
+        finally:
+            for r in baked.values():
+                r.close()
+    keys = {"psnr_%s_bounces_%d" % (k, b): (k, b) for k in ("screen", "baked") for b in which}
+    views = [dict(image_name=r["image_name"], pixels_covered=int(r["pixels"]), **{name: float(r[kb]) for name, kb in keys.items()})
+             for r in rows]
+    cmp = dict(mesh=mesh_path, bounces=B, sky_res=int(args.sky_res), rays=int(args.ao_rays), light_rays=int(args.light_rays),
+               light=bake, tracer=report, views=views, average={k: sum(v[k] for v in views) / len(views) for k in keys})
+    path = os.path.join(base, "raytraced_vs_screen.json")
+    with open(path, "w") as f:
+        json.dump(cmp, f, indent=4)
+    return dict(raytraced_vs_screen_json=path, raytraced_vs_screen=cmp["average"], raytraced_diffuse=files)
+
+
 def open_mesh(path: str, device):
     """The rasterizer of a mesh file: textured for an .obj, per-vertex for a PLY."""
     import mesh_render
@@ -218,6 +313,21 @@ def open_mesh(path: str, device):
 
 
 MESH_VS_MESH_KEYS = ("coverage_iou", "albedo_psnr", "roughness_psnr", "metallic_psnr", "normal_angle_deg")
+
+
+def mesh_relighter(lights, gi: Dict, args: Namespace, lut, rast, occlusion: str, dev):
+    """(the turntable relighter of a mesh, its tracer or None): mesh_render.MeshTurntableRelighter, or for occlusion
+    "raytraced" relight.TurntableRelighter over a RaytracedGBuffer that traces against the rasterizer's own mesh."""
+    import mesh_render
+    import relight
+    if occlusion != "raytraced":
+        return mesh_render.MeshTurntableRelighter(lights, gi, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
+                                                  brdf_lut=lut, occlusion=occlusion), None
+    tracer = mesh_render.RaytracedLight(mesh_render.occluder_mesh(rast), rays=args.ao_rays, ao_distance=args.ao_distance,
+                                        bias=args.ray_bias, device=dev)
+    source = mesh_render.RaytracedGBuffer(mesh_render.MeshGBuffer(gi, args.metallic), tracer)
+    return relight.TurntableRelighter(lights, gi, 0, metallic=args.metallic, tone=args.tone, gamma=args.gamma, brdf_lut=lut,
+                                      source=source), tracer
 
 
 def mesh_vs_mesh(o: Dict, r: Dict) -> Dict:
@@ -322,18 +432,17 @@ def render_mesh(args) -> Dict:
     res: Dict = {"mesh": mesh_path, "n_views": len(infos), "lights": names}
     per_view: List[Dict] = []
     vs_mesh: List[Dict] = []
-    ref_rast = ref_tr = None
+    ref_rast = ref_tr = tracer = ref_tracer = None
     try:
         with open_mesh(mesh_path, dev) as rast, image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
             res.update(vertices=rast.V, faces=rast.F)
             textured = isinstance(rast, mesh_render.TexturedMeshRasterizer)
-            tr = mesh_render.MeshTurntableRelighter(lights, gi, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
-                                                    brdf_lut=lut, occlusion=occlusion)
+            tr, tracer = mesh_relighter(lights, gi, args, lut, rast, occlusion, dev)
             if ref_path:
                 ref_rast = open_mesh(ref_path, dev)
-                ref_tr = mesh_render.MeshTurntableRelighter(
-                    lights, gi, metallic=args.metallic, tone=args.tone, gamma=args.gamma, brdf_lut=lut,
-                    occlusion=occlusion if isinstance(ref_rast, mesh_render.TexturedMeshRasterizer) else "ssao")
+                ref_tr, ref_tracer = mesh_relighter(
+                    lights, gi, args, lut, ref_rast,
+                    occlusion if occlusion == "raytraced" or isinstance(ref_rast, mesh_render.TexturedMeshRasterizer) else "ssao", dev)
             splat = relight.Relighter(lights[0], gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
                                       brdf_lut=lut) if args.compare else None
             try:
@@ -376,6 +485,9 @@ def render_mesh(args) -> Dict:
                     ref_tr.close()
                 if ref_rast is not None:
                     ref_rast.close()
+                for t in (tracer, ref_tracer):
+                    if t is not None:
+                        t.close()
         res.update(files=wr.files, png_bytes=wr.bytes_written)
         if ref_path:
             cmp = dict(mesh=mesh_path, reference=ref_path, occlusion=occlusion, lights=names, **mesh_vs_mesh_report(vs_mesh, names))
@@ -398,6 +510,8 @@ def render_mesh(args) -> Dict:
             res.update(compare_json=path, compare=cmp["average"])
         if getattr(args, "lighting", "screen") == "baked":
             res.update(render_baked(args, mesh_path, lights[0], gi, lut, infos, dev, out))
+        if getattr(args, "lighting", "screen") == "raytraced":
+            res.update(render_raytraced(args, mesh_path, lights[0], gi, lut, infos, dev, out))
     finally:
         pipeline._collect_idle()
     res["total_s"] = round(time.perf_counter() - t0, 4)

@@ -967,6 +967,48 @@ int gigs_mesh_gather_light(int n_vertices, int n_faces, const float* vertices, c
                            const float* directions, int n_rays, int n_rotations, unsigned long long seed, const int* hit_face,
                            const float* hit_bary, int sky_res, const float* sky, const float* reflectance, const float* previous,
                            float* irradiance, float* radiosity, int* overflow, void* stream);
+/* Ray-traced light per point (gigs-hip extension; the device half of mesh.gather_points / mesh.final_gather): "Baking
+ * occlusion" and "Baking light" for ANY set of surface points with normals -- in practice the covered pixels of a G-buffer --
+ * in one kernel, a lightmap final gather: the open share of the hemisphere, the irradiance under the environment cube
+ * shadowed by the mesh, and the diffuse light bounced from the mesh's baked radiosity.  The conventions are those of the two
+ * sections: DEVICE arrays except `lo` and `dims`, no synchronisation, no allocation, float64 on the float32 inputs, + - * /
+ * only, no sqrt, no float atomics: tests/mesh_gather_ref.py reproduces every bit in numpy.
+ *   1 Points.  points [N, 3], normals [N, 3] float32; mask [N] uint8 or NULL.  Point q with mask[q] == 0 is MASKED
+ *     (counts[4] += 1); otherwise a point that fails the no_normal rule of "Baking occlusion", 8 (position not finite,
+ *     dot(n, n) not in [1 - 2^-10, 1 + 2^-10]) counts as no_normal (counts[3] += 1).  Either way hits = 0, occlusion = 1 and
+ *     both light outputs are 0; its rays are in no other counter.
+ *   2 Rays.  Those of "Baking occlusion", 8, by the same code with the point in the vertex's place: the rotation
+ *     k = mix((seed 2^32 + q) mod 2^64) mod K, the basis of the point's normal, the origin o = p + bias n, the direction of
+ *     row (k, i) of the table [K, R, 3].
+ *   3 Classification.  Ray i is traversed as in 2 to 7 there with t_max = max_distance (+inf: no limit) and classified as in
+ *     "Baking light", 2: a miss, a FRONT hit (dot(d, n_g) < 0) or a BACK hit.  counts[0..2] = misses, front hits, back hits.
+ *   4 Occlusion.  hits[q] = the rays whose nearest accepted face has t <= ao_distance (float64 t);
+ *     occlusion[q] = float32(double(R - hits) / double(R)), 1 = open.
+ *   5 Occlusion only.  With sky == NULL the rays are traversed with t_max = min(ao_distance, max_distance) (ao_distance, if
+ *     max_distance is not the smaller), and irradiance and indirect are not touched (pass NULL).  hits is the same: whether a
+ *     face is accepted at t does not depend on t_max >= t, so a ray has an accepted face within ao_distance exactly when
+ *     its NEAREST accepted face lies there.  The counters 0..2 then classify within that distance.
+ *   6 Light.  The contribution c_i of "Baking light", 4: a miss brings the sky texel of d_i (3 there); a front hit of face
+ *     (i0, i1, i2) brings (b0 Q[i0] + b1 Q[i1]) + b2 Q[i2], Q = radiosity [V, 3] float32 as doubles (0 if radiosity ==
+ *     NULL), b1 = double(float32(w1 / W)), b2 = double(float32(w2 / W)) -- the float32 rounding the records have --
+ *     b0 = max(0, (1 - b1) - b2); a back hit brings 0.
+ *   7 Sums.  Lane l adds c_i for i = l, l + 64, .. in that order from 0.0 into S, and the front hits' c_i alone, in the same
+ *     order, into S_ind; both go through the butterfly of "Baking light", 5.  irradiance[q] = float32(S / R),
+ *     indirect[q] = float32(S_ind / R), per channel.  With the radiosity of pass b - 1 of gigs_mesh_gather_light and points
+ *     = the vertices this is I(b) of "Baking light", 6, bit for bit.
+ * gigs_mesh_gather_points, one one-wave block per row of `order` [N] int64 (the points sorted by cell, or NULL): the wave
+ *   walks the R / 64 chunks, one direction per lane, and stores hits [N] int32, occlusion [N] float32, irradiance [N, 3] and
+ *   indirect [N, 3] float32 itself; counts [5] uint64 (cleared inside the call) = misses, front hits, back hits, no_normal
+ *   points, masked points.  sky_res = n in [1, 4096] when sky is given.  n_points == 0 launches nothing.
+ * An order row, a cell_start entry, a pair key or a face index outside its range sets *overflow (cleared by the caller) and
+ *   the wave stores nothing. */
+int gigs_mesh_gather_points(int n_vertices, int n_faces, const float* vertices, const int* faces, const float* lo, double cell,
+                            const int* dims, const long long* cell_start, const long long* pair_keys, long long n_pairs,
+                            double scale, int n_points, const float* points, const float* normals, const unsigned char* mask,
+                            const long long* order, const float* directions, int n_rays, int n_rotations, unsigned long long seed,
+                            double ao_distance, double max_distance, double bias, int sky_res, const float* sky,
+                            const float* radiosity, int* hits, float* occlusion, float* irradiance, float* indirect,
+                            unsigned long long* counts, int* overflow, void* stream);
 /* Texturing meshes (gigs-hip extension; the device half of mesh.bake_atlas / mesh.transfer_attributes): the per-vertex
  * channels of a heavy SOURCE mesh stored in the texels of an atlas over a light TARGET mesh.  Every texel of the atlas gets
  * the point of the target's surface it stands for (gigs_mesh_atlas_points), the search of "Comparing meshes" finds the
