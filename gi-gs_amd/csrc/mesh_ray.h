@@ -1,5 +1,5 @@
-// mesh_ray.h -- what mesh_raycast.hip, mesh_light.hip and mesh_gather.hip share: the ray against one face, the slab traversal
-// of the triangle grid (include/gigs_hip.h, "Baking occlusion", 2 to 7), the hemisphere of a vertex (8: the no_normal rule, the
+// mesh_ray.h -- what mesh_raycast.hip, mesh_light.hip, mesh_gather.hip and mesh_shadow.hip share: the ray against one face, the
+// slab traversal of the triangle grid (include/gigs_hip.h, "Baking occlusion", 2 to 7) and its any-hit form, the hemisphere of a vertex (8: the no_normal rule, the
 // basis of Duff et al., the origin, the rotation and the direction of a table row) and the sky texel of a direction ("Baking
 // light", 3).  Header-only; nothing here is a symbol of the
 // library.  float64 on the float32 inputs, + - * / only, and the library is built with -ffp-contract=off.
@@ -137,6 +137,65 @@ __device__ __forceinline__ bool traverse(const MeshView& m, const double* o, con
       }
   }
   return ok;
+}
+
+// Any hit: true iff the ray has an accepted face within tmax, i.e. iff traverse() would leave best->face >= 0 (DESIGN.md,
+// "Analytic lights and shadows", has the proof).  The slab walk, the range checks and ray_triangle are traverse()'s; the
+// walk returns at the first accepted face and keeps no nearest one.  *ok (true on entry) turns false if an index left its
+// range before that.
+__device__ __forceinline__ bool occluded(const MeshView& m, const double* o, const double* d, double tmax, bool* ok) {
+  const Grid& g = m.g;
+  const double ax = fabs(d[0]), ay = fabs(d[1]), az = fabs(d[2]);
+  const int A = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2), U = A == 2 ? 0 : A + 1, W = A == 0 ? 2 : A - 1;
+  const double oA = pick(o, A), dA = pick(d, A), oU = pick(o, U), dU = pick(d, U), oW = pick(o, W), dW = pick(d, W);
+  const double loA = pick(g.lo, A), loU = pick(g.lo, U), loW = pick(g.lo, W), cell = g.cell;
+  const int GA = pick(g.G, A), GU = pick(g.G, U), GW = pick(g.G, W);
+  const int stride[3] = {1, g.G[0], g.G[0] * g.G[1]};
+  const int sA = pick(stride, A), sU = pick(stride, U), sW = pick(stride, W);
+  const double sigma = kSlack * (m.M + max3(fabs(o[0]), fabs(o[1]), fabs(o[2])));
+  const double s2 = 2.0 * sigma, s3 = 3.0 * sigma;
+  const double dd = dot3(d, d);
+  const bool up = dA > 0.0;
+  const int step = up ? 1 : -1;
+  for (int k = cell_at(loA, cell, GA, up ? oA - s3 : oA + s3); k >= 0 && k < GA; k += step) {
+    const double ta = ((plane_at(loA, cell, k) - s2) - oA) / dA, tb = ((plane_at(loA, cell, k + 1) + s2) - oA) / dA;
+    double tn = fmin(ta, tb), tf = fmax(ta, tb);
+    if (tf < 0.0) continue;  // the slab lies behind the origin
+    if (tn > tmax) break;    // every later slab starts later still
+    tn = fmax(tn, 0.0), tf = fmin(tf, tmax);
+    const double u_n = oU + tn * dU, u_f = oU + tf * dU, w_n = oW + tn * dW, w_f = oW + tf * dW;
+    const int u0 = cell_at(loU, cell, GU, fmin(u_n, u_f) - s2), u1 = cell_at(loU, cell, GU, fmax(u_n, u_f) + s2);
+    const int w0 = cell_at(loW, cell, GW, fmin(w_n, w_f) - s2), w1 = cell_at(loW, cell, GW, fmax(w_n, w_f) + s2);
+    for (int w = w0; w <= w1; w++)
+      for (int u = u0; u <= u1; u++) {
+        const long long c = (long long)k * sA + (long long)u * sU + (long long)w * sW;
+        const long long s = m.cell_start[c], e = m.cell_start[c + 1];
+        if (s < 0 || e < s || e > m.n_pairs) {
+          *ok = false;
+          continue;
+        }
+        for (long long r = s; r < e; r++) {
+          const long long key = m.pairs[r];
+          const long long f = key & 0xffffffffLL;
+          if ((key >> 32) != c || f >= m.F) {
+            *ok = false;
+            continue;
+          }
+          const int idx[3] = {m.faces[3 * (size_t)f], m.faces[3 * (size_t)f + 1], m.faces[3 * (size_t)f + 2]};
+          if (!in_range(idx[0], idx[1], idx[2], m.V)) {
+            *ok = false;
+            continue;
+          }
+          double p0[3], p1[3], p2[3];
+          load3(m.vertices, idx[0], p0);
+          load3(m.vertices, idx[1], p1);
+          load3(m.vertices, idx[2], p2);
+          Hit h;
+          if (ray_triangle(o, d, dd, sigma, tmax, idx, p0, p1, p2, &h)) return true;
+        }
+      }
+  }
+  return false;
 }
 
 // ---- the hemisphere of a vertex ("Baking occlusion", 8) -----------------------------------------------------------------------

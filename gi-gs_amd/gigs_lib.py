@@ -163,6 +163,10 @@ SIGNATURES = {
     "gigs_mesh_gather_points": (_i, [_i, _i, _f, _f, C.POINTER(_fl), C.c_double, C.POINTER(_i), _f, _f, C.c_longlong, C.c_double,
                                      _i, _f, _f, _f, _f, _f, _i, _i, C.c_ulonglong, C.c_double, C.c_double, C.c_double, _i, _f, _f,
                                      _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_shadow_points": (_i, [_i, _i, _f, _f, C.POINTER(_fl), C.c_double, C.POINTER(_i), _f, _f, C.c_longlong, C.c_double,
+                                     _i, _f, _f, _f, _f, _i, _f, _f, _i, _i, C.c_ulonglong, C.c_double, C.c_double, _f, _f, _f, _f,
+                                     C.c_void_p]),
+    "gigs_shade_lights": (_i, [_i, _f, _f, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_atlas_points": (_i, [_i, _i, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_transfer": (_i, [_i, _i, _f, _f, _i, _f, _i, _f, _f, _f, C.c_longlong, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_project": (_i, [_i, _f, _f, _fl, _fl, _i, _i, _f, _f, _f, C.c_void_p]),

@@ -1317,6 +1317,136 @@ def final_gather(points, normals, mesh, cube, bounces=1, reflectance=None, light
     return light, report
 
 
+# ---- shadows of analytic lights per point (include/gigs_hip.h, "Shadows of analytic lights") --------------------------------
+SHADOW_MAX_SAMPLES, SHADOW_MAX_ROTATIONS = 64, 64
+SHADOW_COUNTERS = ("rays", "blocked", "below_horizon", "no_normal", "masked")
+
+
+def shadow_points(points, normals, mesh, lights, samples=1, rotations=16, bias=None, max_distance=None, seed=0, mask=None,
+                  grid=None):
+    """(visibility [N,L] float32, lit [N,L] int32, report): for every point (`points`, `normals` [N,3] float32 on the mesh's
+    device, gather_points' conventions for `mask` and the no_normal rule) and every one of the L analytic lights (a sequence of
+    analytic_lights.AnalyticLight, or their packed [L,8] float32 rows) the share of the light's `samples` samples that reach
+    the point past `mesh`, in one launch of any-hit shadow rays (gigs_mesh_shadow_points): the origin is point + bias normal,
+    sample s of a point light aims at centre + radius u, of a directional light at -direction + tan(angle) u, with u row s of
+    rotation mix64(seed 2^32 + q) mod rotations of analytic_lights.ball_offsets(samples, rotations); samples = 1 is the hard
+    shadow towards the light's centre.  A sample whose direction does not rise above the point's tangent plane is dark
+    without a ray; a directional light's rays stop at `max_distance` (None: no limit).  lit counts the samples that arrive,
+    visibility = lit / samples; a masked or no_normal point gets visibility 1 and no rays.  bias defaults as gather_points'.
+    The result is a pure function of the arguments and does not depend on the `grid`.  N == 0 or a mesh with no usable face
+    launches nothing and returns 1 everywhere a ray would have been cast.  Report: n, lights, samples, rotations, seed,
+    bias, max_distance (None: unlimited), rays, blocked, below_horizon, no_normal, masked, faces_skipped, cell, dims, pairs.
+    One read-back."""
+    import analytic_lights
+    what = "shadow_points"
+    S, K = int(samples), int(rotations)
+    if S < 1 or S > SHADOW_MAX_SAMPLES:
+        raise ValueError("%s: samples must lie in [1, %d], got %d" % (what, SHADOW_MAX_SAMPLES, S))
+    if K < 1 or K > SHADOW_MAX_ROTATIONS:
+        raise ValueError("%s: rotations must lie in [1, %d], got %d" % (what, SHADOW_MAX_ROTATIONS, K))
+    for name, x in (("max_distance", max_distance), ("bias", bias)):
+        if x is not None and not (float(x) >= 0 and np.isfinite(float(x))):
+            raise ValueError("%s: %s must be finite and >= 0 or None, got %r" % (what, name, x))
+    rows = analytic_lights.light_rows(lights, what)
+    L = int(rows.shape[0])
+    m = _mesh_tensors(mesh, what)
+    dev = m.vertices.device
+    points = _check_points(points, dev, what)
+    normals = _check_points(normals, dev, what, "normals")
+    N, V, F = int(points.shape[0]), int(m.vertices.shape[0]), int(m.faces.shape[0])
+    if int(normals.shape[0]) != N:
+        raise ValueError("%s: %d points, %d normals" % (what, N, int(normals.shape[0])))
+    if mask is not None:
+        if (not isinstance(mask, torch.Tensor) or mask.device != dev or mask.dtype not in (torch.uint8, torch.bool)
+                or tuple(mask.shape) != (N,)):
+            raise ValueError("%s: mask must be a [%d] uint8 or bool tensor on the mesh's device" % (what, N))
+        mask = mask.detach().to(torch.uint8).contiguous()
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    report = dict(n=N, lights=L, samples=S, rotations=K, seed=seed, bias=0.0 if bias is None else float(bias),
+                  max_distance=None if max_distance is None else float(max_distance))
+    report.update(dict.fromkeys(SHADOW_COUNTERS, 0))
+    visibility = torch.ones((N, L), dtype=torch.float32, device=dev)
+    lit = torch.full((N, L), S, dtype=torch.int32, device=dev)
+    if N == 0:
+        report.update(_grid_report(None, F))
+        return visibility, lit, report
+    with torch.cuda.device(dev):
+        if grid is None:
+            grid = triangle_grid(m)
+        report.update(_grid_report(grid, F))
+        if bias is None and grid is not None:
+            bias = 1e-3 * (0.1 * (max(grid.dims) * grid.cell))
+            report["bias"] = float(bias)
+        if grid is None:  # no usable face: nothing is launched; what would have been a ray arrives
+            return _shadow_points_open(points, normals, rows, analytic_lights.ball_offsets(S, K), seed, 0.0 if bias is None else bias,
+                                       mask, report)
+        counts = _shadow_points(points, normals, m, grid, rows, analytic_lights.ball_offsets(S, K), seed, bias, max_distance, mask,
+                                lit, visibility)
+        got = [int(x) for x in counts.cpu()]  # the one read-back
+        if got[5] != 0:
+            raise MeshOverflow("shadow_points: an index left its range (%d points, %d vertices, %d faces)" % (N, V, F))
+    report.update(zip(SHADOW_COUNTERS, got[:5]))
+    return visibility, lit, report
+
+
+def _shadow_points(points, normals, m: Mesh, grid, rows, offsets, seed, bias, max_distance, mask, lit, visibility, sort: bool = True):
+    """The launch of shadow_points on checked arguments (grid is not None, N > 0) into lit and visibility [N,L] -> counts [6]
+    int64 on the device: the five counters and overflow (an int32 in its low half).  sort=False: the points as they come."""
+    dev = m.vertices.device
+    N, L, (K, S) = int(points.shape[0]), int(rows.shape[0]), offsets.shape[:2]
+    order = _cell_order(points.double(), grid) if sort else None
+    d_rows, table = torch.from_numpy(rows).to(dev), torch.from_numpy(offsets).to(dev)
+    counts = torch.zeros(6, dtype=torch.int64, device=dev)
+    c_lo, c_dims = _c_grid(grid.lo, grid.dims)
+    gigs_lib.check(gigs_lib.lib().gigs_mesh_shadow_points(
+        int(m.vertices.shape[0]), int(m.faces.shape[0]), _p(m.vertices), _p(m.faces), c_lo, grid.cell, c_dims, _p(grid.cell_start),
+        _p(grid.pairs), int(grid.pairs.shape[0]), _scale(grid), N, _p(points), _p(normals), _p(mask) if mask is not None else None,
+        _p(order) if order is not None else None, L, _p(d_rows), _p(table), int(S), int(K), seed, float(bias),
+        float("inf") if max_distance is None else float(max_distance), _p(lit), _p(visibility), counts.data_ptr(),
+        counts[5:].data_ptr(), _stream()), "mesh_shadow_points")
+    return counts
+
+
+def _shadow_points_open(points, normals, rows, offsets, seed, bias, mask, report):
+    """shadow_points against a mesh with no usable face, in torch float64: the classification of every sample with nothing
+    to block it -> (visibility, lit, report).  Not a fall-back for the kernel: there is nothing to trace."""
+    dev = points.device
+    N, L, (K, S) = int(points.shape[0]), int(rows.shape[0]), offsets.shape[:2]
+    live = mask != 0 if mask is not None else torch.ones(N, dtype=torch.bool, device=dev)
+    n = normals.double()
+    n2 = (n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]
+    good = live & torch.isfinite(points).all(1) & (n2 >= 1.0 - 2.0 ** -10) & (n2 <= 1.0 + 2.0 ** -10)
+    o = points.double() + float(bias) * n
+    q = np.arange(N, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        k = (_mix64((np.uint64(seed) << np.uint64(32)) + q) % np.uint64(K)).astype(np.int64)
+    u = torch.from_numpy(offsets.astype(np.float64)).to(dev)[torch.from_numpy(k).to(dev)]  # [N,S,3]
+    r = torch.from_numpy(rows.astype(np.float64)).to(dev)
+    lit = torch.full((N, L), int(S), dtype=torch.int32, device=dev)
+    below = 0
+    for l in range(L):
+        e = r[l, 4]
+        d = (r[l, 1:4] + e * u) - o[:, None, :] if rows[l, 0] == 0 else (-r[l, 1:4]) + e * u
+        rise = (d[..., 0] * n[:, None, 0] + d[..., 1] * n[:, None, 1]) + d[..., 2] * n[:, None, 2]
+        dark = ~(rise > 0) & good[:, None]
+        lit[:, l] -= dark.sum(1).to(torch.int32)
+        below += int(dark.sum())
+    visibility = (lit.double() / float(S)).float()
+    report["masked"], report["no_normal"] = int((~live).sum()), int((live & ~good).sum())
+    report["below_horizon"], report["blocked"] = below, 0
+    report["rays"] = int(good.sum()) * L * int(S) - below
+    return visibility, lit, report
+
+
+def _mix64(z):
+    """The splitmix64 finaliser on uint64 arrays: the counter hash of the kernels (csrc/mesh_grid.h)."""
+    z = np.asarray(z, np.uint64)
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
 def sky_cube(light_or_base, res: int = 32) -> torch.Tensor:
     """[6,res,res,3] float32: a light's base cube ([6,N,N,3], a CubemapLight or its `base`) average-pooled to `res` texels an
     edge (N a multiple of res; res >= N returns the cube as it is) and clamped at 0, in torch: the sky gather_light looks up

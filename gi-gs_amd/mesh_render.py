@@ -418,6 +418,33 @@ def occluder_mesh(rast: MeshRasterizer) -> mesh_ops.Mesh:
                          m.get("metallic", zero1))
 
 
+@torch.no_grad()
+def prepare_points(pos_view, normal, viewmatrix, mask, normal_space, dev):
+    """RaytracedLight.prepare's transform on device `dev`; its text states the arithmetic."""
+    if normal_space not in NORMAL_SPACES:
+        raise ValueError("RaytracedLight: normal_space is one of %s, got %r" % (", ".join(NORMAL_SPACES), normal_space))
+    if not (isinstance(pos_view, torch.Tensor) and isinstance(normal, torch.Tensor) and pos_view.dim() == 3
+            and pos_view.shape[0] == 3 and normal.shape == pos_view.shape):
+        raise ValueError("RaytracedLight: pos_view and normal are [3,H,W] tensors")
+    _, H, W = pos_view.shape
+    if not isinstance(mask, torch.Tensor) or mask.numel() != H * W:
+        raise ValueError("RaytracedLight: mask is a tensor of %d x %d pixels" % (H, W))
+    M = MeshRasterizer._viewmatrix(dict(viewmatrix=viewmatrix), dev).double()
+    R = [[float(x) for x in row] for row in M[:3, :3].cpu().tolist()]
+    t = [float(x) for x in M[3, :3].cpu().tolist()]
+    p = pos_view.detach().to(dev).double().reshape(3, H * W)
+    v = normal.detach().to(dev).double().reshape(3, H * W)
+    d = [p[j] - t[j] for j in range(3)]
+    points = torch.stack([(d[0] * R[i][0] + d[1] * R[i][1]) + d[2] * R[i][2] for i in range(3)], 1)
+    if normal_space == "view":
+        w = [-((v[0] * R[i][0] + v[1] * R[i][1]) + v[2] * R[i][2]) for i in range(3)]
+    else:
+        w = [v[0], v[1], v[2]]
+    length = torch.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
+    normals = torch.stack([w[i] / length for i in range(3)], 1)
+    return points.float().contiguous(), normals.float().contiguous(), (mask.detach().to(dev).reshape(H * W) != 0).to(torch.uint8)
+
+
 class RaytracedLight:
     """A mesh as the occluder and bounce surface of any view's pixels: the triangle grid is built once, and with a `cube`
     ([6,n,n,3] float32, mesh.sky_cube's) so is the vertex radiosity of the passes 0 .. bounces - 1 (mesh.trace_hemispheres with
@@ -480,29 +507,7 @@ class RaytracedLight:
             n_i = w_i / sqrt((w_0 w_0 + w_1 w_1) + w_2 w_2)
         and both are rounded to float32.  A zero normal gives NaN: a no_normal point if its mask is set."""
         self._check()
-        if normal_space not in NORMAL_SPACES:
-            raise ValueError("RaytracedLight: normal_space is one of %s, got %r" % (", ".join(NORMAL_SPACES), normal_space))
-        dev = self.device
-        if not (isinstance(pos_view, torch.Tensor) and isinstance(normal, torch.Tensor) and pos_view.dim() == 3
-                and pos_view.shape[0] == 3 and normal.shape == pos_view.shape):
-            raise ValueError("RaytracedLight: pos_view and normal are [3,H,W] tensors")
-        _, H, W = pos_view.shape
-        if not isinstance(mask, torch.Tensor) or mask.numel() != H * W:
-            raise ValueError("RaytracedLight: mask is a tensor of %d x %d pixels" % (H, W))
-        M = MeshRasterizer._viewmatrix(dict(viewmatrix=viewmatrix), dev).double()
-        R = [[float(x) for x in row] for row in M[:3, :3].cpu().tolist()]
-        t = [float(x) for x in M[3, :3].cpu().tolist()]
-        p = pos_view.detach().to(dev).double().reshape(3, H * W)
-        v = normal.detach().to(dev).double().reshape(3, H * W)
-        d = [p[j] - t[j] for j in range(3)]
-        points = torch.stack([(d[0] * R[i][0] + d[1] * R[i][1]) + d[2] * R[i][2] for i in range(3)], 1)
-        if normal_space == "view":
-            w = [-((v[0] * R[i][0] + v[1] * R[i][1]) + v[2] * R[i][2]) for i in range(3)]
-        else:
-            w = [v[0], v[1], v[2]]
-        length = torch.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
-        normals = torch.stack([w[i] / length for i in range(3)], 1)
-        return points.float().contiguous(), normals.float().contiguous(), (mask.detach().to(dev).reshape(H * W) != 0).to(torch.uint8)
+        return prepare_points(pos_view, normal, viewmatrix, mask, normal_space, self.device)
 
     @torch.no_grad()
     def planes(self, pos_view, normal, viewmatrix, mask, normal_space: str = "world", bounces=None) -> Dict:
@@ -521,6 +526,16 @@ class RaytracedLight:
         plane3 = lambda x: None if x is None else x.t().reshape(3, H, W).contiguous()  # noqa: E731
         return dict(occlusion=light.occlusion.reshape(1, H, W), hits=light.hits.reshape(H, W), irradiance=plane3(light.irradiance),
                     indirect=plane3(light.indirect), points=points, normals=normals, mask=m, report=report)
+
+    @torch.no_grad()
+    def shadows(self, pos_view, normal, viewmatrix, mask, lights, samples: int = 1, normal_space: str = "world"):
+        """prepare(), then mesh.shadow_points of the analytic `lights` (analytic_lights.AnalyticLight) with the tracer's grid,
+        bias, seed and rotations -> (visibility [L,H,W] float32, points, normals, mask: the prepared arrays, report)."""
+        points, normals, m = self.prepare(pos_view, normal, viewmatrix, mask, normal_space)
+        _, H, W = pos_view.shape
+        visibility, _, report = mesh_ops.shadow_points(points, normals, self.mesh, lights, samples, self.rotations, self.bias, None,
+                                                       self.seed, m, self.grid)
+        return visibility.t().reshape(-1, H, W).contiguous(), points, normals, m, report
 
 
 class RaytracedGBuffer:

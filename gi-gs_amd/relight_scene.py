@@ -6,6 +6,7 @@ over relight.TurntableRelighter, relight.RelightEvaluator and image_writer.Image
                                       [--rotations N [--rotation_axis x y z]]
                                       [--occluder mesh.ply [--ao_rays 64 --ao_distance D --ray_bias B
                                        --occluder_mode replace|multiply]]
+                                      [--lights lights.json [--shadow_samples S]]
     relight_scene(args) -> {split: {...}}
 
 Flags and defaults are relight.py's (:340-356), with --hdri taking one or more maps (Radiance .hdr or .npy [H,W,3]): all
@@ -31,6 +32,13 @@ view's pixels against that mesh in place of SSAO (mesh_render.RaytracedGBuffer o
 pixel, a multiple of 64, within --ao_distance, started --ray_bias off the surface; both default as mesh.bake_occlusion's), so
 geometry the view does not see occludes too; --occluder_mode multiply shades with the product of both.  The occlusion PNG is
 then that plane, and the split's result holds the last view's tracer report as `occluder`.
+
+--lights lights.json also renders every view under the point and directional lights of that file (analytic_lights.py states
+its format): <image_name>_lights.png, analytic_lights.AnalyticRelighter's lights_rgb over the splats' G-buffer, beside the
+relit images.  With --occluder the lights cast ray-traced shadows against that mesh (--shadow_samples S samples a light, 1:
+hard shadows; --ray_bias as above) and <image_name>_shadow_<l>.png is the visibility of light l; without it they are
+unshadowed, no shadow image is written, and lights_report.json -- the lights' echo and every view's counters, in the same
+folder -- says so.  Without --lights nothing of this runs.
 
 Deviation: the reference writes <split>/envmap_relight.png, which every light of relight_all.bash overwrites; here the
 file carries the light's name.
@@ -106,6 +114,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ray_bias", type=float, default=None, help="the rays' start off the surface (default: 1e-3 ao_distance)")
     p.add_argument("--occluder_mode", choices=OCCLUDER_MODES, default="replace",
                    help="shade with the traced occlusion, or with its product with SSAO")
+    p.add_argument("--lights", type=str, default=None, help="a JSON list of point and directional lights: also render under them")
+    p.add_argument("--shadow_samples", type=int, default=1, help="shadow samples per light in [1, 64] (needs --occluder)")
     return p
 
 
@@ -129,6 +139,61 @@ def check_occluder(args: Namespace) -> bool:
         if x is not None and not (0.0 <= float(x) < float("inf")):
             raise ValueError("%s: finite and >= 0, got %r" % (name, x))
     return True
+
+
+def check_lights(args: Namespace) -> bool:
+    """Whether --lights is given; refuses --shadow_samples without it or without --occluder, and a count outside [1, 64]."""
+    samples = int(getattr(args, "shadow_samples", 1))
+    if not getattr(args, "lights", None):
+        if samples != 1:
+            raise ValueError("--shadow_samples needs --lights")
+        return False
+    if samples != 1 and not getattr(args, "occluder", None):
+        raise ValueError("--shadow_samples needs --occluder: without a mesh the lights are unshadowed")
+    if samples < 1 or samples > 64:
+        raise ValueError("--shadow_samples: a count in [1, 64], got %d" % samples)
+    return True
+
+
+def lights_split(args: Namespace, split: str, infos, g, sh_degree: int, iteration: int, dev) -> Dict:
+    """--lights: the files and the report described in the module docstring, for one split."""
+    import torch
+
+    import analytic_lights
+    import dataset_readers as dr
+    import image_writer
+    import relight
+    import render_mesh
+    out = args.model_path
+    lights = analytic_lights.load_lights(args.lights)
+    base = os.path.join(rs.split_dir(out, split, iteration), "relight")
+    os.makedirs(base, exist_ok=True)
+    gi = {k: getattr(args, k) for k in rs.GI_FLAGS}
+    shadows, S = bool(getattr(args, "occluder", None)), int(args.shadow_samples)
+    views, files = [], []
+    with image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
+        tracer = None
+        if shadows:
+            import mesh_render
+            path = args.occluder if os.path.isabs(args.occluder) or os.path.exists(args.occluder) else os.path.join(out, args.occluder)
+            tracer = mesh_render.RaytracedLight(path, bias=args.ray_bias, device=dev)
+        try:
+            relighter = analytic_lights.AnalyticRelighter(lights, relight.SplatGBuffer(gi, sh_degree, args.metallic), tracer, S, gamma=True)
+            for ci in infos:
+                c = dr.camera_from_info(ci, args.resolution, device=dev)
+                o = relighter(c, g)
+                paths = render_mesh.lights_paths(base, ci.image_name, len(lights), shadows)
+                images = [image_writer.Image(paths["lights"], o["lights_rgb"])]
+                images += [image_writer.Image(p, o["shadow"][l:l + 1], bias=0.0) for l, p in enumerate(paths["shadow"])]
+                wr.submit(images)
+                files += [paths["lights"]] + paths["shadow"]
+                views.append(dict(o["report"], image_name=ci.image_name))
+        finally:
+            if tracer is not None:
+                tracer.close()
+    path = os.path.join(base, "lights_report.json")
+    render_mesh.write_lights_report(path, lights, shadows, S, views, occluder=getattr(args, "occluder", None))
+    return dict(report_json=path, files=files, shadows=shadows, views=views)
 
 
 def check_rotations(args: Namespace) -> int:
@@ -226,6 +291,7 @@ def relight_scene(args) -> Dict[str, Dict]:
     args = rs.as_namespace(args, parse_args)
     n_rot = check_rotations(args)  # before anything is read
     check_occluder(args)
+    with_lights = check_lights(args)
     args = rs.combine_args(args)
     if not args.hdri:
         raise ValueError("--hdri: at least one environment map is required")
@@ -258,6 +324,8 @@ def relight_scene(args) -> Dict[str, Dict]:
             if not skip and cams[split]:
                 results[split] = relight_split(args, split, cams[split], g, sh_degree, lights, names, iteration, dev, ratio, lp)
                 results[split]["albedo_ratio"] = ratio
+                if with_lights:
+                    results[split]["analytic_lights"] = lights_split(args, split, cams[split], g, sh_degree, iteration, dev)
         return results
     finally:
         pipeline._collect_idle()

@@ -5,7 +5,8 @@ its scene (mesh_render.py), and compared with the splat render it came from or w
                                     [--rotations N] [--compare] [--reference_mesh other.ply|other.obj]
                                     [--occlusion ssao|baked|both] [--split test] [--metallic --tone --gamma]
                                     [--lighting baked|raytraced [--bounces 1] [--sky_res 32] [--light_rays 256]]
-                                    [--occlusion raytraced] [--ao_rays 64] [--ao_distance D] [--ray_bias B]      (CLI)
+                                    [--occlusion raytraced] [--ao_rays 64] [--ao_distance D] [--ray_bias B]
+                                    [--lights lights.json [--shadow_samples S] [--no_shadows]]                   (CLI)
     render_mesh(args) -> {...}                                                                                   (API)
 
 The scene path and the resolution come from <out>/cfg_args as in render_scene.py, command-line values first; a relative
@@ -52,6 +53,13 @@ above) and casts --ao_rays rays from every covered pixel of the mesh's own posit
 mesh_<split>/raytraced_vs_screen.json holds, per view and on average, the PSNR (peak 1, over the covered pixels) of that plane
 against the screen-space diffuse (psnr_screen_bounces_<b>) and against the per-vertex baked plane of --lighting baked
 (psnr_baked_bounces_<b>), for b = 0 and --bounces, with the bake's report and the tracer's report of the last view.
+
+--lights lights.json (a PLY or an OBJ) also renders every view under the point and directional lights of that file
+(analytic_lights.py states its format) with shadows ray-traced against the mesh itself: <image_name>_lights.png is
+analytic_lights.AnalyticRelighter's lights_rgb after linear_to_srgb, <image_name>_shadow_<l>.png the visibility of light l,
+--shadow_samples S samples a light (1: hard shadows), started --ray_bias off the surface; --no_shadows leaves the lights
+unshadowed and writes no shadow images.  mesh_<split>/lights_report.json echoes the lights and holds the counters of every
+view.  Without --lights nothing of this runs.
 """
 from __future__ import annotations
 
@@ -100,6 +108,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ao_rays", type=int, default=64, help="rays per pixel of the ray-traced modes, a multiple of 64 in [64, 1024]")
     p.add_argument("--ao_distance", type=float, default=None, help="how far an occluder counts (default: mesh.bake_occlusion's)")
     p.add_argument("--ray_bias", type=float, default=None, help="the rays' start off the surface (default: 1e-3 ao_distance)")
+    p.add_argument("--lights", type=str, default=None, help="a JSON list of point and directional lights: also render under them")
+    p.add_argument("--shadow_samples", type=int, default=1, help="shadow samples per light in [1, 64]; 1: hard shadows")
+    p.add_argument("--no_shadows", action="store_true", help="--lights without ray-traced shadows")
     return p
 
 
@@ -167,6 +178,16 @@ def _check(args: Namespace) -> int:
             x = getattr(args, name, None)
             if x is not None and not (0.0 <= float(x) < float("inf")):
                 raise ValueError("--%s: finite and >= 0, got %r" % (name, x))
+    samples = int(getattr(args, "shadow_samples", 1))
+    if not getattr(args, "lights", None):
+        if samples != 1 or getattr(args, "no_shadows", False):
+            raise ValueError("--shadow_samples and --no_shadows need --lights")
+    else:
+        if samples < 1 or samples > 64:
+            raise ValueError("--shadow_samples: a count in [1, 64], got %d" % samples)
+        x = getattr(args, "ray_bias", None)
+        if x is not None and not (0.0 <= float(x) < float("inf")):
+            raise ValueError("--ray_bias: finite and >= 0, got %r" % (x,))
     return n_rot
 
 
@@ -302,6 +323,54 @@ def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, info
     with open(path, "w") as f:
         json.dump(cmp, f, indent=4)
     return dict(raytraced_vs_screen_json=path, raytraced_vs_screen=cmp["average"], raytraced_diffuse=files)
+
+
+def lights_paths(base: str, image_name: str, n_lights: int, shadows: bool) -> Dict:
+    return dict(lights=os.path.join(base, "%s_lights.png" % image_name),
+                shadow=[os.path.join(base, "%s_shadow_%d.png" % (image_name, l)) for l in range(n_lights)] if shadows else [])
+
+
+def write_lights_report(path: str, lights, shadows: bool, samples: int, views: List[Dict], **more) -> Dict:
+    """lights_report.json: the lights' echo, whether and how they were shadowed, and every view's counters."""
+    import analytic_lights
+    report = dict(lights=[analytic_lights.light_entry(x) for x in lights], shadows=bool(shadows), shadow_samples=int(samples),
+                  views=views, **more)
+    with open(path, "w") as f:
+        json.dump(report, f, indent=4)
+    return report
+
+
+def render_lights(args: Namespace, mesh_path: str, gi: Dict, infos, dev, out: str) -> Dict:
+    """--lights: the files and the report described in the module docstring -> what render_mesh adds to its result."""
+    import torch
+
+    import analytic_lights
+    import dataset_readers as dr
+    import image_writer
+    import mesh_render
+    lights = analytic_lights.load_lights(args.lights)
+    shadows, S = not args.no_shadows, int(args.shadow_samples)
+    base = os.path.join(out, "mesh_" + args.split)
+    views, files = [], []
+    with open_mesh(mesh_path, dev) as rast, image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
+        tracer = mesh_render.RaytracedLight(mesh_render.occluder_mesh(rast), bias=args.ray_bias, device=dev) if shadows else None
+        try:
+            relighter = analytic_lights.AnalyticRelighter(lights, mesh_render.MeshGBuffer(gi, args.metallic), tracer, S, gamma=True)
+            for ci in infos:
+                c = dr.camera_from_info(ci, args.resolution, device=dev)
+                o = relighter(c, rast)
+                paths = lights_paths(base, ci.image_name, len(lights), shadows)
+                images = [image_writer.Image(paths["lights"], o["lights_rgb"])]
+                images += [image_writer.Image(p, o["shadow"][l:l + 1], bias=0.0) for l, p in enumerate(paths["shadow"])]
+                wr.submit(images)
+                files += [paths["lights"]] + paths["shadow"]
+                views.append(dict(o["report"], image_name=ci.image_name))
+        finally:
+            if tracer is not None:
+                tracer.close()
+    path = os.path.join(base, "lights_report.json")
+    write_lights_report(path, lights, shadows, S, views, mesh=mesh_path)
+    return dict(lights_report_json=path, lights_files=files, lights_views=views)
 
 
 def open_mesh(path: str, device):
@@ -512,6 +581,8 @@ def render_mesh(args) -> Dict:
             res.update(render_baked(args, mesh_path, lights[0], gi, lut, infos, dev, out))
         if getattr(args, "lighting", "screen") == "raytraced":
             res.update(render_raytraced(args, mesh_path, lights[0], gi, lut, infos, dev, out))
+        if getattr(args, "lights", None):
+            res.update(render_lights(args, mesh_path, gi, infos, dev, out))
     finally:
         pipeline._collect_idle()
     res["total_s"] = round(time.perf_counter() - t0, 4)

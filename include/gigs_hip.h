@@ -1009,6 +1009,64 @@ int gigs_mesh_gather_points(int n_vertices, int n_faces, const float* vertices, 
                             double ao_distance, double max_distance, double bias, int sky_res, const float* sky,
                             const float* radiosity, int* hits, float* occlusion, float* irradiance, float* indirect,
                             unsigned long long* counts, int* overflow, void* stream);
+/* Shadows of analytic lights (gigs-hip extension; the device half of mesh.shadow_points): for the points of "Ray-traced
+ * light per point" and L point or directional lights, the share of each light's S samples that reach the point past the
+ * mesh.  The conventions are that section's: DEVICE arrays except `lo` and `dims`, no synchronisation, no allocation,
+ * float64 on the float32 inputs, + - * / only, no sqrt, no float atomics: tests/mesh_shadow_ref.py reproduces every bit.
+ *   1 Lights.  lights [L, GIGS_LIGHT_ROW] float32, 1 <= L <= GIGS_MAX_LIGHTS; the caller keeps every entry finite.  Row l:
+ *       [0]     kind: 0 a POINT light, anything else (1) a DIRECTIONAL light
+ *       [1..3]  point: its position c;  directional: w, the unit direction the light TRAVELS in
+ *       [4]     the extent e >= 0.  point: the radius of its sphere;  directional: the tangent of its half-angle
+ *       [5..7]  0, reserved
+ *   2 Offsets.  offsets [K, S, 3] float32, points of the unit ball, 1 <= S <= 64 samples, 1 <= K <= 64 rotations.
+ *   3 Points.  Point q with mask[q] == 0 is MASKED (counts[4] += 1); otherwise a point that fails the no_normal rule of
+ *     "Baking occlusion", 8 counts as no_normal (counts[3] += 1).  Either way no ray is cast, lit[q, :] = S and
+ *     visibility[q, :] = 1.
+ *   4 Rays.  o = p + bias n and k = mix((seed 2^32 + q) mod 2^64) mod K by the code of "Baking occlusion", 8.  For light l and
+ *     sample s let u = offsets[k, s] and, per component,
+ *       point:        d = (c + e u) - o,  t_max = 1             (the sample of the sphere lies at t = 1)
+ *       directional:  d = (-w) + e u,     t_max = max_distance  (+inf: no limit)
+ *   5 Classification.  The sample is BELOW THE HORIZON if !(dot(d, n) > 0) -- d = 0 and a NaN as well -- and then no ray is
+ *     cast (counts[2] += 1).  Otherwise a ray is cast (counts[0] += 1) and the sample is BLOCKED iff the ray has an accepted
+ *     face within t_max ("Baking occlusion", 2 to 7): iff the nearest-face traversal would find one (counts[1] += 1).  The
+ *     kernel's walk returns at the first accepted face; DESIGN.md, "Analytic lights and shadows", proves the two agree.
+ *   6 lit[q, l] = the samples that are neither; visibility[q, l] = float32(double(lit) / double(S)).
+ * gigs_mesh_shadow_points, one thread per (row of `order` [N] int64 -- the points sorted by cell, or NULL --, light, sample),
+ *   flattened in that order over one-wave blocks; lit [N, L] int32 is cleared inside the call and counted with integer
+ *   atomics, a second launch stores visibility [N, L] float32.  counts [5] uint64 (cleared inside the call) = rays cast,
+ *   blocked, below the horizon, no_normal points, masked points.  n_points == 0 launches nothing.
+ * An order row, a cell_start entry, a pair key or a face index outside its range sets *overflow (cleared by the caller) and
+ *   the thread adds nothing. */
+#define GIGS_LIGHT_ROW 8
+int gigs_mesh_shadow_points(int n_vertices, int n_faces, const float* vertices, const int* faces, const float* lo, double cell,
+                            const int* dims, const long long* cell_start, const long long* pair_keys, long long n_pairs,
+                            double scale, int n_points, const float* points, const float* normals, const unsigned char* mask,
+                            const long long* order, int n_lights, const float* lights, const float* offsets, int n_samples,
+                            int n_rotations, unsigned long long seed, double bias, double max_distance, int* lit,
+                            float* visibility, unsigned long long* counts, int* overflow, void* stream);
+/* Shading under analytic lights (gigs-hip extension; the device half of analytic_lights.shade_lights): the points of the
+ * section above under its L lights, Lambert plus GGX with Smith-correlated masking and Schlick Fresnel -- the arithmetic of
+ * the reference's pbr/renderutils/bsdf.py bsdf_pbr(kd = albedo, arm = (0, roughness, metallic), pos = p, nrm = n,
+ * view_pos = campos, light_pos = p + wi, min_roughness = 0.08, BSDF = 0), which the reference never calls.  float32, one
+ * thread per point, DEVICE arrays, no synchronisation, no allocation, no atomics.  eps = 1e-4 (specular_epsilon),
+ * clamp(c) = min(max(c, eps), 1 - eps), normalize(v) = v / max(|v|, 1e-12).
+ *   1 Points.  A point with mask[q] == 0 or one that fails the no_normal rule (float64, as above) gets zeros.
+ *   2 Material.  m = metallic[q] (NULL: 0); ks = 0.04 (1 - m) + albedo m; kd = albedo (1 - m); alpha = min(max(roughness^2,
+ *     0.08^2), 1); a2 = alpha^2; wo = normalize(campos - p).
+ *   3 Per light l = 0 .. L - 1, in this order; E_l = radiance[l] (colour x intensity), vis = visibility[q, l] (NULL: 1):
+ *       point:        v = c - p;  wi = v / sqrt(v.v);  E = E_l / max(v.v, 1e-8)
+ *       directional:  wi = -w;                         E = E_l
+ *     h = normalize(wo + wi);  D = a2 / (d d pi) with c = clamp(n.h), d = (c a2 - c) c + 1;
+ *     Lambda(x) = 0.5 (sqrt(1 + a2 (1 - c c) / (c c)) - 1) with c = clamp(x);  G = 1 / (1 + Lambda(n.wo) + Lambda(n.wi));
+ *     F = ks + (1 - ks) f^5 with f = 1 - clamp(wo.h), f^5 = ((f f)(f f)) f;
+ *     spec = F D G 0.25 / max(n.wo, eps) if n.wo > eps and n.wi > eps, else 0.  Both terms carry the cosine n.wi:
+ *       diffuse[q]  += (vis E) (kd max(n.wi, 0) / pi)          (a NaN n.wi, a light at the point itself, gives 0)
+ *       specular[q] += (vis E) spec
+ *     from 0, so two lights give the float32 sum of the two single results.
+ * Outputs diffuse, specular [N, 3] float32, linear radiance.  1 <= L <= GIGS_MAX_LIGHTS.  n_points == 0 launches nothing. */
+int gigs_shade_lights(int n_points, const float* points, const float* normals, const unsigned char* mask, const float* albedo,
+                      const float* roughness, const float* metallic, const float* campos, int n_lights, const float* lights,
+                      const float* radiance, const float* visibility, float* diffuse, float* specular, void* stream);
 /* Texturing meshes (gigs-hip extension; the device half of mesh.bake_atlas / mesh.transfer_attributes): the per-vertex
  * channels of a heavy SOURCE mesh stored in the texels of an atlas over a light TARGET mesh.  Every texel of the atlas gets
  * the point of the target's surface it stands for (gigs_mesh_atlas_points), the search of "Comparing meshes" finds the
