@@ -14,6 +14,7 @@
 //     cached per device.  That cache is this file's only mutable state.
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -345,18 +346,25 @@ __device__ __forceinline__ float group_sum_last(float v) {
 // The pass streams the table once (0.74 GB per direction for the reference's 256..16 chain).  Plain loads, not
 // nontemporal ones: the kU loads of an 8- or 16-lane group fall into one cache line, and a nontemporal load drops
 // the line behind it (measured: +20 % time).
-template <bool kBackward, bool kNorm, int kLanes>
+// kListed (the sparse forward, specular_apply_multi_fwd_sparse_kernel): group number j takes its output texel from
+// list[j], j < n_listed, not from its own number.  The lanes of a group, their candidates, the order of a lane's additions
+// and the reduction do not depend on which texels share the wave, so a listed texel gets the bits it has from the dense
+// launch; texels that are not listed are not written.
+template <bool kBackward, bool kNorm, int kLanes, bool kListed = false>
 __device__ __forceinline__ void specular_apply_body(int block, int N, const float* __restrict__ src,
                                                     const float* __restrict__ bounds, const uint32_t* __restrict__ offsets,
                                                     const float* __restrict__ W, float* __restrict__ dst,
-                                                    float* __restrict__ wsum_out) {
+                                                    float* __restrict__ wsum_out, const int* __restrict__ list = nullptr,
+                                                    int n_listed = 0) {
   constexpr int kPerWave = 64 / kLanes;
   constexpr int kU = 4;
   const int lane = threadIdx.x & 63;
   const int total = 6 * N * N;
   const int o_raw = (block * 4 + (threadIdx.x >> 6)) * kPerWave + lane / kLanes;
-  const bool valid = o_raw < total;
-  const int o = valid ? o_raw : total - 1;  // surplus groups stay in the wave for the DPP sums
+  if (kListed && (block * 4 + (int)(threadIdx.x >> 6)) * kPerWave >= n_listed) return;  // wave-uniform: no slot of the wave is listed
+  const bool valid = kListed ? o_raw < n_listed : o_raw < total;
+  // surplus groups stay in the wave for the DPP sums
+  const int o = kListed ? (valid ? list[o_raw] : 0) : (valid ? o_raw : total - 1);
   const int g = lane % kLanes;
   const int stride = (kBackward && !kNorm) ? 4 : 3;
 
@@ -396,7 +404,15 @@ __device__ __forceinline__ void specular_apply_body(int block, int N, const floa
   // Both streams are addressed as a wave-uniform base plus a 32-bit byte offset (a 64-bit address per load in flight
   // would cost the registers the pipeline below needs).  The texels of a wave are consecutive and so are their runs
   // of the table, so the weights are addressed from the first lane's run.
-  const uint32_t first0 = __builtin_amdgcn_readfirstlane(first);
+  // (listed texels come in no order: there the base is the smallest run of the wave's listed texels, and the host admits
+  // a level to the list only if its whole table lies within the 32-bit byte offset)
+  uint32_t first_min = first;
+  if (kListed) {
+    first_min = valid ? first : 0xffffffffu;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) first_min = min(first_min, (uint32_t)__shfl_xor((int)first_min, d));
+  }
+  const uint32_t first0 = __builtin_amdgcn_readfirstlane(first_min);
   const char* wbase = reinterpret_cast<const char*>(W + first0);
   const char* tbase = reinterpret_cast<const char*>(src);
   const int wrel = (int)(first - first0);
@@ -929,6 +945,41 @@ __global__ void __launch_bounds__(64) specular_sparse_finish_kernel(SparseCaps c
   state[t] = 0;
 }
 
+// The forward over the listed texels of the fine levels (gigs_specular_cubemap_multi_fwd_sparse), one launch behind the
+// list census: first the workgroups of the listed texels -- a level's capacity worth of groups; a workgroup past the
+// count returns at entry --, then specular_apply_multi_kernel<false>'s workgroups for the levels whose count exceeds
+// their capacity (they return at entry where the level is listed).  Same report in `state` as the backward's.
+__global__ void __launch_bounds__(256)
+specular_apply_multi_fwd_sparse_kernel(SpecLevels L, SparseLevels S, int listed_blocks, const int* __restrict__ state) {
+  if ((int)blockIdx.x < listed_blocks) {
+    int k = 0;
+#pragma unroll
+    for (int i = 1; i < 8; i++)
+      if (i < S.n && (int)blockIdx.x >= S.lv[i].unit_begin) k = i;
+    const SparseLevel& q = S.lv[k];
+    const int count = state[k];
+    if (count > q.cap) return;  // a dense level
+    const SpecLevel& v = L.lv[k];
+    const int block = (int)blockIdx.x - q.unit_begin;
+    if (block * 4 * (64 / v.lanes) >= count) return;  // uniform over the workgroup
+    if (v.lanes == 8) specular_apply_body<false, true, 8, true>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out, q.list, count);
+    else if (v.lanes == 16) specular_apply_body<false, true, 16, true>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out, q.list, count);
+    else specular_apply_body<false, true, 64, true>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out, q.list, count);
+    return;
+  }
+  const int gblock = (int)blockIdx.x - listed_blocks;
+  int k = 0;
+#pragma unroll
+  for (int i = 1; i < 8; i++)
+    if (i < L.n && gblock >= L.lv[i].block_begin) k = i;
+  if (state[k] <= S.lv[k].cap) return;  // a listed level
+  const SpecLevel& v = L.lv[k];
+  const int block = gblock - v.block_begin;
+  if (v.lanes == 8) specular_apply_body<false, true, 8>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out);
+  else if (v.lanes == 16) specular_apply_body<false, true, 16>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out);
+  else specular_apply_body<false, true, 64>(block, v.N, v.src, v.bounds, v.offsets, v.W, v.dst, v.wsum_out);
+}
+
 static int spec_sparse_capacity(const Options& o, int res) {
   return (int)((long long)6 * res * res * o.spec_sparse_permille / 1000);
 }
@@ -1113,6 +1164,49 @@ int gigs_specular_cubemap_multi_bwd_sparse(gigs_ctx* ctx, int n_levels, const gi
   hipLaunchKernelGGL(gigs::specular_apply_multi_bwd_sparse_kernel, dim3(units + blocks), dim3(256), 0, s, L, S, units, state);
   hipLaunchKernelGGL(gigs::specular_sparse_finish_kernel, dim3(1), dim3(64), 0, s, caps, state);
   return gigs_internal_check_launch("specular_cubemap_multi_bwd_sparse");
+}
+
+int gigs_specular_cubemap_multi_fwd_sparse(gigs_ctx* ctx, int n_levels, const gigs_spec_level* levels, float* const* needed,
+                                           const int* capacities, int* state, int* lists, void* stream) {
+  const gigs::Options& o = *gigs_internal_options(ctx);
+  if (n_levels <= 0 || n_levels > 8 || !levels || !needed || !capacities || !state || !lists)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_multi_fwd_sparse: bad argument");
+  gigs::SpecLevels L;
+  gigs::SparseLevels S;
+  L.n = S.n = n_levels;
+  int blocks = 0, census_blocks = 0, units = 0;
+  gigs::SparseCaps caps = {};
+  caps.n = n_levels;
+  size_t list_begin = 0;
+  for (int i = 0; i < n_levels; i++) {
+    const gigs_spec_level& a = levels[i];
+    if (a.res <= 0 || a.res > 4096 || !a.src || !a.bounds || !a.offsets || !a.weights || !a.dst || !a.wsum || !needed[i] ||
+        capacities[i] < 0)
+      return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_multi_fwd_sparse: bad level");
+    const int total = fill_spec_level(o, a, L.lv[i], blocks);
+    gigs::SparseLevel& q = S.lv[i];
+    memset(&q, 0, sizeof(q));
+    // the listed body addresses a level's whole table with a 32-bit byte offset (avg_window is the floor of the mean)
+    const bool addressable = ((long long)a.avg_window + 1) * total < (1ll << 29);
+    q.total = total; q.cap = addressable ? (capacities[i] < total ? capacities[i] : total) : 0;
+    q.block_begin = census_blocks; q.unit_begin = units; q.N = a.res;
+    // the list census reads the marks and clears them for the next call: src = dst = needed
+    q.vec = (((uintptr_t)needed[i]) & 15) == 0;
+    q.src = needed[i]; q.dst = needed[i];
+    q.list = lists + list_begin;
+    const int per_block = 256 * gigs::kCensusPerThread;
+    census_blocks += (total + per_block - 1) / per_block;
+    const int per_wg = 4 * (64 / L.lv[i].lanes);  // listed texels per workgroup
+    units += (q.cap + per_wg - 1) / per_wg;
+    caps.cap[i] = q.cap;
+    list_begin += (size_t)capacities[i];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // no StageTimer, as for gigs_spec_tap_census: beside the march these launches take 7 times what they take alone
+  hipLaunchKernelGGL(gigs::specular_census_kernel, dim3(census_blocks), dim3(256), 0, s, S, state);
+  hipLaunchKernelGGL(gigs::specular_apply_multi_fwd_sparse_kernel, dim3(units + blocks), dim3(256), 0, s, L, S, units, state);
+  hipLaunchKernelGGL(gigs::specular_sparse_finish_kernel, dim3(1), dim3(64), 0, s, caps, state);
+  return gigs_internal_check_launch("specular_cubemap_multi_fwd_sparse");
 }
 
 }  // extern "C"

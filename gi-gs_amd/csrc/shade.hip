@@ -71,14 +71,42 @@ __device__ __forceinline__ float aces(float x, float& d) {  // pbr/shade.py:33-4
   return num / den;
 }
 
-// Everything both passes need, computed identically in forward and backward.
-struct ShadePix {
-  v3 a, dl_raw, dl, drgb, sp, s0, s1, F0, refl, srgb;
-  float r, occ, m, fgx, fgy, dfgx_dv, dfgy_dv, lf, dmdr;
+// What the specular lookup of a pixel reads: the level pair of its roughness and the four bilinear taps of the reflected
+// direction in each of the two levels.  shade_pixel_n samples through it and spec_tap_census_kernel marks through it: one
+// function, so the texels the census lists are the texels the shade reads.
+struct SpecTaps {
+  float lf, dmdr;
   int l0, l1;
   bool lvl_inside;
-  Taps td, t0, t1;
-  bool has_d, has0, has1;
+  Taps t0, t1;
+  bool has0, has1;  // has1 only where l1 != l0
+};
+
+// r: the shading roughness, n: the shading normal, v: the view direction.  The library is compiled with
+// -ffp-contract=off (build.py: part of its numerical contract), so the expressions below are the same IEEE operations in
+// every kernel this is inlined into: the census and the shade get the same taps from the same inputs, bit for bit.
+__device__ __forceinline__ void spec_taps(int L, const int (&spec_res)[8], float r, v3 n, v3 v, SpecTaps& q) {
+  const float ndv = n.x * v.x + n.y * v.y + n.z * v.z;
+  const float c2 = 2.0f * fmaxf(ndv, 0.0f);
+  const v3 ref = {c2 * n.x - v.x, c2 * n.y - v.y, c2 * n.z - v.z};
+  const v3 rt = {-ref.y, ref.z, -ref.x};
+  const float lvl_raw = get_mip(r, L, q.dmdr);
+  const float lvl = fminf(fmaxf(lvl_raw, 0.0f), (float)(L - 1));
+  q.lvl_inside = lvl_raw >= 0.0f && lvl_raw <= (float)(L - 1);
+  q.l0 = min((int)floorf(lvl), L - 1);
+  q.l1 = min(q.l0 + 1, L - 1);
+  q.lf = lvl - (float)q.l0;
+  q.has0 = cube_taps(spec_res[q.l0], rt.x, rt.y, rt.z, q.t0);
+  q.has1 = false;
+  if (q.l1 != q.l0) q.has1 = cube_taps(spec_res[q.l1], rt.x, rt.y, rt.z, q.t1);
+}
+
+// Everything both passes need, computed identically in forward and backward.
+struct ShadePix : SpecTaps {
+  v3 a, dl_raw, dl, drgb, sp, s0, s1, F0, refl, srgb;
+  float r, occ, m, fgx, fgy, dfgx_dv, dfgy_dv;
+  Taps td;
+  bool has_d;
 };
 
 // n: the shading normal of pixel p (A.normals' value, or the one the caller has just formed in registers)
@@ -87,10 +115,7 @@ __device__ __forceinline__ void shade_pixel_n(const ShadeArgs& A, int p, v3 n, S
   const v3 v = {A.view_dirs[3 * p], A.view_dirs[3 * p + 1], A.view_dirs[3 * p + 2]};
   q.a = {A.albedo[e], A.albedo[e + cs], A.albedo[e + 2 * cs]};
   q.r = A.roughness[p] * A.rough_scale + A.rough_bias;  // scale 1, bias 0 (exact) unless the caller fuses the remap
-  const float ndv = n.x * v.x + n.y * v.y + n.z * v.z;
-  const float c2 = 2.0f * fmaxf(ndv, 0.0f);
-  const v3 ref = {c2 * n.x - v.x, c2 * n.y - v.y, c2 * n.z - v.z};
-  const v3 nt = {-n.y, n.z, -n.x}, vt = {-v.y, v.z, -v.x}, rt = {-ref.y, ref.z, -ref.x};
+  const v3 nt = {-n.y, n.z, -n.x}, vt = {-v.y, v.z, -v.x};
   q.has_d = cube_taps(A.diffuse_res, nt.x, nt.y, nt.z, q.td);
   q.dl_raw = q.has_d ? cube_sample(A.diffuse, q.td) : v3{0, 0, 0};
   q.occ = A.occlusion ? A.occlusion[p] : 1.0f;
@@ -114,18 +139,10 @@ __device__ __forceinline__ void shade_pixel_n(const ShadeArgs& A, int p, v3 n, S
     q.dfgx_dv = ((t01.x - t00.x) * (1 - tu) + (t11.x - t10.x) * tu) * (float)A.lut_h;
     q.dfgy_dv = ((t01.y - t00.y) * (1 - tu) + (t11.y - t10.y) * tu) * (float)A.lut_h;
   }
-  const float lvl_raw = get_mip(q.r, A.L, q.dmdr);
-  const float lvl = fminf(fmaxf(lvl_raw, 0.0f), (float)(A.L - 1));
-  q.lvl_inside = lvl_raw >= 0.0f && lvl_raw <= (float)(A.L - 1);
-  q.l0 = min((int)floorf(lvl), A.L - 1);
-  q.l1 = min(q.l0 + 1, A.L - 1);
-  q.lf = lvl - (float)q.l0;
-  q.has0 = cube_taps(A.spec_res[q.l0], rt.x, rt.y, rt.z, q.t0);
+  spec_taps(A.L, A.spec_res, q.r, n, v, q);
   q.s0 = q.has0 ? cube_sample(A.spec[q.l0], q.t0) : v3{0, 0, 0};
-  q.has1 = false;
   q.s1 = {0, 0, 0};
   if (q.l1 != q.l0) {
-    q.has1 = cube_taps(A.spec_res[q.l1], rt.x, rt.y, rt.z, q.t1);
     if (q.has1) q.s1 = cube_sample(A.spec[q.l1], q.t1);
     q.sp = {q.s0.x * (1 - q.lf) + q.s1.x * q.lf, q.s0.y * (1 - q.lf) + q.s1.y * q.lf, q.s0.z * (1 - q.lf) + q.s1.z * q.lf};
   } else {
@@ -206,55 +223,73 @@ struct ShadePostArgs {
   float *mask_f, *onv;
 };
 constexpr int kPostW = 64, kPostH = 4;
+typedef float PostTile[3][kPostH + 2][kPostW + 2];
 
-__global__ void __launch_bounds__(256)
-shade_fwd_post_kernel(ShadeArgs A, ShadePostArgs P) {
-  __shared__ float s_n[2][3][kPostH + 2][kPostW + 2];
-  const int H = A.H, W = A.W;
+// normalize_where(src) of the workgroup's 64 x 4 tile and its 1-pixel halo; taps outside the image are zero
+__device__ __forceinline__ void post_stage(PostTile& s, const float* __restrict__ src, int H, int W) {
   const size_t HW = (size_t)H * W;
   constexpr int kHalo = (kPostH + 2) * (kPostW + 2);
-  for (int i = threadIdx.x; i < 2 * kHalo; i += 256) {
-    const int m = i / kHalo, r = i - m * kHalo;
+  for (int r = threadIdx.x; r < kHalo; r += 256) {
     const int ty = r / (kPostW + 2), tx = r - ty * (kPostW + 2);
     const int yy = (int)blockIdx.y * kPostH - 1 + ty, xx = (int)blockIdx.x * kPostW - 1 + tx;
     v3 v = {0.0f, 0.0f, 0.0f};
     if (!(yy < 0 || yy >= H || xx < 0 || xx >= W)) {
-      const float* src = m ? P.out_normal_view : P.normal_map;
       const size_t t = (size_t)yy * W + xx;
       v = normalize_where({src[t], src[HW + t], src[2 * HW + t]});
     }
-    s_n[m][0][ty][tx] = v.x; s_n[m][1][ty][tx] = v.y; s_n[m][2][ty][tx] = v.z;
+    s[0][ty][tx] = v.x; s[1][ty][tx] = v.y; s[2][ty][tx] = v.z;
   }
+}
+
+// the three medians of the lane's 3 x 3 window; a NaN in the window -> NaN (median_of_normalized)
+__device__ __forceinline__ void post_median(const PostTile& s, int lx, int ly, float (&med)[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    float t[9];
+    bool has_nan = false;
+    int k = 0;
+#pragma unroll
+    for (int dy = 0; dy <= 2; dy++)
+#pragma unroll
+      for (int dx = 0; dx <= 2; dx++, k++) {
+        t[k] = s[c][ly + dy][lx + dx];
+        has_nan |= t[k] != t[k];
+      }
+    med[c] = has_nan ? __builtin_nanf("") : median9(t);
+  }
+}
+
+// -(n @ R), R = viewmatrix[:3, :3] of the row-major 4x4 tensor
+__device__ __forceinline__ v3 post_rotate(const float* __restrict__ vm, const float (&m)[3]) {
+  return {-(m[0] * vm[0] + m[1] * vm[4] + m[2] * vm[8]),
+          -(m[0] * vm[1] + m[1] * vm[5] + m[2] * vm[9]),
+          -(m[0] * vm[2] + m[1] * vm[6] + m[2] * vm[10])};
+}
+
+// the normal mask of the stage-2 step: every channel of normal_map is nonzero
+__device__ __forceinline__ bool post_mask(const float* __restrict__ normal_map, size_t HW, int p) {
+  return normal_map[p] != 0.0f && normal_map[HW + p] != 0.0f && normal_map[2 * HW + p] != 0.0f;
+}
+
+__global__ void __launch_bounds__(256)
+shade_fwd_post_kernel(ShadeArgs A, ShadePostArgs P) {
+  __shared__ PostTile s_n[2];
+  const int H = A.H, W = A.W;
+  const size_t HW = (size_t)H * W;
+  post_stage(s_n[0], P.normal_map, H, W);
+  post_stage(s_n[1], P.out_normal_view, H, W);
   __syncthreads();
   const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
   const int x = blockIdx.x * kPostW + lx, y = blockIdx.y * kPostH + ly;
   if (x >= W || y >= H) return;
   const int p = y * W + x;
-  const bool mk = P.normal_map[p] != 0.0f && P.normal_map[HW + p] != 0.0f && P.normal_map[2 * HW + p] != 0.0f;
+  const bool mk = post_mask(P.normal_map, HW, p);
   P.mask_u8[p] = mk ? 1 : 0;
   if (P.mask_f) P.mask_f[p] = mk ? 1.0f : 0.0f;
   float med[2][3];
-#pragma unroll
-  for (int m = 0; m < 2; m++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      float t[9];
-      bool has_nan = false;
-      int k = 0;
-#pragma unroll
-      for (int dy = 0; dy <= 2; dy++)
-#pragma unroll
-        for (int dx = 0; dx <= 2; dx++, k++) {
-          t[k] = s_n[m][c][ly + dy][lx + dx];
-          has_nan |= t[k] != t[k];
-        }
-      med[m][c] = has_nan ? __builtin_nanf("") : median9(t);  // NaN window -> NaN (median_of_normalized)
-    }
-  // -(n @ R), R = viewmatrix[:3, :3] of the row-major 4x4 tensor
-  const float* vm = P.vm;
-  const v3 n = {-(med[0][0] * vm[0] + med[0][1] * vm[4] + med[0][2] * vm[8]),
-                -(med[0][0] * vm[1] + med[0][1] * vm[5] + med[0][2] * vm[9]),
-                -(med[0][0] * vm[2] + med[0][1] * vm[6] + med[0][2] * vm[10])};
+  post_median(s_n[0], lx, ly, med[0]);
+  post_median(s_n[1], lx, ly, med[1]);
+  const v3 n = post_rotate(P.vm, med[0]);
   P.normals_view[p] = n.x; P.normals_view[HW + p] = n.y; P.normals_view[2 * HW + p] = n.z;
   P.onv[p] = med[1][0]; P.onv[HW + p] = med[1][1]; P.onv[2 * HW + p] = med[1][2];
   ShadePix q;
@@ -313,6 +348,69 @@ shade_fwd_multi_kernel(ShadeArgs A, ShadeLights Ls) {
 #pragma unroll
       for (int c = 0; c < 3; c++) lin[p + c * (size_t)A.cs] = srgb2lin(rr[c]);
     }
+  }
+}
+
+// gigs_spec_tap_census: which texels of the fine specular levels this view's shade reads.  One lane per pixel, 64 x 4
+// tiles like shade_fwd_post_kernel; a pixel forms its shading normal (kPost: from normal_map, with that kernel's staging,
+// medians and rotation; otherwise read from `normals`), its roughness and view direction as shade_pixel_n does, takes
+// spec_taps and stores a 1 into channel 0 of every tap of a level that has a `needed` array ([6 res^2 3] floats, zero
+// before the call, the level gradient's shape: specular_census_kernel lists it).  Every tap cube_sample would read is
+// marked, whatever its weight.  Plain stores of one value: idempotent, no atomics.
+// EVERY pixel marks, inside the normal mask or not: the shade kernels sample the levels for every pixel (a pixel outside
+// the mask has its colour selected away afterwards, and specular_rgb and the gradients of gigs_shade_*_ex are defined
+// there), so nothing the shade reads is left out of the list.  Only the entry point's optional `mask` (!kPost) skips
+// pixels, for a caller that will not shade them.
+struct TapCensusArgs {
+  int H, W, L;
+  int spec_res[8];
+  float* needed[8];       // null: the level is not listed
+  const float* normals;   // !kPost: element (p, c) at p * ps + c * cs
+  int ps, cs;
+  const float *normal_map, *vm;  // kPost ([3,H,W] planes, row-major 4x4)
+  const uint8_t* mask;    // !kPost; null = every pixel (what the shade kernels sample)
+  const float *view_dirs, *roughness;
+  float rough_scale, rough_bias;
+};
+
+template <bool kPost>
+__global__ void __launch_bounds__(256)
+spec_tap_census_kernel(TapCensusArgs T) {
+  __shared__ PostTile s_n;
+  const int H = T.H, W = T.W;
+  if (kPost) {
+    post_stage(s_n, T.normal_map, H, W);
+    __syncthreads();
+  }
+  const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
+  const int x = blockIdx.x * kPostW + lx, y = blockIdx.y * kPostH + ly;
+  if (x >= W || y >= H) return;
+  const int p = y * W + x;
+  v3 n;
+  if (kPost) {
+    float med[3];
+    post_median(s_n, lx, ly, med);
+    n = post_rotate(T.vm, med);
+  } else {
+    if (T.mask && T.mask[p] == 0) return;
+    const size_t e = (size_t)p * T.ps, cs = T.cs;
+    n = {T.normals[e], T.normals[e + cs], T.normals[e + 2 * cs]};
+  }
+  const v3 v = {T.view_dirs[3 * p], T.view_dirs[3 * p + 1], T.view_dirs[3 * p + 2]};
+  const float r = T.roughness[p] * T.rough_scale + T.rough_bias;
+  SpecTaps q;
+  spec_taps(T.L, T.spec_res, r, n, v, q);
+  float* const m0 = T.needed[q.l0];
+  if (q.has0 && m0) {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (q.t0.idx[k] >= 0) m0[3 * (size_t)q.t0.idx[k]] = 1.0f;
+  }
+  float* const m1 = T.needed[q.l1];
+  if (q.l1 != q.l0 && q.has1 && m1) {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (q.t1.idx[k] >= 0) m1[3 * (size_t)q.t1.idx[k]] = 1.0f;
   }
 }
 
@@ -687,6 +785,34 @@ int gigs_shade_fwd_multi(gigs_ctx* ctx, int n_lights, int H, int W, const float*
   gigs::StageTimer timer(gigs::Stage::kShadeFwd, stream);
   hipLaunchKernelGGL(gigs::shade_fwd_multi_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, A, Ls);
   return gigs_internal_check_launch("shade_fwd_multi");
+}
+
+int gigs_spec_tap_census(gigs_ctx* ctx, int H, int W, const float* normals, int planar, const float* normal_map,
+                         const float* viewmatrix, const float* view_dirs, const float* roughness, const uint8_t* mask,
+                         float rough_scale, float rough_bias, int n_levels, const int* spec_res, float* const* needed,
+                         void* stream) {
+  (void)ctx;
+  if (H <= 0 || W <= 0 || !view_dirs || !roughness || !spec_res || !needed || n_levels < 2 || n_levels > 8)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "spec_tap_census: bad argument");
+  if ((normals == nullptr) == (normal_map == nullptr) || (normal_map && !viewmatrix))
+    return gigs_internal_fail(GIGS_ERR_INVALID, "spec_tap_census: give either normals or normal_map with viewmatrix");
+  gigs::TapCensusArgs T;
+  memset(&T, 0, sizeof(T));
+  T.H = H; T.W = W; T.L = n_levels;
+  for (int i = 0; i < n_levels; i++) {
+    if (spec_res[i] <= 0 || spec_res[i] > 4096) return gigs_internal_fail(GIGS_ERR_INVALID, "spec_tap_census: bad level");
+    T.spec_res[i] = spec_res[i];
+    T.needed[i] = needed[i];
+  }
+  T.normals = normals; T.ps = planar ? 1 : 3; T.cs = planar ? H * W : 1;
+  T.normal_map = normal_map; T.vm = viewmatrix; T.mask = mask;
+  T.view_dirs = view_dirs; T.roughness = roughness; T.rough_scale = rough_scale; T.rough_bias = rough_bias;
+  // no StageTimer: the call is made for a second stream beside the SSAO march, where a pair of events times the march's
+  // shadow (23 us there, 17 us alone), not this kernel
+  const dim3 grid((W + gigs::kPostW - 1) / gigs::kPostW, (H + gigs::kPostH - 1) / gigs::kPostH);
+  if (normal_map) hipLaunchKernelGGL(gigs::spec_tap_census_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, T);
+  else hipLaunchKernelGGL(gigs::spec_tap_census_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, T);
+  return gigs_internal_check_launch("spec_tap_census");
 }
 
 int gigs_shade_bwd(int H, int W, const float* normals, const float* view_dirs, const float* albedo,

@@ -80,6 +80,7 @@ class _Scopes(threading.local):
     THREAD like the library contexts of gigs_lib: two Python threads driving two streams do not see each other's."""
     pool = None         # OutputPool
     after_blend = None  # callable
+    before_ssao = None  # callable
     prefetch_events = None  # {device: (step begin, blend begin)} events of the drop-in light prefetch
     grad_sink = None    # {name: tensor}
     async_ = None       # AsyncBinning
@@ -134,6 +135,25 @@ class after_blend:
 
     def __exit__(self, *exc):
         _st.after_blend = self._prev
+        return False
+
+
+class before_ssao:
+    """`with before_ssao(fn):` -- GaussianRasterizer.forward calls fn(normal_map, roughness_map, viewmatrix) once the
+    normal derivation has been queued and before the SSAO march is: the G-buffer planes of the view exist behind that
+    point of the stream (gigs-hip extension, off by default).  If fn returns a callable, that is called once the march
+    has been queued: work for another stream that waits for an event fn recorded is best launched there -- in a captured
+    graph the march then stays the first successor of the normal derivation and keeps the caller's queue."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def __enter__(self):
+        self._prev, _st.before_ssao = _st.before_ssao, self.fn
+        return self
+
+    def __exit__(self, *exc):
+        _st.before_ssao = self._prev
         return False
 
 
@@ -885,10 +905,15 @@ class GaussianRasterizer(nn.Module):
             normal_from_depth = filters.bilateral_blur(normal_from_depth[None, ...], (3, 3), 1, (3, 3))[0]
 
             depth_pos_filter = filters.median_blur(depth_pos[None, ...], (3, 3))[0]
+        after_ssao = None
+        if _st.before_ssao is not None:
+            after_ssao = _st.before_ssao(out_normal, roughness_map, raster_settings.viewmatrix)
         occlusion = _C.SSAO(
             raster_settings.image_width, raster_settings.image_height, focal_x, focal_y,
             raster_settings.radius, raster_settings.bias, raster_settings.thick, raster_settings.delta,
             raster_settings.step, raster_settings.start, out_normal_view, depth_pos_filter)
+        if after_ssao is not None:
+            after_ssao()
 
         return (color, radii, opacity_map, depth, normal_from_depth, out_normal, occlusion, albedo_map,
                 roughness_map, metallic_map, out_normal_view, depth_pos_filter)

@@ -84,6 +84,10 @@ SIGNATURES = {
     "gigs_spec_sparse_capacity": (_i, [C.c_void_p, _i]),
     "gigs_specular_cubemap_multi_bwd_sparse": (_i, [C.c_void_p, _i, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gigs_spec_tap_census": (_i, [C.c_void_p, _i, _i, _f, _i, _f, _f, _f, _f, _f, _fl, _fl, _i, C.POINTER(C.c_int),
+                                  C.POINTER(C.c_void_p), C.c_void_p]),
+    "gigs_specular_cubemap_multi_fwd_sparse": (_i, [C.c_void_p, _i, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "gigs_cubemap_mip_fwd": (_i, [_i, _i, _f, _f, C.c_void_p]),
     "gigs_cubemap_mip_bwd_add": (_i, [_i, _f, _f, _f, C.c_void_p]),
     "gigs_cubemap_mip_bwd_add2": (_i, [_i, _f, _f, _f, _f, C.c_void_p]),

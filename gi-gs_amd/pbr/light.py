@@ -129,6 +129,7 @@ class CubemapLight(nn.Module):
         self.base = nn.Parameter(base)
         self.register_parameter("env_base", self.base)
         self._pre, self._wanted, self._prefetch_ok, self._side, self._ready = None, False, True, None, None
+        self.fine_levels_partial = False  # set by build_mips(sparse=...): the fine levels hold one view's texels only
         self.prefetch_stats = dict(started=0, adopted=0, discarded=0)
         gigs_lib.prefetchers.add(self)
 
@@ -173,11 +174,16 @@ class CubemapLight(nn.Module):
             + len(self.specular) - 2,
         )
 
-    def build_mips(self, cutoff: float = 0.99) -> None:
+    def build_mips(self, cutoff: float = 0.99, sparse=None) -> None:
+        """sparse (a renderutils.ops.SparseFineLevels; only for a caller that builds on its own stream,
+        build_on_current_stream): the two finest GGX levels are left to sparse.fill().  Default: the dense build."""
         pre, self._pre = self._pre, None
         if not self.base.is_cuda or _tls.build_here or torch.cuda.is_current_stream_capturing():
             # inside a graph capture, or for a stepper that schedules the light itself: on the current stream
-            self.specular, self.diffuse = self._build(cutoff)
+            sparse = sparse if _tls.build_here else None
+            self.specular, self.diffuse = self._build(cutoff, sparse)
+            # True: specular[0:2] are complete only for the view sparse.fill() is called for
+            self.fine_levels_partial = sparse is not None and sparse.pending is not None
             return
         self._wanted = True  # the caller filters every iteration: the next rasterizer forward may start the next one early
         main = torch.cuda.current_stream()
@@ -202,6 +208,7 @@ class CubemapLight(nn.Module):
         for t in [pre["diffuse"], *pre["specular"]]:
             t.record_stream(main)
         self.specular, self.diffuse = pre["specular"], pre["diffuse"]
+        self.fine_levels_partial = False
 
     # ---- drop-in overlap (gigs-hip extension; the switch light_prefetch = 0 turns it off) ------------------
     # train.py:330-345 calls render() (the rasterizer, with its SSAO march) and THEN cubemap.build_mips(): op by op, the
@@ -244,7 +251,7 @@ class CubemapLight(nn.Module):
         self._pre = self._build_on_side(cutoff)
         self.prefetch_stats["started"] += 1
 
-    def _build(self, cutoff: float = 0.99):
+    def _build(self, cutoff: float = 0.99, sparse=None):
         specular = [self.base]
         diffuse_in = None
         if gigs_lib.current().switch("mip_chain") and self.base.shape[3] == 3:
@@ -262,7 +269,7 @@ class CubemapLight(nn.Module):
         rough = [(idx / (n - 2)) * (self.MAX_ROUGHNESS - self.MIN_ROUGHNESS) + self.MIN_ROUGHNESS for idx in range(n - 1)] + [1.0]
         coarsest = diffuse_in if diffuse_in is not None else specular[-1]
         # the levels are independent: one launch filters them all (and one launch back-propagates them all)
-        merged = specular_cubemap_levels(specular, rough, cutoff)
+        merged = specular_cubemap_levels(specular, rough, cutoff, sparse)
         # created after the GGX node, the diffuse filter's backward runs BEFORE the GGX backward (autograd walks
         # the later node first): 0.02 ms of short workgroups in front of the launch that floods every CU
         diffuse = diffuse_cubemap(coarsest)

@@ -178,22 +178,32 @@ class _specular_levels(torch.autograd.Function):
     backward table of every level (otherwise CubemapLight.build_mips falls back to one call per level)."""
 
     @staticmethod
-    def forward(ctx, meta, *mips):
+    def forward(ctx, meta, sparse, *mips):
         import ctypes as C
         cs = [_gpu(m, "cubemap") for m in mips]
         dev = cs[0].device
+        shapes = [c.shape[1] for c in cs]
+        # `sparse` (a SparseFineLevels): the fine levels live in its persistent buffers; once those hold a dense build, this
+        # launch filters the coarse levels only and the fine ones follow in sparse.fill(), for the view's texels alone
+        fine = sparse.begin(shapes, dev) if sparse is not None else 0
         outs, wsums, arr = [], [], (gigs_lib.SpecLevel * len(cs))()
         for i, (c, (bounds, tables)) in enumerate(zip(cs, meta)):
             res = c.shape[1]
-            out = torch.empty((6, res, res, 3), dtype=torch.float32, device=dev)
-            wsum = torch.empty((6, res, res, 1), dtype=torch.float32, device=dev)
+            if sparse is not None and i < len(sparse.out):
+                out, wsum = sparse.out[i], sparse.wsum[i]
+            else:
+                out = torch.empty((6, res, res, 3), dtype=torch.float32, device=dev)
+                wsum = torch.empty((6, res, res, 1), dtype=torch.float32, device=dev)
             outs.append(out)
             wsums.append(wsum)
             arr[i] = gigs_lib.SpecLevel(res, _avg_window(tables, res), c.data_ptr(), bounds.data_ptr(), tables.offsets.data_ptr(),
                                         tables.fwd.data_ptr(), out.data_ptr(), wsum.data_ptr())
         with torch.cuda.device(dev):
-            gigs_lib.check(_lib.gigs_specular_cubemap_multi_w(gigs_lib.ctx_ptr(), len(cs), C.cast(arr, C.c_void_p), 0, _stream()),
-                           "specular_cubemap_multi_w")
+            dense = (gigs_lib.SpecLevel * (len(cs) - fine))(*arr[fine:])
+            gigs_lib.check(_lib.gigs_specular_cubemap_multi_w(gigs_lib.ctx_ptr(), len(cs) - fine, C.cast(dense, C.c_void_p), 0,
+                                                              _stream()), "specular_cubemap_multi_w")
+        if fine:
+            sparse.pending = ((gigs_lib.SpecLevel * fine)(*arr[:fine]), cs[:fine])  # the mips stay alive with the record
         ctx.meta = meta
         ctx.lib_ctx = gigs_lib.current()
         ctx.shapes = [c.shape[1] for c in cs]
@@ -225,7 +235,88 @@ class _specular_levels(torch.autograd.Function):
                                                                        None if state is None else state.data_ptr(),
                                                                        None if lists is None else lists.data_ptr(), _stream()),
                            "specular_cubemap_multi_bwd_sparse")
-        return (None, *gs)
+        return (None, None, *gs)
+
+
+class SparseFineLevels:
+    """The sparse forward of a light's fine GGX levels, for a caller that shades ONE view with the light it has just built
+    (a training step; pipeline.Stage2Step).  The view's shade reads a few percent of the two finest levels, which are two
+    thirds of the cached weight table, so these levels are filtered for the texels it reads only:
+      * specular_cubemap_levels(..., sparse=self) filters the coarse levels as ever and leaves the fine ones pending;
+      * fill(), called once the view's G-buffer exists and before the shade, marks the texels the shade will read -- for
+        every pixel, as the shade kernels sample for every pixel (gigs_spec_tap_census) --, lists them and filters them
+        (gigs_specular_cubemap_multi_fwd_sparse: the dense bits).
+    The fine levels' outputs are persistent tensors of this object.  A texel that is not listed keeps an older value,
+    which this view's shade never reads; for any other reader the levels are incomplete (CubemapLight.fine_levels_partial).
+    The first build through the object is dense, so that the tensors never expose uninitialised memory, and so is any level
+    whose count of texels exceeds its capacity.  One object per light and stepper; its calls are ordered by the caller's
+    streams."""
+
+    N_FINE = 2           # the two finest levels; the levels below them always stay dense
+    # Per fine level, the fraction of its texels up to which it is listed; beyond it the dense level is launched.  Measured
+    # alone on the device (tools/spec_fwd_sweep.py, profiles/r28/spec_fwd_sweep.txt): with the 17 us tap census charged to
+    # each level in full, the listed 256^2 level stays below its dense launch minus that launch's spread (53 us) up to
+    # 10 % (46 us; 25 %: 51 - 56 us, the break-even) and the 128^2 level (133 us) far beyond 25 % (60 us; 50 %: 87 us).
+    # The bench views need 4 - 6 % and 10 - 11 %.  A scalar serves both levels.
+    CAPACITY = (0.10, 0.25)
+
+    def __init__(self):
+        self.shapes = None
+        self.out, self.wsum, self.needed = [], [], []
+        self.caps, self.state, self.lists = (), None, None
+        self.primed, self.pending = False, None
+
+    def begin(self, shapes, device) -> int:
+        """Called by the levels' forward: (re)allocates for the chain `shapes` and returns how many fine levels THIS build
+        leaves to fill() -- 0 for the first build, which is dense."""
+        self.pending = None
+        n_fine = self.N_FINE if len(shapes) > self.N_FINE else 0
+        key = (tuple(shapes), str(device))
+        if key != self.shapes:
+            self.shapes = key
+            fine = shapes[:n_fine]
+            self.out = [torch.empty((6, r, r, 3), dtype=torch.float32, device=device) for r in fine]
+            self.wsum = [torch.empty((6, r, r, 1), dtype=torch.float32, device=device) for r in fine]
+            self.needed = [torch.zeros((6, r, r, 3), dtype=torch.float32, device=device) for r in fine]
+            frac = self.CAPACITY if isinstance(self.CAPACITY, tuple) else (self.CAPACITY,) * n_fine
+            self.caps = tuple(int(6 * r * r * f) for r, f in zip(fine, frac))
+            self.state = torch.zeros(gigs_lib.SPEC_SPARSE_STATE_INTS, dtype=torch.int32, device=device)
+            self.lists = torch.empty(max(1, sum(self.caps)), dtype=torch.int32, device=device)
+            self.primed = False
+        if not self.primed:
+            self.primed = True
+            return 0
+        return n_fine
+
+    def fill(self, H, W, view_dirs, roughness, normals=None, planar=False, mask=None, normal_map=None, viewmatrix=None,
+             rough_scale=1.0, rough_bias=0.0) -> bool:
+        """Filters the pending fine levels for the view whose shade has these inputs (see gigs_spec_tap_census for the two
+        ways to give the normal), on the current stream.  False if nothing is pending (the last build was dense).  The record
+        of the last build is kept: a build that is replayed from a graph, without its Python code, is filled like the captured one."""
+        import ctypes as C
+        if self.pending is None:
+            return False
+        arr, _keep = self.pending
+        n, L = len(arr), len(self.shapes[0])
+        res = (C.c_int * L)(*self.shapes[0])
+        need_all = (C.c_void_p * L)(*([t.data_ptr() for t in self.needed] + [None] * (L - n)))
+        need = (C.c_void_p * n)(*[t.data_ptr() for t in self.needed])
+        caps = (C.c_int * n)(*self.caps)
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(view_dirs.device):
+            gigs_lib.check(_lib.gigs_spec_tap_census(gigs_lib.ctx_ptr(), H, W, p(normals), int(bool(planar)), p(normal_map),
+                                                     p(viewmatrix), p(view_dirs), p(roughness), p(mask), float(rough_scale),
+                                                     float(rough_bias), L, res, need_all, _stream()), "spec_tap_census")
+            gigs_lib.check(_lib.gigs_specular_cubemap_multi_fwd_sparse(gigs_lib.ctx_ptr(), n, C.cast(arr, C.c_void_p), need, caps,
+                                                                       self.state.data_ptr(), self.lists.data_ptr(), _stream()),
+                           "specular_cubemap_multi_fwd_sparse")
+        return True
+
+    def report(self):
+        """[(listed, texels marked)] per fine level from the last fill(): a device read after a synchronisation."""
+        torch.cuda.synchronize(self.state.device)
+        v = self.state.cpu().tolist()
+        return [(bool(v[8 + i]), v[16 + i]) for i in range(len(self.out))]
 
 
 # Persistent device buffers of gigs_specular_cubemap_multi_bwd_sparse: the state ints (zero before the first call; the
@@ -280,9 +371,10 @@ def spec_sparse_report(shapes, device=None):
     return [(bool(v[8 + i]), v[16 + i]) for i in range(len(shapes))]
 
 
-def specular_cubemap_levels(mips, roughnesses, cutoff=0.99):
+def specular_cubemap_levels(mips, roughnesses, cutoff=0.99, sparse=None):
     """[specular_cubemap(m, r, cutoff) for m, r in zip(mips, roughnesses)] as one launch each way, or None if a level
-    lacks its cached tables (then the caller filters level by level)."""
+    lacks its cached tables (then the caller filters level by level).  sparse = a SparseFineLevels: the fine levels are
+    returned pending, the caller completes them with sparse.fill() before anything reads them."""
     if not gigs_lib.current().switch("spec_multi") or torch.is_anomaly_enabled() or not mips[0].is_cuda:
         return None
     meta = []
@@ -292,7 +384,7 @@ def specular_cubemap_levels(mips, roughnesses, cutoff=0.99):
         if tables is None or tables.bwd_scaled is None:
             return None
         meta.append((bounds, tables))
-    return list(_specular_levels.apply(meta, *mips))
+    return list(_specular_levels.apply(meta, sparse, *mips))
 
 
 # Cached pair-weight tables (see csrc/light_filter.hip): 0.74 GB for the 256..16 chain, x2 for the backward.

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 import gigs_lib  # noqa: E402  (importable once the package's __init__ has put this directory on sys.path)
 
 from diff_gaussian_rasterization import (AsyncBinning, BinningOverflow, GaussianRasterizationSettings, GaussianRasterizer,
-                                         Gaussian_SSR, OutputPool, _C as _ops, after_blend, filters)
+                                         Gaussian_SSR, OutputPool, _C as _ops, after_blend, before_ssao, filters)
 
 
 def linear_to_srgb(linear: torch.Tensor) -> torch.Tensor:  # train.py:54-68
@@ -945,15 +945,19 @@ class Stage2Step(_Stepper):
     def __init__(self, light, brdf_lut, gi: Dict, sh_degree: int, metallic: bool = True, indirect: bool = True,
                  gamma: bool = False, tone: bool = False, graphs: bool = False, fused: bool = False,
                  prepare=None, regularizer=None, optimizers=None, post_update=None, before_update=None,
-                 geometry_cache: bool = False, materials_only: bool = False):
+                 geometry_cache: bool = False, materials_only: bool = False, sparse_light: bool = True):
         """The last five arguments turn the step into a COMPLETE training iteration (train_iteration.Stage2Trainer):
         `prepare(raw) -> g` maps the optimizer's tensors to the rasterizer's inputs (the GaussianModel getters;
         `__call__` then takes the raw dictionary), `regularizer(maps) -> scalar` adds the BRDF / envmap terms of
         train.py:387-420 (maps: normal_map, albedo_map, roughness_map, metallic_map -- the rasterizer's planes --
         and gt_image), `optimizers` (FusedAdam) are stepped after the backward, `before_update()` runs between the two
         (the multi-GPU gradient all-reduce) and `post_update()` after (cubemap.clamp_, train.py:522).  All of it is
-        part of the captured step when graphs=True (pipeline.WholeStepGraph)."""
+        part of the captured step when graphs=True (pipeline.WholeStepGraph).
+        sparse_light (fused steps only): the light's two finest GGX levels are filtered for the texels this view's shade
+        reads, behind the normal derivation (pbr.renderutils.ops.SparseFineLevels); False = the dense build."""
         super().__init__()
+        self.sparse_light = bool(sparse_light)
+        self.sparse = self.gbuffer_ready = None  # the light's SparseFineLevels and the event its fill waits for
         self.prepare, self.regularizer, self.optimizers = prepare, regularizer, list(optimizers or [])
         self.post_update, self.before_update = post_update, before_update
         self.gi, self.sh_degree, self.metallic = gi, sh_degree, metallic
@@ -983,7 +987,7 @@ class Stage2Step(_Stepper):
 
     def _make_inner(self):
         return Stage2Step(self.light, self.brdf_lut, self.gi, self.sh_degree, graphs=False, fused=True,
-                          regularizer=self.regularizer, **self.flags)
+                          regularizer=self.regularizer, sparse_light=self.sparse_light, **self.flags)
 
     def _leaves(self, g):
         out, seen = [], set()
@@ -1062,7 +1066,9 @@ class Stage2Step(_Stepper):
         pre_grads = _snapshot_grads(self._leaves(g)) if abin is not None else None
         # the blend-begin event belongs to THIS step's forward: it is part of the library context the forward runs with
         # (gigs_ctx_set_blend_begin_event), not of the process
-        with hook, (abin if abin is not None else contextlib.nullcontext()):
+        H, W = cam["image_height"], cam["image_width"]
+        fill = before_ssao((lambda *planes: self._fused_fill(H, W, view_dirs, *planes)) if self.fused else None)
+        with hook, fill, (abin if abin is not None else contextlib.nullcontext()):
             ev_ctx = (gigs_lib.use(gigs_lib.current().derive(blend_event=self.blend_begin)) if self.fused
                       else contextlib.nullcontext())
             with ev_ctx, (self.pool if self.pool is not None else contextlib.nullcontext()):
@@ -1133,7 +1139,10 @@ class Stage2Step(_Stepper):
             if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
                 torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
             self.side = torch.cuda.Stream()
-            self.mips = LightMips(self.light)
+            if self.sparse_light:
+                from pbr.renderutils.ops import SparseFineLevels
+                self.sparse = SparseFineLevels()
+            self.mips = LightMips(self.light, self.sparse)
             self.dummy = torch.zeros(1, device=self.light.base.device)
             if self.graphs:
                 with torch.no_grad():
@@ -1155,6 +1164,35 @@ class Stage2Step(_Stepper):
                 self.lights_ready = torch.cuda.Event()
             self.lights_ready.record()
         return out
+
+    def _fused_fill(self, H, W, view_dirs, normal_map, roughness_map, viewmatrix):
+        """The second half of the light's build (sparse_light): called from inside the rasterizer's forward once the normal
+        derivation is queued (diff_gaussian_rasterization.before_ssao).  The side stream, which has finished the mips, the
+        coarse GGX levels and the diffuse filter inside the blend kernel, waits for the G-buffer and filters the texels of the
+        fine levels that this view's shade reads, beside the SSAO march: small kernels, a fraction of the dense levels'
+        bytes.  The shade waits for `lights_ready`, re-recorded behind them."""
+        sp = self.sparse
+        if sp is None or sp.pending is None:
+            return None
+        main = torch.cuda.current_stream()
+        if self.gbuffer_ready is None:
+            self.gbuffer_ready = torch.cuda.Event()
+        self.gbuffer_ready.record(main)
+        planes = [t.detach().contiguous().float() for t in (view_dirs, roughness_map, normal_map, viewmatrix)]
+
+        def launch():
+            # queued behind the march (see before_ssao): in the step graph the march stays the normal derivation's first
+            # successor, on the main queue, and these nodes continue the light's branch
+            self.side.wait_event(self.gbuffer_ready)
+            with torch.cuda.stream(self.side):
+                # the shade's own inputs: roughness = raw * 0.96 + 0.04 and the normal of stage2_fused._Stage2Fused
+                sp.fill(H, W, planes[0], planes[1], normal_map=planes[2], viewmatrix=planes[3], rough_scale=1.0 - 0.04,
+                        rough_bias=0.04)
+                self.lights_ready.record()
+            for t in planes:
+                t.record_stream(self.side)
+
+        return launch
 
     def _fused_step(self, cam, gt_image, view_dirs, st, radii, screenspace_points, normal_map, out_normal_view,
                     albedo_map, roughness_map, metallic_map, occlusion_map, depth_pos, lights, extra_loss=None):

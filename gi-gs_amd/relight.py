@@ -55,6 +55,14 @@ from pbr.shade import _ptr_array
 _lib = gigs_lib.lib()
 
 
+
+def _complete(light) -> None:
+    """A light whose last build_mips() left the fine levels to a stepper's sparse fill holds one view's texels only."""
+    if getattr(light, "fine_levels_partial", False):
+        raise RuntimeError("this light's fine GGX levels were filtered for one training view only "
+                           "(build_mips(sparse=...)): call light.build_mips() before relighting with it")
+
+
 def latlong_to_cubemap(latlong_map: torch.Tensor, res: List[int]) -> torch.Tensor:
     """relight.py:92-111: [H, W, C] equirectangular map -> [6, res[0], res[1], C] cubemap."""
     if not latlong_map.is_cuda:
@@ -332,6 +340,7 @@ def shade_ssr(light: CubemapLight, brdf_lut, gi: Dict, metallic: bool, tone: boo
     render_rgb = torch.empty((3, H, W), device=dev)
     acc, loss = scratch("acc", (4 + 4 * 256,), torch.float32, dev), scratch("loss", (1,), torch.float32, dev)
     diffuse_rgb, specular_rgb = (torch.empty((3, H, W), device=dev) for _ in range(2)) if parts else (None, None)
+    _complete(light)
     spec = [s.contiguous() for s in light.specular]
     spec_ptr = _ptr_array(spec)
     spec_res = (C.c_int * len(spec))(*[int(s.shape[1]) for s in spec])
@@ -592,6 +601,8 @@ class _LightsRelighter(_Relighter):
                 chunk = self.lights[first:first + MAX_LIGHTS]
                 K = len(chunk)
                 rd, irr, rgb = render_direct[first:first + K], IRR[first:first + K], render_rgb[first:first + K]
+                for light in chunk:
+                    _complete(light)
                 spec = [[x.contiguous() for x in light.specular] for light in chunk]
                 L = len(spec[0])
                 gigs_lib.check(_lib.gigs_shade_fwd_multi(

@@ -152,12 +152,12 @@ class LightMips(torch.nn.Module):
     """light.build_mips() as a tensor function of light.base: (diffuse, *specular).  The dummy argument only
     gives make_graphed_callables a tensor input."""
 
-    def __init__(self, light):
+    def __init__(self, light, sparse=None):
         super().__init__()
-        self.light = light
+        self.light, self.sparse = light, sparse  # sparse: renderutils.ops.SparseFineLevels, see CubemapLight.build_mips
 
     def forward(self, _dummy):
-        self.light.build_mips()
+        self.light.build_mips(sparse=self.sparse)
         return (self.light.diffuse, *self.light.specular)
 
 

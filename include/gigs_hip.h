@@ -326,6 +326,30 @@ int gigs_spec_sparse_capacity(const gigs_ctx* ctx, int res);
 int gigs_specular_cubemap_multi_bwd_sparse(gigs_ctx* ctx, int n_levels, const gigs_spec_level* levels,
                                            const float* const* weights_fwd, const float* const* wsum, int* state,
                                            int* lists, void* stream);
+/* The forward of gigs_specular_cubemap_multi_w for a caller that shades ONE view with the light it has just built (a
+ * training step): only the texels that view's shade reads are filtered.  Two calls, no read-back (capturable):
+ *   gigs_spec_tap_census   marks, per pixel, the (up to 8) texels the specular lookup of the shade reads: the level
+ *            pair of the pixel's roughness (raw * rough_scale + rough_bias) and the four bilinear taps of the reflected
+ *            direction in each, through the very function the shade kernels sample through.  The shading normal is either
+ *            `normals` ([H,W,3], or [3,H,W] with planar = 1) or derived from normal_map [3,H,W] and viewmatrix exactly as
+ *            gigs_shade_fwd_post derives it (normals null).  The shade kernels sample the levels for EVERY pixel, inside
+ *            their mask or not, so every pixel marks; `mask` ([H,W] bytes, with `normals` only, null = every pixel) is for
+ *            a caller that will not shade the pixels it leaves out -- a shade over them reads texels that are not listed.
+ *            needed[l]: [6,res_l,res_l,3] floats, ZERO before the call, or null for a level that is not listed; channel 0
+ *            of a marked texel becomes 1.  view_dirs [H,W,3], roughness [H,W].
+ *   gigs_specular_cubemap_multi_fwd_sparse   for the given levels (as for gigs_specular_cubemap_multi_w, backward = 0):
+ *            lists the marked texels of needed[l] (and clears the marks: the arrays are zero again afterwards), then filters
+ *            in ONE launch the listed texels of every level whose count is within capacities[l] -- each gets the bits the
+ *            dense launch gives it; dst and wsum of the other texels are NOT written -- and every texel of a level whose
+ *            count exceeds its capacity.  state / lists as for gigs_specular_cubemap_multi_bwd_sparse (a state of its own:
+ *            state[8 + l] = 1 listed, 0 dense; state[16 + l] = texels marked; lists holds sum(capacities) ints).
+ * Texels that are not listed keep whatever dst held: the result is a light for this view's shade only. */
+int gigs_spec_tap_census(gigs_ctx* ctx, int H, int W, const float* normals, int planar, const float* normal_map,
+                         const float* viewmatrix, const float* view_dirs, const float* roughness, const uint8_t* mask,
+                         float rough_scale, float rough_bias, int n_levels, const int* spec_res, float* const* needed,
+                         void* stream);
+int gigs_specular_cubemap_multi_fwd_sparse(gigs_ctx* ctx, int n_levels, const gigs_spec_level* levels, float* const* needed,
+                                           const int* capacities, int* state, int* lists, void* stream);
 /* cubemap_mip (pbr/light.py:54-79): forward 2x2 average pool [6,2r,2r,C] -> [6,r,r,C]; backward =
  * bilinear cube lookup of 0.25*dout at every fine texel direction, dout [6,r,r,3] -> din [6,2r,2r,3]. */
 int gigs_cubemap_mip_fwd(int res_out, int channels, const float* in, float* out, void* stream);
