@@ -129,12 +129,16 @@ constexpr int kGiTileLog2W = 3;
 // ray set into four contiguous chunks (25 000 x 4 waves at 800x800 instead of 10 000 long-running
 // ones: the tail of the launch is short and empty tiles retire immediately).  Partial sums are
 // combined through LDS in the fixed order ((w0 + w1) + w2) + w3.
-__device__ __forceinline__ bool gi_pixel(const GiParams& p, int& x, int& y, int& wave) {
-  const int lane = threadIdx.x & 63;
-  wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // provably uniform: the ray table is then read with s_load
+// `tid` is threadIdx.x (a parameter: the SSR kernel derives its pixel a second time behind the march, see there)
+__device__ __forceinline__ bool gi_pixel(const GiParams& p, unsigned tid, int& x, int& y, int& wave) {
+  const int lane = tid & 63;
+  wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably uniform: the ray table is then read with s_load
   x = (blockIdx.x << p.tile_log2w) + (lane & ((1 << p.tile_log2w) - 1));
   y = blockIdx.y * (64 >> p.tile_log2w) + (lane >> p.tile_log2w);
   return x < p.W && y < p.H;
+}
+__device__ __forceinline__ bool gi_pixel(const GiParams& p, int& x, int& y, int& wave) {
+  return gi_pixel(p, threadIdx.x, x, y, wave);
 }
 
 #ifndef GIGS_GI_WAVES
@@ -145,9 +149,19 @@ __device__ __forceinline__ bool gi_pixel(const GiParams& p, int& x, int& y, int&
 #define GIGS_SSR_OCC GIGS_GI_OCC
 #else
 #define GIGS_GI_OCC
-// the certified SSR march allocates 100 VGPRs (4 waves/SIMD) on its own; asked for 5 it fits 96 without spilling and runs
-// 9 % faster (1.29 -> 1.17 ms at C2; 6 waves spill and lose it again)
-#define GIGS_SSR_OCC __attribute__((amdgpu_waves_per_eu(5)))
+// The single-light SSR march asks for GIGS_SSR_WAVES waves per SIMD.  On its own the certified march allocated 100 VGPRs
+// (4 waves); asked for 5 it fitted 96 and ran 9 % faster (1.29 -> 1.17 ms at C2), and 6 spilled in the march and lost it
+// again -- as long as the finish's position and tangent frame (12 VGPRs), the planes' offsets (6) and the in-image mask
+// and wave index (3 SGPRs, which at the scalar limit cost a VGPR for their lanes) lived across the march.  They no
+// longer do (see ssr_kernel): at 6 waves the default instance takes 80 VGPRs, the exact marches 79, none with scratch;
+// only the hit-list fill (kHits 2) keeps two register pairs of the per-pixel frame in scratch (20 B), reloaded once per
+// ray pair, outside the per-group loop (DESIGN.md section 5 and profiles/r29/gi_resource_usage.txt have the listing).
+// LDS allows 6: at 800^2 a workgroup holds 3 072 B static + 21 632 B of table = 24 704 B, six of them 148 224 B of the
+// CU's 163 840 (a seventh does not fit; SSAO's 1 024 + 21 632 = 22 656 B would, 158 592 B).
+#ifndef GIGS_SSR_WAVES
+#define GIGS_SSR_WAVES 6
+#endif
+#define GIGS_SSR_OCC __attribute__((amdgpu_waves_per_eu(GIGS_SSR_WAVES)))
 #endif
 // The march over K radiance planes (kLights > 1, gigs_ssr_multi) holds 3 (K - 1) more accumulators: they do not fit the
 // single-light budget, so those instances ask for GIGS_SSR_MULTI_WAVES ("Relighting under K maps").
@@ -157,7 +171,7 @@ __device__ __forceinline__ bool gi_pixel(const GiParams& p, int& x, int& y, int&
 #if GIGS_GI_WAVES > 0
 #define GIGS_SSR_OCC_L(L) GIGS_SSR_OCC
 #else
-#define GIGS_SSR_OCC_L(L) __attribute__((amdgpu_waves_per_eu((L) == 1 ? 5 : GIGS_SSR_MULTI_WAVES)))
+#define GIGS_SSR_OCC_L(L) __attribute__((amdgpu_waves_per_eu((L) == 1 ? GIGS_SSR_WAVES : GIGS_SSR_MULTI_WAVES)))
 #endif
 
 // What a kernel instance marches with (gi_dispatch_march picks it).  The exact march has a cheaper form for a power-of-two
@@ -175,6 +189,19 @@ __device__ __forceinline__ void stage_cert_table(const GiParams& p, const float2
   for (int i = threadIdx.x; i < nb; i += 256) s_cert[i] = cert_tab[i];
   __syncthreads();
 }
+// Does any pixel of the workgroup march?  `marches` must be a function of the lane's PIXEL and the launch parameters alone
+// (inside the image, start < step, a frame that can hit, magnitudes the march accepts) -- never of the wave or its share of
+// the rays: the four waves of a workgroup hold the same 64 pixels in the same lanes (gi_pixel), so each of them takes the
+// same vote, and a workgroup either stages the table -- barrier included -- with all four waves or with none.  A workgroup
+// that marches nothing (background tiles, start >= step) goes straight to its tail.
+__device__ __forceinline__ bool gi_any_lane_marches(bool marches) { return __builtin_amdgcn_ballot_w64(marches) != 0ull; }
+// A pointer the compiler cannot relate to the one it was made from: loads through it are not merged with, nor kept alive
+// from, earlier loads of the same address.
+template <class T>
+__device__ __forceinline__ const T* launder_ptr(const T* q) {
+  asm volatile("" : "+s"(q));
+  return q;
+}
 
 // ssao_kernel and ssr_kernel each state the per-pixel preamble and the two ray drivers (projective: pairs; exact: groups,
 // singles, tail) and differ only in what they do with a hit.  They are kept in step by hand: one shared driver compiled
@@ -187,26 +214,38 @@ ssao_kernel(GiParams p, const float4* __restrict__ rays, float sum_w,
   __shared__ float s_part[kGiWaves][64];
   constexpr bool kPow2 = kMarch == March::kExactPow2, kCert = kMarch == March::kProjCert;
   constexpr int kCertOff = sizeof(float) * kGiWaves * 64;  // dynamic LDS follows the static array
-  if constexpr (kCert) stage_cert_table<kCertOff>(p, cert_tab);
   int x, y, wave;
   const bool inside = gi_pixel(p, x, y, wave);
   const int lane = threadIdx.x & 63;
-  const size_t HW = (size_t)p.H * p.W;
-  const size_t pix_id = inside ? (size_t)p.W * y + x : 0;
+  const unsigned HW = (unsigned)(p.H * p.W), pix_id = inside ? (unsigned)(p.W * y + x) : 0u;  // W, H < 2^15: 3 HW < 2^32
   float occ = 0.0f;
+  // the pixel's frame and position are read in front of the table's staging: what they decide -- does this lane march --
+  // decides whether the workgroup needs the table at all
+  Tbn tbn = {};
+  v3 pos = {};
+  float a = 0.0f;
+  bool mag_ok = false, marches = false;
   if (inside && p.start < p.step) {
-    const Tbn tbn = make_tbn({nrm[pix_id], nrm[HW + pix_id], nrm[2 * HW + pix_id]});
+    tbn = make_tbn({nrm[pix_id], nrm[HW + pix_id], nrm[2 * HW + pix_id]});
     if (!tbn_never_hits(tbn)) {
-      const v3 pos = {pos_map[pix_id], pos_map[HW + pix_id], pos_map[2 * HW + pix_id]};
-      const __amdgpu_buffer_rsrc_t pos_z = z_plane_rsrc(pos_map + 2 * HW, HW);
-      const float a = 1 + pos.z / 100;
+      pos = {pos_map[pix_id], pos_map[HW + pix_id], pos_map[2 * HW + pix_id]};
+      a = 1 + pos.z / 100;
+      mag_ok = gi_mag_ok(pos, a, p.radius);
+      marches = march_is_proj(kMarch) ? mag_ok : true;  // see below: the projective march takes no pixel of absurd magnitude
+    }
+  }
+  if constexpr (kCert) {
+    if (gi_any_lane_marches(marches)) stage_cert_table<kCertOff>(p, cert_tab);
+  }
+  if (inside && p.start < p.step) {
+    if (!tbn_never_hits(tbn)) {
+      const __amdgpu_buffer_rsrc_t pos_z = z_plane_rsrc(pos_map + 2 * (size_t)HW, HW);
       const float cx = float(p.W) / 2.0f, cy = float(p.H) / 2.0f;
       // the live rays [0, n_live) are split across the waves; rays behind them (zero-weight ones a caller asked to be
       // marched all the same: none by default) go round-robin to the waves afterwards, so the live rays' partial sums do
       // not depend on them
       const int chunk = (p.n_live + kGiWaves - 1) / kGiWaves;
       const int r0 = wave * chunk, r1 = min(p.n_live, r0 + chunk);
-      const bool mag_ok = gi_mag_ok(pos, a, p.radius);
       if constexpr (march_is_proj(kMarch)) {
         // absurd magnitudes (|pos| >= 2^59) are outside the projective march's contract: such a pixel takes no hits
         if (mag_ok) {
@@ -297,25 +336,30 @@ ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict_
   static_assert(kHits == 0 || march_is_proj(kMarch), "hit lists exist for the projective march only");
   constexpr bool kPow2 = kMarch == March::kExactPow2, kCert = kMarch == March::kProjCert;
   constexpr int kCertOff = sizeof(float) * kGiWaves * 3 * 64;  // dynamic LDS follows the static array
-  if constexpr (kCert) stage_cert_table<kCertOff>(p, cert_tab);
   int x, y, wave;
   const bool inside = gi_pixel(p, x, y, wave);
-  const int lane = threadIdx.x & 63;
-  const size_t HW = (size_t)p.H * p.W;
-  const size_t pix_id = inside ? (size_t)p.W * y + x : 0;
-  const v3 pos = {pos_map[pix_id], pos_map[HW + pix_id], pos_map[2 * HW + pix_id]};
-  const Tbn tbn = make_tbn({nrm[pix_id], nrm[HW + pix_id], nrm[2 * HW + pix_id]});
+  const unsigned HW = (unsigned)(p.H * p.W), pix_id = inside ? (unsigned)(p.W * y + x) : 0u;  // W, H < 2^15: 3 HW < 2^32
   v3 diffuse[kLights];
 #pragma unroll
   for (int l = 0; l < kLights; l++) diffuse[l] = {0, 0, 0};
   unsigned hpos = 0;  // kHits: hits of this (pixel, wave) so far / the next entry's position
-  if (inside && p.start < p.step && !tbn_never_hits(tbn)) {
-    const __amdgpu_buffer_rsrc_t pos_z = z_plane_rsrc(pos_map + 2 * HW, HW);
-    const float a = 1 + pos.z / 100;
+  // The pixel's position and tangent frame belong to the march's PREAMBLE: they are folded into the march's own per-pixel
+  // state (FastPix, FastTbn, CertPix; the exact marches keep them for their sample vectors) and end with it.  The finish
+  // behind the march builds its own copies -- twelve registers that would otherwise live across every ray of every lane
+  // for the sake of wave 0's last forty instructions.
+  const v3 pos = {pos_map[pix_id], pos_map[HW + pix_id], pos_map[2 * HW + pix_id]};
+  const Tbn tbn = make_tbn({nrm[pix_id], nrm[HW + pix_id], nrm[2 * HW + pix_id]});
+  const float a = 1 + pos.z / 100;
+  const bool mag_ok = gi_mag_ok(pos, a, p.radius);
+  const bool enters = inside && p.start < p.step && !tbn_never_hits(tbn);
+  if constexpr (kCert) {
+    if (gi_any_lane_marches(enters && mag_ok)) stage_cert_table<kCertOff>(p, cert_tab);  // else: nothing reads the table
+  }
+  if (enters) {
+    const __amdgpu_buffer_rsrc_t pos_z = z_plane_rsrc(pos_map + 2 * (size_t)HW, HW);
     const float cx = float(p.W) / 2.0f, cy = float(p.H) / 2.0f;
     const int chunk = (p.n_live + kGiWaves - 1) / kGiWaves;  // see ssao_kernel
     const int r0 = wave * chunk, r1 = min(p.n_live, r0 + chunk);
-    const bool mag_ok = gi_mag_ok(pos, a, p.radius);
     if constexpr (kHits == 2) hpos = hits.offsets[4 * pix_id + wave];
     auto add_hit = [&](int q, float cos_t, float sin_t, int ray) {
       if (q >= 0) {
@@ -397,36 +441,45 @@ ssr_kernel(GiParams p, const float4* __restrict__ rays, const float* __restrict_
     for (r = p.n_live + wave; r < p.nrays; r += kGiWaves) single(r);
     }
   }
+  // Behind the march the lane, the wave, the pixel and the planes' offsets are derived again from the thread index (which
+  // the compiler cannot relate to the preamble's): otherwise the three 64-bit plane offsets, the in-image mask and the
+  // wave index stay allocated across the march.
+  unsigned tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
+  int xf, yf, wave_f;
+  const bool inside_f = gi_pixel(p, tid, xf, yf, wave_f);
+  const unsigned pix_f = inside_f ? (unsigned)(p.W * yf + xf) : 0u;
   if constexpr (kHits == 1) {
-    if (inside) hits.counts[4 * pix_id + wave] = hpos;
+    if (inside_f) hits.counts[4 * pix_f + wave_f] = hpos;
   }
   // lights 0 .. kLights - 2 through LDS one at a time (multi-light instances only) ...
 #pragma unroll
   for (int l = 0; l < kLights - 1; l++) {
-    s_part[wave][0][lane] = diffuse[l].x;
-    s_part[wave][1][lane] = diffuse[l].y;
-    s_part[wave][2][lane] = diffuse[l].z;
+    s_part[wave_f][0][lane] = diffuse[l].x;
+    s_part[wave_f][1][lane] = diffuse[l].y;
+    s_part[wave_f][2][lane] = diffuse[l].z;
     __syncthreads();
-    if (wave == 0 && inside) diffuse[l] = fold_waves(s_part, lane);
+    if (wave_f == 0 && inside_f) diffuse[l] = fold_waves(s_part, lane);
     __syncthreads();  // wave 0 has read them before the next light overwrites them
   }
-  // ... and the last one as the single-light kernel has always done it (this exact form keeps its code unchanged)
+  // ... and the last one
   constexpr int kLast = kLights - 1;
-  s_part[wave][0][lane] = diffuse[kLast].x;
-  s_part[wave][1][lane] = diffuse[kLast].y;
-  s_part[wave][2][lane] = diffuse[kLast].z;
+  s_part[wave_f][0][lane] = diffuse[kLast].x;
+  s_part[wave_f][1][lane] = diffuse[kLast].y;
+  s_part[wave_f][2][lane] = diffuse[kLast].z;
   __syncthreads();
-  if (wave != 0 || !inside) return;
+  if (wave_f != 0 || !inside_f) return;
   diffuse[kLast] = fold_waves(s_part, lane);
+  // the finish's own position and frame: the same planes, the same make_tbn, hence the same bits as the preamble's -- for
+  // every pixel, a NaN frame or one that never marched included -- read through pointers the compiler cannot trace back
+  const float *nrm_f = launder_ptr(nrm), *pos_f = launder_ptr(pos_map);
+  const v3 pos_fin = {pos_f[pix_f], pos_f[HW + pix_f], pos_f[2 * HW + pix_f]};
+  const Tbn tbn_fin = make_tbn({nrm_f[pix_f], nrm_f[HW + pix_f], nrm_f[2 * HW + pix_f]});
 #pragma unroll
-  for (int l = 0; l < kLast; l++)
-    ssr_finish(diffuse[l], tbn, pos, pix_id, HW, p.nrays_total, albedo_map, metallic_map, F0_map,
+  for (int l = 0; l < kLights; l++)
+    ssr_finish(diffuse[l], tbn_fin, pos_fin, pix_f, HW, p.nrays_total, albedo_map, metallic_map, F0_map,
                color + (size_t)l * 3 * HW, abd + (size_t)l * 3 * HW);
-  if constexpr (kLast > 0) {
-    color += (size_t)kLast * 3 * HW;
-    abd += (size_t)kLast * 3 * HW;
-  }
-  ssr_finish(diffuse[kLast], tbn, pos, pix_id, HW, p.nrays_total, albedo_map, metallic_map, F0_map, color, abd);
 }
 
 constexpr int kSsrMaxLights = 4;  // GIGS_SSR_LIGHTS_PER_MARCH (include/gigs_hip.h)
