@@ -21,6 +21,7 @@
 // same bits alone, inside a batch, in either argument order (the head is symmetric) and on every call.
 #include <cmath>
 
+#include "block_reduce.h"
 #include "gigs_internal.h"
 
 namespace gigs {
@@ -241,15 +242,6 @@ pool_kernel(int B, int H, int W, int C, const float* __restrict__ in, float* __r
   }
 }
 
-__device__ __forceinline__ double block_sum_d(double v, double* s_red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-}
-
 // sum over the 16 lanes of a group by an xor butterfly: every lane gets the same bits (a + b == b + a)
 __device__ __forceinline__ float group16_sum(float v) {
 #pragma unroll
@@ -294,7 +286,7 @@ head_kernel(int n, int HW, int C, const float* __restrict__ act, const float* __
     acc = group16_sum(acc);
     if (j == 0) d += (double)acc;
   }
-  d = block_sum_d(d, s_red);
+  d = block_sum(d, s_red);
   if (threadIdx.x == 0) part[(size_t)i * gridDim.x + blockIdx.x] = d;
 }
 
@@ -315,7 +307,7 @@ finish_kernel(int n, const double* __restrict__ part, TapGrid g, int* slot, doub
       const double* q = part + g.offset[l] + (size_t)i * g.blocks[l];
       double s = 0.0;
       for (int r = threadIdx.x; r < g.blocks[l]; r += 256) s += q[r];
-      s = block_sum_d(s, s_red) / g.npix[l];
+      s = block_sum(s, s_red) / g.npix[l];
       val += s;
       if (threadIdx.x == 0) rec[6 * (size_t)i + 1 + l] = s;
     }

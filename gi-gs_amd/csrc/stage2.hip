@@ -16,6 +16,7 @@
 // All planes are [C,H,W] fp32, the rasterizer's layout.  HBM-bound streaming kernels.
 #include <cstdint>
 
+#include "block_reduce.h"
 #include "gigs_internal.h"
 #include "pixel_ops.h"
 
@@ -239,18 +240,6 @@ __device__ __forceinline__ LossTaps srgb_taps(const float (*s_c)[kHaloW], int ly
   return t;
 }
 
-template <typename T>
-__device__ __forceinline__ T block_sum_256(T v, T* s_red) {
-  // wave sum by shuffles, then the 4 waves through LDS; result valid in thread 0
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[wave] = v;
-  __syncthreads();
-  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
-
 __global__ void __launch_bounds__(256)
 stage2_loss_fwd_kernel(int H, int W, const float* __restrict__ direct, const float* __restrict__ irr,
                        const float* __restrict__ gt, const float* __restrict__ mask_f,
@@ -309,10 +298,10 @@ stage2_loss_fwd_kernel(int H, int W, const float* __restrict__ direct, const flo
     ms = metallic[p] * m;
     cnt = m;
   }
-  l1 = block_sum_256(l1, s_red);
-  rs = block_sum_256(rs, s_red);
-  ms = block_sum_256(ms, s_red);
-  cnt = block_sum_256(cnt, s_red);
+  l1 = block_sum(l1, s_red);
+  rs = block_sum(rs, s_red);
+  ms = block_sum(ms, s_red);
+  cnt = block_sum(cnt, s_red);
   // Thousands of workgroups adding to the same four floats serialise in L2 (measured: 0.1 ms of a 0.14 ms
   // kernel), so the partial sums are spread over kAccSlots rows and the finish kernel adds the rows up.
   if (threadIdx.x == 0) {
@@ -451,10 +440,10 @@ stage2_loss_gather_kernel(int H, int W, const float* __restrict__ direct, const 
       d_irr_unit[c * HW + p] = d != 0.0f ? acc : 0.0f;
     }
   }
-  l1 = block_sum_256(l1, s_red);
-  rs = block_sum_256(rs, s_red);
-  ms = block_sum_256(ms, s_red);
-  cnt = block_sum_256(cnt, s_red);
+  l1 = block_sum(l1, s_red);
+  rs = block_sum(rs, s_red);
+  ms = block_sum(ms, s_red);
+  cnt = block_sum(cnt, s_red);
   if (threadIdx.x == 0) {
     double* row = rows + 4 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
     row[0] = l1; row[1] = rs; row[2] = ms; row[3] = cnt;

@@ -1,6 +1,6 @@
-"""GPU: the profile session's accounting.  Every translation unit that times stages (api, pbr, stage2, train_glue, knn)
-is exercised by three small cases, and the {stage name: launches} dictionary of each has to equal the one recorded in
-tests/golden/profile_stages.json -- recorded once with the library as it was before the stage ids moved into
+"""GPU: the profile session's accounting.  The translation units that time the stages of a training iteration (api,
+light_filter, cube_texture, shade, stage2, image_loss, adam, activations) and knn are exercised by three small cases,
+and the {stage name: launches} dictionary of each has to equal the one recorded in tests/golden/profile_stages.json -- recorded once with the library as it was before the stage ids moved into
 csrc/gigs_internal.h, so a stage that is re-labelled, lost or counted twice by a host-side change shows here.
 
 Recording (GIGS_LIB = the library whose accounting is the reference):
