@@ -1,4 +1,4 @@
-// mesh_ray.h -- what mesh_raycast.hip, mesh_light.hip, mesh_gather.hip and mesh_shadow.hip share: the ray against one face, the
+// mesh_ray.h -- what mesh_raycast.hip, mesh_light.hip, mesh_gather.hip, mesh_reflect.hip and mesh_shadow.hip share: the ray against one face, the
 // slab traversal of the triangle grid (include/gigs_hip.h, "Baking occlusion", 2 to 7) and its any-hit form, the hemisphere of a vertex (8: the no_normal rule, the
 // basis of Duff et al., the origin, the rotation and the direction of a table row) and the sky texel of a direction ("Baking
 // light", 3).  Header-only; nothing here is a symbol of the
@@ -233,7 +233,7 @@ __device__ __forceinline__ void hemisphere_direction(const Hemisphere& h, const 
   for (int c = 0; c < 3; c++) d[c] = (x * h.T[c] + y * h.B[c]) + z * h.n[c];
 }
 
-// ---- the sky of a direction ("Baking light", 3): shared by mesh_light.hip and mesh_gather.hip ----------------------------------
+// ---- the sky of a direction ("Baking light", 3): shared by mesh_light.hip, mesh_gather.hip and mesh_reflect.hip ----------------
 // the texel of u in [0, 1] on an edge of n texels: min(n - 1, floor(u n)); a NaN goes to 0
 __device__ __forceinline__ int texel_of(double u, int n) {
   const double t = floor(u * (double)n);

@@ -167,6 +167,10 @@ SIGNATURES = {
     "gigs_mesh_gather_points": (_i, [_i, _i, _f, _f, C.POINTER(_fl), C.c_double, C.POINTER(_i), _f, _f, C.c_longlong, C.c_double,
                                      _i, _f, _f, _f, _f, _f, _i, _i, C.c_ulonglong, C.c_double, C.c_double, C.c_double, _i, _f, _f,
                                      _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_mesh_reflect_points": (_i, [_i, _i, _f, _f, C.POINTER(_fl), C.c_double, C.POINTER(_i), _f, _f, C.c_longlong, C.c_double,
+                                      _i, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, C.c_ulonglong, C.c_double, C.c_double, _i, _f, _f,
+                                      _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_reflect_compose": (_i, [_i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, C.c_void_p]),
     "gigs_mesh_shadow_points": (_i, [_i, _i, _f, _f, C.POINTER(_fl), C.c_double, C.POINTER(_i), _f, _f, C.c_longlong, C.c_double,
                                      _i, _f, _f, _f, _f, _i, _f, _f, _i, _i, C.c_ulonglong, C.c_double, C.c_double, _f, _f, _f, _f,
                                      C.c_void_p]),

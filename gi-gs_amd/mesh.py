@@ -36,6 +36,9 @@
     gather_points(points, normals, mesh, cube, radiosity)   the same rays from ANY surface points (a G-buffer's pixels):
                                          occlusion, shadowed sky and bounced light in one launch (gigs_mesh_gather_points);
                                          final_gather bakes the vertex radiosity first
+    reflect_points(points, normals, views, roughness, mesh, cube, radiosity)   a GGX lobe of rays about each point's mirror
+                                         direction: traced specular radiance and specular occlusion
+                                         (gigs_mesh_reflect_points); ggx_directions is its table of half vectors (host)
     atlas_layout(F, block, width)        the texture atlas of equal per-face charts, face_uvs(F, layout) its UVs (host)
     transfer_attributes(points, src, values)   per-vertex channels of src interpolated at the closest point of src to
                                          every query (gigs_mesh_closest, gigs_mesh_transfer)
@@ -1315,6 +1318,178 @@ def final_gather(points, normals, mesh, cube, bounces=1, reflectance=None, light
                                       directions, mask, cell, grid)
     report["bounces"], report["bake"] = bounces, baked
     return light, report
+
+
+# ---- ray-traced reflections per point (include/gigs_hip.h, "Ray-traced reflections per point") -----------------------------
+REFLECT_MAX_LEVELS = 64
+REFLECT_COUNTERS = ("misses", "front_hits", "back_hits", "below_horizon", "no_normal", "no_view", "masked")
+
+
+class Reflection(NamedTuple):
+    specular: torch.Tensor    # [N,3] float32 or None (no cube): the radiance the GGX lobe brings, sky and mesh
+    reflected: torch.Tensor   # [N,3] float32 or None: the share of the front hits (the mesh's radiosity) alone
+    visibility: torch.Tensor  # [N] float32: the n.l-weighted share of the lobe that escapes, 1 = open
+    valid: torch.Tensor       # [N] int32: the rays above the horizon
+    blocked: torch.Tensor     # [N] int32: those of them that hit a face
+
+
+def ggx_directions(rays: int = 64, rotations: int = 16, levels: int = 16) -> np.ndarray:
+    """[levels, rotations, rays, 3] float32: GGX-distributed HALF vectors in the tangent frame (z is the normal), the table of
+    reflect_points.  Level l of L stands for roughness r_l = (l + 1/2) / L, alpha = r_l^2; point i of R has u = (i + 1/2) / R,
+    cos^2(theta) = (1 - u) / (1 + (alpha^2 - 1) u) -- the inverse of the GGX distribution's CDF (Karis 2013) -- and the
+    azimuth of occlusion_directions' spiral, i times the golden angle + 2 pi k / K for rotation k.  numpy float64 on the
+    host, rounded to float32: the device does no trigonometry and no sqrt."""
+    R, K, L = int(rays), int(rotations), int(levels)
+    if R < 64 or R > BAKE_MAX_RAYS or R % 64 != 0:
+        raise ValueError("ggx_directions: rays must be a multiple of 64 in [64, %d], got %d" % (BAKE_MAX_RAYS, R))
+    if K < 1 or K > BAKE_MAX_ROTATIONS:
+        raise ValueError("ggx_directions: rotations must lie in [1, %d], got %d" % (BAKE_MAX_ROTATIONS, K))
+    if L < 1 or L > REFLECT_MAX_LEVELS:
+        raise ValueError("ggx_directions: levels must lie in [1, %d], got %d" % (REFLECT_MAX_LEVELS, L))
+    i = np.arange(R, dtype=np.float64)
+    u = (i + 0.5) / R
+    alpha = ((np.arange(L, dtype=np.float64) + 0.5) / L) ** 2
+    cos2 = (1.0 - u)[None, :] / (1.0 + (alpha[:, None] ** 2 - 1.0) * u[None, :])  # [L,R]
+    z, r = np.sqrt(cos2), np.sqrt(1.0 - cos2)
+    golden = np.pi * (3.0 - np.sqrt(5.0))
+    phi = i[None, :] * golden + (2.0 * np.pi * np.arange(K, dtype=np.float64) / K)[:, None]  # [K,R]
+    return np.stack([r[:, None, :] * np.cos(phi)[None], r[:, None, :] * np.sin(phi)[None],
+                     np.broadcast_to(z[:, None, :], (L, K, R))], -1).astype(np.float32)
+
+
+def _reflect_args(what: str, rays, rotations, levels, directions, max_distance, bias):
+    """The checks of reflect_points' table.  -> (R, K, L, the table [L,K,R,3] float32 numpy)."""
+    if directions is None:
+        directions = ggx_directions(rays, rotations, levels)
+    else:
+        directions = np.ascontiguousarray(directions, dtype=np.float32)
+        if directions.ndim != 4 or directions.shape[3] != 3:
+            raise ValueError("%s: directions must be [L,K,R,3], got %s" % (what, directions.shape,))
+        if not (np.isfinite(directions).all() and (directions[..., 2] >= 0).all()):
+            raise ValueError("%s: directions must be finite with z >= 0" % what)
+    L, K, R = (int(x) for x in directions.shape[:3])
+    if R < 64 or R > BAKE_MAX_RAYS or R % 64 != 0:
+        raise ValueError("%s: rays must be a multiple of 64 in [64, %d], got %d" % (what, BAKE_MAX_RAYS, R))
+    if K < 1 or K > BAKE_MAX_ROTATIONS:
+        raise ValueError("%s: rotations must lie in [1, %d], got %d" % (what, BAKE_MAX_ROTATIONS, K))
+    if L < 1 or L > REFLECT_MAX_LEVELS:
+        raise ValueError("%s: levels must lie in [1, %d], got %d" % (what, REFLECT_MAX_LEVELS, L))
+    for name, x in (("max_distance", max_distance), ("bias", bias)):
+        if x is not None and not (float(x) >= 0 and np.isfinite(float(x))):
+            raise ValueError("%s: %s must be finite and >= 0 or None, got %r" % (what, name, x))
+    return R, K, L, directions
+
+
+def _reflect_points(points, normals, views, roughness, m: Mesh, grid, cube, radiosity, table, max_distance, bias, seed, mask,
+                    report):
+    """The launch of reflect_points on checked arguments (grid is not None, N > 0) -> Reflection; fills the counters of report.
+    table: [L,K,R,3] float32 on the device."""
+    dev = m.vertices.device
+    N, V, F = int(points.shape[0]), int(m.vertices.shape[0]), int(m.faces.shape[0])
+    L, K, R = (int(x) for x in table.shape[:3])
+    visibility = torch.ones(N, dtype=torch.float32, device=dev)
+    valid = torch.zeros(N, dtype=torch.int32, device=dev)
+    blocked = torch.zeros(N, dtype=torch.int32, device=dev)
+    specular = torch.zeros((N, 3), dtype=torch.float32, device=dev) if cube is not None else None
+    reflected = torch.zeros((N, 3), dtype=torch.float32, device=dev) if cube is not None else None
+    order = _cell_order(points.double(), grid)
+    counts = torch.zeros(8, dtype=torch.int64, device=dev)  # the seven counters; overflow (an int32 in its low half)
+    c_lo, c_dims = _c_grid(grid.lo, grid.dims)
+    gigs_lib.check(gigs_lib.lib().gigs_mesh_reflect_points(
+        V, F, _p(m.vertices), _p(m.faces), c_lo, grid.cell, c_dims, _p(grid.cell_start), _p(grid.pairs), int(grid.pairs.shape[0]),
+        _scale(grid), N, _p(points), _p(normals), _p(views), _p(roughness), _p(mask) if mask is not None else None, _p(order),
+        _p(table), L, R, K, seed, float("inf") if max_distance is None else float(max_distance), float(bias),
+        int(cube.shape[1]) if cube is not None else 0, _p(cube) if cube is not None else None,
+        _p(radiosity) if radiosity is not None else None, _p(specular) if cube is not None else None,
+        _p(reflected) if cube is not None else None, _p(visibility), _p(valid), _p(blocked), counts.data_ptr(),
+        counts[7:].data_ptr(), _stream()), "mesh_reflect_points")
+    got = [int(x) for x in counts.cpu()]  # the one read-back
+    if got[7] != 0:
+        raise MeshOverflow("reflect_points: an index left its range (%d points, %d vertices, %d faces)" % (N, V, F))
+    report.update(zip(REFLECT_COUNTERS, got[:7]))
+    return Reflection(specular, reflected, visibility, valid, blocked)
+
+
+def reflect_points(points, normals, views, roughness, mesh, cube=None, radiosity=None, rays=64, levels=16, rotations=16,
+                   max_distance=None, bias=None, seed=0, directions=None, mask=None, cell=None, grid=None):
+    """(Reflection(specular, reflected, visibility, valid, blocked), report): the traced counterpart of the shade's lookup in
+    the pre-filtered environment cube, for ANY surface points -- `points`, `normals`, `views` [N,3] and `roughness` [N]
+    float32 on the mesh's device, in practice the covered pixels of a G-buffer; `views` are unit vectors from the surface
+    towards the eye (mesh_render.prepare_views) -- in one launch (gigs_mesh_reflect_points).  A wave per point casts `rays`
+    rays (a multiple of 64 in [64, 1024]) from point + bias normal: row i of the point's level and rotation of the table
+    ggx_directions(rays, rotations, levels) is a GGX half vector h in the point's frame (gather_points' frame and rotation;
+    the level is min(levels - 1, floor(roughness levels))), and the ray is the view mirrored about it,
+    l = 2 (v.h) h - v.  A ray with v.h <= 0 or n.l <= 0 is below the horizon and is not cast.  With a `cube` ([6,n,n,3]
+    float32, as gather_light's) specular [N,3] is the n.l-weighted mean of what the rays bring -- the sky texel where a ray
+    escapes, `radiosity` [V,3] float32 (finite; None: nothing) interpolated where it meets the front of a face, nothing at a
+    back -- which is the first sum of the split-sum approximation taken about the true view direction; reflected [N,3] is
+    the share of the front hits; a hit returns DIFFUSE radiosity only, there is no specular inter-reflection.  visibility [N]
+    is the n.l-weighted share of the rays that escape (1 = open; specular occlusion), valid and blocked [N] int32 count the
+    rays cast and those that hit a face.  Without a cube specular and reflected are None and the rest is the same.  The rays
+    run to `max_distance` (None: no limit).  A point with mask [N] (uint8 or bool) == 0 is `masked`, a point whose position
+    is not finite or whose normal is not of unit length within 2^-10 is `no_normal`, one whose view is not finite or not of
+    unit length within 2^-10 is `no_view`: no rays, specular 0, visibility 1.  bias defaults as gather_points'.
+    `directions` [L,K,R,3] overrides the table.  The result is a pure function of the arguments and does not depend on the
+    grid (`cell`, `grid`).  N == 0 or a mesh with no usable face launches nothing and leaves every point open, and then
+    nothing is reflected either: specular and reflected are 0, valid and blocked 0, and no ray is counted.  Report: n, misses,
+    front_hits, back_hits, below_horizon, no_normal, no_view, masked, rays, rotations, levels, seed, max_distance (None:
+    unlimited), bias, sky_res (None: no cube), radiosity (bool), faces_skipped, cell, dims, pairs.  One read-back (after the
+    checks of cube and radiosity)."""
+    what = "reflect_points"
+    R, K, L, directions = _reflect_args(what, rays, rotations, levels, directions, max_distance, bias)
+    m = _mesh_tensors(mesh, what)
+    dev = m.vertices.device
+    points = _check_points(points, dev, what)
+    normals = _check_points(normals, dev, what, "normals")
+    views = _check_points(views, dev, what, "views")
+    N, F = int(points.shape[0]), int(m.faces.shape[0])
+    if int(normals.shape[0]) != N or int(views.shape[0]) != N:
+        raise ValueError("%s: %d points, %d normals, %d views" % (what, N, int(normals.shape[0]), int(views.shape[0])))
+    if (not isinstance(roughness, torch.Tensor) or roughness.device != dev or roughness.dtype != torch.float32
+            or tuple(roughness.shape) != (N,)):
+        raise ValueError("%s: roughness must be a [%d] float32 tensor on the mesh's device" % (what, N))
+    roughness = roughness.detach().contiguous()
+    if mask is not None:
+        if (not isinstance(mask, torch.Tensor) or mask.device != dev or mask.dtype not in (torch.uint8, torch.bool)
+                or tuple(mask.shape) != (N,)):
+            raise ValueError("%s: mask must be a [%d] uint8 or bool tensor on the mesh's device" % (what, N))
+        mask = mask.detach().to(torch.uint8).contiguous()
+    if cube is not None:
+        cube = _check_cube(cube, what)
+        if cube.device != dev:
+            raise RuntimeError("%s: the cube must be a tensor on the mesh's device: gigs-hip has no CPU path" % what)
+    if radiosity is not None:
+        radiosity = _check_radiosity(radiosity, m, what)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    report = dict(n=N, rays=R, rotations=K, levels=L, seed=seed, max_distance=None if max_distance is None else float(max_distance),
+                  bias=0.0 if bias is None else float(bias), sky_res=int(cube.shape[1]) if cube is not None else None,
+                  radiosity=radiosity is not None)
+    report.update(dict.fromkeys(REFLECT_COUNTERS, 0))
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    light = (torch.zeros((N, 3), **f32), torch.zeros((N, 3), **f32)) if cube is not None else (None, None)
+    empty = Reflection(*light, torch.ones(N, **f32), torch.zeros(N, **i32), torch.zeros(N, **i32))
+    if N == 0:
+        report.update(_grid_report(None, F))
+        return empty, report
+    with torch.cuda.device(dev):
+        if grid is None:
+            grid = triangle_grid(m, cell)
+        report.update(_grid_report(grid, F))
+        if grid is None:  # no usable face: every point is open and nothing is launched
+            live = mask != 0 if mask is not None else torch.ones(N, dtype=torch.bool, device=dev)
+            n2, v2 = (normals.double() ** 2).sum(1), (views.double() ** 2).sum(1)
+            lo, hi = 1.0 - 2.0 ** -10, 1.0 + 2.0 ** -10
+            bad = live & ~(torch.isfinite(points).all(1) & (n2 >= lo) & (n2 <= hi))
+            blind = live & ~bad & ~(torch.isfinite(views).all(1) & (v2 >= lo) & (v2 <= hi))
+            got = torch.stack(((~live).sum(), bad.sum(), blind.sum())).cpu().tolist()
+            report["masked"], report["no_normal"], report["no_view"] = int(got[0]), int(got[1]), int(got[2])
+            return empty, report
+        if bias is None:
+            bias = 1e-3 * (0.1 * (max(grid.dims) * grid.cell))
+        report["bias"] = float(bias)
+        table = torch.from_numpy(directions).to(dev)
+        return _reflect_points(points, normals, views, roughness, m, grid, cube, radiosity, table, max_distance, bias, seed, mask,
+                               report), report
 
 
 # ---- shadows of analytic lights per point (include/gigs_hip.h, "Shadows of analytic lights") --------------------------------

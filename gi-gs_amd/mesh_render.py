@@ -23,7 +23,13 @@ behind them is the existing one, unchanged.
                                       viewmatrix, mask) -> occlusion, hits, irradiance, indirect by mesh.gather_points
                                       (gigs_mesh_gather_points): a final gather per pixel over the mesh's baked radiosity
     RaytracedGBuffer(inner, tracer)   a G-buffer source around MeshGBuffer or relight.SplatGBuffer whose occlusion plane is the
-                                      traced one, or its product with the inner plane: the relighters take it through source=
+                                      traced one, or its product with the inner plane: the relighters take it through source=;
+                                      reflections=True adds the traced specular planes to its extras
+    RaytracedLight.reflections(pos_view, normal, roughness, viewmatrix, campos, mask)   a GGX lobe of rays about every pixel's
+                                      mirror direction by mesh.reflect_points (gigs_mesh_reflect_points): specular, reflected,
+                                      visibility; prepare_views(points, campos) makes its view vectors
+    compose_reflections(normals, views, roughness, radiance, ...)   the shade's specular_rgb = radiance (F0 fg.x + fg.y) on a
+                                      supplied radiance (gigs_reflect_compose)
 
 The arithmetic is stated in include/gigs_hip.h and restated in numpy by tests/mesh_raster_ref.py (the textured resolve by
 tests/mesh_texture_ref.py).  There is no clipping:
@@ -445,6 +451,71 @@ def prepare_points(pos_view, normal, viewmatrix, mask, normal_space, dev):
     return points.float().contiguous(), normals.float().contiguous(), (mask.detach().to(dev).reshape(H * W) != 0).to(torch.uint8)
 
 
+@torch.no_grad()
+def prepare_views(points, campos):
+    """[N,3] float32: the unit vectors from `points` [N,3] float32 (prepare_points') towards the eye `campos` [3], the `views`
+    of mesh.reflect_points and compose_reflections, on the points' device.  In float64 on the float32 inputs, elementwise
+    and in this order:
+        d_i = c_i - p_i;   v_i = d_i / sqrt((d_0 d_0 + d_1 d_1) + d_2 d_2)
+    rounded to float32.  The sqrt is taken here, in torch on the host's side of the launch: the trace kernel has none.  A
+    point at the eye or one that is not finite gives NaN: a no_view point if its mask is set."""
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[1] == 3):
+        raise ValueError("prepare_views: points is an [N,3] tensor")
+    c = torch.as_tensor(campos, dtype=torch.float32).detach().reshape(-1).cpu().tolist()
+    if len(c) != 3:
+        raise ValueError("prepare_views: campos has three components")
+    p = points.detach().double()
+    d = [float(c[i]) - p[:, i] for i in range(3)]
+    length = torch.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+    return torch.stack([d[i] / length for i in range(3)], 1).float().contiguous()
+
+
+@torch.no_grad()
+def compose_reflections(normals, views, roughness, radiance, albedo=None, metallic=None, mask=None, visibility=None,
+                        brdf_lut=None):
+    """[N,3] float32: specular_rgb = radiance * (F0 * fg.x + fg.y), the specular half of pbr_shading with a supplied
+    `radiance` [N,3] (mesh.reflect_points' specular) in the place of the lookup in the pre-filtered cube
+    (gigs_reflect_compose; include/gigs_hip.h, "Ray-traced reflections per point", restates the shade's float32 lines):
+    nov = clamp(n.v, 1e-4, 1), fg the bilinear, clamped lookup of `brdf_lut` (None: pbr.get_brdf_lut()) at (nov, roughness),
+    F0 = (1 - m) 0.04 + albedo m, or 0.04 without `metallic` [N] (`albedo` [N,3] is then not needed).  normals, views [N,3]
+    and roughness [N] are float32 on one device; a point with mask [N] (uint8 or bool) == 0 gets 0.  With `visibility` [N]
+    the radiance is multiplied by it first: an external radiance -- a splat shade's cube lookup -- under traced specular
+    occlusion."""
+    what = "compose_reflections"
+    if not isinstance(normals, torch.Tensor) or not normals.is_cuda:
+        raise RuntimeError("%s: normals must be a CUDA/HIP tensor: gigs-hip has no CPU path" % what)
+    dev, N = normals.device, int(normals.shape[0])
+
+    def arr(t, name, shape, optional=False):
+        if t is None and optional:
+            return None
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be a %s float32 tensor on the normals' device" % (what, name, list(shape)))
+        return t.detach().contiguous()
+
+    normals, views = arr(normals, "normals", (N, 3)), arr(views, "views", (N, 3))
+    roughness, radiance = arr(roughness, "roughness", (N,)), arr(radiance, "radiance", (N, 3))
+    metallic, visibility = arr(metallic, "metallic", (N,), True), arr(visibility, "visibility", (N,), True)
+    albedo = arr(albedo, "albedo", (N, 3), metallic is None)
+    if mask is not None:
+        if (not isinstance(mask, torch.Tensor) or mask.device != dev or mask.dtype not in (torch.uint8, torch.bool)
+                or tuple(mask.shape) != (N,)):
+            raise ValueError("%s: mask must be a [%d] uint8 or bool tensor on the normals' device" % (what, N))
+        mask = mask.detach().to(torch.uint8).contiguous()
+    if brdf_lut is None:
+        from pbr import get_brdf_lut
+        brdf_lut = get_brdf_lut()
+    lut = brdf_lut.detach().to(dev).float().contiguous()
+    if lut.dim() < 3 or lut.shape[-1] != 2:
+        raise ValueError("%s: brdf_lut is [..., h, w, 2], got %s" % (what, tuple(lut.shape)))
+    out = torch.zeros((N, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        gigs_lib.check(_lib.gigs_reflect_compose(N, _p(normals), _p(views), _p(albedo), _p(roughness), _p(metallic), _p(mask),
+                                                 _p(radiance), _p(visibility), _p(lut), int(lut.shape[-2]), int(lut.shape[-3]),
+                                                 _p(out), _stream()), "reflect_compose")
+    return out
+
+
 class RaytracedLight:
     """A mesh as the occluder and bounce surface of any view's pixels: the triangle grid is built once, and with a `cube`
     ([6,n,n,3] float32, mesh.sky_cube's) so is the vertex radiosity of the passes 0 .. bounces - 1 (mesh.trace_hemispheres with
@@ -537,6 +608,35 @@ class RaytracedLight:
                                                        self.seed, m, self.grid)
         return visibility.t().reshape(-1, H, W).contiguous(), points, normals, m, report
 
+    @torch.no_grad()
+    def reflections(self, pos_view, normal, roughness, viewmatrix, campos, mask, normal_space: str = "world", bounces=None,
+                    rays=None, levels: int = 16, cube=None) -> Dict:
+        """prepare() and prepare_views(points, campos), then mesh.reflect_points with the tracer's grid, bias, seed and rotations
+        -> {specular, reflected [3,H,W] float32 or None (no cube), visibility [1,H,W] float32, valid, blocked [H,W] int32,
+        points, normals, views, roughness, mask (the prepared arrays), report}.  roughness: the plane [1,H,W] or [H,W];
+        campos [3]: the eye in world space.  rays (None: the constructor's) and levels size the table mesh.ggx_directions.
+        cube (None: the tracer's) is the sky the escaping rays look up: a finer one than the diffuse gather's may be given,
+        because a 32 x 32 sky is coarse for a glossy lobe; the front hits bring the radiosity of the tracer's own cube after
+        `bounces` - 1 vertex passes (planes()' rule; None: the constructor's)."""
+        points, normals, m = self.prepare(pos_view, normal, viewmatrix, mask, normal_space)
+        _, H, W = pos_view.shape
+        if not isinstance(roughness, torch.Tensor) or roughness.numel() != H * W:
+            raise ValueError("RaytracedLight: roughness is a plane of %d x %d pixels" % (H, W))
+        b = self.bounces if bounces is None else int(bounces)
+        if b < 0 or b > self.bounces:
+            raise ValueError("RaytracedLight: bounces must lie in [0, %d], got %d" % (self.bounces, b))
+        sky = self.cube if cube is None else mesh_ops._check_cube(cube, "RaytracedLight").to(self.device)
+        radiosity = self.radiosity[b - 1] if (b > 0 and self.radiosity is not None and sky is not None) else None
+        views = prepare_views(points, campos)
+        rough = roughness.detach().to(self.device).float().reshape(H * W).contiguous()
+        got, report = mesh_ops.reflect_points(points, normals, views, rough, self.mesh, sky, radiosity, self.rays if rays is None else rays,
+                                              levels, self.rotations, None, self.bias, self.seed, mask=m, grid=self.grid)
+        report["bounces"] = b if sky is not None else None
+        plane3 = lambda x: None if x is None else x.t().reshape(3, H, W).contiguous()  # noqa: E731
+        return dict(specular=plane3(got.specular), reflected=plane3(got.reflected), visibility=got.visibility.reshape(1, H, W),
+                    valid=got.valid.reshape(H, W), blocked=got.blocked.reshape(H, W), points=points, normals=normals, views=views,
+                    roughness=rough, mask=m, report=report)
+
 
 class RaytracedGBuffer:
     """A G-buffer source around another (MeshGBuffer, relight.SplatGBuffer) whose `occlusion` plane is ray-traced against a
@@ -546,17 +646,21 @@ class RaytracedGBuffer:
     raytraced_indirect when the tracer has a cube; `report` is the tracer's of the last view.  The relighters take it through
     source=; graphs=True raises there, because a traced view replays no hipGraph.  depth_pos comes from the FILTERED depth and
     lies off the mesh by up to the depth range of a pixel's 3x3 neighbourhood: give the tracer a `bias` above that, or the points
-    under the surface see its back (the report's back_hits show it)."""
+    under the surface see its back (the report's back_hits show it).  reflections=True also traces the view's glossy
+    reflections (RaytracedLight.reflections from the same planes, the inner roughness_map and cam's campos): `extra` gains
+    raytraced_specular, raytraced_reflected (with a cube) and raytraced_specular_visibility, `reflection_report` is that
+    trace's report, and every other output is what it is without."""
     replayable = False
 
-    def __init__(self, inner, tracer: RaytracedLight, occlusion: str = "replace"):
+    def __init__(self, inner, tracer: RaytracedLight, occlusion: str = "replace", reflections: bool = False):
         if occlusion not in RAYTRACED_MODES:
             raise ValueError("RaytracedGBuffer: occlusion is one of %s, got %r" % (", ".join(RAYTRACED_MODES), occlusion))
         if not isinstance(tracer, RaytracedLight):
             raise TypeError("RaytracedGBuffer: the tracer is a RaytracedLight")
         self.inner, self.tracer, self.occlusion = inner, tracer, occlusion
         self.metallic = inner.metallic
-        self.report = None
+        self.reflections = bool(reflections)
+        self.report = self.reflection_report = None
 
     @torch.no_grad()
     def __call__(self, cam: Dict, scene) -> Dict:
@@ -571,5 +675,12 @@ class RaytracedGBuffer:
         extra = dict(b.get("extra", {}), raytraced_occlusion=t["occlusion"])
         if t["irradiance"] is not None:
             extra["raytraced_irradiance"], extra["raytraced_indirect"] = t["irradiance"], t["indirect"]
+        if self.reflections:
+            r = self.tracer.reflections(b["depth_pos"], b["normals_view"], b["roughness_map"], cam["viewmatrix"], cam["campos"],
+                                        b["mask_u8"], normal_space="view")
+            self.reflection_report = r["report"]
+            extra["raytraced_specular_visibility"] = r["visibility"]
+            if r["specular"] is not None:
+                extra["raytraced_specular"], extra["raytraced_reflected"] = r["specular"], r["reflected"]
         b["extra"] = extra
         return b

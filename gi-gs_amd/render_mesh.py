@@ -5,6 +5,7 @@ its scene (mesh_render.py), and compared with the splat render it came from or w
                                     [--rotations N] [--compare] [--reference_mesh other.ply|other.obj]
                                     [--occlusion ssao|baked|both] [--split test] [--metallic --tone --gamma]
                                     [--lighting baked|raytraced [--bounces 1] [--sky_res 32] [--light_rays 256]]
+                                    [--reflections [--reflection_rays 64] [--roughness_levels 16] [--reflection_sky_res 128]]
                                     [--occlusion raytraced] [--ao_rays 64] [--ao_distance D] [--ray_bias B]
                                     [--lights lights.json [--shadow_samples S] [--no_shadows]]                   (CLI)
     render_mesh(args) -> {...}                                                                                   (API)
@@ -53,6 +54,12 @@ above) and casts --ao_rays rays from every covered pixel of the mesh's own posit
 mesh_<split>/raytraced_vs_screen.json holds, per view and on average, the PSNR (peak 1, over the covered pixels) of that plane
 against the screen-space diffuse (psnr_screen_bounces_<b>) and against the per-vertex baked plane of --lighting baked
 (psnr_baked_bounces_<b>), for b = 0 and --bounces, with the bake's report and the tracer's report of the last view.
+With --reflections [--reflection_rays 64] [--roughness_levels 16] [--reflection_sky_res 128] the same tracer also casts a GGX
+lobe of --reflection_rays rays about every covered pixel's mirror direction (RaytracedLight.reflections; the escaping rays
+look up a sky of --reflection_sky_res texels an edge, the hits bring the baked radiosity) and mesh_render.compose_reflections
+turns it into the shade's specular term: <image_name>_raytraced_specular.png is linear_to_srgb of that plane,
+<image_name>_raytraced.png of diffuse + specular, clamped, and the JSON gains psnr_specular_screen_bounces_<--bounces> (against
+shade_ssr's specular_rgb) and, under "reflections", that trace's report of the last view.  Without the flag nothing changes.
 
 --lights lights.json (a PLY or an OBJ) also renders every view under the point and directional lights of that file
 (analytic_lights.py states its format) with shadows ray-traced against the mesh itself: <image_name>_lights.png is
@@ -108,6 +115,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ao_rays", type=int, default=64, help="rays per pixel of the ray-traced modes, a multiple of 64 in [64, 1024]")
     p.add_argument("--ao_distance", type=float, default=None, help="how far an occluder counts (default: mesh.bake_occlusion's)")
     p.add_argument("--ray_bias", type=float, default=None, help="the rays' start off the surface (default: 1e-3 ao_distance)")
+    p.add_argument("--reflections", action="store_true", help="--lighting raytraced: also trace the glossy reflections per pixel")
+    p.add_argument("--reflection_rays", type=int, default=64, help="rays per pixel of --reflections, a multiple of 64 in [64, 1024]")
+    p.add_argument("--roughness_levels", type=int, default=16, help="roughness levels of the GGX table of --reflections, in [1, 64]")
+    p.add_argument("--reflection_sky_res", type=int, default=128, help="texels an edge of the sky cube the reflection rays look up")
     p.add_argument("--lights", type=str, default=None, help="a JSON list of point and directional lights: also render under them")
     p.add_argument("--shadow_samples", type=int, default=1, help="shadow samples per light in [1, 64]; 1: hard shadows")
     p.add_argument("--no_shadows", action="store_true", help="--lights without ray-traced shadows")
@@ -178,6 +189,16 @@ def _check(args: Namespace) -> int:
             x = getattr(args, name, None)
             if x is not None and not (0.0 <= float(x) < float("inf")):
                 raise ValueError("--%s: finite and >= 0, got %r" % (name, x))
+    if getattr(args, "reflections", False):
+        if lighting != "raytraced":
+            raise ValueError("--reflections needs --lighting raytraced")
+        rays, levels = int(getattr(args, "reflection_rays", 64)), int(getattr(args, "roughness_levels", 16))
+        if rays < 64 or rays > 1024 or rays % 64 != 0:
+            raise ValueError("--reflection_rays: a multiple of 64 in [64, 1024], got %d" % rays)
+        if levels < 1 or levels > 64:
+            raise ValueError("--roughness_levels: a count in [1, 64], got %d" % levels)
+        if int(getattr(args, "reflection_sky_res", 128)) < 1:
+            raise ValueError("--reflection_sky_res: texels an edge, got %d" % int(args.reflection_sky_res))
     samples = int(getattr(args, "shadow_samples", 1))
     if not getattr(args, "lights", None):
         if samples != 1 or getattr(args, "no_shadows", False):
@@ -282,6 +303,9 @@ def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, info
     source, scratch = mesh_render.MeshGBuffer(gi, args.metallic), relight.Scratch()
     base = os.path.join(out, "mesh_" + args.split)
     rows, files, report = [], [], None
+    reflect = bool(getattr(args, "reflections", False))
+    spec_files, full_files, reflect_report = [], [], None
+    glossy_sky = shade_frame_sky(light, args.reflection_sky_res) if reflect else None
     with mesh_render.MeshRasterizer(m, device=dev) as plain, image_writer.ImageWriter(workers=args.workers) as wr, \
             mesh_render.RaytracedLight(m, rays=args.ao_rays, ao_distance=args.ao_distance, bias=args.ray_bias, cube=sky, bounces=B,
                                        reflectance=rho, light_rays=args.light_rays, device=dev) as tracer, torch.no_grad():
@@ -293,8 +317,9 @@ def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, info
                 if rays is None:
                     rays = pipeline.canonical_rays(c, dev)
                 g = source(c, plain)
-                screen = relight.shade_ssr(light, lut, gi, args.metallic, False, True, c, pipeline.view_dirs_for(c, rays, dev), g,
-                                           g["albedo_map"], scratch, parts=True)[3].nan_to_num().clamp(0, 1).double()
+                shaded = relight.shade_ssr(light, lut, gi, args.metallic, False, True, c, pipeline.view_dirs_for(c, rays, dev), g,
+                                           g["albedo_map"], scratch, parts=True)
+                screen = shaded[3].nan_to_num().clamp(0, 1).double()
                 o = plain(c)  # the mesh's own position and normal planes: sharper than the G-buffer's filtered ones
                 cover = o["tri_id"] >= 0
                 n = cover.sum().clamp(min=1).double() * 3.0
@@ -310,19 +335,44 @@ def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, info
                     if b == B:
                         files.append(os.path.join(base, "%s_raytraced_diffuse.png" % ci.image_name))
                         wr.submit([image_writer.Image(files[-1], plane)])
+                if reflect:  # the glossy lobe of every covered pixel, composed as the shade composes its cube lookup
+                    r = tracer.reflections(o["pos"], o["normal"], o["roughness"], c["viewmatrix"], c["campos"], cover, "world",
+                                           bounces=B, rays=args.reflection_rays, levels=args.roughness_levels, cube=glossy_sky)
+                    reflect_report = r["report"]
+                    rows3 = lambda x: x.reshape(3, -1).t().contiguous()  # noqa: E731
+                    H, W = cover.shape
+                    spec = mesh_render.compose_reflections(
+                        r["normals"], r["views"], r["roughness"], rows3(r["specular"]), rows3(o["albedo"]),
+                        o["metallic"].reshape(-1).contiguous() if args.metallic else None, r["mask"], brdf_lut=lut)
+                    spec = spec.t().reshape(3, H, W).contiguous()
+                    plane = pipeline.linear_to_srgb(spec)
+                    row["specular", B] = psnr(plane.nan_to_num().clamp(0, 1).double(), shaded[4].nan_to_num().clamp(0, 1).double())
+                    diffuse = o["albedo"] * (1.0 - o["metallic"]) * t["irradiance"]  # t: the pass of b == B, the last one
+                    spec_files.append(os.path.join(base, "%s_raytraced_specular.png" % ci.image_name))
+                    full_files.append(os.path.join(base, "%s_raytraced.png" % ci.image_name))
+                    wr.submit([image_writer.Image(spec_files[-1], plane),
+                               image_writer.Image(full_files[-1], pipeline.linear_to_srgb((diffuse + spec).nan_to_num().clamp(0, 1)))])
                 rows.append(row)
         finally:
             for r in baked.values():
                 r.close()
     keys = {"psnr_%s_bounces_%d" % (k, b): (k, b) for k in ("screen", "baked") for b in which}
+    if reflect:
+        keys["psnr_specular_screen_bounces_%d" % B] = ("specular", B)
     views = [dict(image_name=r["image_name"], pixels_covered=int(r["pixels"]), **{name: float(r[kb]) for name, kb in keys.items()})
              for r in rows]
     cmp = dict(mesh=mesh_path, bounces=B, sky_res=int(args.sky_res), rays=int(args.ao_rays), light_rays=int(args.light_rays),
                light=bake, tracer=report, views=views, average={k: sum(v[k] for v in views) / len(views) for k in keys})
+    if reflect:
+        cmp.update(reflection_rays=int(args.reflection_rays), roughness_levels=int(args.roughness_levels),
+                   reflection_sky_res=int(args.reflection_sky_res), reflections=reflect_report)
     path = os.path.join(base, "raytraced_vs_screen.json")
     with open(path, "w") as f:
         json.dump(cmp, f, indent=4)
-    return dict(raytraced_vs_screen_json=path, raytraced_vs_screen=cmp["average"], raytraced_diffuse=files)
+    res = dict(raytraced_vs_screen_json=path, raytraced_vs_screen=cmp["average"], raytraced_diffuse=files)
+    if reflect:
+        res.update(raytraced_specular=spec_files, raytraced=full_files)
+    return res
 
 
 def lights_paths(base: str, image_name: str, n_lights: int, shadows: bool) -> Dict:

@@ -1033,6 +1033,64 @@ int gigs_mesh_gather_points(int n_vertices, int n_faces, const float* vertices, 
                             double ao_distance, double max_distance, double bias, int sky_res, const float* sky,
                             const float* radiosity, int* hits, float* occlusion, float* irradiance, float* indirect,
                             unsigned long long* counts, int* overflow, void* stream);
+/* Ray-traced reflections per point (gigs-hip extension; the device half of mesh.reflect_points and
+ * mesh_render.compose_reflections): the SPECULAR counterpart of the section above.  For the points of "Ray-traced light per
+ * point", each with a view direction and a roughness, a GGX lobe of rays about the mirror direction is traced against the
+ * mesh: the radiance the lobe brings (the first sum of the split-sum approximation, Karis 2013: the n.l-weighted mean over
+ * half vectors drawn from the GGX distribution, here about the TRUE view direction and not under n = v = r), its share from
+ * the mesh, and the open share of the lobe.  The conventions are that section's: DEVICE arrays except `lo` and `dims`, no
+ * synchronisation, no allocation, float64 on the float32 inputs, + - * / only, no sqrt, no float atomics:
+ * tests/mesh_reflect_ref.py reproduces every bit in numpy.
+ *   1 Table.  directions [L, K, R, 3] float32: GGX-distributed HALF vectors in the tangent frame (z the normal), L = n_levels
+ *     in [1, 64] roughness levels of K rotations of R rows (mesh.ggx_directions computes it on the host).
+ *   2 Points.  points, normals, views [N, 3], roughness [N] float32; mask [N] uint8 or NULL.  Point q with mask[q] == 0 is
+ *     MASKED (counts[6] += 1); otherwise a point that fails the no_normal rule of "Baking occlusion", 8 counts as no_normal
+ *     (counts[4] += 1); otherwise, with v = views[q] (pointing from the surface TOWARDS the eye), a point whose v is not
+ *     finite or has dot(v, v) outside [1 - 2^-10, 1 + 2^-10] counts as no_view (counts[5] += 1).  Such a point gets
+ *     specular = reflected = 0, visibility = 1, valid = blocked = 0; its rays are in no other counter.
+ *   3 Frame.  "Baking occlusion", 8, by the same code: the rotation k = mix((seed 2^32 + q) mod 2^64) mod K, the basis (T, B)
+ *     of the point's normal n, the origin o = p + bias n.  The level is lev = min(L - 1, floor(roughness[q] L)), 0 for a NaN
+ *     or a negative product; lane i of chunk j reads row (lev, k, 64 j + i) = (x, y, z).
+ *   4 Rays.  h = (x T + y B) + z n per component;  vh = dot(v, h);  l_c = (2 vh) h_c - v_c;  w = dot(n, l).  The ray is
+ *     VALID iff vh > 0 && w > 0; otherwise it is BELOW THE HORIZON (counts[3] += 1), is not traversed and adds +0.0 to every
+ *     sum.  l is not normalised.
+ *   5 Classification.  A valid ray (o, l) is traversed as in "Baking occlusion", 2 to 7 with t_max = max_distance (+inf: no
+ *     limit) and classified as in "Baking light", 2: a miss, a FRONT hit (dot(l, n_g) < 0) or a BACK hit.
+ *     counts[0..2] = misses, front hits, back hits.
+ *   6 Radiance.  c of a miss is the sky texel of l ("Baking light", 3); of a front hit (b0 Q[i0] + b1 Q[i1]) + b2 Q[i2] with
+ *     the float32-rounded weights of "Ray-traced light per point", 6 (0 if radiosity == NULL); of a back hit 0.
+ *   7 Sums.  Lane i adds, for its rows in ascending chunk order from 0.0:  S_c += w c;  S_front_c += w c at a front hit (+0.0
+ *     otherwise);  W += w;  W_miss += w at a miss (+0.0 otherwise).  All eight go through the butterfly of "Baking light", 5.
+ *     specular[q] = float32(S / W), reflected[q] = float32(S_front / W) per channel, visibility[q] = float32(W_miss / W);
+ *     W == 0 (no valid ray) gives 0, 0 and 1.  valid[q] = the valid rays, blocked[q] = those that hit any face.
+ *   8 No cube.  With sky == NULL, specular and reflected are not touched (pass NULL); the rays are still traversed and
+ *     classified, for visibility, valid, blocked and the counters: specular occlusion alone.
+ * gigs_mesh_reflect_points, one one-wave block per row of `order` [N] int64 (the points sorted by cell, or NULL); counts [7]
+ *   uint64 (cleared inside the call) = misses, front hits, back hits, rays below the horizon, no_normal points, no_view points,
+ *   masked points.  sky_res = n in [1, 4096] when sky is given.  n_points == 0 launches nothing.
+ * An order row, a cell_start entry, a pair key or a face index outside its range sets *overflow (cleared by the caller) and
+ *   the wave stores nothing.
+ * gigs_reflect_compose turns a radiance into the shade's specular_rgb, float32, one thread per point, no atomics: the lines
+ *   of gigs_shade_fwd's specular term restated, every product and sum rounded on its own, in this order:
+ *     nov = min(max((n_y v_y + n_z v_z) + n_x v_x, 1e-4), 1)
+ *     fu = nov lut_w - 0.5, fv = roughness lut_h - 0.5;  tu = fu - floor(fu), tv = fv - floor(fv);  x0, x1 = floor(fu),
+ *     floor(fu) + 1 and y0, y1 likewise, each clamped to the table;  lut [lut_h, lut_w, 2]
+ *     fg = ((lut[y0,x0] (1-tu)(1-tv) + lut[y0,x1] tu (1-tv)) + lut[y1,x0] (1-tu) tv) + lut[y1,x1] tu tv
+ *     F0_c = (1 - m) 0.04 + albedo_c m  (metallic == NULL: 0.04, and albedo is not read)
+ *     specular_rgb_c = s_c (F0_c fg.x + fg.y),  s_c = radiance_c, or radiance_c visibility[q] when visibility is given
+ *   normals, views, albedo, radiance, specular_rgb [N, 3], roughness, metallic, visibility [N] float32, mask [N] uint8 or
+ *   NULL: a point with mask[q] == 0 gets 0. */
+int gigs_mesh_reflect_points(int n_vertices, int n_faces, const float* vertices, const int* faces, const float* lo, double cell,
+                             const int* dims, const long long* cell_start, const long long* pair_keys, long long n_pairs,
+                             double scale, int n_points, const float* points, const float* normals, const float* views,
+                             const float* roughness, const unsigned char* mask, const long long* order, const float* directions,
+                             int n_levels, int n_rays, int n_rotations, unsigned long long seed, double max_distance, double bias,
+                             int sky_res, const float* sky, const float* radiosity, float* specular, float* reflected,
+                             float* visibility, int* valid, int* blocked, unsigned long long* counts, int* overflow,
+                             void* stream);
+int gigs_reflect_compose(int n_points, const float* normals, const float* views, const float* albedo, const float* roughness,
+                         const float* metallic, const unsigned char* mask, const float* radiance, const float* visibility,
+                         const float* lut, int lut_w, int lut_h, float* specular_rgb, void* stream);
 /* Shadows of analytic lights (gigs-hip extension; the device half of mesh.shadow_points): for the points of "Ray-traced
  * light per point" and L point or directional lights, the share of each light's S samples that reach the point past the
  * mesh.  The conventions are that section's: DEVICE arrays except `lo` and `dims`, no synchronisation, no allocation,
