@@ -236,10 +236,11 @@ class AnalyticRelighter:
     against `tracer` (a mesh_render.RaytracedLight; None: no shadows, visibility 1) and shades.  -> {lights_diffuse,
     lights_specular [3,H,W] linear, lights_rgb [3,H,W] = clamp(diffuse + specular, 0, 1), through linear_to_srgb when `gamma`,
     shadow [L,H,W], report}; an uncovered pixel is 0 in the three images and 1 in shadow.  A traced view replays no
-    hipGraph."""
+    hipGraph.  denoise=n > 0 filters each light's visibility plane with n a-trous iterations (denoise.atrous, one channel per
+    light, the tracer's plane_distance()) before the shade; report["denoise"] lists the filter's reports.  0 changes no bit."""
     replayable = False
 
-    def __init__(self, lights, source, tracer=None, samples: int = 1, gamma: bool = True):
+    def __init__(self, lights, source, tracer=None, samples: int = 1, gamma: bool = True, denoise: int = 0):
         import mesh_render
         self.lights = parse_lights(list(lights))
         self.source, self.tracer, self.samples, self.gamma = source, tracer, int(samples), bool(gamma)
@@ -247,10 +248,14 @@ class AnalyticRelighter:
             raise TypeError("AnalyticRelighter: the tracer is a mesh_render.RaytracedLight or None")
         if not 1 <= self.samples <= mesh_ops.SHADOW_MAX_SAMPLES:
             raise ValueError("AnalyticRelighter: samples must lie in [1, %d], got %d" % (mesh_ops.SHADOW_MAX_SAMPLES, self.samples))
+        self.denoise = mesh_render.denoise_iterations("AnalyticRelighter", denoise)
+        if self.denoise and tracer is None:
+            raise ValueError("AnalyticRelighter: denoise filters traced shadows: it needs a tracer")
         self.report = None
 
     @torch.no_grad()
     def __call__(self, cam: Dict, scene) -> Dict:
+        import denoise as denoise_ops
         import mesh_render
         b = self.source(cam, scene)
         pos, mask = b["depth_pos"], b["mask_u8"]
@@ -259,8 +264,17 @@ class AnalyticRelighter:
         if self.tracer is not None:
             visibility, points, normals, m, report = self.tracer.shadows(pos, b["normals_view"], cam["viewmatrix"], mask, self.lights,
                                                                          self.samples, normal_space="view")
-            flat = visibility.reshape(L, H * W).t().contiguous()
             report = dict(report, shadows=True)
+            if self.denoise:  # one channel per light, each with its own weight; at most MAX_CHANNELS lights a call
+                reports = []
+                for l0 in range(0, L, denoise_ops.MAX_CHANNELS):
+                    chunk = visibility[l0:l0 + denoise_ops.MAX_CHANNELS]
+                    chunk, _, rep = denoise_ops.atrous(chunk, points, normals, m, None, self.denoise,
+                                                       plane_distance=self.tracer.plane_distance())
+                    visibility[l0:l0 + denoise_ops.MAX_CHANNELS] = chunk
+                    reports.append(rep)
+                report["denoise"] = reports
+            flat = visibility.reshape(L, H * W).t().contiguous()
         else:
             points, normals, m = mesh_render.prepare_points(pos, b["normals_view"], cam["viewmatrix"], mask, "view", pos.device)
             flat, visibility = None, torch.ones((L, H, W), dtype=torch.float32, device=pos.device)

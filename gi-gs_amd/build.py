@@ -21,7 +21,7 @@ LIB = os.environ.get("GIGS_LIB", os.path.join(HERE, "libgigs_hip.so"))
 SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "blend.hip", "normal_filters.hip", "gi.hip", "ssr_apply.hip", "light_filter.hip", "cube_texture.hip", "shade.hip", "stage2.hip", "image_loss.hip", "eval_metrics.hip", "adam.hip", "activations.hip", "densify.hip", "knn.hip", "lpips.hip",
            "image_out.hip", "mesh.hip", "mesh_raster.hip", "mesh_clean.hip", "mesh_simplify.hip", "mesh_distance.hip",
            "mesh_raycast.hip", "mesh_light.hip", "mesh_gather.hip", "mesh_reflect.hip", "mesh_shadow.hip", "shade_lights.hip",
-           "mesh_atlas.hip"]
+           "mesh_atlas.hip", "denoise.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17",

@@ -175,6 +175,10 @@ SIGNATURES = {
                                      _i, _f, _f, _f, _f, _i, _f, _f, _i, _i, C.c_ulonglong, C.c_double, C.c_double, _f, _f, _f, _f,
                                      C.c_void_p]),
     "gigs_shade_lights": (_i, [_i, _f, _f, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_denoise_pack": (_i, [_i, _i, _i, _i, C.POINTER(_i), _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "gigs_denoise_variance": (_i, [_i, _i, _i, _i, C.POINTER(_i), _i, _fl, _i, _fl, _f, _f, _f, C.c_void_p]),
+    "gigs_denoise_atrous": (_i, [_i, _i, _i, _i, C.POINTER(_i), _i, _i, _fl, _i, _fl, _fl, _fl, _f, _f, _f, C.c_void_p]),
+    "gigs_denoise_unpack": (_i, [_i, _i, _i, _i, C.POINTER(_i), _f, _f, _f, C.c_void_p]),
     "gigs_mesh_atlas_points": (_i, [_i, _i, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_transfer": (_i, [_i, _i, _f, _f, _i, _f, _i, _f, _f, _f, C.c_longlong, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_mesh_project": (_i, [_i, _f, _f, _fl, _fl, _i, _i, _f, _f, _f, C.c_void_p]),

@@ -45,6 +45,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+import denoise as denoise_ops
 import gigs_lib
 import mesh as mesh_ops
 import relight
@@ -581,17 +582,19 @@ class RaytracedLight:
         return prepare_points(pos_view, normal, viewmatrix, mask, normal_space, self.device)
 
     @torch.no_grad()
-    def planes(self, pos_view, normal, viewmatrix, mask, normal_space: str = "world", bounces=None) -> Dict:
+    def planes(self, pos_view, normal, viewmatrix, mask, normal_space: str = "world", bounces=None, rays=None) -> Dict:
         """prepare(), then mesh.gather_points -> {occlusion [1,H,W] float32, hits [H,W] int32, irradiance, indirect [3,H,W]
         float32 or None (no cube), points, normals, mask (the prepared arrays), report}.  bounces (None: the constructor's)
-        picks the vertex pass whose radiosity the front hits bring: irradiance is the light after that many bounces."""
+        picks the vertex pass whose radiosity the front hits bring: irradiance is the light after that many bounces.  rays
+        (None: the constructor's) as in reflections(): a converged trace of the same view for comparison."""
         points, normals, m = self.prepare(pos_view, normal, viewmatrix, mask, normal_space)
         _, H, W = pos_view.shape
         b = self.bounces if bounces is None else int(bounces)
         if b < 0 or b > self.bounces:
             raise ValueError("RaytracedLight: bounces must lie in [0, %d], got %d" % (self.bounces, b))
         radiosity = self.radiosity[b - 1] if (b > 0 and self.radiosity is not None) else None
-        light, report = mesh_ops.gather_points(points, normals, self.mesh, self.cube, radiosity, self.rays, self.ao_distance, None,
+        light, report = mesh_ops.gather_points(points, normals, self.mesh, self.cube, radiosity, self.rays if rays is None else int(rays),
+                                               self.ao_distance, None,
                                                self.bias, self.seed, self.rotations, mask=m, grid=self.grid)
         report["bounces"] = b if self.cube is not None else None
         plane3 = lambda x: None if x is None else x.t().reshape(3, H, W).contiguous()  # noqa: E731
@@ -637,6 +640,50 @@ class RaytracedLight:
                     valid=got.valid.reshape(H, W), blocked=got.blocked.reshape(H, W), points=points, normals=normals, views=views,
                     roughness=rough, mask=m, report=report)
 
+    DIFFUSE_PLANES = (("occlusion", 1), ("irradiance", 3), ("indirect", 3))
+    GLOSSY_PLANES = (("specular", 3), ("reflected", 3), ("visibility", 1))
+
+    def plane_distance(self):
+        """The denoiser's default plane_distance: 0.1 x ao_distance, a hundredth of the grid's largest extent with the default
+        ao_distance -- some pixels' spacing on a surface that fills the view, far below the gaps the tracer resolves.  None
+        for an empty mesh (denoise.atrous then takes it from the points)."""
+        return None if self.ao_distance is None or not float(self.ao_distance) > 0.0 else 0.1 * float(self.ao_distance)
+
+    @torch.no_grad()
+    def denoise(self, traced: Dict, iterations: int = denoise_ops.ITERATIONS, **kw) -> Dict:
+        """The dict planes() or reflections() returned with its traced planes filtered by ONE denoise.atrous call over the
+        prepared points, normals and mask it carries: occlusion, irradiance and indirect (groups [1, 3, 3]), or specular,
+        reflected and visibility (groups [3, 3, 1]) with the prepared roughness as a further guide; the planes a tracer without
+        a cube leaves None are left out.  The result is a copy with those planes replaced, <plane>_variance [1,H,W] added for
+        each, and denoise_report.  kw: denoise.atrous's; plane_distance defaults to self.plane_distance()."""
+        self._check()
+        if not isinstance(traced, dict) or not ("occlusion" in traced or "specular" in traced):
+            raise ValueError("RaytracedLight.denoise: takes the dict planes() or reflections() returned")
+        glossy = "specular" in traced
+        names = [(k, c) for k, c in (self.GLOSSY_PLANES if glossy else self.DIFFUSE_PLANES) if traced.get(k) is not None]
+        H, W = (int(x) for x in traced[names[0][0]].shape[-2:])
+        signal = torch.cat([traced[k].to(self.device).float().reshape(c, H, W) for k, c in names], 0)
+        kw = dict(kw)
+        kw.setdefault("plane_distance", self.plane_distance())
+        if glossy:
+            kw.setdefault("roughness", traced["roughness"])
+        filtered, variance, report = denoise_ops.atrous(signal, traced["points"], traced["normals"], traced["mask"],
+                                                        [c for _, c in names], iterations, **kw)
+        out, c0 = dict(traced), 0
+        for j, (k, c) in enumerate(names):
+            out[k] = filtered[c0:c0 + c].reshape(traced[k].shape).contiguous()
+            out[k + "_variance"] = variance[j:j + 1].contiguous()
+            c0 += c
+        out["denoise_report"] = dict(report, planes=[k for k, _ in names])
+        return out
+
+
+def denoise_iterations(what: str, n) -> int:
+    """The denoise= keyword of the traced sources: 0 (off) .. denoise.MAX_ITERATIONS a-trous iterations."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= denoise_ops.MAX_ITERATIONS:
+        raise ValueError("%s: denoise is 0 (off) or 1 to %d a-trous iterations, got %r" % (what, denoise_ops.MAX_ITERATIONS, n))
+    return int(n)
+
 
 class RaytracedGBuffer:
     """A G-buffer source around another (MeshGBuffer, relight.SplatGBuffer) whose `occlusion` plane is ray-traced against a
@@ -649,10 +696,12 @@ class RaytracedGBuffer:
     under the surface see its back (the report's back_hits show it).  reflections=True also traces the view's glossy
     reflections (RaytracedLight.reflections from the same planes, the inner roughness_map and cam's campos): `extra` gains
     raytraced_specular, raytraced_reflected (with a cube) and raytraced_specular_visibility, `reflection_report` is that
-    trace's report, and every other output is what it is without."""
+    trace's report, and every other output is what it is without.  denoise=n > 0 filters the traced planes with n a-trous
+    iterations (RaytracedLight.denoise) before they go into `occlusion` and `extra`; denoise_report and
+    reflection_denoise_report are the filter's reports.  0, the default, launches nothing and changes no bit."""
     replayable = False
 
-    def __init__(self, inner, tracer: RaytracedLight, occlusion: str = "replace", reflections: bool = False):
+    def __init__(self, inner, tracer: RaytracedLight, occlusion: str = "replace", reflections: bool = False, denoise: int = 0):
         if occlusion not in RAYTRACED_MODES:
             raise ValueError("RaytracedGBuffer: occlusion is one of %s, got %r" % (", ".join(RAYTRACED_MODES), occlusion))
         if not isinstance(tracer, RaytracedLight):
@@ -660,13 +709,17 @@ class RaytracedGBuffer:
         self.inner, self.tracer, self.occlusion = inner, tracer, occlusion
         self.metallic = inner.metallic
         self.reflections = bool(reflections)
-        self.report = self.reflection_report = None
+        self.denoise = denoise_iterations("RaytracedGBuffer", denoise)
+        self.report = self.reflection_report = self.denoise_report = self.reflection_denoise_report = None
 
     @torch.no_grad()
     def __call__(self, cam: Dict, scene) -> Dict:
         b = dict(self.inner(cam, scene))
         t = self.tracer.planes(b["depth_pos"], b["normals_view"], cam["viewmatrix"], b["mask_u8"], normal_space="view")
         self.report = t["report"]
+        if self.denoise:
+            t = self.tracer.denoise(t, self.denoise)
+            self.denoise_report = t["denoise_report"]
         inner = b["occlusion"]
         plane = t["occlusion"].to(inner.device)
         if self.occlusion == "multiply":
@@ -679,6 +732,9 @@ class RaytracedGBuffer:
             r = self.tracer.reflections(b["depth_pos"], b["normals_view"], b["roughness_map"], cam["viewmatrix"], cam["campos"],
                                         b["mask_u8"], normal_space="view")
             self.reflection_report = r["report"]
+            if self.denoise:
+                r = self.tracer.denoise(r, self.denoise)
+                self.reflection_denoise_report = r["denoise_report"]
             extra["raytraced_specular_visibility"] = r["visibility"]
             if r["specular"] is not None:
                 extra["raytraced_specular"], extra["raytraced_reflected"] = r["specular"], r["reflected"]

@@ -6,7 +6,7 @@ over relight.TurntableRelighter, relight.RelightEvaluator and image_writer.Image
                                       [--rotations N [--rotation_axis x y z]]
                                       [--occluder mesh.ply [--ao_rays 64 --ao_distance D --ray_bias B
                                        --occluder_mode replace|multiply]]
-                                      [--lights lights.json [--shadow_samples S]]
+                                      [--lights lights.json [--shadow_samples S]] [--denoise N]
     relight_scene(args) -> {split: {...}}
 
 Flags and defaults are relight.py's (:340-356), with --hdri taking one or more maps (Radiance .hdr or .npy [H,W,3]): all
@@ -31,7 +31,9 @@ and its 400 x 400 resize target (the ground truth is resized to the prediction's
 view's pixels against that mesh in place of SSAO (mesh_render.RaytracedGBuffer over relight.SplatGBuffer: --ao_rays rays a
 pixel, a multiple of 64, within --ao_distance, started --ray_bias off the surface; both default as mesh.bake_occlusion's), so
 geometry the view does not see occludes too; --occluder_mode multiply shades with the product of both.  The occlusion PNG is
-then that plane, and the split's result holds the last view's tracer report as `occluder`.
+then that plane, and the split's result holds the last view's tracer report as `occluder`.  --denoise N (1 to 5, needs
+--occluder) filters the traced occlusion -- and the shadow planes of --lights -- with N iterations of denoise.atrous before they
+are used; the result then holds the filter's report as `occluder_denoise`, and lights_report.json gains "denoise".
 
 --lights lights.json also renders every view under the point and directional lights of that file (analytic_lights.py states
 its format): <image_name>_lights.png, analytic_lights.AnalyticRelighter's lights_rgb over the splats' G-buffer, beside the
@@ -116,6 +118,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="shade with the traced occlusion, or with its product with SSAO")
     p.add_argument("--lights", type=str, default=None, help="a JSON list of point and directional lights: also render under them")
     p.add_argument("--shadow_samples", type=int, default=1, help="shadow samples per light in [1, 64] (needs --occluder)")
+    p.add_argument("--denoise", type=int, default=0,
+                   help="a-trous iterations (1 to 5) over the traced occlusion and shadow planes (needs --occluder)")
     return p
 
 
@@ -127,9 +131,14 @@ def check_occluder(args: Namespace) -> bool:
     """Whether --occluder is given; refuses the tracer's flags without it and values outside their ranges."""
     rays, mode = int(getattr(args, "ao_rays", 64)), getattr(args, "occluder_mode", "replace")
     distance, bias = getattr(args, "ao_distance", None), getattr(args, "ray_bias", None)
+    n = getattr(args, "denoise", 0) or 0
+    if not 0 <= int(n) <= 5:
+        raise ValueError("--denoise: 1 to 5 a-trous iterations (0: off), got %r" % (n,))
     if not getattr(args, "occluder", None):
         if rays != 64 or distance is not None or bias is not None or mode != "replace":
             raise ValueError("--ao_rays, --ao_distance, --ray_bias and --occluder_mode need --occluder")
+        if int(n):
+            raise ValueError("--denoise needs --occluder: it filters ray-traced planes")
         return False
     if mode not in OCCLUDER_MODES:
         raise ValueError("--occluder_mode: one of %s, got %r" % (", ".join(OCCLUDER_MODES), mode))
@@ -170,6 +179,7 @@ def lights_split(args: Namespace, split: str, infos, g, sh_degree: int, iteratio
     os.makedirs(base, exist_ok=True)
     gi = {k: getattr(args, k) for k in rs.GI_FLAGS}
     shadows, S = bool(getattr(args, "occluder", None)), int(args.shadow_samples)
+    n_denoise = int(getattr(args, "denoise", 0) or 0) if shadows else 0
     views, files = [], []
     with image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
         tracer = None
@@ -178,7 +188,8 @@ def lights_split(args: Namespace, split: str, infos, g, sh_degree: int, iteratio
             path = args.occluder if os.path.isabs(args.occluder) or os.path.exists(args.occluder) else os.path.join(out, args.occluder)
             tracer = mesh_render.RaytracedLight(path, bias=args.ray_bias, device=dev)
         try:
-            relighter = analytic_lights.AnalyticRelighter(lights, relight.SplatGBuffer(gi, sh_degree, args.metallic), tracer, S, gamma=True)
+            relighter = analytic_lights.AnalyticRelighter(lights, relight.SplatGBuffer(gi, sh_degree, args.metallic), tracer, S, gamma=True,
+                                                          denoise=n_denoise)
             for ci in infos:
                 c = dr.camera_from_info(ci, args.resolution, device=dev)
                 o = relighter(c, g)
@@ -192,7 +203,8 @@ def lights_split(args: Namespace, split: str, infos, g, sh_degree: int, iteratio
             if tracer is not None:
                 tracer.close()
     path = os.path.join(base, "lights_report.json")
-    render_mesh.write_lights_report(path, lights, shadows, S, views, occluder=getattr(args, "occluder", None))
+    render_mesh.write_lights_report(path, lights, shadows, S, views, occluder=getattr(args, "occluder", None),
+                                    **(dict(denoise=n_denoise) if n_denoise else {}))
     return dict(report_json=path, files=files, shadows=shadows, views=views)
 
 
@@ -238,7 +250,8 @@ def relight_split(args: Namespace, split: str, infos, g, sh_degree: int, lights,
             import mesh_render
             path = args.occluder if os.path.isabs(args.occluder) or os.path.exists(args.occluder) else os.path.join(out, args.occluder)
             tracer = mesh_render.RaytracedLight(path, rays=args.ao_rays, ao_distance=args.ao_distance, bias=args.ray_bias, device=dev)
-            source = mesh_render.RaytracedGBuffer(relight.SplatGBuffer(gi, sh_degree, args.metallic), tracer, args.occluder_mode)
+            source = mesh_render.RaytracedGBuffer(relight.SplatGBuffer(gi, sh_degree, args.metallic), tracer, args.occluder_mode,
+                                                  denoise=int(getattr(args, "denoise", 0) or 0))
         tr = relight.TurntableRelighter(lights, gi, sh_degree, metallic=args.metallic, tone=args.tone, gamma=args.gamma,
                                         brdf_lut=lut, source=source)  # build_mips per light (:141)
         ev = relight.RelightEvaluator(names, device=dev, lpips=lp) if args.gt_dir else None
@@ -274,6 +287,8 @@ def relight_split(args: Namespace, split: str, infos, g, sh_degree: int, lights,
             tr.close()
             if tracer is not None:
                 res["occluder"] = source.report
+                if source.denoise:
+                    res["occluder_denoise"] = source.denoise_report
                 tracer.close()
     res.update(files=wr.files, png_bytes=wr.bytes_written, submit_blocked_s=round(wr.blocked_s, 4),
                total_s=round(time.perf_counter() - t0, 4))

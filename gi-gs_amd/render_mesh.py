@@ -7,6 +7,7 @@ its scene (mesh_render.py), and compared with the splat render it came from or w
                                     [--lighting baked|raytraced [--bounces 1] [--sky_res 32] [--light_rays 256]]
                                     [--reflections [--reflection_rays 64] [--roughness_levels 16] [--reflection_sky_res 128]]
                                     [--occlusion raytraced] [--ao_rays 64] [--ao_distance D] [--ray_bias B]
+                                    [--denoise N [--denoise_reference_rays R]]
                                     [--lights lights.json [--shadow_samples S] [--no_shadows]]                   (CLI)
     render_mesh(args) -> {...}                                                                                   (API)
 
@@ -67,6 +68,15 @@ analytic_lights.AnalyticRelighter's lights_rgb after linear_to_srgb, <image_name
 --shadow_samples S samples a light (1: hard shadows), started --ray_bias off the surface; --no_shadows leaves the lights
 unshadowed and writes no shadow images.  mesh_<split>/lights_report.json echoes the lights and holds the counters of every
 view.  Without --lights nothing of this runs.
+
+--denoise N (1 to 5) filters every ray-traced plane with N iterations of the edge-avoiding a-trous filter (denoise.atrous,
+guided by the traced points and normals) before it is used: the occlusion of --occlusion raytraced, the occlusion, irradiance,
+indirect and -- with --reflections -- specular, reflected and visibility planes of --lighting raytraced, and the shadow planes
+of --lights.  raytraced_vs_screen.json gains "denoise" (the filter's reports of the last view) and psnr_denoised_* (the
+comparisons above of the filtered planes, which are the ones written; psnr_* stay those of the raw planes) and lights_report.json gains
+"denoise" (N) and, per view, the filter's reports.  --denoise_reference_rays R (with --lighting raytraced) traces every view once
+more at R rays and adds, per view and plane, the RMSE over the covered pixels of the raw and of the filtered plane against
+it.  Without --denoise every file and every JSON is what it was.
 """
 from __future__ import annotations
 
@@ -122,6 +132,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lights", type=str, default=None, help="a JSON list of point and directional lights: also render under them")
     p.add_argument("--shadow_samples", type=int, default=1, help="shadow samples per light in [1, 64]; 1: hard shadows")
     p.add_argument("--no_shadows", action="store_true", help="--lights without ray-traced shadows")
+    p.add_argument("--denoise", type=int, default=0,
+                   help="a-trous iterations (1 to 5) over the ray-traced planes of --occlusion raytraced, --lighting raytraced and --lights")
+    p.add_argument("--denoise_reference_rays", type=int, default=0,
+                   help="--lighting raytraced --denoise: trace every view once more at this many rays and write the RMSE of the raw and "
+                        "of the filtered planes against it")
     return p
 
 
@@ -209,7 +224,24 @@ def _check(args: Namespace) -> int:
         x = getattr(args, "ray_bias", None)
         if x is not None and not (0.0 <= float(x) < float("inf")):
             raise ValueError("--ray_bias: finite and >= 0, got %r" % (x,))
+    n, ref = getattr(args, "denoise", 0) or 0, getattr(args, "denoise_reference_rays", 0) or 0
+    if not 0 <= int(n) <= 5:
+        raise ValueError("--denoise: 1 to 5 a-trous iterations (0: off), got %r" % (n,))
+    traced_lights = bool(getattr(args, "lights", None)) and not getattr(args, "no_shadows", False)
+    if int(n) and not (lighting == "raytraced" or occlusion == "raytraced" or traced_lights):
+        raise ValueError("--denoise filters ray-traced planes: it needs --occlusion raytraced, --lighting raytraced or shadowed --lights")
+    if int(ref):
+        if not int(n) or lighting != "raytraced":
+            raise ValueError("--denoise_reference_rays needs --denoise and --lighting raytraced")
+        if int(ref) < 64 or int(ref) > 1024 or int(ref) % 64 != 0:
+            raise ValueError("--denoise_reference_rays: a multiple of 64 in [64, 1024], got %d" % int(ref))
     return n_rot
+
+
+def _rmse(x, y, cover) -> float:
+    """The root mean square difference of two [C,H,W] planes over the covered pixels, in float64."""
+    d = (x.double() - y.double()).nan_to_num() * cover
+    return float(((d * d).sum() / (cover.sum().clamp(min=1).double() * x.shape[0])).sqrt())
 
 
 def shade_frame_sky(light, res: int):
@@ -305,6 +337,8 @@ def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, info
     rows, files, report = [], [], None
     reflect = bool(getattr(args, "reflections", False))
     spec_files, full_files, reflect_report = [], [], None
+    n_denoise, ref_rays = int(getattr(args, "denoise", 0) or 0), int(getattr(args, "denoise_reference_rays", 0) or 0)
+    denoise_report, denoise_rmse = {}, []
     glossy_sky = shade_frame_sky(light, args.reflection_sky_res) if reflect else None
     with mesh_render.MeshRasterizer(m, device=dev) as plain, image_writer.ImageWriter(workers=args.workers) as wr, \
             mesh_render.RaytracedLight(m, rays=args.ao_rays, ao_distance=args.ao_distance, bias=args.ray_bias, cube=sky, bounces=B,
@@ -328,10 +362,20 @@ def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, info
                 for b in which:
                     t = tracer.planes(o["pos"], o["normal"], c["viewmatrix"], cover, "world", bounces=b)
                     report = t["report"]
-                    plane = pipeline.linear_to_srgb(o["albedo"] * (1.0 - o["metallic"]) * t["irradiance"])
-                    mine = plane.nan_to_num().clamp(0, 1).double()
-                    row["screen", b] = psnr(mine, screen)
-                    row["baked", b] = psnr(mine, pipeline.linear_to_srgb(baked[b](c)["albedo"]).clamp(0, 1).double())
+                    if n_denoise:
+                        raw, t = t, tracer.denoise(t, n_denoise)
+                        denoise_report["planes"] = t["denoise_report"]
+                        if ref_rays and b == B:  # the same view at ref_rays rays: what the filter should approach
+                            ref = tracer.planes(o["pos"], o["normal"], c["viewmatrix"], cover, "world", bounces=b, rays=ref_rays)
+                            denoise_rmse.append(dict(image_name=ci.image_name, **{
+                                k: dict(raw=_rmse(raw[k], ref[k], cover), filtered=_rmse(t[k], ref[k], cover))
+                                for k in ("occlusion", "irradiance", "indirect")}))
+                    vertex = pipeline.linear_to_srgb(baked[b](c)["albedo"]).clamp(0, 1).double()
+                    for tag, tt in (("", raw), ("_denoised", t)) if n_denoise else (("", t),):  # the last plane is the one written
+                        plane = pipeline.linear_to_srgb(o["albedo"] * (1.0 - o["metallic"]) * tt["irradiance"])
+                        mine = plane.nan_to_num().clamp(0, 1).double()
+                        row["screen" + tag, b] = psnr(mine, screen)
+                        row["baked" + tag, b] = psnr(mine, vertex)
                     if b == B:
                         files.append(os.path.join(base, "%s_raytraced_diffuse.png" % ci.image_name))
                         wr.submit([image_writer.Image(files[-1], plane)])
@@ -339,14 +383,23 @@ def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, info
                     r = tracer.reflections(o["pos"], o["normal"], o["roughness"], c["viewmatrix"], c["campos"], cover, "world",
                                            bounces=B, rays=args.reflection_rays, levels=args.roughness_levels, cube=glossy_sky)
                     reflect_report = r["report"]
+                    if n_denoise:
+                        raw, r = r, tracer.denoise(r, n_denoise)
+                        denoise_report["reflections"] = r["denoise_report"]
+                        if ref_rays:
+                            ref = tracer.reflections(o["pos"], o["normal"], o["roughness"], c["viewmatrix"], c["campos"], cover, "world",
+                                                     bounces=B, rays=ref_rays, levels=args.roughness_levels, cube=glossy_sky)
+                            denoise_rmse[-1].update({k: dict(raw=_rmse(raw[k], ref[k], cover), filtered=_rmse(r[k], ref[k], cover))
+                                                     for k in ("specular", "reflected", "visibility")})
                     rows3 = lambda x: x.reshape(3, -1).t().contiguous()  # noqa: E731
                     H, W = cover.shape
-                    spec = mesh_render.compose_reflections(
-                        r["normals"], r["views"], r["roughness"], rows3(r["specular"]), rows3(o["albedo"]),
-                        o["metallic"].reshape(-1).contiguous() if args.metallic else None, r["mask"], brdf_lut=lut)
-                    spec = spec.t().reshape(3, H, W).contiguous()
-                    plane = pipeline.linear_to_srgb(spec)
-                    row["specular", B] = psnr(plane.nan_to_num().clamp(0, 1).double(), shaded[4].nan_to_num().clamp(0, 1).double())
+                    for tag, rr in (("", raw), ("_denoised", r)) if n_denoise else (("", r),):  # the last plane is the one written
+                        spec = mesh_render.compose_reflections(
+                            rr["normals"], rr["views"], rr["roughness"], rows3(rr["specular"]), rows3(o["albedo"]),
+                            o["metallic"].reshape(-1).contiguous() if args.metallic else None, rr["mask"], brdf_lut=lut)
+                        spec = spec.t().reshape(3, H, W).contiguous()
+                        plane = pipeline.linear_to_srgb(spec)
+                        row["specular" + tag, B] = psnr(plane.nan_to_num().clamp(0, 1).double(), shaded[4].nan_to_num().clamp(0, 1).double())
                     diffuse = o["albedo"] * (1.0 - o["metallic"]) * t["irradiance"]  # t: the pass of b == B, the last one
                     spec_files.append(os.path.join(base, "%s_raytraced_specular.png" % ci.image_name))
                     full_files.append(os.path.join(base, "%s_raytraced.png" % ci.image_name))
@@ -359,6 +412,9 @@ def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, info
     keys = {"psnr_%s_bounces_%d" % (k, b): (k, b) for k in ("screen", "baked") for b in which}
     if reflect:
         keys["psnr_specular_screen_bounces_%d" % B] = ("specular", B)
+    plain_keys = dict(keys)
+    if n_denoise:  # the same comparisons of the filtered planes, beside those of the raw ones
+        keys.update({name.replace("psnr_", "psnr_denoised_", 1): (k + "_denoised", b) for name, (k, b) in plain_keys.items()})
     views = [dict(image_name=r["image_name"], pixels_covered=int(r["pixels"]), **{name: float(r[kb]) for name, kb in keys.items()})
              for r in rows]
     cmp = dict(mesh=mesh_path, bounces=B, sky_res=int(args.sky_res), rays=int(args.ao_rays), light_rays=int(args.light_rays),
@@ -366,6 +422,10 @@ def render_raytraced(args: Namespace, mesh_path: str, light, gi: Dict, lut, info
     if reflect:
         cmp.update(reflection_rays=int(args.reflection_rays), roughness_levels=int(args.roughness_levels),
                    reflection_sky_res=int(args.reflection_sky_res), reflections=reflect_report)
+    if n_denoise:
+        cmp["denoise"] = dict(iterations=n_denoise, **denoise_report)
+        if ref_rays:
+            cmp["denoise"].update(reference_rays=ref_rays, rmse=denoise_rmse)
     path = os.path.join(base, "raytraced_vs_screen.json")
     with open(path, "w") as f:
         json.dump(cmp, f, indent=4)
@@ -400,12 +460,14 @@ def render_lights(args: Namespace, mesh_path: str, gi: Dict, infos, dev, out: st
     import mesh_render
     lights = analytic_lights.load_lights(args.lights)
     shadows, S = not args.no_shadows, int(args.shadow_samples)
+    n_denoise = int(getattr(args, "denoise", 0) or 0) if shadows else 0
     base = os.path.join(out, "mesh_" + args.split)
     views, files = [], []
     with open_mesh(mesh_path, dev) as rast, image_writer.ImageWriter(workers=args.workers) as wr, torch.no_grad():
         tracer = mesh_render.RaytracedLight(mesh_render.occluder_mesh(rast), bias=args.ray_bias, device=dev) if shadows else None
         try:
-            relighter = analytic_lights.AnalyticRelighter(lights, mesh_render.MeshGBuffer(gi, args.metallic), tracer, S, gamma=True)
+            relighter = analytic_lights.AnalyticRelighter(lights, mesh_render.MeshGBuffer(gi, args.metallic), tracer, S, gamma=True,
+                                                          denoise=n_denoise)
             for ci in infos:
                 c = dr.camera_from_info(ci, args.resolution, device=dev)
                 o = relighter(c, rast)
@@ -419,7 +481,7 @@ def render_lights(args: Namespace, mesh_path: str, gi: Dict, infos, dev, out: st
             if tracer is not None:
                 tracer.close()
     path = os.path.join(base, "lights_report.json")
-    write_lights_report(path, lights, shadows, S, views, mesh=mesh_path)
+    write_lights_report(path, lights, shadows, S, views, mesh=mesh_path, **(dict(denoise=n_denoise) if n_denoise else {}))
     return dict(lights_report_json=path, lights_files=files, lights_views=views)
 
 
@@ -444,7 +506,7 @@ def mesh_relighter(lights, gi: Dict, args: Namespace, lut, rast, occlusion: str,
                                                   brdf_lut=lut, occlusion=occlusion), None
     tracer = mesh_render.RaytracedLight(mesh_render.occluder_mesh(rast), rays=args.ao_rays, ao_distance=args.ao_distance,
                                         bias=args.ray_bias, device=dev)
-    source = mesh_render.RaytracedGBuffer(mesh_render.MeshGBuffer(gi, args.metallic), tracer)
+    source = mesh_render.RaytracedGBuffer(mesh_render.MeshGBuffer(gi, args.metallic), tracer, denoise=int(getattr(args, "denoise", 0) or 0))
     return relight.TurntableRelighter(lights, gi, 0, metallic=args.metallic, tone=args.tone, gamma=args.gamma, brdf_lut=lut,
                                       source=source), tracer
 

@@ -1149,6 +1149,63 @@ int gigs_mesh_shadow_points(int n_vertices, int n_faces, const float* vertices, 
 int gigs_shade_lights(int n_points, const float* points, const float* normals, const unsigned char* mask, const float* albedo,
                       const float* roughness, const float* metallic, const float* campos, int n_lights, const float* lights,
                       const float* radiance, const float* visibility, float* diffuse, float* specular, void* stream);
+/* Denoising ray-traced planes (gigs-hip extension; the device half of denoise.atrous): an edge-avoiding a-trous wavelet
+ * filter in the manner of Dammertz 2010 and SVGF, single frame, over the planes the per-pixel tracers return, guided by
+ * their prepared points and normals.  DEVICE arrays except `groups`, no synchronisation, no allocation, no atomics.
+ * float32, + - * / only, built with -ffp-contract=off: every product and sum below is rounded on its own, in the order the
+ * brackets give.  No exp, pow or sqrt: every edge-stopping function is a polynomial of compact support, so a weight across a
+ * real edge is exactly 0 and tests/denoise_ref.py reproduces every bit in numpy float32.  max(a, b) is (a > b) ? a : b.
+ *   1 Inputs.  signal [C, H, W] float32, 1 <= C <= GIGS_DENOISE_MAX_CHANNELS.  groups [G] int (HOST): channel counts, each 1
+ *     or 3, summing to C; the channels of a group are consecutive and share one weight.  The VALUE of a group at a pixel is
+ *     y = x_0, or (x_0 + x_1) + x_2.  points, normals [H W, 3] float32 and mask [H W] uint8 are the prepared arrays of
+ *     "Ray-traced light per point", row-major over the pixels; roughness [H W] float32 or NULL.
+ *   2 Live pixels.  A pixel is LIVE iff its mask is non-zero and its 6 guide components, its roughness (if given) and its C
+ *     signal values are all finite (|v| <= FLT_MAX).  A pixel that is not live keeps the bits of its input, is skipped as
+ *     a tap everywhere, and has variance 0.
+ *   3 Geometry weight of tap q seen from centre p (P the point, N the normal, r the roughness):
+ *       c   = (Np.x Nq.x + Np.y Nq.y) + Np.z Nq.z;  c = max(c, 0);  then c = c c, e times    (normal_power = 2^e, 0 <= e <= 7)
+ *       d   = ((Pq.x - Pp.x) Np.x + (Pq.y - Pp.y) Np.y) + (Pq.z - Pp.z) Np.z         (q's distance from p's tangent plane)
+ *       z   = max(1 - (d d) inv_plane2, 0)                   (inv_plane2 = float32(1 / plane_distance^2), made on the host)
+ *       g   = c (z z)
+ *       with a roughness guide:  t = rq - rp;  u = max(1 - (t t) inv_rough2, 0);  g = g (u u)
+ *   4 Launch A, the variance (gigs_denoise_variance).  For a live pixel p and each group, over the live taps q of the 5 x 5
+ *     window of step 1 that lie inside the image, in row-major order, every sum started at 0:
+ *       G = sum g;   T = sum (g (y_q - y_p));   if !(G > 0): var = 0, else
+ *       m = y_p + T / G;   U = sum (g ((y_q - m) (y_q - m)));   var = U / G
+ *     Two passes, not E[y^2] - m^2, and the mean in the difference form of 5: (sum g y_q) / G of a constant y is y only up to
+ *     rounding, y_p + 0 / G is y, so a constant signal has variance exactly 0.  (G = 0 needs a centre whose normal has no
+ *     length: such a pixel weighs nothing.)
+ *   5 Launches B_i, i = 0 .. n - 1 (gigs_denoise_atrous), step s = 2^i <= GIGS_DENOISE_MAX_STEP.  Taps at the offsets
+ *     {-2s, -s, 0, s, 2s} in y (outer) and x (inner), h = (1/16, 1/4, 3/8, 1/4, 1/16); taps outside the image and taps that
+ *     are not live are skipped, the centre is a tap.  For a live pixel p and group j, sums started at 0, taps row-major:
+ *       r     = 1 / (sigma_l2 var_p + eps)                  (eps > 0; sigma_l2 = 0 with eps = +inf gives r = 0: the signal
+ *                                                            weight is off)
+ *       delta = y_q - y_p;   l = max(1 - (delta delta) r, 0);   w = ((h[dy] h[dx]) g) (l l)
+ *       Wsum += w;   D_c += w (x_q,c - x_p,c) for each channel c of the group;   V += (w w) var_q
+ *       if Wsum > 0:  x'_p,c = x_p,c + D_c / Wsum,  var'_p = V / (Wsum Wsum);   otherwise x' = x and var' = var.
+ *     The difference form returns a constant signal with its own bits.  `/` is the correctly rounded float32 division.
+ *   6 Layout.  gigs_denoise_pack writes pixel-major records: guide [H W, 8] float32 = (P, N, roughness or 0, live ? 1 : 0)
+ *     and record [H W, S] float32, S = 4 ceil((C + G) / 4) = (the C values, G variances (0), padding (0)).
+ *     gigs_denoise_variance and gigs_denoise_atrous read one record array and write ANOTHER (record_in != record_out; the
+ *     caller owns the ping-pong pair); gigs_denoise_unpack writes filtered [C, H, W] and variance [G, H, W] from a record
+ *     array.  The filter launches take 16 x 16 pixels of one sub-lattice (x mod s, y mod s) per 256-thread block and stage the
+ *     20 x 20 records around them in 400 (8 + S) 4 <= 64000 bytes of LDS.  Nothing outside [0, H) x [0, W) is read.
+ * H W = 0 launches nothing.  Refused: C, G or a group outside its range, groups that do not sum to C, H W > 2^31 - 1, e
+ *   outside [0, 7], a step that is no power of two in [1, GIGS_DENOISE_MAX_STEP], inv_plane2, inv_rough2 or sigma_l2 negative,
+ *   NaN or infinite, eps <= 0 or NaN, record_in == record_out, a NULL array. */
+#define GIGS_DENOISE_MAX_CHANNELS 16
+#define GIGS_DENOISE_MAX_STEP 16
+int gigs_denoise_pack(int width, int height, int channels, int n_groups, const int* groups, const float* signal,
+                      const float* points, const float* normals, const unsigned char* mask, const float* roughness,
+                      float* guide, float* record, void* stream);
+int gigs_denoise_variance(int width, int height, int channels, int n_groups, const int* groups, int normal_exponent,
+                          float inv_plane2, int use_roughness, float inv_rough2, const float* guide, const float* record_in,
+                          float* record_out, void* stream);
+int gigs_denoise_atrous(int width, int height, int channels, int n_groups, const int* groups, int step, int normal_exponent,
+                        float inv_plane2, int use_roughness, float inv_rough2, float sigma_l2, float eps, const float* guide,
+                        const float* record_in, float* record_out, void* stream);
+int gigs_denoise_unpack(int width, int height, int channels, int n_groups, const int* groups, const float* record, float* filtered,
+                        float* variance, void* stream);
 /* Texturing meshes (gigs-hip extension; the device half of mesh.bake_atlas / mesh.transfer_attributes): the per-vertex
  * channels of a heavy SOURCE mesh stored in the texels of an atlas over a light TARGET mesh.  Every texel of the atlas gets
  * the point of the target's surface it stands for (gigs_mesh_atlas_points), the search of "Comparing meshes" finds the
