@@ -7,9 +7,14 @@
 //   SpecularCubemapFwd/BwdKernel         RU/cubemap.cu:246-350
 //
 // MI355X design
-//   * the cubemap-filter backward passes are GATHERS, not the reference's atomic scatters: the
-//     GGX window test dot(L, V) >= cutoff is symmetric in (L, V), so the set of outputs that
-//     touch a texel is that texel's own window; same terms, no atomics, reproducible sums;
+//   * the cubemap-filter backward passes are GATHERS, not the reference's atomic scatters, wherever the
+//     set of outputs that touch a texel is that texel's own window: same terms, no atomics,
+//     reproducible sums.  The cone test dot(L, V) >= cutoff is symmetric in (L, V); the ACCEPTED set is
+//     not everywhere: a pair also needs the input inside the output's per-face AABB, and the bounds'
+//     corner-only tile cull (restated from the reference on purpose) drops in-cone texels at small
+//     resolutions, e.g. (16, 0.22), (9, 0.3), (7, 0.4).  Whether a (resolution, cutoff) is symmetric is
+//     decided once and cached (window_symmetric); an asymmetric level's backward is the transpose in
+//     scatter form, float atomics over each output's window (the *_scatter kernels below);
 //   * pixel-invariant tables (solid angle per texel) are built once on the host with libm and
 //     cached per device.  That cache is this file's only mutable state.
 #include <cmath>
@@ -167,15 +172,16 @@ __device__ __forceinline__ v3 normalize_exact(v3 v) {
 }
 
 // forward: out[o] = (sum_in tex[in] w, sum w) over in in window(o)
-// backward (gather over the same, symmetric, window): g_in[i] = sum_o g[o].rgb * w(o, i)
-// forward: out[o] = (sum_in tex[in] w, sum w) over in in window(o)
-// backward (gather over the same window, which is symmetric because the test dot(L, V) >= cutoff
-// is): g_in[i] = sum_o g[o].rgb * w(o, i).
+// backward: g_in[i] = sum_o g[o].rgb * w(o, i) over the outputs o whose window accepts i.
+//   kBackward (gather): texel i sums over its OWN window with the roles exchanged -- the same set only where the
+//     accepted set is symmetric (see the header; the host launches it for such levels only);
+//   kScatter: the wave of output o walks o's window as the forward does and adds g[o].rgb * w(o, i) into dst[i]
+//     (zeroed by the host) with float atomics: the transpose whatever the bounds are.
 // Per accepted pair H = safeNormalize(L + V), c = V.H and d = (c a^2 - c) c + 1 are the reference's
 // own IEEE sequence (RU/cubemap.cu:174-179, 270-277) on the cached unit directions.  This matters: d = 1 - c^2 (1 - alpha^2) cancels to ~alpha^2 at the lobe centre, so a 1-ulp change of
 // c = V.H (e.g. the algebraic shortcut sqrt((1 + L.V) / 2)) moves a weight by ~1e-7 / alpha^2 --
 // 2e-3 at the roughness-0.08 level.
-template <bool kBackward>
+template <bool kBackward, bool kScatter = false>
 __global__ void __launch_bounds__(256)
 specular_cubemap_kernel(int N, const float4* __restrict__ table, const float* __restrict__ src,
                         const float* __restrict__ bounds, float roughness, float cutoff,
@@ -188,6 +194,8 @@ specular_cubemap_kernel(int N, const float4* __restrict__ table, const float* __
   const float alpha = roughness * roughness, alphaSqr = alpha * alpha;
   float wsum = 0.0f, c0 = 0, c1 = 0, c2 = 0;
   const int stride = kBackward ? 4 : 3;
+  float g0 = 0, g1 = 0, g2 = 0;
+  if (kScatter) { const float* g = src + 4 * (size_t)o; g0 = g[0]; g1 = g[1]; g2 = g[2]; }
   const float4* b4 = reinterpret_cast<const float4*>(bounds + 24 * (size_t)o);
   for (int s = 0; s < 6; ++s) {
     const float4 b = b4[s];
@@ -211,12 +219,21 @@ specular_cubemap_kernel(int N, const float4* __restrict__ table, const float* __
           const float dd = (c * alphaSqr - c) * c + 1.0f;
           const float ndf = alphaSqr / ((dd * dd) * 3.14159265358979323846f);
           const float w = wiDotN * ndf * (kBackward ? me.w : ot.w) / 4.0f;
+          if (kScatter) {
+            float* q = dst + 3 * (size_t)i;
+            const float v0 = g0 * w, v1 = g1 * w, v2 = g2 * w;
+            if (v0 != 0.0f) atomicAdd(q, v0);  // true for NaN: it reaches dst
+            if (v1 != 0.0f) atomicAdd(q + 1, v1);
+            if (v2 != 0.0f) atomicAdd(q + 2, v2);
+            continue;
+          }
           const float* t = src + (size_t)stride * i;
           c0 += t[0] * w; c1 += t[1] * w; c2 += t[2] * w;
           wsum += w;
         }
       }
   }
+  if (kScatter) return;
   c0 = wave_sum63(c0); c1 = wave_sum63(c1); c2 = wave_sum63(c2);
   if (!kBackward) wsum = wave_sum63(wsum);
   if (lane == 63) {
@@ -230,6 +247,103 @@ specular_cubemap_kernel(int N, const float4* __restrict__ table, const float* __
   }
 }
 
+// 1 -> *asymmetric if some pair (o, i) is accepted by o and not by i (i in AABB_o, o outside AABB_i; the dot product
+// is the same float both ways: the products commute and the additions keep their order).
+__global__ void __launch_bounds__(256)
+specular_symmetry_kernel(int N, const float4* __restrict__ table, const float* __restrict__ bounds, float cutoff,
+                         int* __restrict__ asymmetric) {
+  const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (o >= 6 * N * N) return;  // wave-uniform
+  const int lx = lane & 7, ly = lane >> 3;
+  const int so = o / (N * N), yo = (o / N) % N, xo = o % N;
+  const float4 me = table[o];
+  const float4* b4 = reinterpret_cast<const float4*>(bounds + 24 * (size_t)o);
+  bool bad = false;
+  for (int s = 0; s < 6; ++s) {
+    const float4 b = b4[s];
+    const int xmin = (int)b.x, xmax = (int)b.y, ymin = (int)b.z, ymax = (int)b.w;
+    if (xmin > xmax) continue;
+    for (int y = ymin + ly; y <= ymax; y += 8)
+      for (int x = xmin + lx; x <= xmax; x += 8) {
+        const int i = (s * N + y) * N + x;
+        const float4 ot = table[i];
+        if (ot.x * me.x + ot.y * me.y + ot.z * me.z >= cutoff) {
+          const float4 r = reinterpret_cast<const float4*>(bounds + 24 * (size_t)i)[so];
+          bad |= !(xo >= (int)r.x && xo <= (int)r.y && yo >= (int)r.z && yo <= (int)r.w);
+        }
+      }
+  }
+  if (bad) *asymmetric = 1;  // every writer stores the same value
+}
+
+// Whether the accepted set of (resolution, cutoff) is symmetric: 1 yes, 0 no, -1 on a HIP error.  Decided once per
+// (device, resolution, cutoff) from the library's own bounds and cached for the lifetime of the process; the first
+// query synchronises the stream (like the texel table's), so it belongs where bounds and tables are built, or to a
+// first, eager, call -- not into a graph capture.
+static std::map<std::pair<long long, uint32_t>, int> g_symmetric;
+
+static int window_symmetric(int N, float cutoff, hipStream_t s) {
+  const float4* table = texel_table(N, s);
+  int dev = 0;
+  if (!table || hipGetDevice(&dev) != hipSuccess) return -1;
+  uint32_t bits;
+  memcpy(&bits, &cutoff, sizeof bits);
+  const std::pair<long long, uint32_t> key(((long long)dev << 32) | (unsigned)N, bits);
+  std::lock_guard<std::mutex> lk(g_table_mu);
+  auto it = g_symmetric.find(key);
+  if (it != g_symmetric.end()) return it->second;
+  const int total = 6 * N * N;
+  float* bounds = nullptr;
+  int* flag = nullptr;
+  int host = 0;
+  bool ok = hipMalloc(&bounds, (size_t)24 * total * sizeof(float)) == hipSuccess && hipMalloc(&flag, sizeof(int)) == hipSuccess &&
+            hipMemsetAsync(flag, 0, sizeof(int), s) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(specular_bounds_kernel, dim3((total + 63) / 64), dim3(64), 0, s, N, cutoff, bounds);
+    hipLaunchKernelGGL(specular_symmetry_kernel, dim3((total + 3) / 4), dim3(256), 0, s, N, table, bounds, cutoff, flag);
+    ok = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  }
+  if (bounds) hipFree(bounds);
+  if (flag) hipFree(flag);
+  if (!ok) return -1;
+  return g_symmetric[key] = host ? 0 : 1;
+}
+
+// The transpose from the FORWARD table, for the levels whose accepted set is not symmetric: the wave of output o walks
+// o's runs as specular_weights_kernel laid them out and adds (w / wsum[o]) * g[o] -- w * g[o] without wsum -- into
+// dst[i] (zeroed by the host) with float atomics.  The quotient is the float the sparse scatter forms.  Such levels are
+// small (the tile cull drops texels at coarse resolutions); no tuning.
+__global__ void __launch_bounds__(256)
+specular_table_scatter_kernel(int N, const float* __restrict__ grad, int gstride, const float* __restrict__ bounds,
+                              const uint32_t* __restrict__ offsets, const float* __restrict__ W,
+                              const float* __restrict__ wsum, float* __restrict__ dst) {
+  const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (o >= 6 * N * N) return;  // wave-uniform
+  const float* g = grad + (size_t)gstride * o;
+  const float g0 = g[0], g1 = g[1], g2 = g[2];
+  const float4* b4 = reinterpret_cast<const float4*>(bounds + 24 * (size_t)o);
+  for (int s = 0; s < 6; ++s) {
+    const float4 b = b4[s];
+    const int xmin = (int)b.x, xmax = (int)b.y, ymin = (int)b.z, ymax = (int)b.w;
+    if (xmin > xmax || ymin > ymax) continue;
+    const int wd = xmax - xmin + 1, n = wd * (ymax - ymin + 1);
+    const float inv = 1.0f / (float)wd;
+    const uint32_t base = offsets[6 * (size_t)o + s];
+    for (int i = lane; i < n; i += 64) {
+      const float w = W[(size_t)base + i];
+      if (!(w >= 0.0f)) continue;  // -1 marks a candidate outside the cone
+      const int yy = (int)(((float)i + 0.5f) * inv), xx = i - yy * wd;
+      const float q = wsum ? w / wsum[o] : w;
+      float* d = dst + 3 * ((size_t)(s * N + ymin + yy) * N + xmin + xx);
+      const float v0 = q * g0, v1 = q * g1, v2 = q * g2;
+      if (v0 != 0.0f) atomicAdd(d, v0);  // true for NaN: it reaches dst
+      if (v1 != 0.0f) atomicAdd(d + 1, v1);
+      if (v2 != 0.0f) atomicAdd(d + 2, v2);
+    }
+  }
+}
 
 // ------------------------------------------------------------------------------------------
 // GGX pre-filter through a cached weight table.
@@ -1036,9 +1150,39 @@ int gigs_specular_cubemap_bwd(int res, const float* bounds, const float* grad_ou
   hipStream_t s = (hipStream_t)stream;
   const float4* table = gigs::texel_table(res, s);
   if (!table) return gigs_internal_fail(GIGS_ERR_HIP, "texel table");
+  const int symmetric = gigs::window_symmetric(res, costheta_cutoff, s);
+  if (symmetric < 0) return gigs_internal_fail(GIGS_ERR_HIP, "specular_cubemap_bwd: symmetry verdict");
   gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
-  hipLaunchKernelGGL(gigs::specular_cubemap_kernel<true>, dim3((6 * res * res + 3) / 4), dim3(256), 0, s, res, table, grad_out, bounds, roughness, costheta_cutoff, grad_cubemap);
+  const dim3 grid((6 * res * res + 3) / 4);
+  if (symmetric) {
+    hipLaunchKernelGGL(gigs::specular_cubemap_kernel<true>, grid, dim3(256), 0, s, res, table, grad_out, bounds, roughness, costheta_cutoff, grad_cubemap);
+  } else {
+    if (hipMemsetAsync(grad_cubemap, 0, (size_t)18 * res * res * sizeof(float), s) != hipSuccess)
+      return gigs_internal_fail(GIGS_ERR_HIP, "specular_cubemap_bwd: clearing the gradient");
+    hipLaunchKernelGGL((gigs::specular_cubemap_kernel<false, true>), grid, dim3(256), 0, s, res, table, grad_out, bounds, roughness, costheta_cutoff, grad_cubemap);
+  }
   return gigs_internal_check_launch("specular_cubemap_bwd");
+}
+
+int gigs_specular_window_symmetric(int res, float costheta_cutoff, void* stream) {
+  if (res <= 0) return gigs_internal_fail(GIGS_ERR_INVALID, "specular_window_symmetric: bad argument");
+  const int symmetric = gigs::window_symmetric(res, costheta_cutoff, (hipStream_t)stream);
+  if (symmetric < 0) return gigs_internal_fail(GIGS_ERR_HIP, "specular_window_symmetric");
+  return symmetric;
+}
+
+int gigs_specular_cubemap_bwd_scatter_w(int res, const float* bounds, const uint32_t* offsets, const float* weights_fwd,
+                                        const float* wsum, const float* grad_out, int grad_is_rgb, float* grad_cubemap,
+                                        void* stream) {
+  if (res <= 0 || !bounds || !offsets || !weights_fwd || !grad_out || !grad_cubemap)
+    return gigs_internal_fail(GIGS_ERR_INVALID, "specular_cubemap_bwd_scatter_w: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  gigs::StageTimer timer(gigs::Stage::kCubemapBwd, stream);
+  if (hipMemsetAsync(grad_cubemap, 0, (size_t)18 * res * res * sizeof(float), s) != hipSuccess)
+    return gigs_internal_fail(GIGS_ERR_HIP, "specular_cubemap_bwd_scatter_w: clearing the gradient");
+  hipLaunchKernelGGL(gigs::specular_table_scatter_kernel, dim3((6 * res * res + 3) / 4), dim3(256), 0, s, res, grad_out,
+                     grad_is_rgb ? 3 : 4, bounds, offsets, weights_fwd, wsum, grad_cubemap);
+  return gigs_internal_check_launch("specular_cubemap_bwd_scatter_w");
 }
 
 int gigs_specular_weights(int res, const float* bounds, const uint32_t* offsets, float roughness,

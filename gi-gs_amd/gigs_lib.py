@@ -80,6 +80,8 @@ SIGNATURES = {
     "gigs_specular_weights_divide": (_i, [_i, _f, _f, _f, _f, _f, C.c_void_p]),
     "gigs_specular_cubemap_fwd_w": (_i, [C.c_void_p, _i, _f, _f, _f, _f, _i, _f, _f, C.c_void_p]),
     "gigs_specular_cubemap_bwd_w": (_i, [C.c_void_p, _i, _f, _f, _f, _i, _f, _i, _f, C.c_void_p]),
+    "gigs_specular_window_symmetric": (_i, [_i, _fl, C.c_void_p]),
+    "gigs_specular_cubemap_bwd_scatter_w": (_i, [_i, _f, _f, _f, _f, _f, _i, _f, C.c_void_p]),
     "gigs_specular_cubemap_multi_w": (_i, [C.c_void_p, _i, C.c_void_p, _i, C.c_void_p]),
     "gigs_spec_sparse_capacity": (_i, [C.c_void_p, _i]),
     "gigs_specular_cubemap_multi_bwd_sparse": (_i, [C.c_void_p, _i, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

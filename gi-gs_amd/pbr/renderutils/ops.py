@@ -90,12 +90,23 @@ class _specular_cubemap(torch.autograd.Function):
                 gigs_lib.check(_lib.gigs_specular_cubemap_bwd(ctx.res, bounds.data_ptr(), d.data_ptr(), float(ctx.roughness),
                                                               float(ctx.theta_cutoff), g.data_ptr(), _stream()),
                                "specular_cubemap_bwd")
+            elif not ctx.tables.symmetric:
+                _scatter_backward(ctx.res, bounds, ctx.tables, None, d, 0, g)
             else:
                 gigs_lib.check(_lib.gigs_specular_cubemap_bwd_w(gigs_lib.ctx_ptr(), ctx.res, bounds.data_ptr(), ctx.tables.offsets.data_ptr(),
                                                                 ctx.tables.bwd.data_ptr(), _avg_window(ctx.tables, ctx.res),
                                                                 d.data_ptr(), 0, g.data_ptr(), _stream()),
                                "specular_cubemap_bwd_w")
         return g, None, None, None, None
+
+
+def _scatter_backward(res, bounds, tables, wsum, d, grad_is_rgb, g):
+    """The backward of a level whose accepted set is not symmetric (WeightTables.symmetric): the gather through the
+    role-swapped tables is not the transpose of the forward there, the scatter from the forward table is."""
+    gigs_lib.check(_lib.gigs_specular_cubemap_bwd_scatter_w(res, bounds.data_ptr(), tables.offsets.data_ptr(), tables.fwd.data_ptr(),
+                                                            None if wsum is None else wsum.data_ptr(), d.data_ptr(),
+                                                            int(grad_is_rgb), g.data_ptr(), _stream()),
+                   "specular_cubemap_bwd_scatter_w")
 
 
 def _avg_window(tables, res: int) -> int:
@@ -155,6 +166,12 @@ class _specular_cubemap_normalized(torch.autograd.Function):
     @gigs_lib.with_forward_context
     def backward(ctx, dout):
         bounds, wsum = ctx.saved_tensors
+        if not ctx.tables.symmetric:
+            d = _gpu(dout, "dout")
+            g = torch.empty((6, ctx.res, ctx.res, 3), dtype=torch.float32, device=d.device)
+            with torch.cuda.device(d.device):
+                _scatter_backward(ctx.res, bounds, ctx.tables, wsum, d, 1, g)
+            return g, None, None
         if ctx.tables.bwd_scaled is not None:
             # the 1 / wsum of d(rgb / w) / d(rgb) is folded into the cached table (gigs_specular_weights_divide)
             d, table = _gpu(dout, "dout"), ctx.tables.bwd_scaled
@@ -214,27 +231,38 @@ class _specular_levels(torch.autograd.Function):
     def backward(ctx, *douts):
         import ctypes as C
         dev = next(d for d in douts if d is not None).device
-        n = len(douts)
-        gs, arr, keep = [], (gigs_lib.SpecLevel * n)(), []
-        w_fwd, w_sum = (C.c_void_p * n)(), (C.c_void_p * n)()
-        for i, (d, res, (bounds, tables)) in enumerate(zip(douts, ctx.shapes, ctx.meta)):
+        # the levels whose accepted set is symmetric share one launch (the standard chains are symmetric at every level);
+        # any other level is scattered from its forward table, on its own, behind that launch
+        n = sum(1 for _, tables in ctx.meta if tables.symmetric)
+        gs, keep, scattered, shapes = [], [], [], []
+        arr, w_fwd, w_sum = (gigs_lib.SpecLevel * max(n, 1))(), (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+        i = 0
+        for d, res, (bounds, tables) in zip(douts, ctx.shapes, ctx.meta):
             d = torch.zeros((6, res, res, 3), dtype=torch.float32, device=dev) if d is None else _gpu(d, "dout")
             keep.append(d)
             g = torch.empty((6, res, res, 3), dtype=torch.float32, device=dev)
             gs.append(g)
+            if not tables.symmetric:
+                scattered.append((res, bounds, tables, d, g))
+                continue
             arr[i] = gigs_lib.SpecLevel(res, _avg_window(tables, res), d.data_ptr(), bounds.data_ptr(), tables.offsets.data_ptr(),
                                         tables.bwd_scaled.data_ptr(), g.data_ptr(), None)
             w_fwd[i], w_sum[i] = tables.fwd.data_ptr(), tables.wsum.data_ptr()
+            shapes.append(res)
+            i += 1
         with torch.cuda.device(dev):
             if bwd_head_start_ns > 0:  # see gigs_stream_delay: set by pipeline.WholeStepGraph while it captures the backward
                 gigs_lib.check(_lib.gigs_stream_delay(int(bwd_head_start_ns), _stream()), "stream_delay")
-            # nonzero-texel census, then one launch: tile gather or scatter of the sparse levels, gather of the others
-            # (gigs_options.spec_sparse = 0: the gather alone)
-            state, lists = _sparse_buffers(tuple(ctx.shapes), dev)
-            gigs_lib.check(_lib.gigs_specular_cubemap_multi_bwd_sparse(gigs_lib.ctx_ptr(), n, C.cast(arr, C.c_void_p), w_fwd, w_sum,
-                                                                       None if state is None else state.data_ptr(),
-                                                                       None if lists is None else lists.data_ptr(), _stream()),
-                           "specular_cubemap_multi_bwd_sparse")
+            if n > 0:
+                # nonzero-texel census, then one launch: tile gather or scatter of the sparse levels, gather of the others
+                # (gigs_options.spec_sparse = 0: the gather alone)
+                state, lists = _sparse_buffers(tuple(shapes), dev)
+                gigs_lib.check(_lib.gigs_specular_cubemap_multi_bwd_sparse(gigs_lib.ctx_ptr(), n, C.cast(arr, C.c_void_p), w_fwd, w_sum,
+                                                                           None if state is None else state.data_ptr(),
+                                                                           None if lists is None else lists.data_ptr(), _stream()),
+                               "specular_cubemap_multi_bwd_sparse")
+            for res, bounds, tables, d, g in scattered:
+                _scatter_backward(res, bounds, tables, tables.wsum, d, 1, g)
         return (None, None, *gs)
 
 
@@ -360,8 +388,9 @@ _sparseLast = {}
 
 
 def spec_sparse_report(shapes, device=None):
-    """[(scattered, nonzero texels)] per level from the last backward queued for the chain `shapes` (level resolutions),
-    or None if none ran: a device read after a synchronisation, for tests and diagnostics."""
+    """[(scattered, nonzero texels)] per level from the last backward queued for the chain `shapes` (the resolutions of the
+    levels with a symmetric accepted set: the others never enter that launch), or None if none ran: a device read after a
+    synchronisation, for tests and diagnostics."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     state = _sparseLast.get((tuple(shapes), str(device)))
     if state is None:
@@ -396,12 +425,15 @@ _weightTables = {}
 class WeightTables(NamedTuple):
     """The cached tables of one (resolution, roughness, cutoff): `fwd` / `bwd` hold the pair weights in the forward's
     and the gather-form backward's roles, `bwd_scaled` is `bwd` pre-divided by the forward's weight sums `wsum` (both
-    None without the switch spec_prescaled or past the byte budget)."""
+    None without the switch spec_prescaled or past the byte budget).  `symmetric`: whether every accepted pair (o, i) is
+    also accepted as (i, o), decided once when the tables are built (gigs_specular_window_symmetric); only then is the gather
+    through `bwd` / `bwd_scaled` the transpose of the forward, else the backward scatters from `fwd`."""
     offsets: torch.Tensor
     fwd: torch.Tensor
     bwd: torch.Tensor
     bwd_scaled: Optional[torch.Tensor]
     wsum: Optional[torch.Tensor]
+    symmetric: bool = True
 
 
 def _weight_tables(res, roughness, cutoff, device):
@@ -441,7 +473,10 @@ def _weight_tables(res, roughness, cutoff, device):
                     gigs_lib.check(_lib.gigs_specular_weights_divide(res, bounds.data_ptr(), offsets.data_ptr(),
                                                                      tabs[1].data_ptr(), wsum.data_ptr(), scaled.data_ptr(),
                                                                      _stream()), "specular_weights_divide")
-            _weightTables[key] = WeightTables(offsets, tabs[0], tabs[1], scaled, wsum if scaled is not None else None)
+            with torch.cuda.device(device):
+                symmetric = bool(gigs_lib.check(_lib.gigs_specular_window_symmetric(res, float(cos_cut), _stream()),
+                                                "specular_window_symmetric"))
+            _weightTables[key] = WeightTables(offsets, tabs[0], tabs[1], scaled, wsum if scaled is not None else None, symmetric)
     return _weightTables[key]
 
 

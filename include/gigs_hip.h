@@ -258,7 +258,11 @@ int gigs_diffuse_cubemap_bwd(int res, const float* grad_out, float* grad_cubemap
 /* specular_bounds (torch_bindings.cpp:797-822 -> cubemap.cu:181-244): bounds = [6,res,res,24]. */
 int gigs_specular_bounds(int res, float costheta_cutoff, float* bounds, void* stream);
 /* specular_cubemap_fwd / _bwd (torch_bindings.cpp:824-890 -> cubemap.cu:246-350).  out and grad_out
- * are [6,res,res,4] (rgb, weight sum); grad_cubemap [6,res,res,3] is fully overwritten. */
+ * are [6,res,res,4] (rgb, weight sum); grad_cubemap [6,res,res,3] is fully overwritten.  bounds = what
+ * gigs_specular_bounds gives for (res, costheta_cutoff).  The backward is the transpose of the forward: a gather
+ * over the texel's own window where the accepted set of (res, costheta_cutoff) is symmetric, else a scatter over
+ * each output's window with float atomics (the bounds' tile cull drops in-cone texels at coarse resolutions).  The
+ * first backward of a (device, res, costheta_cutoff) decides which and synchronises the stream once. */
 int gigs_specular_cubemap_fwd(int res, const float* cubemap, const float* bounds, float roughness,
                               float costheta_cutoff, float* out, void* stream);
 int gigs_specular_cubemap_bwd(int res, const float* bounds, const float* grad_out, float roughness,
@@ -287,6 +291,20 @@ int gigs_specular_cubemap_fwd_w(gigs_ctx* ctx, int res, const float* cubemap, co
 int gigs_specular_cubemap_bwd_w(gigs_ctx* ctx, int res, const float* bounds, const uint32_t* offsets,
                                 const float* weights_swapped, int avg_window, const float* grad_out,
                                 int grad_is_rgb, float* grad_cubemap, void* stream);
+/* 1 if the accepted set of (res, costheta_cutoff) is symmetric -- every pair (o, i) with i inside o's AABB and inside the
+ * cone also has o inside i's AABB --, 0 if not, < 0 on error.  Decided once per (device, res, costheta_cutoff) from
+ * gigs_specular_bounds' own output and cached; the first query synchronises the stream, so ask where the bounds and tables
+ * are built.  The role-swapped tables (gigs_specular_cubemap_bwd_w, the backward of gigs_specular_cubemap_multi_w and the
+ * gathered levels of gigs_specular_cubemap_multi_bwd_sparse) are the transpose of the forward ONLY for a symmetric level;
+ * the backward of any other level is gigs_specular_cubemap_bwd_scatter_w (pbr.renderutils.ops routes them). */
+int gigs_specular_window_symmetric(int res, float costheta_cutoff, void* stream);
+/* The backward from the FORWARD table in scatter form, for any level: grad_cubemap[i] = sum over the outputs o whose run
+ * holds i with a weight >= 0 of (w / wsum[o]) * grad_out[o].rgb (wsum = the forward's weight sums [6,res,res]: the backward
+ * of the normalised filter) or, with wsum == NULL, of w * grad_out[o].rgb.  grad_out is [6,res,res,3] (grad_is_rgb != 0) or
+ * [6,res,res,4].  grad_cubemap is cleared, then added into with float atomics: the order of the additions is not fixed. */
+int gigs_specular_cubemap_bwd_scatter_w(int res, const float* bounds, const uint32_t* offsets, const float* weights_fwd,
+                                        const float* wsum, const float* grad_out, int grad_is_rgb, float* grad_cubemap,
+                                        void* stream);
 
 /* The table-driven GGX filter of ALL levels of a light in one launch (gigs-hip extension): the levels of
  * CubemapLight.build_mips (pbr/light.py:166-170) are independent of each other, so their texels share one grid instead of

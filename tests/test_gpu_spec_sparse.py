@@ -1,18 +1,25 @@
 """The sparse GGX backward (gigs_specular_cubemap_multi_bwd_sparse in csrc/light_filter.hip): census of the nonzero gradient
-texels, scatter of the levels whose list fits its capacity, gather of the others.
+texels, a sparse path for the levels whose list fits its capacity, gather of the others.
 
 The level API is driven directly, one level per call at res 16 and 32 with roughness 0.08, 0.22 and 1.0 (8-, 16- and
 64-lane gathers, windows over one to six faces), plus one two-level chain whose levels take different paths.  Every
-case reads the path taken and the count from the state buffer, so none can pass without entering the scatter.
-The scatter kernel has two branches, chosen per level on the host (scatter_plan below restates the choice): narrow windows
-add to memory directly, `chunks` waves per listed texel; wide windows (a mean window of at least 1 / 16 of the level) go
-through LDS images of 32 x 32-texel face tiles.  Res 64 at roughness 0.08, 0.28 and 0.36 adds what res 16 and 32 cannot
-show: a narrow window shared by more than one wave (0.28), and a face of more than one tile (0.36).
+case reads the path taken and the count from the state buffer, so none can pass without entering a sparse path.
+There are two sparse paths, chosen per level on the host: a level whose mean window holds at most 256 candidates is
+SCATTERED, one wave per listed texel adding into memory with float atomics; a level with wider windows is summed on chip
+by the workgroups that own 16 x 16-texel tiles of the destination (the tile gather, tests/test_gpu_spec_tile_gather.py).
+Res 64 at roughness 0.08, 0.28 and 0.36 adds what res 16 and 32 cannot show: windows of several waves' worth of candidates
+(0.28) and faces of more than one tile (0.36).  (scatter_plan below restates an earlier host rule, 32 x 32 LDS tiles; it
+only serves test_levels_cover_the_three_lane_classes, which asks the levels for narrow and wide windows.)
 
 Accuracy: the reference is formed in float64 from the forward table and the forward's weight sums (the float32 quotient
-w / wsum, as both paths use it, times the gradient).  The sparse result's largest deviation from it may be at most 4x
-the gather's on the same input (floor: one ulp of the largest output magnitude): the scatter's additions arrive in any
-order, the gather's order is fixed.  A gradient over the capacity must give the bits of gigs_options.spec_sparse = 0.
+w / wsum, as both paths use it, times the gradient) -- sums formed from the library's own tables: the float64 check of
+these paths against independent values is tests/test_gpu_light_f64.py.  The sparse result's largest deviation from it
+may be at most 4x the gather's on the same input (floor: one ulp of the largest output magnitude): the scatter's additions
+arrive in any order, the gather's order is fixed.  This reference is the TRANSPOSE of the forward; the gather is one only
+where the level's accepted set is symmetric.  (16, 0.22) is not such a level (the bounds' tile cull drops in-cone
+texels): there the gather's own deviation from this reference is of the order of the values, so the 4x rule holds the
+scatter to nothing at that level -- pbr.renderutils.ops never gathers it (WeightTables.symmetric), and the float64
+suite checks what it does instead.  A gradient over the capacity must give the bits of gigs_options.spec_sparse = 0.
 """
 import ctypes as C
 
